@@ -324,6 +324,8 @@ def bench_full(args, cfg, W, eng, batch, noise, lr, rank, local, world, B, P):
         loss3 = step()
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_trainer_outputs(args.dump_outputs, ft, loss3, args.objective)
     if world > 1:
         t = torch.tensor([dt], device=f"cuda:{local}", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -388,6 +390,8 @@ def bench_lora(args, cfg, W, eng, batch, noise, lr, rank, local, world, B, P):
             loss3 = step()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and fp8 == args.fp8_only:      # the bf16 step (the line's `value`), or the fp8 one when it is timed alone
+            dump_trainer_outputs(args.dump_outputs, ft, loss3, args.objective)
         roof = None
         if not args.no_probe:
             roof = roofline_block(measure_gemm_roofline(eng, batch, noise, lr, step_fn=lambda: ft.train_step(batch, lr, noise)), conv)
@@ -437,6 +441,38 @@ def bench_lora(args, cfg, W, eng, batch, noise, lr, rank, local, world, B, P):
         }), flush=True)
 
 
+DUMP_SAMPLE = 1 << 22               # --dump-outputs: entries kept of a larger trainable buffer (16 MB as float32)
+
+
+def dump_outputs(out_dir, loss3, pred, params):
+    """--dump-outputs: what the timed path computed in its last step, as float32 .npy files under `out_dir` - the step's
+    loss triple (loss.npy), its predicted actions (pred_actions.npy, L1 objective only) and the trainable parameters after
+    the update (<name>.npy per flat buffer: all of it if it has at most DUMP_SAMPLE entries, else the entries at a fixed,
+    seeded set of DUMP_SAMPLE indices).  At most 2 x 16 MB plus a few KB; two builds run with the same arguments can be
+    compared file by file.  Inputs are seeded and the gradient sums of the L1 steps run in a fixed order, so two runs of one
+    build write the same bits (tests/test_ddp_gpu.py); the token cross-entropy objective still sums its loss with atomics."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"loss": loss3}
+    if pred is not None:
+        arrays["pred_actions"] = pred
+    for name, flat in params.items():
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[idx.to(flat.device)]
+        arrays[name] = flat
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def dump_trainer_outputs(out_dir, ft, loss3, objective):
+    """dump_outputs of a --mode full / lora step: the trainer's own flat buffer, and with the L1 objective the action head's
+    prediction and parameters (the token cross-entropy objective does not run the head)."""
+    l1 = objective == "l1"
+    dump_outputs(out_dir, loss3, ft._pred if l1 else None, dict(params=ft.P.data, **({"head_params": ft.head.P.data} if l1 else {})))
+
+
 MARKER_BYTES = 16 * 256 * 4099      # 4099 workgroups of 256 threads x 16 B (tools/summarise_profiles.py looks for this grid)
 
 
@@ -470,7 +506,12 @@ def main():
                          "documented recipe, README.md:254-274); config5: DINOv2+SigLIP fused + Qwen2.5-1.5B (BASELINE configs[4]'s backbone)")
     ap.add_argument("--n-img", type=int, default=None, help="images per sample (default 1; the documented recipe and BASELINE configs[4] use 2)")
     ap.add_argument("--ragged", action="store_true", help="prompt lengths in [24, 32], right-padded (exercises the mask path; SURVEY 8d)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed step computed in its last step (loss, predicted actions, a seeded sample of the updated "
+                         "trainable parameters) to DIR/<name>.npy as float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from vla_adapter_amd import ddp, engine as E, flops, synthetic as S
     rank, local, world = ddp.init_process_group_from_env()
@@ -485,7 +526,10 @@ def main():
     eng = E.VLAEngine(cfg, W, dev)
     batch = S.make_batch(cfg, B, dev, seed=1000 + rank, P=P, ragged=args.ragged)  # every rank draws its own samples (finetune.py:988-994)
     batch["pixel_values"] = batch["pixel_values"].to(torch.bfloat16)   # finetune.py:339
-    noise = (torch.randn(cfg.chunk, cfg.action_dim * cfg.llm.d, device=dev) * 0.02).to(torch.bfloat16)  # phase="Training"
+    # phase="Training"; a seeded generator of its own: torch seeds its default generator differently in every process, and
+    # runs with the same arguments must see the same inputs (--dump-outputs compares two builds output for output)
+    noise_gen = torch.Generator(device=dev).manual_seed(2000)
+    noise = (torch.randn(cfg.chunk, cfg.action_dim * cfg.llm.d, device=dev, generator=noise_gen) * 0.02).to(torch.bfloat16)
     if world > 1:
         eng.reducer = ddp.FlatGradReducer(algo=args.ddp_algo)
     elif args.rehearse_exchange:
@@ -542,6 +586,8 @@ def main():
     if marker is not None:
         _ops.zero_(marker)
         torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:          # before the variants and the probe below train the same weights further
+        dump_outputs(args.dump_outputs, loss3, eng.head.pred.view(B, cfg.chunk, cfg.action_dim), {"params": eng.head.P.data})
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -31,7 +31,9 @@ def _worker(rank, world, port, q, algo="allreduce"):
     red.reduce_async(flat, 100_000, None)       # small tail (action queries)
     red.wait()
     flat *= red.grad_scale
-    q.put((rank, flat))
+    # by value: a queued tensor travels as a file descriptor that this process must still be alive to hand over when the
+    # parent unpickles it, and the rank exits right after the barrier
+    q.put((rank, flat.numpy()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -46,7 +48,7 @@ def test_flat_grad_allreduce_world2_gloo(algo):
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q, algo)) for r in range(2)]
     for p in procs:
         p.start()
-    got = dict(q.get(timeout=120) for _ in range(2))
+    got = {r: torch.from_numpy(a) for r, a in (q.get(timeout=120) for _ in range(2))}
     for p in procs:
         p.join(60)
         assert p.exitcode == 0

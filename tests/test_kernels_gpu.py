@@ -914,6 +914,49 @@ def test_norms_transpose_colsum_random_shapes(ops):
         check(cs, x.float().sum(1), rel=1e-5, mx=1e-5, name=f"colsum {nb}x{R}x{Cc}")
 
 
+@pytest.mark.parametrize("rows,cols,off", [(300, 904, 0), (3001, 1160, 0), (300, 904, 1), (3001, 136, 1)])
+def test_weight_gradient_sums_in_a_fixed_order(ops, rows, cols, off):
+    """LayerNorm dw / db, RMSNorm dw, bias column sums and the LayerScale gradient against a float64 sum, and bit-identical when
+    repeated: short and tall (thousands of rows) inputs; off = 1 element makes the
+    operands unaligned (the one-thread-per-column form)."""
+    x, dy = gen(rows, cols, seed=3100 + rows), gen(rows, cols, seed=3200 + rows)
+    w, b = (1 + 0.1 * gen(cols, seed=3300).float()).to(BF).to(DEV), gen(cols, seed=3400, scale=0.1).to(DEV)
+    _, stats = ops.layernorm_fwd(x.to(DEV), w, b, 1e-5, want_stats=True)
+    _, rstd = ops.rmsnorm_fwd(x.to(DEV), w, 1e-6, want_rstd=True)
+
+    def shifted(t):                        # the same values at an element offset of `off`
+        buf = torch.zeros(t.numel() + 8, dtype=BF, device=DEV)
+        buf[off:off + t.numel()] = t.reshape(-1).to(DEV)
+        return buf[off:off + t.numel()].view(t.shape)
+
+    xs, dys = shifted(x), shifted(dy)
+
+    def sums():
+        dw, db, rw, cs = (torch.zeros(cols, device=DEV) for _ in range(4))
+        ops.layernorm_bwd(dys, xs, w, stats, dw, db, want_dx=False)
+        ops.N.check(ops._lib().vla_rmsnorm_dw(ops._st(), ops._p(dys), ops._p(xs), ops._p(rstd), ops._p(rw), rows, cols), "rmsnorm_dw")
+        ops.colsum_(dys, cs)
+        return dw, db, rw, cs
+
+    first, again = sums(), sums()
+    for a, c in zip(first, again):
+        assert torch.equal(a, c), "sums must not depend on launch timing"
+    d64, x64, st = dy.double(), x.double(), f(stats).double().view(rows, 2)
+    xh = (x64 - st[:, :1]) * st[:, 1:]
+    xr = (x.float() * f(rstd)[:, None]).to(BF).double()
+    for got, want, name in ((first[0], (d64 * xh).sum(0), "layernorm dw"), (first[1], d64.sum(0), "layernorm db"),
+                            (first[2], (d64 * xr).sum(0), "rmsnorm dw"), (first[3], d64.sum(0), "colsum")):
+        check(got, want, rel=1e-5, mx=1e-4, name=f"{name} {rows}x{cols}+{off}")
+    if off == 0:                           # LayerScale requires aligned operands
+        a_, ls = gen(rows, cols, seed=3500 + rows), (0.5 + 0.1 * gen(cols, seed=3600).float()).to(BF).to(DEV)
+        dls1, dls2 = torch.zeros(cols, device=DEV), torch.zeros(cols, device=DEV)
+        da = ops.layerscale_bwd(dy.to(DEV), a_.to(DEV), ls, dls1)
+        ops.layerscale_bwd(dy.to(DEV), a_.to(DEV), ls, dls2)
+        assert torch.equal(dls1, dls2)
+        check(dls1, (d64 * a_.double()).sum(0), rel=1e-5, mx=1e-4, name=f"layerscale dls {rows}x{cols}")
+        check(da, dy.float() * f(ls), name=f"layerscale da {rows}x{cols}")
+
+
 def test_glue_and_optimizer_random_sweep(ops):
     """Seeded sweep over the integer / index kernels (bit-exact), the fused epilogue GEMMs and AdamW:
     random label layouts for the action masks and the splice, random (B, S, heads) for the RoPE-in-GEMM epilogues,

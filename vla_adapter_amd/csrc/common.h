@@ -100,3 +100,46 @@ __device__ __forceinline__ void glds16(const void* gptr, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gptr,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
+
+// ---------------------------------------------------------------- column reductions with a fixed summation order
+// Weight / bias gradients summed over rows (norm dw / db, bias colsums, LayerScale) are reproducible bit for bit: one
+// 1024-thread workgroup owns a slice of columns over ALL rows - LPR lanes x 8 columns per row segment, 1024 / LPR row groups
+// (row r goes to group r % groups) - and sums in a fixed order: the row groups of a wave by a lane butterfly, then the 16 waves
+// in index order.  Its total is added with one atomic per column; no two workgroups of a launch add to the same column, so the
+// result does not depend on which workgroup finishes first (cross-workgroup f32 atomics did).
+// LPR 8: 64 columns and 128 row groups per workgroup (narrower slices for tall inputs measured slower: 32-B row segments).
+constexpr int CR_THREADS = 1024;
+
+template <int LPR>
+struct CR {
+  static constexpr int COLS = 8 * LPR, GROUPS = CR_THREADS / LPR;
+  // thread -> (first of its 8 columns, first row): columns blockIdx.x * COLS + [0, COLS), rows row0, row0 + GROUPS, ...
+  static __device__ __forceinline__ int col() { return blockIdx.x * COLS + (threadIdx.x % LPR) * 8; }
+  static __device__ __forceinline__ int row0() { return threadIdx.x / LPR; }
+  static int blocks(int cols) { return (cols + COLS - 1) / COLS; }
+
+  // out[c] += sum over the workgroup of a[] (every thread of the workgroup must call it)
+  static __device__ __forceinline__ void add(float (&a)[8], float* __restrict__ out, int cols, float (*sm)[64]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+      for (int o = LPR; o < 64; o <<= 1) a[k] += __shfl_xor(a[k], o, 64);
+    if (lane < LPR)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) sm[w][lane * 8 + k] = a[k];
+    __syncthreads();
+    const int c = blockIdx.x * COLS + threadIdx.x;
+    if (threadIdx.x < COLS && c < cols) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < CR_THREADS / 64; ++i) s += sm[i][threadIdx.x];
+      atomicAdd(out + c, s);
+    }
+    __syncthreads();                                       // sm may be reused by the next call
+  }
+};
+
+// launch KERNEL<8> over `cols` columns (grid y = 1, z = batch)
+#define CR_LAUNCH(KERNEL, rows, cols, batch, stream, ...) \
+  hipLaunchKernelGGL(KERNEL<8>, dim3(CR<8>::blocks(cols), 1, (batch)), dim3(CR_THREADS), 0, (hipStream_t)(stream), __VA_ARGS__)

@@ -785,7 +785,7 @@ __global__ __launch_bounds__(256, 3) void head_bwd_tiles(HP p, float* __restrict
 }
 
 // dq[b, q, head, :] = RoPE^T(sum over key tiles, in tile order, of the fp32 partials); dgate += (1 - tanh^2 g) * sum of the
-// gate partials (one atomic per (sample, head), as the combined kernel did).  One workgroup per (sample, head).
+// gate partials (workgroup 0, in a fixed order).  One workgroup per (sample, head).
 template <int D>
 __global__ __launch_bounds__(256) void head_dq_reduce(HP p, const float* __restrict__ ws_dq, const float* __restrict__ ws_gate) {
   const int gid = blockIdx.x, b = gid / p.H, hd = gid - b * p.H;
@@ -811,11 +811,22 @@ __global__ __launch_bounds__(256) void head_dq_reduce(HP p, const float* __restr
     }
     *reinterpret_cast<uint2*>(p.dq + ((long long)b * p.T + q) * p.ld_q + hd * D + d) = uint2{pack2(a.x, a.y), pack2(a.z, a.w)};
   }
-  if (threadIdx.x == 0 && p.dgate) {
-    float g = 0.f;
-    for (int t = 0; t < ntile; ++t) g += ws_gate[gid * ntile + t];
+  if (gid == 0 && p.dgate) {              // all gate partials come from the previous launch: workgroup 0 sums them in a
+    __shared__ float red[256];           // fixed order (tiles, then (sample, head) pairs, then a tree) and adds once
     const float th = tanhf(bf2f(p.gate[0]));
-    atomicAdd(p.dgate, g * (1.f - th * th));
+    float acc = 0.f;
+    for (int j = threadIdx.x; j < p.B * p.H; j += 256) {
+      float g = 0.f;
+      for (int t = 0; t < ntile; ++t) g += ws_gate[j * ntile + t];
+      acc += g * (1.f - th * th);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicAdd(p.dgate, red[0]);
   }
 }
 

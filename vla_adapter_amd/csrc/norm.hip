@@ -166,20 +166,40 @@ __global__ __launch_bounds__(256) void layernorm_bwd_dx_kernel(const bf16_t* __r
   }
 }
 
-// dw[c] += sum_rows dy*xhat, db[c] += sum_rows dy.  grid (ceil(cols/256), row_splits)
-__global__ __launch_bounds__(256) void layernorm_bwd_wb_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
-                                                               const float* __restrict__ stats, float* __restrict__ dw,
-                                                               float* __restrict__ db, int rows, int cols, int ldx,
-                                                               int lddy, int rows_per) {
+// dw[c] += sum_rows dy*xhat, db[c] += sum_rows dy, in a fixed order (common.h, CR).  grid CR<LPR>::blocks(cols)
+template <int LPR>
+__global__ __launch_bounds__(CR_THREADS) void layernorm_bwd_wb_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                                      const float* __restrict__ stats, float* __restrict__ dw,
+                                                                      float* __restrict__ db, int rows, int cols, int ldx, int lddy) {
+  __shared__ float sm[CR_THREADS / 64][64];
+  const int c = CR<LPR>::col();
+  float aw[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ab[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (c < cols)
+    for (int r = CR<LPR>::row0(); r < rows; r += CR<LPR>::GROUPS) {
+      float fd[8], fx[8];
+      unpack8(*reinterpret_cast<const uint4*>(dy + (long long)r * lddy + c), fd);
+      unpack8(*reinterpret_cast<const uint4*>(x + (long long)r * ldx + c), fx);
+      const float mean = stats[2 * r], rstd = stats[2 * r + 1];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        aw[k] += fd[k] * ((fx[k] - mean) * rstd);
+        ab[k] += fd[k];
+      }
+    }
+  if (dw) CR<LPR>::add(aw, dw, cols, sm);
+  if (db) CR<LPR>::add(ab, db, cols, sm);
+}
+
+// the same sums for operands that are not 16-B aligned: one thread per column, rows in order
+__global__ __launch_bounds__(256) void layernorm_bwd_wb_scalar_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                                      const float* __restrict__ stats, float* __restrict__ dw,
+                                                                      float* __restrict__ db, int rows, int cols, int ldx, int lddy) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= cols) return;
-  const int r0 = blockIdx.y * rows_per, r1 = min(rows, r0 + rows_per);
   float aw = 0.f, ab = 0.f;
-#pragma unroll 4
-  for (int r = r0; r < r1; ++r) {
+  for (int r = 0; r < rows; ++r) {
     const float d = bf2f(dy[(long long)r * lddy + c]);
-    const float xh = (bf2f(x[(long long)r * ldx + c]) - stats[2 * r]) * stats[2 * r + 1];
-    aw += d * xh;
+    aw += d * ((bf2f(x[(long long)r * ldx + c]) - stats[2 * r]) * stats[2 * r + 1]);
     ab += d;
   }
   if (dw) atomicAdd(dw + c, aw);
@@ -324,12 +344,11 @@ extern "C" int vla_layernorm_bwd(void* stream, const void* dy, const void* x, co
     VLA_CHECK_LAUNCH("layernorm_bwd_dx");
   }
   if (dw || db) {
-    // short serial row loops (the kernel sits on the action head's backward critical chain with rows = 256):
-    // rows/32 per block, clamped to [8, 64]; partial sums meet through fp32 atomics
-    const int rows_per = rows / 32 < 8 ? 8 : (rows / 32 > 64 ? 64 : rows / 32);
-    dim3 grid((cols + 255) / 256, (rows + rows_per - 1) / rows_per);
-    hipLaunchKernelGGL(layernorm_bwd_wb_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)x, stats, dw, db, rows, cols, ldx, lddy, rows_per);
+    if ((((uintptr_t)dy | (uintptr_t)x) & 15) == 0)
+      CR_LAUNCH(layernorm_bwd_wb_kernel, rows, cols, 1, stream, (const bf16_t*)dy, (const bf16_t*)x, stats, dw, db, rows, cols, ldx, lddy);
+    else
+      hipLaunchKernelGGL(layernorm_bwd_wb_scalar_kernel, dim3((cols + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                         (const bf16_t*)dy, (const bf16_t*)x, stats, dw, db, rows, cols, ldx, lddy);
     VLA_CHECK_LAUNCH("layernorm_bwd_wb");
   }
   return VLA_OK;
@@ -384,24 +403,40 @@ extern "C" int vla_rmsnorm_bwd(void* stream, const void* dy, const void* x, cons
 
 // ---------------------------------------------------------------- RMSNorm weight gradient (full fine-tune, BASELINE config 4)
 // Qwen2RMSNorm: y = w * bf16(x * rstd)  ->  dw[c] += sum_rows dy[r, c] * bf16(x[r, c] * rstd[r])   (fp32 accumulator, += ).
-// grid (ceil(cols / 256), row splits): same shape as layernorm_bwd_wb_kernel.
-__global__ __launch_bounds__(256) void rmsnorm_dw_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
-                                                         const float* __restrict__ rstd, float* __restrict__ dw, int rows, int cols,
-                                                         int rows_per) {
+// Fixed summation order (common.h, CR); the scalar form (cols % 8 or unaligned operands) runs one thread per column.
+template <int LPR>
+__global__ __launch_bounds__(CR_THREADS) void rmsnorm_dw_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                                const float* __restrict__ rstd, float* __restrict__ dw, int rows, int cols) {
+  __shared__ float sm[CR_THREADS / 64][64];
+  const int c = CR<LPR>::col();
+  float a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (c < cols)
+    for (int r = CR<LPR>::row0(); r < rows; r += CR<LPR>::GROUPS) {
+      float fd[8], fx[8];
+      unpack8(*reinterpret_cast<const uint4*>(dy + (long long)r * cols + c), fd);
+      unpack8(*reinterpret_cast<const uint4*>(x + (long long)r * cols + c), fx);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) a[k] += fd[k] * rbf(fx[k] * rstd[r]);
+    }
+  CR<LPR>::add(a, dw, cols, sm);
+}
+
+__global__ __launch_bounds__(256) void rmsnorm_dw_scalar_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                                const float* __restrict__ rstd, float* __restrict__ dw, int rows, int cols) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= cols) return;
-  const int r0 = blockIdx.y * rows_per, r1 = min(rows, r0 + rows_per);
   float a = 0.f;
-#pragma unroll 4
-  for (int r = r0; r < r1; ++r) a += bf2f(dy[(long long)r * cols + c]) * rbf(bf2f(x[(long long)r * cols + c]) * rstd[r]);
+  for (int r = 0; r < rows; ++r) a += bf2f(dy[(long long)r * cols + c]) * rbf(bf2f(x[(long long)r * cols + c]) * rstd[r]);
   atomicAdd(dw + c, a);
 }
 
 extern "C" int vla_rmsnorm_dw(void* stream, const void* dy, const void* x, const float* rstd, float* dw, int rows, int cols) {
   VLA_REQUIRE(dy && x && rstd && dw && rows > 0 && cols > 0, "rmsnorm_dw: null/empty");
-  const int rows_per = 64;
-  dim3 grid((cols + 255) / 256, (rows + rows_per - 1) / rows_per);
-  hipLaunchKernelGGL(rmsnorm_dw_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x, rstd, dw, rows, cols, rows_per);
+  if (cols % 8 == 0 && (((uintptr_t)dy | (uintptr_t)x) & 15) == 0)
+    CR_LAUNCH(rmsnorm_dw_kernel, rows, cols, 1, stream, (const bf16_t*)dy, (const bf16_t*)x, rstd, dw, rows, cols);
+  else
+    hipLaunchKernelGGL(rmsnorm_dw_scalar_kernel, dim3((cols + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)dy, (const bf16_t*)x, rstd, dw, rows, cols);
   VLA_CHECK_LAUNCH("rmsnorm_dw");
   return VLA_OK;
 }

@@ -51,38 +51,48 @@ __global__ void layerscale_fwd_kernel(const bf16_t* __restrict__ a, const bf16_t
   }
 }
 
-// da = bf16(dy * ls) ; dls[c] += sum_r dy[r, c] * a[r, c]   (each lane owns 8 columns; the 4 waves of a block split the rows of
-// its chunk, partial sums meet in LDS, one f32 atomic per column per block - the colsum_vec structure)
-__global__ __launch_bounds__(256) void layerscale_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ a, const bf16_t* __restrict__ ls,
-                                                             bf16_t* __restrict__ da, float* __restrict__ dls, int rows, int cols, int rows_per) {
-  __shared__ float sm[4][512];
+// da = bf16(dy * ls) (no dls: each lane owns 8 columns, the 4 waves of a block split the rows of its chunk)
+__global__ __launch_bounds__(256) void layerscale_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ ls,
+                                                             bf16_t* __restrict__ da, int rows, int cols, int rows_per) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c = blockIdx.x * 512 + lane * 8;
   const int r0 = blockIdx.y * rows_per, r1 = min(rows, r0 + rows_per);
+  if (c >= cols) return;
+  float fl[8];
+  unpack8(*reinterpret_cast<const uint4*>(ls + c), fl);
+  for (int r = r0 + w; r < r1; r += 4) {
+    float fd[8], o[8];
+    unpack8(*reinterpret_cast<const uint4*>(dy + (long long)r * cols + c), fd);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = fd[k] * fl[k];
+    *reinterpret_cast<uint4*>(da + (long long)r * cols + c) = pack8(o);
+  }
+}
+
+// the same with dls in a fixed summation order (common.h, CR): one workgroup per column slice over all rows
+template <int LPR>
+__global__ __launch_bounds__(CR_THREADS) void layerscale_bwd_dls_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ a,
+                                                                        const bf16_t* __restrict__ ls, bf16_t* __restrict__ da,
+                                                                        float* __restrict__ dls, int rows, int cols) {
+  __shared__ float sm[CR_THREADS / 64][64];
+  const int c = CR<LPR>::col();
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (c < cols) {
     float fl[8];
     unpack8(*reinterpret_cast<const uint4*>(ls + c), fl);
-    for (int r = r0 + w; r < r1; r += 4) {
+    for (int r = CR<LPR>::row0(); r < rows; r += CR<LPR>::GROUPS) {
       float fd[8], fa[8], o[8];
       unpack8(*reinterpret_cast<const uint4*>(dy + (long long)r * cols + c), fd);
-      if (dls) unpack8(*reinterpret_cast<const uint4*>(a + (long long)r * cols + c), fa);
+      unpack8(*reinterpret_cast<const uint4*>(a + (long long)r * cols + c), fa);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         o[k] = fd[k] * fl[k];
-        if (dls) acc[k] += fd[k] * fa[k];
+        acc[k] += fd[k] * fa[k];
       }
       *reinterpret_cast<uint4*>(da + (long long)r * cols + c) = pack8(o);
     }
   }
-  if (!dls) return;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) sm[w][lane * 8 + k] = acc[k];
-  __syncthreads();
-  for (int i = threadIdx.x; i < 512; i += 256) {
-    const int cc = blockIdx.x * 512 + i;
-    if (cc < cols) atomicAdd(dls + cc, sm[0][i] + sm[1][i] + sm[2][i] + sm[3][i]);
-  }
+  CR<LPR>::add(acc, dls, cols, sm);
 }
 
 inline dim3 grid1d(long long n, int per) {
@@ -121,13 +131,19 @@ extern "C" int vla_layerscale_fwd(void* stream, const void* a, const void* ls, c
 extern "C" int vla_layerscale_bwd(void* stream, const void* dy, const void* a, const void* ls, void* da, float* dls, int rows, int cols) {
   VLA_REQUIRE(dy && ls && da && rows > 0 && cols > 0 && cols % 8 == 0 && (dls == nullptr || a != nullptr), "layerscale_bwd: bad args (cols % 8 == 0)");
   VLA_REQUIRE(((((uintptr_t)dy) | ((uintptr_t)ls) | ((uintptr_t)da) | ((uintptr_t)a)) & 15) == 0, "layerscale_bwd: 16-B aligned contiguous tensors");
+  if (dls) {
+    CR_LAUNCH(layerscale_bwd_dls_kernel, rows, cols, 1, stream, (const bf16_t*)dy, (const bf16_t*)a, (const bf16_t*)ls, (bf16_t*)da, dls,
+              rows, cols);
+    VLA_CHECK_LAUNCH("layerscale_bwd");
+    return VLA_OK;
+  }
   const int gx = (cols + 511) / 512;
   int gy = (rows + 63) / 64;
   if (gy > 1024) gy = 1024;
   const int rows_per = (rows + gy - 1) / gy;
   gy = (rows + rows_per - 1) / rows_per;
-  hipLaunchKernelGGL(layerscale_bwd_kernel, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)a, (const bf16_t*)ls,
-                     (bf16_t*)da, dls, rows, cols, rows_per);
+  hipLaunchKernelGGL(layerscale_bwd_kernel, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)ls,
+                     (bf16_t*)da, rows, cols, rows_per);
   VLA_CHECK_LAUNCH("layerscale_bwd");
   return VLA_OK;
 }
