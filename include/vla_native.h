@@ -34,8 +34,9 @@ extern "C" {
  *   5  round 4: the RMSNorm fields are gone again (the fold measured slower and left the tree: tools/diag/gemm256_pruned_paths.patch);
  *      fp8 = 1 may be combined with the K extension (and, in that form, with the SwiGLU-backward epilogue).
  *   6  round 4: new entry points vla_gemm_latency_hint, vla_dropout_bf16, vla_dropout_bwd_add_bf16, vla_inc_i32 (no layout change).
+ *   7  new entry points vla_augment_slab_floats, vla_augment_stats, vla_augment_apply (no layout change).
  * A binder checks vla_version() AND vla_desc_size() against its own struct definitions before the first call. */
-#define VLA_ABI_VERSION 6
+#define VLA_ABI_VERSION 7
 int vla_version(void);
 /* sizeof() of the descriptor structs as this library was compiled: which = 0 vla_gemm_desc, 1 vla_attn_desc, 2 vla_head_attn_desc,
  * 3 vla_gemm_tn_desc; -1 for an unknown index.  A caller whose struct is shorter would make the library read past its end. */
@@ -235,6 +236,44 @@ int vla_rope_interleaved(void* stream, void* x, const float* cos_t, const float*
  * torchvision's order; stored bf16, or f32 if out_f32) inside a channel-stacked [B, Ctot, H, W] tensor.  mean3 / std3: host. */
 int vla_image_normalize_u8(void* stream, const void* img, void* out, int B, int H, int W, int Ctot, int c0,
                            const float* mean3 /* host */, const float* std3 /* host */, int out_f32);
+/* Training-time image augmentation of the reference's RLDS pipeline (prismatic/vla/datasets/datasets.py:204-218 ->
+ * dlimp augment_image, applied in rlds/dataset.py:412-419) and the evaluator's center crop (experiments/robot/openvla_utils.py:
+ * 568-648), fused with the ToTensor + Normalize above.  frames u8 [N, H, W, 3] = [B, n_img, H, W, 3] (image n is image n % n_img
+ * of sample n / n_img); per image in f32: x = q * (1/255), then the enabled ops of `ops` in this order, each followed by
+ * clip(0, 1): crop (tf.image.crop_and_resize of box (y1, x1, y2, x2) back to H x W, bilinear, extrapolation 0), brightness
+ * (x + d), contrast ((x - mean_c) * f + mean_c, mean over H x W of the post-brightness image), saturation (HSV s * f clamped
+ * to [0, 1]), hue (HSV h + d wrapped into [0, 1)); then q' = min(255, floor(x * 255.5)), optionally stored to frames_out
+ * (u8 [N, H, W, 3]), and out[b, 3 * (im * n_bb + j) + c] = ((q' / 255) - mean[3j + c]) / std[3j + c] (bf16, or f32 if out_f32)
+ * in a [B, 3 * n_bb * n_img, H, W] tensor.  A disabled op is skipped, not run with neutral parameters.
+ * params f32 [N, VLA_AUG_NPARAM] (u, y1, x1, y2, x2, brightness delta, contrast factor, saturation factor, hue delta): read, or
+ * with VLA_AUG_DRAW drawn in the kernel from one 24-bit uniform u of splitmix64(seed, rank, step, sample, image) and written
+ * by vla_augment_apply.  cfg: host f32[7] = (crop side = sqrt(area scale), brightness max delta, contrast lo, hi, saturation
+ * lo, hi, hue max delta) of the draw mapping.  slab f32 [vla_augment_slab_floats(N, H, W)]: per-chunk channel sums written by
+ * vla_augment_stats, read by vla_augment_apply (needed when VLA_AUG_CONTRAST is set; run stats first on the same stream with the
+ * same arguments).  Deterministic: no atomics. */
+#define VLA_AUG_CROP 1
+#define VLA_AUG_BRIGHTNESS 2
+#define VLA_AUG_CONTRAST 4
+#define VLA_AUG_SATURATION 8
+#define VLA_AUG_HUE 16
+#define VLA_AUG_DRAW 32
+#define VLA_AUG_ALL 63
+#define VLA_AUG_NPARAM 9
+#define VLA_AUG_P_U 0
+#define VLA_AUG_P_Y1 1
+#define VLA_AUG_P_X1 2
+#define VLA_AUG_P_Y2 3
+#define VLA_AUG_P_X2 4
+#define VLA_AUG_P_BRIGHT 5
+#define VLA_AUG_P_CONTRAST 6
+#define VLA_AUG_P_SAT 7
+#define VLA_AUG_P_HUE 8
+long long vla_augment_slab_floats(int N, int H, int W);     /* host only; -1 on bad sizes */
+int vla_augment_stats(void* stream, const void* frames, const float* params, float* slab, int N, int H, int W, int n_img,
+                      unsigned ops, const float* cfg /* host */, unsigned long long seed, long long rank, long long step);
+int vla_augment_apply(void* stream, const void* frames, float* params, const float* slab, void* out, void* frames_out, int N,
+                      int H, int W, int n_img, int n_bb, const float* mean /* host */, const float* std /* host */, int out_f32,
+                      unsigned ops, const float* cfg /* host */, unsigned long long seed, long long rank, long long step);
 /* ActionTokenizer.__call__ (prismatic/vla/action_tokenizer.py:60-74, use_minivlm): ids[i] = tokenizer_len -
  * digitize(clip(actions[i], lo, hi), bins) with numpy semantics (bins: device f64 [nbins], increasing). */
 int vla_action_tokenize(void* stream, const float* actions, const double* bins, long long* ids, long long n, int nbins,

@@ -4,7 +4,8 @@ Keeps the reference's flat ``FinetuneConfig`` (finetune.py:66-128) and its ``--f
 absent here: parsed with argparse from the dataclass fields), the per-step metric names (finetune.py:421-444), the LR
 warm-up / MultiStepLR schedule (:903-921, 1061-1065) and the checkpoint file names (:527-572).  What is NOT here, on
 purpose: HF-hub / network loaders (:752-754), the RLDS/TensorFlow input pipeline (out of scope) -
-batches come from an iterable / ``--batch_file`` (a .pt dict or a directory of them: the collator's contract) or
+batches come from an iterable / ``--batch_file`` (a .pt dict or a directory of them: the collator's contract), from
+``--frame_batch_file`` (the same with raw uint8 frames, augmented on the device under ``--image_aug``) or
 ``synthetic.make_batch``; weights are random-init unless ``--vlm_path`` / ``--resum_vla_path`` point at local state-dict
 files.  Every reference flag is either honoured or refused with an error (``check_supported``); none is silently dropped.
 """
@@ -78,6 +79,8 @@ class FinetuneConfig:
     tiny: bool = False                    # prismatic-tiny plumbing config (BASELINE configs[0])
     seed: int = 0
     batch_file: Optional[str] = None      # torch-saved dict with the collator's keys
+    frame_batch_file: Optional[str] = None  # same, with raw frames: frames_u8 uint8 [B, n_img, H, W, 3] instead of pixel_values (the
+                                          # input stage normalises them on the device, augmented under --image_aug)
     use_graph: bool = True                # replay the captured hipGraphs
     max_seq_len: int = 0                  # static token length every batch is right-padded to (0: length of the first batch)
     conservative_rows: bool = False       # captured live-row window starts at the first text row instead of the first batch's action block
@@ -116,8 +119,9 @@ def parse_args(argv=None) -> FinetuneConfig:
 
 # Flags of the reference that only configure subsystems outside the accelerated path (RLDS/TensorFlow input pipeline,
 # W&B, HF hub): the native entry point consumes pre-collated batches, so their DEFAULT values are inert - but a value the
-# user passes explicitly cannot be honoured and is refused instead of ignored.
-OUT_OF_PATH_FLAGS = ("data_root_dir", "shuffle_buffer_size", "image_aug", "wandb_entity", "wandb_project", "run_id_note",
+# user passes explicitly cannot be honoured and is refused instead of ignored.  (--image_aug is honoured where batches carry
+# raw frames, --frame_batch_file: check_supported / batch_stream.)
+OUT_OF_PATH_FLAGS = ("data_root_dir", "shuffle_buffer_size", "wandb_entity", "wandb_project", "run_id_note",
                      "config_file_path", "phase1_path", "num_diffusion_steps", "diffusion_sample_freq", "val_freq", "val_time_limit",
                      "use_minivlm")
 
@@ -129,8 +133,13 @@ def train_mode(cfg: FinetuneConfig) -> str:
     return "lora" if cfg.use_lora else ("adapter" if cfg.use_fz else "full")
 
 
-def check_supported(cfg: FinetuneConfig, explicit=()) -> None:
-    """Raise for every reference option this path does not implement (nothing is parsed and silently dropped)."""
+IMAGE_AUG_REFUSAL = ("--image_aug: already normalised pixel_values cannot be augmented; pass raw uint8 frames (frames_u8) with "
+                     "--frame_batch_file, or in the batches handed to finetune()")
+
+
+def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = False) -> None:
+    """Raise for every reference option this path does not implement (nothing is parsed and silently dropped).
+    ``frame_batches``: finetune() was handed a batch iterable, which may carry raw frames (--image_aug is then checked per batch)."""
     if cfg.grad_accumulation_steps < 1:
         raise ValueError("grad_accumulation_steps must be >= 1")
     if cfg.use_lora and not 0.0 <= cfg.lora_dropout < 1.0:
@@ -161,6 +170,11 @@ def check_supported(cfg: FinetuneConfig, explicit=()) -> None:
         raise ValueError("grad_accumulation_steps must be >= 1")
     if cfg.resume and cfg.resume_step is None:
         raise ValueError("--resume needs --resume_step (finetune.py:1056 computes log_step = resume_step + gradient_step_idx)")
+    if cfg.batch_file and cfg.frame_batch_file:
+        raise ValueError("--batch_file and --frame_batch_file are two batch sources: pass one")
+    frames = bool(cfg.frame_batch_file) or frame_batches
+    if "image_aug" in explicit and not frames:
+        raise NotImplementedError(IMAGE_AUG_REFUSAL)
     bad = [n for n in explicit if n in OUT_OF_PATH_FLAGS]
     if bad:
         raise NotImplementedError(f"flags {bad} configure parts of the reference outside the accelerated path (input pipeline / "
@@ -262,26 +276,57 @@ def _pad_to(batch: dict, L: int, pad_id: int) -> dict:
     return out
 
 
-def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None):
-    """Endless iterator over collated batches: an explicit iterable, ``--batch_file`` (one .pt dict, or a directory of them,
-    cycled in sorted order; every rank starts at its own offset - the reference's ranks draw independent shuffles,
-    finetune.py:988-994), or seeded synthetic batches (a new one every micro-step)."""
+def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, explicit=()):
+    """Endless iterator over collated batches: an explicit iterable, ``--batch_file`` / ``--frame_batch_file`` (one .pt dict, or
+    a directory of them, cycled in sorted order; every rank starts at its own offset - the reference's ranks draw independent
+    shuffles, finetune.py:988-994), or seeded synthetic batches (a new one every micro-step).
+
+    A batch carrying ``frames_u8`` (uint8 [B, n_img, H, W, 3]) instead of ``pixel_values`` goes through the GPU input stage here:
+    with --image_aug (default True, as in the reference) the training augmentation of the reference's RLDS pipeline
+    (datasets.py:204-218, drawn per image from --seed, the rank and this rank's micro-step counter), else a plain normalise.  The
+    normalisation per backbone follows the model config (input_stage.backbone_norms: DINOv2-like ViTs ImageNet, others SigLIP).
+    Frames not at the model's image size go through the Pillow-exact bicubic resize of the processor first; the reference's RLDS
+    stage resizes with TF's lanczos3 there, which is not reproduced."""
     from . import synthetic as S
+    from .input_stage import GPUInputStage, ImageAugment, backbone_norms
+    stage, step = None, 0
+
+    def collate(b):
+        nonlocal stage, step
+        b = {k: v.to(dev) for k, v in b.items()}
+        if "frames_u8" not in b:
+            if "image_aug" in explicit:
+                raise NotImplementedError(IMAGE_AUG_REFUSAL)
+            return b
+        fr = b.pop("frames_u8")
+        if fr.dtype != torch.uint8 or fr.dim() != 5 or fr.shape[-1] != 3:
+            raise ValueError(f"frames_u8 must be uint8 [B, n_img, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
+        if stage is None:
+            stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img)
+        aug = ImageAugment(seed=cfg.seed, rank=rank, step=step) if cfg.image_aug else None
+        b["pixel_values"] = stage.pixels(fr, augment=aug)
+        step += 1
+        return b
+
     if batches is not None:
         while True:
             n = 0
             for b in batches:
                 n += 1
-                yield {k: v.to(dev) for k, v in b.items()}
+                yield collate(b)
             if n == 0:
                 raise ValueError("empty batch iterable")
-    elif cfg.batch_file:
-        files = sorted(str(p) for p in Path(cfg.batch_file).glob("*.pt")) if os.path.isdir(cfg.batch_file) else [cfg.batch_file]
+    elif cfg.batch_file or cfg.frame_batch_file:
+        src = cfg.batch_file or cfg.frame_batch_file
+        files = sorted(str(p) for p in Path(src).glob("*.pt")) if os.path.isdir(src) else [src]
         if not files:
-            raise FileNotFoundError(f"no .pt batch files under {cfg.batch_file}")
+            raise FileNotFoundError(f"no .pt batch files under {src}")
         i = rank % len(files)
         while True:
-            yield {k: v.to(dev) for k, v in torch.load(files[i], weights_only=True).items()}
+            b = torch.load(files[i], weights_only=True)
+            if cfg.frame_batch_file and "frames_u8" not in b:
+                raise ValueError(f"{files[i]}: --frame_batch_file batches carry frames_u8 (uint8 [B, n_img, H, W, 3])")
+            yield collate(b)
             i = (i + 1) % len(files)
     else:
         i = 0
@@ -294,7 +339,8 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=()) -> dict:
     """``batches``: optional iterable of collated batch dicts (util/data_utils.py:165-172 contract); ``explicit``: names of
     the flags given on the command line (parse_args records them)."""
     from . import ddp, engine as E, synthetic as S
-    check_supported(cfg, explicit or getattr(cfg, "_explicit", ()))
+    explicit = explicit or getattr(cfg, "_explicit", ())
+    check_supported(cfg, explicit, frame_batches=batches is not None)
     rank, local, world = ddp.init_process_group_from_env()
     torch.cuda.set_device(local)
     dev = f"cuda:{local}"
@@ -350,7 +396,7 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=()) -> dict:
     (trainer or eng).set_grad_accumulation(cfg.grad_accumulation_steps)
     if cfg.objective != "l1":
         trainer.set_objective(cfg.objective)
-    stream = batch_stream(cfg, mcfg, dev, rank, batches)
+    stream = batch_stream(cfg, mcfg, dev, rank, batches, explicit)
     pad_id = min(S.PAD_ID, mcfg.llm.vocab - 1)
     cur = next(stream)
     L = cfg.max_seq_len or cur["input_ids"].shape[1]

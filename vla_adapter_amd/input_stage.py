@@ -19,7 +19,8 @@ the same 8 filler tokens.
 from __future__ import annotations
 
 import random
-from typing import Dict, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -30,6 +31,59 @@ from .constants import IGNORE_INDEX, NUM_TOKENS
 # timm data configs of the two backbones (pretrained_models/configs/preprocessor_config.json: means / stds)
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)        # DINOv2 (featurizer, channels 0-2)
 SIGLIP_MEAN, SIGLIP_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)                          # SigLIP (fused_featurizer, channels 3-5)
+
+
+def backbone_norms(mcfg) -> Tuple[str, ...]:
+    """Which Normalize each vision backbone of a model config gets (the ``backbones`` argument of GPUInputStage): a DINOv2-like
+    ViT - register / cls prefix tokens or LayerScale - takes ImageNet's mean / std, anything else SigLIP's 0.5 / 0.5 (the timm
+    data configs of the reference's two featurizers, preprocessor_config.json)."""
+    return tuple("dino" if (v.layerscale or v.n_prefix > 0) else "siglip" for v in mcfg.vit)
+
+
+AUG_ORDER = ("random_resized_crop", "random_brightness", "random_contrast", "random_saturation", "random_hue")
+
+
+@dataclass
+class ImageAugment:
+    """The reference's training augmentation (prismatic/vla/datasets/datasets.py:204-218 -> dlimp augment_image): defaults are its
+    settings - random_resized_crop(scale=[0.9, 0.9], ratio=[1, 1]), random_brightness(0.2), random_contrast(0.8, 1.2),
+    random_saturation(0.8, 1.2), random_hue(0.05) - applied in that order; ``ops`` names the ones that run (a disabled op is
+    skipped).  Per image one uniform u is drawn on the device from (seed, rank, step, sample, image) and mapped to all five
+    parameters.  ``params``: f32 [B * n_img, 9] supplied instead of drawn (columns: ops.AUG_P_*)."""
+    crop_scale: float = 0.9
+    brightness: float = 0.2
+    contrast: Tuple[float, float] = (0.8, 1.2)
+    saturation: Tuple[float, float] = (0.8, 1.2)
+    hue: float = 0.05
+    ops: Tuple[str, ...] = AUG_ORDER
+    seed: int = 0
+    rank: int = 0
+    step: int = 0
+    params: Optional[torch.Tensor] = None
+
+    def mask(self) -> int:
+        bad = [o for o in self.ops if o not in AUG_ORDER]
+        if bad:
+            raise ValueError(f"unknown augmentation ops {bad}: known {AUG_ORDER}")
+        bits = (ops.AUG_CROP, ops.AUG_BRIGHTNESS, ops.AUG_CONTRAST, ops.AUG_SATURATION, ops.AUG_HUE)
+        m = sum(b for o, b in zip(AUG_ORDER, bits) if o in self.ops)
+        return m | (0 if self.params is not None else ops.AUG_DRAW)
+
+    def cfg7(self):
+        """Settings of the draw mapping, f32: crop side = sqrt(area scale) (tf.sqrt of the f32 scale), then the ranges."""
+        side = np.sqrt(np.float32(self.crop_scale))
+        return [float(side), self.brightness, *self.contrast, *self.saturation, self.hue]
+
+
+def center_crop_params(n: int, crop_scale: float = 0.9) -> torch.Tensor:
+    """Per-image parameters of the evaluator's center crop (experiments/robot/openvla_utils.py:568-648): the centred box of area
+    ``crop_scale``, in f32 as TF computes it - side = clip(sqrt(scale), 0, 1), offset = (1 - side) / 2."""
+    side = np.clip(np.sqrt(np.float32(crop_scale)), np.float32(0), np.float32(1))
+    off = (np.float32(1) - side) / np.float32(2)
+    p = np.zeros((n, ops.AUG_NPARAM), np.float32)
+    p[:, ops.AUG_P_Y1] = p[:, ops.AUG_P_X1] = off
+    p[:, ops.AUG_P_Y2] = p[:, ops.AUG_P_X2] = off + side
+    return torch.from_numpy(p)
 
 
 def _bicubic(x: float) -> float:
@@ -113,24 +167,53 @@ class GPUInputStage:
         """[..., action_dim] f32 on the device -> int64 token ids (same shape)."""
         return ops.action_tokenize(actions.to(self.device, torch.float32).contiguous(), self.bins, self.tokenizer_len, self.lo, self.hi)
 
-    def pixels(self, frames_u8: Sequence[torch.Tensor]) -> torch.Tensor:
-        """frames_u8: list over images per sample (primary first, then wrist ...) of uint8 [B, H, W, 3] tensors ->
-        [B, 3 * n_backbones * n_images, H, W]: per image, one 3-channel block per backbone (apply_transform's vstack)."""
+    def pixels(self, frames_u8, augment: Optional[ImageAugment] = None, center_crop: bool = False, return_aux: bool = False):
+        """frames_u8: list over images per sample (primary first, then wrist ...) of uint8 [B, H, W, 3] tensors, or one uint8
+        [B, n_img, H, W, 3] tensor -> [B, 3 * n_backbones * n_images, H, W]: per image, one 3-channel block per backbone
+        (apply_transform's vstack).  ``augment``: the reference's training augmentation first (ImageAugment); ``center_crop``: the
+        evaluator's center_crop_image first (crop_scale 0.9).  Both run as one fused HIP pass that ends in the same normalise.
+        ``return_aux``: also return dict(frames_u8=uint8 [B, n_img, H, W, 3] as normalised, params=f32 [B, n_img, 9] applied or None)."""
+        if augment is not None and center_crop:
+            raise ValueError("augment and center_crop are the training and the serving path: pass one of them")
+        if isinstance(frames_u8, torch.Tensor) and frames_u8.dim() == 5:
+            stacked = frames_u8
+            frames_u8 = list(frames_u8.unbind(1))
+        else:
+            stacked = None
         if tuple(frames_u8[0].shape[1:3]) != (self.image_size, self.image_size):       # apply_transform: resize first
             frames_u8 = [self.resize(f, self.image_size, self.image_size) for f in frames_u8]
+            stacked = None
         B, H, W, _ = frames_u8[0].shape
         nb = len(self.norm)
         out = torch.empty(B, 3 * nb * len(frames_u8), H, W, device=self.device, dtype=self.out_dtype)
-        for im, fr in enumerate(frames_u8):
-            fr = fr.to(self.device).contiguous()
-            for j, (mean, std) in enumerate(self.norm):
-                ops.image_normalize_u8_(fr, out, 3 * (im * nb + j), mean, std)
-        return out
+        if augment is None and not center_crop:
+            for im, fr in enumerate(frames_u8):
+                fr = fr.to(self.device).contiguous()
+                for j, (mean, std) in enumerate(self.norm):
+                    ops.image_normalize_u8_(fr, out, 3 * (im * nb + j), mean, std)
+            if not return_aux:
+                return out
+            return out, dict(frames_u8=torch.stack([f.to(self.device) for f in frames_u8], 1), params=None)
+        fr = (stacked if stacked is not None else torch.stack(frames_u8, 1)).to(self.device).contiguous()
+        n_img = fr.shape[1]
+        if center_crop:
+            augment = ImageAugment(ops=("random_resized_crop",), params=center_crop_params(B * n_img))
+        params = augment.params
+        params = (torch.empty(B * n_img, ops.AUG_NPARAM, device=self.device, dtype=torch.float32) if params is None
+                  else params.to(self.device, torch.float32).reshape(B * n_img, ops.AUG_NPARAM).contiguous())
+        fr_out = torch.empty_like(fr) if return_aux else None
+        ops.image_augment_normalize_(fr, out, self.norm, augment.mask(), augment.cfg7(), params, seed=augment.seed, rank=augment.rank,
+                                     step=augment.step, frames_out=fr_out)
+        if not return_aux:
+            return out
+        return out, dict(frames_u8=fr_out, params=params.view(B, n_img, ops.AUG_NPARAM))
 
     def build(self, frames_u8: Sequence[torch.Tensor], prompt_ids: List[List[int]], actions: torch.Tensor,
-              proprio: Optional[torch.Tensor] = None, rng: Optional[random.Random] = None) -> Dict[str, torch.Tensor]:
+              proprio: Optional[torch.Tensor] = None, rng: Optional[random.Random] = None, augment: Optional[ImageAugment] = None,
+              center_crop: bool = False) -> Dict[str, torch.Tensor]:
         """prompt_ids: tokenizer output of the chat prompt per sample (still carrying the three trailing ids the reference
-        deletes); actions [B, chunk, action_dim] normalised continuous actions (window: current + future)."""
+        deletes); actions [B, chunk, action_dim] normalised continuous actions (window: current + future); augment /
+        center_crop: see pixels()."""
         rng = rng or random
         B = actions.shape[0]
         tok = self.tokenize_actions(actions.reshape(B, -1)).cpu().tolist()           # 56 ids per sample (8 x 7)
@@ -157,7 +240,7 @@ class GPUInputStage:
             ids_t[b, :n] = torch.tensor(rows[b][:n])
             lab_t[b, :n] = torch.tensor(labels[b][:n])
         ids_t, lab_t = ids_t.to(self.device), lab_t.to(self.device)
-        batch = dict(pixel_values=self.pixels(frames_u8), input_ids=ids_t, labels=lab_t, attention_mask=ids_t.ne(self.pad),
+        batch = dict(pixel_values=self.pixels(frames_u8, augment=augment, center_crop=center_crop), input_ids=ids_t, labels=lab_t, attention_mask=ids_t.ne(self.pad),
                      actions=actions.to(self.device))
         if proprio is not None:
             batch["proprio"] = proprio.to(self.device, torch.float32).reshape(B, -1)

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = (os.environ.get("VLA_NATIVE_LIB") or None) or os.path.join(_HERE, "libvla_native.so")   # override: same-box A/B of two builds
 
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_TANH, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 6          # include/vla_native.h: VLA_ABI_VERSION
+ABI_VERSION = 7          # include/vla_native.h: VLA_ABI_VERSION
 
 
 class NativeLibraryMissing(ImportError):
@@ -113,6 +113,10 @@ _PROTOS = {
     "vla_rmsnorm_dw": ([_P, _P, _P, _P, _P, _I, _I], _I),
     "vla_embed_grad": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
     "vla_resample_u8": ([_P, _P, _P, _L, _I, _I, _I, _P, _P, _I], _I),
+    "vla_augment_slab_floats": ([_I, _I, _I], _L),
+    "vla_augment_stats": ([_P, _P, _P, _P, _I, _I, _I, _I, C.c_uint, C.POINTER(C.c_float), C.c_ulonglong, _L, _L], _I),
+    "vla_augment_apply": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, C.c_uint,
+                           C.POINTER(C.c_float), C.c_ulonglong, _L, _L], _I),
     "vla_token_ce": ([_P, _P, _L, _P, _I, _I, _P], _I),
     "vla_token_ce_bwd": ([_P, _P, _L, _P, _I, _I, _P, _F, _P, _L], _I),
     "vla_copy2d": ([_P, _P, _P, _L, _I, _L, _L, _I, _I, _I, _I, _L], _I),

@@ -755,6 +755,39 @@ def image_normalize_u8_(img_u8: torch.Tensor, out: torch.Tensor, c0: int, mean, 
     return out
 
 
+# op mask bits and parameter columns of vla_augment_stats / vla_augment_apply (include/vla_native.h)
+AUG_CROP, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE, AUG_DRAW = 1, 2, 4, 8, 16, 32
+AUG_NPARAM = 9
+AUG_P_U, AUG_P_Y1, AUG_P_X1, AUG_P_Y2, AUG_P_X2, AUG_P_BRIGHT, AUG_P_CONTRAST, AUG_P_SAT, AUG_P_HUE = range(9)
+
+
+def image_augment_normalize_(frames_u8: torch.Tensor, out: torch.Tensor, norms, ops_mask: int, cfg7, params: torch.Tensor,
+                             seed: int = 0, rank: int = 0, step: int = 0, frames_out: Optional[torch.Tensor] = None):
+    """frames_u8 [B, n_img, H, W, 3] uint8 -> crop / brightness / contrast / saturation / hue (the enabled bits of ``ops_mask``),
+    uint8 quantisation, then out[:, 3 * (im * len(norms) + j) + c] = ((q / 255) - mean_j[c]) / std_j[c] for every backbone
+    (mean_j, std_j) of ``norms``.  params f32 [B * n_img, AUG_NPARAM]: read, or drawn in the kernel from (seed, rank, step, sample,
+    image) and written when AUG_DRAW is set.  cfg7: the draw mapping's settings (crop side, brightness, contrast lo / hi,
+    saturation lo / hi, hue).  frames_out: optional uint8 [B, n_img, H, W, 3] copy of the augmented frames."""
+    assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous() and frames_u8.dim() == 5 and frames_u8.shape[-1] == 3
+    B, n_img, H, W, _ = frames_u8.shape
+    nb = len(norms)
+    assert out.is_contiguous() and tuple(out.shape) == (B, 3 * nb * n_img, H, W) and out.dtype in (BF16, torch.float32)
+    assert params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == (B * n_img, AUG_NPARAM)
+    assert frames_out is None or (frames_out.dtype == torch.uint8 and frames_out.is_contiguous() and frames_out.shape == frames_u8.shape)
+    mean = (C.c_float * (3 * nb))(*[float(x) for mu, _ in norms for x in mu])
+    std = (C.c_float * (3 * nb))(*[float(x) for _, sd in norms for x in sd])
+    cfg = (C.c_float * 7)(*[float(x) for x in cfg7])
+    n = B * n_img
+    slab = None
+    if ops_mask & AUG_CONTRAST:        # the statistics pass: per-chunk channel sums of the post-brightness image
+        slab = torch.empty(_lib().vla_augment_slab_floats(n, H, W), device=frames_u8.device, dtype=torch.float32)
+        N.check(_lib().vla_augment_stats(_st(), _p(frames_u8), _p(params), _p(slab), n, H, W, n_img, ops_mask, cfg, seed, rank, step),
+                "augment_stats")
+    N.check(_lib().vla_augment_apply(_st(), _p(frames_u8), _p(params), _p(slab), _p(out), _p(frames_out), n, H, W, n_img, nb, mean, std,
+                                     int(out.dtype == torch.float32), ops_mask, cfg, seed, rank, step), "augment_apply")
+    return out
+
+
 def action_tokenize(actions_f32: torch.Tensor, bins_f64: torch.Tensor, tokenizer_len: int, lo: float = -1.0, hi: float = 1.0):
     """ActionTokenizer (use_minivlm): int64 ids of the same shape = tokenizer_len - np.digitize(np.clip(a, lo, hi), bins)."""
     assert actions_f32.dtype == torch.float32 and actions_f32.is_contiguous() and bins_f64.dtype == torch.float64 and bins_f64.is_contiguous()
