@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import math
 import os
+import time
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -1033,7 +1034,9 @@ class VLAEngine:
         torch.cuda.current_stream().wait_event(ev[("end", 0)])
         return self._pred_out
 
-    def _predict_segments(self, batch):
+    def _predict_segments(self, batch, noise: Optional[torch.Tensor] = None, loss_of: Optional[torch.Tensor] = None):
+        """Forward-only segments (predict()).  noise: the head's input perturbation (phase "Training"); loss_of: actions whose L1
+        loss against the prediction ends the last head segment (-> self._val_loss3: the validation pass)."""
         cfg, llm, head = self.cfg, self.llm, self.head
         n, nb = cfg.llm.n_layers, cfg.num_blocks
         self._vision_begin(batch)                                 # host-side bookkeeping only
@@ -1055,11 +1058,13 @@ class VLAEngine:
         def h_fwd(c, lo, hi, last):
             def fn():
                 if c == 0:
-                    head.fwd_begin(llm.HS, self.pos1, batch["proprio"], self.Np, None)
+                    head.fwd_begin(llm.HS, self.pos1, batch["proprio"], self.Np, noise)
                 for i in range(lo, min(hi, nb)):
                     head.fwd_layer(i)
                 if last:
                     self._pred_out = head.fwd_end()
+                    if loss_of is not None:
+                        self._val_loss3 = ops.l1_loss(self._pred_out, self._to_bf16(loss_of), want_grad=False)[0]
             return fn
 
         for c, (lo, hi) in enumerate(ch):
@@ -1571,3 +1576,47 @@ class VLAEngine:
         if join:
             cur.wait_event(side_done)
         self.head.dirty = True
+
+    # ---- validation pass (vla-scripts/finetune.py:605-685: eval mode, no_grad, run_forward_pass per held-out batch) ----------
+    # A sweep runs between two training steps at the TRAINING batch shape, so it shares the step's activation buffers - none of
+    # which carries state from one step to the next - and its vision buffers (feats / patches).  What does carry over in the
+    # captured step: the pending parameter update (applied by begin_validation) and the vision stage of the NEXT training batch,
+    # in flight on the vision stream.  The sweep waits for that stage, overwrites its patches, and end_validation() runs it
+    # again on the pixels still staged in _next_px (the same graph on the same input: the same bits).
+    def begin_validation(self):
+        """Before a sweep: apply the pending update, order the sweep behind the in-flight vision stage, refresh the head's
+        forward operands (the captured validation graphs do not carry that refresh)."""
+        self.flush()
+        if getattr(self, "_vis_ev", None) is not None:
+            torch.cuda.current_stream().wait_event(self._vis_ev)
+        self.head.refresh_forward_operands()
+
+    def end_validation(self):
+        """After a sweep: recompute the next training batch's patches (captured step only)."""
+        if getattr(self, "_g_vis", None) is not None:
+            self._launch_vision()
+
+    def val_forward(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Eager validation of one batch: forward() + the L1 loss without gradient -> f32 [3] (loss, current, next actions)."""
+        pred = self.forward(batch, noise)
+        return ops.l1_loss(pred, self._to_bf16(batch["actions"]), want_grad=False)[0]
+
+    def val_step_graphed(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Captured validation of the static ``batch`` / ``noise`` buffers (copy each batch INTO them first): the forward-only
+        segments of predict() ending in the L1 loss, captured on the first call.  No ops.latency_hint(): its GEMM variant
+        changes the fp32 association, and the values must be the eager forward's."""
+        self._ensure_streams()
+        if getattr(self, "_val_graphs", None) is None:
+            for _ in range(2):                       # allocate buffers / set kernel attributes outside the capture
+                self.val_forward(batch, noise)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            segs = self._predict_segments(batch, noise, loss_of=batch["actions"])
+            self._val_graphs = (self._capture_segments(segs, {}), segs)
+            torch.cuda.synchronize()
+            self.val_capture_seconds = time.perf_counter() - t0
+        graphs, segs = self._val_graphs
+        self.head.refresh_forward_operands()
+        ev = self._run_segments(segs, graphs)
+        torch.cuda.current_stream().wait_event(ev[("end", 0)])
+        return self._val_loss3

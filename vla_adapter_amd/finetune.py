@@ -7,7 +7,9 @@ purpose: HF-hub / network loaders (:752-754), the RLDS/TensorFlow input pipeline
 batches come from an iterable / ``--batch_file`` (a .pt dict or a directory of them: the collator's contract), from
 ``--frame_batch_file`` (the same with raw uint8 frames, augmented on the device under ``--image_aug``) or
 ``synthetic.make_batch``; weights are random-init unless ``--vlm_path`` / ``--resum_vla_path`` point at local state-dict
-files.  Every reference flag is either honoured or refused with an error (``check_supported``); none is silently dropped.
+files.  ``--use_val_set`` runs the reference's validation pass (finetune.py:605-685, 1101-1117) on held-out batches of the same
+form (``--val_batch_file`` / ``finetune(val_batches=...)``; ``ValidationPass``); the RLDS val split itself is not read.  Every
+reference flag is either honoured or refused with an error (``check_supported``); none is silently dropped.
 """
 from __future__ import annotations
 
@@ -79,6 +81,8 @@ class FinetuneConfig:
     tiny: bool = False                    # prismatic-tiny plumbing config (BASELINE configs[0])
     seed: int = 0
     batch_file: Optional[str] = None      # torch-saved dict with the collator's keys
+    val_batch_file: Optional[str] = None  # --use_val_set: held-out batches (a .pt dict or a directory of them; pixel_values or frames_u8, never
+                                          # augmented), one pass per validation sweep
     frame_batch_file: Optional[str] = None  # same, with raw frames: frames_u8 uint8 [B, n_img, H, W, 3] instead of pixel_values (the
                                           # input stage normalises them on the device, augmented under --image_aug)
     use_graph: bool = True                # replay the captured hipGraphs
@@ -120,7 +124,8 @@ def parse_args(argv=None) -> FinetuneConfig:
 # Flags of the reference that only configure subsystems outside the accelerated path (RLDS/TensorFlow input pipeline,
 # W&B, HF hub): the native entry point consumes pre-collated batches, so their DEFAULT values are inert - but a value the
 # user passes explicitly cannot be honoured and is refused instead of ignored.  (--image_aug is honoured where batches carry
-# raw frames, --frame_batch_file: check_supported / batch_stream.)
+# raw frames, --frame_batch_file: check_supported / batch_stream; --val_freq / --val_time_limit under --use_val_set with a
+# validation source: ValidationPass.)
 OUT_OF_PATH_FLAGS = ("data_root_dir", "shuffle_buffer_size", "wandb_entity", "wandb_project", "run_id_note",
                      "config_file_path", "phase1_path", "num_diffusion_steps", "diffusion_sample_freq", "val_freq", "val_time_limit",
                      "use_minivlm")
@@ -137,9 +142,13 @@ IMAGE_AUG_REFUSAL = ("--image_aug: already normalised pixel_values cannot be aug
                      "--frame_batch_file, or in the batches handed to finetune()")
 
 
-def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = False) -> None:
+VAL_FLAGS = ("val_freq", "val_time_limit")
+
+
+def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = False, val_batches: bool = False) -> None:
     """Raise for every reference option this path does not implement (nothing is parsed and silently dropped).
-    ``frame_batches``: finetune() was handed a batch iterable, which may carry raw frames (--image_aug is then checked per batch)."""
+    ``frame_batches``: finetune() was handed a batch iterable, which may carry raw frames (--image_aug is then checked per batch).
+    ``val_batches``: finetune() was handed a validation batch iterable (a validation source besides --val_batch_file)."""
     if cfg.grad_accumulation_steps < 1:
         raise ValueError("grad_accumulation_steps must be >= 1")
     if cfg.use_lora and not 0.0 <= cfg.lora_dropout < 1.0:
@@ -160,8 +169,18 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
             raise ValueError(f"--backbone {cfg.backbone!r}: known geometries are {sorted(NAMED_CONFIGS)}")
     if cfg.use_film or cfg.use_diffusion or not cfg.use_l1_regression:
         raise NotImplementedError("native path = L1-regression action head; --use_film / --use_diffusion are not built")
+    validating = False
     if cfg.use_val_set:
-        raise NotImplementedError("--use_val_set: validation needs the RLDS val split (out of scope, SURVEY section 2 #16)")
+        if not (cfg.val_batch_file or val_batches):
+            raise NotImplementedError("--use_val_set needs held-out batches: pass --val_batch_file (a .pt dict or a directory of them) or "
+                                      "finetune(val_batches=...); the RLDS val split is not read (out of scope, SURVEY section 2 #16)")
+        if cfg.objective != "l1":
+            raise NotImplementedError("--use_val_set with --objective token_ce: the reference validates the L1 action head only")
+        if cfg.val_freq < 1:
+            raise ValueError("--val_freq must be >= 1")
+        validating = True
+    elif cfg.val_batch_file or val_batches:
+        raise ValueError("a validation source (--val_batch_file / val_batches) without --use_val_set True would be ignored: pass both")
     if not cfg.use_proprio:
         # the reference passes proprio_projector=None into predict_action, which calls it (action_heads.py:54): TypeError
         raise TypeError("use_proprio=False: 'NoneType' object is not callable (the reference's predict_action requires the "
@@ -175,7 +194,7 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
     frames = bool(cfg.frame_batch_file) or frame_batches
     if "image_aug" in explicit and not frames:
         raise NotImplementedError(IMAGE_AUG_REFUSAL)
-    bad = [n for n in explicit if n in OUT_OF_PATH_FLAGS]
+    bad = [n for n in explicit if n in OUT_OF_PATH_FLAGS and not (validating and n in VAL_FLAGS)]
     if bad:
         raise NotImplementedError(f"flags {bad} configure parts of the reference outside the accelerated path (input pipeline / "
                                   "logging services / hub loaders): the native entry point takes pre-collated batches "
@@ -214,6 +233,115 @@ def loop_plan(cfg: FinetuneConfig):
         if last:
             return
         batch_idx += 1
+
+
+def validation_due(cfg: FinetuneConfig, item) -> bool:
+    """Does the validation pass run behind this loop_plan item?  The reference: ``log_step > 0 and log_step % val_freq == 0``
+    after the optimizer step and the checkpoint save (finetune.py:1101), on EVERY micro-batch of such a gradient step.  Here
+    once per gradient step, as for the checkpoint: behind the optimizer step that completes it - or behind the last micro-batch
+    of the run, where the reference breaks before that optimizer step (loop_plan)."""
+    _, _, log_step, boundary, _, last = item
+    return bool(cfg.use_val_set) and (boundary or last) and log_step > 0 and log_step % cfg.val_freq == 0
+
+
+def validation_noise(cfg: FinetuneConfig, mcfg, rank: int, log_step: int, j: int) -> torch.Tensor:
+    """The head's N(0, 0.02^2) input perturbation (action_heads.py:64-72) of validation batch j of the sweep at log_step, phase
+    "Training": bf16 [chunk, action_dim * D] on the host, from a generator of its own keyed by (seed, rank, log_step, j) - the
+    training stream's draws do not depend on whether (or how long) validation ran.  (The reference draws both from torch's
+    global generator.)"""
+    key = (((int(cfg.seed) * 1_000_003 + int(rank)) * 1_000_033 + int(log_step)) * 10_007 + int(j)) % (2 ** 63 - 1)
+    g = torch.Generator().manual_seed(key)
+    return (torch.randn(mcfg.chunk, mcfg.action_dim * mcfg.llm.d, generator=g) * 0.02).to(torch.bfloat16)
+
+
+class ValidationPass:
+    """The reference's run_validation (finetune.py:605-685) on held-out batches: eval mode (no LoRA dropout, no image
+    augmentation), no gradient; per batch the three L1 values of run_forward_pass, each averaged over the batches of the sweep
+    as the reference does (sum / count of Python floats).  A sweep is ONE pass over the source from this rank's own offset,
+    ended early behind the first batch at which --val_time_limit seconds have passed; a finite source is not cycled to fill the
+    time limit (the reference's RLDS val iterator repeats for ever: the same batches would count twice).  No collective: every
+    rank validates on its own, as every rank of the reference does."""
+
+    def __init__(self, cfg: FinetuneConfig, mcfg, dev: str, rank: int, model, static: dict, L: int, pad_id: int, use_graph: bool,
+                 val_batches=None):
+        self.cfg, self.mcfg, self.dev, self.rank, self.model, self.L, self.pad_id = cfg, mcfg, dev, rank, model, L, pad_id
+        self.use_graph = use_graph
+        self.shapes = {k: (tuple(v.shape), v.dtype) for k, v in static.items()}   # the captured step's batch: shape contract
+        if val_batches is not None:
+            self.items, self.files = list(val_batches), None
+            if not self.items:
+                raise ValueError("empty validation batch iterable")
+        else:
+            src = cfg.val_batch_file
+            self.files = sorted(str(p) for p in Path(src).glob("*.pt")) if os.path.isdir(src) else [src]
+            if not self.files or not os.path.isfile(self.files[0]):
+                raise FileNotFoundError(f"no .pt validation batch files under {src}")
+            self.items = None
+        self.stage, self.static, self.noise = None, None, None
+        self.training_phase = cfg.phase == "Training"
+
+    def _order(self):
+        n = len(self.items if self.items is not None else self.files)
+        o = self.rank % n
+        for i in list(range(o, n)) + list(range(o)):
+            yield self.items[i] if self.items is not None else torch.load(self.files[i], weights_only=True)
+
+    def prepare(self, b: dict) -> dict:
+        """Host collate of one validation batch: frames -> plain normalised pixels, right-padding to the captured length, the
+        training batch's shapes enforced."""
+        from .input_stage import GPUInputStage, backbone_norms
+        b = {k: v.to(self.dev) for k, v in b.items()}
+        if "frames_u8" in b:
+            fr = b.pop("frames_u8")
+            if fr.dtype != torch.uint8 or fr.dim() != 5 or fr.shape[-1] != 3:
+                raise ValueError(f"frames_u8 must be uint8 [B, n_img, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
+            if self.stage is None:
+                self.stage = GPUInputStage(self.dev, backbones=backbone_norms(self.mcfg), image_size=self.mcfg.vit[0].img)
+            b["pixel_values"] = self.stage.pixels(fr)              # never augmented (rlds/dataset.py:412: train=False)
+        B = self.shapes["input_ids"][0][0]
+        if b["input_ids"].shape[0] != B:
+            raise ValueError(f"validation batch of {b['input_ids'].shape[0]} samples: the validation pass runs at the training batch size "
+                             f"({B}, --batch_size)")
+        b = _pad_to(b, self.L, self.pad_id)
+        out = {}
+        for k, (shape, dt) in self.shapes.items():
+            if k not in b:
+                raise ValueError(f"validation batch without {k!r} (the training batches carry {sorted(self.shapes)})")
+            if tuple(b[k].shape) != shape:
+                raise ValueError(f"validation batch {k!r} of shape {tuple(b[k].shape)}: the training step's is {shape}")
+            out[k] = b[k] if b[k].dtype == dt else b[k].to(dt)
+        return out
+
+    def sweep(self, log_step: int) -> dict:
+        model, t0 = self.model, time.time()
+        model.begin_validation()
+        values = []
+        for j, b in enumerate(self._order()):
+            b = self.prepare(b)
+            noise = None
+            if self.training_phase:
+                nz = validation_noise(self.cfg, self.mcfg, self.rank, log_step, j)
+                if self.noise is None:
+                    self.noise = torch.empty(nz.shape, device=self.dev, dtype=nz.dtype)
+                self.noise.copy_(nz)
+                noise = self.noise
+            if self.use_graph:
+                if self.static is None:
+                    self.static = {k: v.clone() for k, v in b.items()}
+                else:
+                    for k in self.static:
+                        self.static[k].copy_(b[k])
+                loss3 = model.val_step_graphed(self.static, noise)
+            else:
+                loss3 = model.val_forward(b, noise)
+            values.append(loss3.tolist())              # host sync on this batch's completion (the reference's .item())
+            if time.time() - t0 > self.cfg.val_time_limit:
+                break
+        model.end_validation()
+        n = len(values)
+        mean = [sum(v[i] for v in values) / n for i in range(3)]
+        return dict(step=log_step, loss_value=mean[0], loss=mean[0], curr_action_l1_loss=mean[1], next_actions_l1_loss=mean[2],
+                    val_batches_count=n)
 
 
 def save_training_checkpoint(cfg: FinetuneConfig, run_dir: Path, step: int, eng, dataset_statistics: Optional[dict] = None,
@@ -335,12 +463,13 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
             i += 1
 
 
-def finetune(cfg: FinetuneConfig, batches=None, explicit=()) -> dict:
+def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -> dict:
     """``batches``: optional iterable of collated batch dicts (util/data_utils.py:165-172 contract); ``explicit``: names of
-    the flags given on the command line (parse_args records them)."""
+    the flags given on the command line (parse_args records them); ``val_batches``: optional held-out batches of the same form
+    for --use_val_set (iterated once per validation sweep; instead of --val_batch_file)."""
     from . import ddp, engine as E, synthetic as S
     explicit = explicit or getattr(cfg, "_explicit", ())
-    check_supported(cfg, explicit, frame_batches=batches is not None)
+    check_supported(cfg, explicit, frame_batches=batches is not None, val_batches=val_batches is not None)
     rank, local, world = ddp.init_process_group_from_env()
     torch.cuda.set_device(local)
     dev = f"cuda:{local}"
@@ -413,8 +542,13 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=()) -> dict:
             trainer.capture(static, noise if training else None)
         else:
             eng.capture(static, noise if training else None, conservative_rows=cfg.conservative_rows)
-    log, t0, saved_at, steps_done = [], time.time(), None, 0
-    for batch_idx, g, log_step, boundary, save, last in loop_plan(cfg):
+    validator = None
+    if cfg.use_val_set:
+        validator = ValidationPass(cfg, mcfg, dev, rank, trainer or eng, static if static is not None else cur, L, pad_id, use_graph,
+                                   val_batches)
+    log, val_log, t0, saved_at, steps_done = [], [], time.time(), None, 0
+    for item in loop_plan(cfg):
+        batch_idx, g, log_step, boundary, save, last = item
         nxt = _pad_to(next(stream), L, pad_id)                    # one batch of look-ahead: its vision stage runs inside this step
         if training:   # fresh N(0, 0.02^2) perturbation every call (action_heads.py:14-17, 69-72)
             noise.copy_((torch.randn(noise.shape, device=dev, generator=gen) * 0.02).to(torch.bfloat16))
@@ -453,6 +587,10 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=()) -> dict:
             saved_at = log_step
             if world > 1:
                 torch.distributed.barrier()  # finetune.py:544, 575
+        if validator is not None and validation_due(cfg, item):
+            val_log.append(validator.sweep(log_step))
+            if rank == 0:
+                print(json.dumps(val_log[-1]), flush=True)
         cur = nxt
         final_step = log_step
     eng.flush()
@@ -461,4 +599,4 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=()) -> dict:
         save_training_checkpoint(cfg, run_dir, final_step, eng, stats, trainer)
     model = dict(vit=[dict(v.as_oracle(), img=v.img) for v in mcfg.vit], llm=dict(mcfg.llm.as_oracle(), d=mcfg.llm.d, inter=mcfg.llm.inter, vocab=mcfg.llm.vocab),
                  n_img=mcfg.n_img, num_blocks=mcfg.num_blocks, pro=mcfg.pro)
-    return dict(log=log, seconds=time.time() - t0, steps=steps_done, world=world, final_step=final_step, run_dir=str(run_dir), mode=mode, model=model)
+    return dict(log=log, val_log=val_log, seconds=time.time() - t0, steps=steps_done, world=world, final_step=final_step, run_dir=str(run_dir), mode=mode, model=model)

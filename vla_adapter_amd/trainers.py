@@ -28,9 +28,11 @@ biases, the token embedding.  The action head, the proprio projector and the act
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
+import time
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -170,6 +172,7 @@ class BackboneTrainer:
         self.group_tn = not os.environ.get("VLA_NO_GROUPED_TN")          # (A/B knob)
         self._deferred = []
         self._refreshed, self._rgraphs = set(), {}      # derived operands rebuilt behind a range's AdamW in this step; their graphs (captured step)
+        self._evaluating, self._val_graphs = False, None     # validation forward (val_forward / val_step_graphed)
 
     # ---- mode hooks ---------------------------------------------------------------------------------------------
     def _lin(self, key, x, W, bias=None, **kw):
@@ -548,8 +551,9 @@ class BackboneTrainer:
             self._mm = eng._embed(batch)
             self._batch = batch
             llm.fwd_begin(eng.B, eng.S, self._mm, 0)
-            self._begin_backward()                  # (fp32 accumulators / sparse embedding gradient: zero before anything adds to them)
-            self._dHS = eng._dhs(0)                 # zeroed hidden-state gradients: the head's backward scatters into them
+            if not self._evaluating:                # (the validation forward has no backward)
+                self._begin_backward()              # (fp32 accumulators / sparse embedding gradient: zero before anything adds to them)
+                self._dHS = eng._dhs(0)             # zeroed hidden-state gradients: the head's backward scatters into them
         if side:
             add("M", f_pre, None, ("pre", 0))
             add("V", lambda: self._vit_forward(1, batch["pixel_values"]), ("pre", 0), ("vf", 1))
@@ -1025,6 +1029,66 @@ class BackboneTrainer:
                 self._g_r.replay()
         return self._loss3
 
+    # ---- validation pass (vla-scripts/finetune.py:605-685: vla.eval(), torch.no_grad()) --------------------------------------
+    # The forward segments of the step (segs[:_n_forward]) in eval mode, then the L1 loss without gradient: no dropout mask, no
+    # backward, no exchange, no update.  They write the step's activation buffers, which the next training step rewrites before
+    # it reads them; the parameters and their derived operands are final when a training step returns.
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        self._evaluating = True
+        try:
+            yield
+        finally:
+            self._evaluating = False
+
+    def begin_validation(self):
+        self.head.refresh_forward_operands()         # (the captured validation graphs do not carry that refresh)
+
+    def end_validation(self):
+        pass
+
+    def _val_segments(self, batch, noise):
+        segs = self._segments(batch, noise)[:self._n_forward]
+
+        def h_loss():
+            self._val_loss3 = ops.l1_loss(self._pred, self.eng._to_bf16(batch["actions"]), want_grad=False)[0]
+        return segs + [("H", h_loss, None, None, None)]
+
+    def val_forward(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Eager validation of one batch on the current stream -> f32 [3] (loss, current action, next actions)."""
+        with self._eval_mode():
+            self._run_inline(self._val_segments(batch, noise))
+        return self._val_loss3
+
+    def val_step_graphed(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Captured validation of the static ``batch`` / ``noise`` buffers (copy each batch INTO them first): one linear hipGraph
+        per forward segment on the step's streams, captured on the first call into memory pools of their own."""
+        if self._val_graphs is None:
+            for _ in range(2):                       # allocate buffers / set kernel attributes outside the capture
+                self.val_forward(batch, noise)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with self._eval_mode():
+                segs = self._val_segments(batch, noise)
+                pools = {k: torch.cuda.graph_pool_handle() for k in "MHGV"}
+                caps = {k: torch.cuda.Stream() for k in "MHGV"}
+                graphs = []
+                for st, fn, _, _, _ in segs:
+                    if fn is None:
+                        graphs.append(None)
+                        continue
+                    kind = st if self._stream(st, None) is not None else "M"
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, pool=pools[kind], stream=caps[kind], capture_error_mode="thread_local"):
+                        fn()
+                    graphs.append(g)
+            torch.cuda.synchronize()
+            self.val_capture_seconds = time.perf_counter() - t0
+            self._val_graphs = (graphs, segs)
+        graphs, segs = self._val_graphs
+        self._run(segs, graphs, exchange=False)
+        return self._val_loss3
+
     def _after_update(self, refresh: bool):
         if self.eng.reducer is not None:
             self.eng.reducer._pending = False        # every collective was joined range by range (_update_ranges)
@@ -1405,6 +1469,18 @@ class LoRAFinetune(BackboneTrainer):
     def _begin_forward(self):
         if self.dropout > 0:
             ops.inc_i32_(self._drop_step)
+
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        """peft's eval mode: lora_dropout is the identity (and the mask counter does not move); the fp8 norm -> quantise
+        hand-over of the training step is left as it was."""
+        p, xq = self.dropout, self._xq
+        self.dropout = 0.0
+        try:
+            with super()._eval_mode():
+                yield
+        finally:
+            self.dropout, self._xq = p, xq
 
     def drop_seed(self, key: str, j: int) -> int:
         """Mask key of pair j of the wrapped Linear `key` (with the step counter: vla_dropout_bf16's (seed, step))."""
