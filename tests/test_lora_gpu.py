@@ -56,6 +56,8 @@ def _cfg(which):
         return E.tiny_config()
     if which == "tiny_fused":          # DINOv2-like (prefix tokens, LayerScale) + SigLIP-like, two images: the reference's default recipe
         return E.tiny_fused_config()
+    if which == "twin":                # two backbones of identical geometry (equal token counts and widths, multiples of 128)
+        return E.tiny_twin_config()
     if which == "padded_mlp":          # ViT MLP width that is not a multiple of 128 (SigLIP so400m: 4304 -> 4352)
         c = E.tiny_config()
         c.vit = [E.ViTCfg(192, 3, 3, 760, 14, 56, 0, False)]
@@ -63,12 +65,19 @@ def _cfg(which):
     return E.qwen15b_geometry_config(2)   # "qwen15b": head dim 128 (unfused RoPE), d 1536, MLP 8960 - BASELINE configs[4]'s layer
 
 
-@pytest.mark.parametrize("which", ["tiny", "tiny_fused", "padded_mlp", "qwen15b"])
+# (bf16 only: this budget measures the native step against an oracle whose every rounding it emulates; with the e4m3 base
+#  products a code that flips between the bf16 and the fp32 input dominates both distances - the fp8 path is pinned against the
+#  oracle's FP8 registry per layer in tests/test_config5_gpu.py, and on the twin geometry against the serial step bit for bit in
+#  tests/test_schedules_gpu.py)
+@pytest.mark.parametrize("which", ["tiny", "tiny_fused", "twin", "padded_mlp", "qwen15b"])
 def test_lora_forward_and_gradients_match_oracle_autograd(which):
     from vla_adapter_amd import engine as E, synthetic as S, ops
     from vla_adapter_amd.lora_finetune import LoRAFinetune
     cfg = _cfg(which)
     W = S.make_weights(cfg, DEV, seed=3, std=0.03 if which == "qwen15b" else 0.05)
+    if which == "twin":                # same geometry, different weights: the backbones draw from one generator in turn
+        assert cfg.vit[0].d == cfg.vit[1].d and cfg.vit[0].n_prefix == cfg.vit[1].n_prefix and cfg.vit[0].mlp == cfg.vit[1].mlp
+        assert not torch.equal(W["vit"][0]["blocks.0.attn.qkv.weight"], W["vit"][1]["blocks.0.attn.qkv.weight"])
     batch = S.make_batch(cfg, 3, DEV, seed=4, P=20, ragged=True)
     eng = E.VLAEngine(cfg, W, DEV)
     lo = LoRAFinetune(eng, rank=8, seed=1)
@@ -115,7 +124,7 @@ def test_lora_forward_and_gradients_match_oracle_autograd(which):
     gmax = max(t[3].norm().item() for t in famA + famB)
     budget_family(famA, "LoRA A gradients (ViT / projector / LLM)", absfloor=1e-3 * gmax)
     budget_family(famB, "LoRA B gradients (ViT / projector / LLM)", absfloor=1e-3 * gmax)
-    if which in ("tiny", "tiny_fused"):      # end-to-end smoke through the whole adapted stack (the single-layer checks of
+    if which in ("tiny", "tiny_fused", "twin"):      # end-to-end smoke through the whole adapted stack (the single-layer checks of
         # tests/test_layer_gradients_gpu.py are the backward's gate; the padded / 1.5B variants are here for their layouts)
         budget(eng.head.P.g("action_queries"), res[True][1]["action_queries"].grad, res[False][1]["action_queries"].grad, "LoRA: action_queries", factor=1.5)
 

@@ -20,6 +20,8 @@ Layout decisions (MI355X-first, 288 GB HBM):
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import math
 import os
 import time
@@ -37,6 +39,22 @@ IGNORE_INDEX = -100
 
 def rup(n: int, m: int) -> int:
     return (n + m - 1) // m * m
+
+
+@contextlib.contextmanager
+def graph_capture(g, **kw):
+    """``torch.cuda.graph(g, **kw)`` with Python's cyclic garbage collector paused for the capture.  A dead reference cycle (an
+    earlier engine / trainer with its graphs, events and memory pools) collected in the middle of a capture runs destructors
+    (hipEventDestroy, hipGraphExecDestroy, frees of a graph pool) that this thread may not call while it captures: the runtime
+    refuses, the destructor cannot raise, and the process aborts.  Paused, such cycles are collected after the capture."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, **kw):
+            yield
+    finally:
+        if was:
+            gc.enable()
 
 
 # ------------------------------------------------------------------------------------------------ configs
@@ -141,6 +159,15 @@ def tiny_fused_config() -> VLACfg:
                   llm=LLMCfg(256, 2, 4, 2, 64, 512, 1e-6, 1e6, 1024), num_blocks=2)
 
 
+def tiny_twin_config() -> VLACfg:
+    """Plumbing-size fused vision with two backbones of IDENTICAL geometry (d 128, 2 blocks, 2 heads, MLP 512, cls + 4 register
+    tokens: equal token counts and widths, as DINOv2-L + CLIP-L), the first with LayerScale; two images per sample.  Every ViT
+    contraction length is a multiple of 128, so LoRAFinetune(fp8=True) runs their base products on e4m3 operands.  The two
+    backbones' per-shape scratch coincides: the configuration that exposes sharing between the trainer's stream kinds."""
+    return VLACfg(vit=[ViTCfg(128, 2, 2, 512, 14, 56, 5, True), ViTCfg(128, 2, 2, 512, 14, 56, 5, False)], n_img=2,
+                  llm=LLMCfg(256, 2, 4, 2, 64, 512, 1e-6, 1e6, 1024), num_blocks=2)
+
+
 def dinosiglip_05b_config(n_img: int = 2) -> VLACfg:
     """The reference's documented recipe (README.md:254-274: ``--vlm_path .../prism-qwen25-extra-dinosiglip-224px-0_5b
     --num_images_in_input 2``): DINOv2-L/14 reg4 + SigLIP-so400m fused vision, 3-layer projector, Qwen2.5-0.5B."""
@@ -155,7 +182,7 @@ def _config5_two_images() -> VLACfg:
 
 # names accepted by ``finetune.py --backbone`` / ``bench.py --backbone`` (n_img follows --num_images_in_input where given)
 NAMED_CONFIGS = {"config2": config2, "dinosiglip-0_5b": dinosiglip_05b_config, "config5": config5_backbone, "tiny": tiny_config,
-                 "tiny_fused": tiny_fused_config, "qwen15b-geometry": qwen15b_geometry_config}
+                 "tiny_fused": tiny_fused_config, "tiny_twin": tiny_twin_config, "qwen15b-geometry": qwen15b_geometry_config}
 
 
 # ------------------------------------------------------------------------------------------------ frozen ViT
@@ -1412,7 +1439,7 @@ class VLAEngine:
                 graphs.append(None)
                 continue
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pools.setdefault(st, torch.cuda.graph_pool_handle()),
+            with graph_capture(g, pool=pools.setdefault(st, torch.cuda.graph_pool_handle()),
                                   stream=self._cap_main if st == "M" else self._stream_of(st, None), capture_error_mode="thread_local"):
                 fn()
             graphs.append(g)
@@ -1458,7 +1485,7 @@ class VLAEngine:
         self._px_stage = batch["pixel_values"].clone()
         self._g_vis = torch.cuda.CUDAGraph()
         # thread_local: other host threads (the RCCL watchdog of a multi-rank job) may touch the HIP runtime meanwhile
-        with torch.cuda.graph(self._g_vis, pool=pools["V"], stream=self.vis_stream, capture_error_mode="thread_local"):
+        with graph_capture(self._g_vis, pool=pools["V"], stream=self.vis_stream, capture_error_mode="thread_local"):
             self._vision(dict(batch, pixel_values=self._px_stage))
         self._vis_ev = None
         self._segs = self._segments(batch, noise)

@@ -173,6 +173,10 @@ class BackboneTrainer:
         self._deferred = []
         self._refreshed, self._rgraphs = set(), {}      # derived operands rebuilt behind a range's AdamW in this step; their graphs (captured step)
         self._evaluating, self._val_graphs = False, None     # validation forward (val_forward / val_step_graphed)
+        # stream kind ("M" | "H" | "G" | "V") of the segment whose Python call is running: per-shape scratch of the mode (LoRA's fp8
+        # row-quantised activations, lora_dropout's u / h) is kept per kind, because two kinds run at the same time on different
+        # streams (eagerly: the segment's stream; captured: the kind's capture stream, whose graphs replay on that same stream)
+        self._lane = "M"
 
     # ---- mode hooks ---------------------------------------------------------------------------------------------
     def _lin(self, key, x, W, bias=None, **kw):
@@ -751,7 +755,7 @@ class BackboneTrainer:
                     t0.record(stream)
                 if fn is not None:
                     if graphs is None:
-                        fn()
+                        self._call(st, fn)
                     elif graphs[k] is not None:
                         graphs[k].replay()
                 if tl is not None and fn is not None:
@@ -770,6 +774,14 @@ class BackboneTrainer:
         for st in (self.hstream, self.gstream, self.vstream):
             if st is not None:
                 main.wait_stream(st)
+
+    def _call(self, st: str, fn):
+        """Run a segment's Python call with its stream kind set (_lane)."""
+        self._lane = st
+        try:
+            fn()
+        finally:
+            self._lane = "M"
 
     def _update_ranges(self, ranges, final_event, update, seg_index=None):
         """AdamW over the ranges a segment has finished, then - round 4 - the derived operands of exactly those parameters (W^T copies of
@@ -982,8 +994,8 @@ class BackboneTrainer:
                 continue
             kind = st if self._stream(st, None) is not None else "M"      # (single-stream mode: everything is an "M" graph)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pools[kind], stream=caps[kind], capture_error_mode="thread_local"):
-                fn()
+            with E.graph_capture(g, pool=pools[kind], stream=caps[kind], capture_error_mode="thread_local"):
+                self._call(st, fn)
             self._graphs.append(g)
         # derived operands: per finished range a small graph behind that range's AdamW (overlapped update only), the rest at the step's end
         self._rgraphs, covered, rpool = {}, set(), torch.cuda.graph_pool_handle()
@@ -996,7 +1008,7 @@ class BackboneTrainer:
                 covered |= self._refreshed - before
                 if fns:
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, pool=rpool, stream=caps["G"], capture_error_mode="thread_local"):     # (a pool of their own: they
+                    with E.graph_capture(g, pool=rpool, stream=caps["G"], capture_error_mode="thread_local"):     # (a pool of their own: they
                         for f_ in fns:                                                                               #  replay between the G graphs)
                             f_()
                     self._rgraphs[k] = g
@@ -1005,7 +1017,7 @@ class BackboneTrainer:
         has_extra = type(self)._refresh_extra is not BackboneTrainer._refresh_extra
         self._g_r = torch.cuda.CUDAGraph() if (not self._rgraphs or rest or has_extra) else None      # (nothing left: LoRA - every pair lies in a range)
         if self._g_r is not None:
-            with torch.cuda.graph(self._g_r, pool=pools["M"], stream=caps["M"], capture_error_mode="thread_local"):
+            with E.graph_capture(self._g_r, pool=pools["M"], stream=caps["M"], capture_error_mode="thread_local"):
                 if self._rgraphs:
                     for f_ in rest:
                         f_()
@@ -1079,8 +1091,8 @@ class BackboneTrainer:
                         continue
                     kind = st if self._stream(st, None) is not None else "M"
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, pool=pools[kind], stream=caps[kind], capture_error_mode="thread_local"):
-                        fn()
+                    with E.graph_capture(g, pool=pools[kind], stream=caps[kind], capture_error_mode="thread_local"):
+                        self._call(st, fn)
                     graphs.append(g)
             torch.cuda.synchronize()
             self.val_capture_seconds = time.perf_counter() - t0
@@ -1432,8 +1444,15 @@ class LoRAFinetune(BackboneTrainer):
         return self.llm.layers[int(rest[0])][{"qkv": "wqkvT", "o": "woT", "gu": "wguT", "down": "wdT"}[rest[1]]]
 
     # ---- fp8: row-quantised activations
+    # Scratch is keyed by the stream kind as well as the shape: with two vision backbones of the same token count and width (DINOv2-L +
+    # CLIP-L, tiny_twin_config) the "V" backbone and the "M" chain quantise / drop rows of the same shape AT THE SAME TIME on two
+    # streams, and a buffer shared between them is a data race (no error, slightly wrong gradients).  Cost: one extra set of per-shape
+    # buffers for the "V" kind (that backbone's rows x width codes + scales; lora_dropout: its u / h products) - M, H and G need none
+    # apart, G and H never call these.  The norm -> quantise hand-over (_xq) needs no key: the host sets it in _ln / _rms and consumes
+    # it in the _lin that follows within the SAME segment call (a norm's output feeds the next Linear of its block), so it never
+    # crosses from one stream's segment to another's; a left-over entry only matches the very tensor it was made for.
     def _qscratch(self, rows: int, cols: int, slot: str):
-        k = (rows, cols, slot)
+        k = (rows, cols, slot, self._lane)
         b = self._qbuf.get(k)
         if b is None:
             b = self._qbuf[k] = (torch.empty(rows, cols, device=self.dev, dtype=torch.uint8), torch.empty(rows, device=self.dev, dtype=torch.float32))
@@ -1546,7 +1565,7 @@ class LoRAFinetune(BackboneTrainer):
         return dx
 
     def _uscratch(self, rows: int, cols: int, slot: str):
-        k = (rows, cols, slot)
+        k = (rows, cols, slot, self._lane)         # (per stream kind: see _qscratch)
         b = self._ubuf.get(k)
         if b is None:
             b = self._ubuf[k] = torch.empty(rows, cols, device=self.dev, dtype=BF16)
