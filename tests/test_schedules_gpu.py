@@ -241,7 +241,7 @@ def test_trainer_scratch_has_one_owner_stream(mode, monkeypatch):
     assert "capture" in uses and len(uses) >= 2, sorted(uses)
     shared = [(ph, w, len(s)) for ph, d in uses.items() for (w, _), s in d.items() if len(s) > 1]
     assert not shared, f"scratch used from two streams within one step (phase, buffer kind, streams): {shared}"
-    assert gc_during_capture and not any(gc_during_capture), "the cyclic GC must be paused while the step is captured (engine.graph_capture)"
+    assert gc_during_capture and not any(gc_during_capture), "the cyclic GC must be paused while the step is captured (schedule.graph_capture)"
 
 
 # ---- the head backward's gate reduction ---------------------------------------------------------------------------------------
@@ -289,7 +289,7 @@ def test_no_schedule_reaches_the_atomic_gate_reduction(monkeypatch):
         D = c().llm.d
         assert D % 8 == 0 and D // 8 in (16, 32, 64, 112, 128, 192), (c.__name__, D)
     assert calls and all(dh in (16, 32, 64, 112, 128, 192) and 1 <= T <= 32 and big for dh, T, big in calls), set(calls)
-    assert gc_during_capture and not any(gc_during_capture), "trainer and engine captures must pause the cyclic GC (engine.graph_capture)"
+    assert gc_during_capture and not any(gc_during_capture), "trainer and engine captures must pause the cyclic GC (schedule.graph_capture)"
     assert not os.environ.get("VLA_HEAD_BWD_COMBINED") and not os.environ.get("VLA_HEAD_ATTN_VALU")
 
 

@@ -1,4 +1,4 @@
-"""Un-profiled timeline of the captured step: HIP timing events around every schedule segment (engine._run_segments)."""
+"""Un-profiled timeline of the captured step: HIP timing events around every schedule segment (schedule.run)."""
 import sys
 
 import torch

@@ -20,8 +20,6 @@ Layout decisions (MI355X-first, 288 GB HBM):
 """
 from __future__ import annotations
 
-import contextlib
-import gc
 import math
 import os
 import time
@@ -30,8 +28,9 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import ops, schedule
 from .ops import ACT_GELU, ACT_GELU_TANH, ACT_NONE, ACT_RELU, ACT_SWIGLU, BF16
+from .schedule import Segment, capture_graph, chunks
 
 NUM_TOKENS = 64          # prismatic/vla/constants.py:15
 IGNORE_INDEX = -100
@@ -39,22 +38,6 @@ IGNORE_INDEX = -100
 
 def rup(n: int, m: int) -> int:
     return (n + m - 1) // m * m
-
-
-@contextlib.contextmanager
-def graph_capture(g, **kw):
-    """``torch.cuda.graph(g, **kw)`` with Python's cyclic garbage collector paused for the capture.  A dead reference cycle (an
-    earlier engine / trainer with its graphs, events and memory pools) collected in the middle of a capture runs destructors
-    (hipEventDestroy, hipGraphExecDestroy, frees of a graph pool) that this thread may not call while it captures: the runtime
-    refuses, the destructor cannot raise, and the process aborts.  Paused, such cycles are collected after the capture."""
-    was = gc.isenabled()
-    gc.disable()
-    try:
-        with torch.cuda.graph(g, **kw):
-            yield
-    finally:
-        if was:
-            gc.enable()
 
 
 # ------------------------------------------------------------------------------------------------ configs
@@ -1050,14 +1033,14 @@ class VLAEngine:
             torch.cuda.synchronize()
             segs = self._predict_segments(static)
             with ops.latency_hint():                 # sub-chip launches on an idle chip: the deep-ring GEMM (bit-identical; baked into the graphs)
-                graphs = self._capture_segments(segs, {})
+                graphs = schedule.capture(segs, {}, self._cap_stream)
             torch.cuda.synchronize()
             cache[key] = (graphs, static, segs)
         graphs, static, segs = cache[key]
         for k, v in batch.items():
             static[k].copy_(v)
         self.head.refresh_forward_operands()     # parameters may have changed since the capture (no-op when fresh)
-        ev = self._run_segments(segs, graphs, getattr(self, "_timeline", None))
+        ev = schedule.run(segs, self._stream_of, graphs, timeline=getattr(self, "_timeline", None))
         torch.cuda.current_stream().wait_event(ev[("end", 0)])
         return self._pred_out
 
@@ -1068,8 +1051,8 @@ class VLAEngine:
         n, nb = cfg.llm.n_layers, cfg.num_blocks
         self._vision_begin(batch)                                 # host-side bookkeeping only
         n_all, n = n, self.n_act                                  # (layers above the head's last block do not reach the actions)
-        segs = [(f"V{j}", (lambda j=j: self._vision_backbone(j, batch)), None, ("v", j)) for j in range(len(self.vits))]
-        ch = self._chunks(n, [6] * max(0, (n - 6) // 6) + [4, 2]) if n >= 12 else self._chunks(n, [1])   # few launches: the caller blocks on every call
+        segs = [Segment(f"V{j}", (lambda j=j: self._vision_backbone(j, batch)), None, ("v", j)) for j in range(len(self.vits))]
+        ch = chunks(n, [6] * max(0, (n - 6) // 6) + [4, 2]) if n >= 12 else chunks(n, [1])   # few launches: the caller blocks on every call
 
         def m_fwd(c, lo, hi):
             def fn():
@@ -1095,8 +1078,8 @@ class VLAEngine:
             return fn
 
         for c, (lo, hi) in enumerate(ch):
-            segs.append(("M", m_fwd(c, lo, hi), [("v", j) for j in range(len(self.vits))] if c == 0 else None, ("f", c)))
-            segs.append(("H", h_fwd(c, lo, hi, c == len(ch) - 1), ("f", c), ("end", 0) if c == len(ch) - 1 else None))
+            segs.append(Segment("M", m_fwd(c, lo, hi), [("v", j) for j in range(len(self.vits))] if c == 0 else None, ("f", c)))
+            segs.append(Segment("H", h_fwd(c, lo, hi, c == len(ch) - 1), ("f", c), ("end", 0) if c == len(ch) - 1 else None))
         return segs
 
     # modeling_prismatic.py:596-655 (multimodal forward): fills llm.HS with the n+1 hidden states
@@ -1281,12 +1264,8 @@ class VLAEngine:
     # of the LLM backward (which needs dHS[i+1] from block i).  The head's kernels fill the idle CUs / tile-quantisation
     # tails of the LLM's large GEMMs instead of serialising with them.
     #
-    # The step is cut into SEGMENTS, each living on exactly one stream ("M": vision/LLM, "H": head); segments are
-    # ordered so that every event is recorded before it is waited on.  Eagerly a segment is a Python call under its
-    # stream; captured, every segment is its own single-stream (linear) hipGraph and the cross-stream edges are plain
-    # hipEvents between graph launches.  (One multi-stream hipGraph of the whole step was measured to serialise the two
-    # backward chains in the runtime's graph executor - rocprofv3 trace, tools/timeline.py: LLM backward started only
-    # after the head backward's last kernel - so the overlap is not left to it.)  Layer chunks are short next to the
+    # The step is cut into SEGMENTS, each living on exactly one stream ("M": vision/LLM, "H": head), which schedule.run
+    # enqueues and schedule.capture turns into one linear hipGraph each.  Layer chunks are short next to the
     # forward->backward turn-around (little pipeline fill/drain) and longer elsewhere (fewer graph launches).
     def _ensure_streams(self):
         if getattr(self, "side", None) is None:
@@ -1294,16 +1273,6 @@ class VLAEngine:
             self._cap_main = torch.cuda.Stream()       # capture stream of the "M" graphs (replayed on the current stream)
             self.vis_stream = torch.cuda.Stream()      # vision stage of the NEXT step (fills the backward's idle CUs)
             self._vstreams = [self.vis_stream] + [torch.cuda.Stream() for _ in range(max(0, len(self.vits) - 1))]   # one per backbone
-
-    @staticmethod
-    def _chunks(n: int, sizes) -> List[Tuple[int, int]]:
-        """[lo, hi) layer ranges covering 0..n with the given chunk sizes (last size repeats / is clipped)."""
-        out, lo, k = [], 0, 0
-        while lo < n:
-            sz = sizes[min(k, len(sizes) - 1)]
-            out.append((lo, min(n, lo + sz)))
-            lo, k = out[-1][1], k + 1
-        return out
 
     def _prep_backward(self, batch):
         """Everything the backward needs that depends only on the batch (runs at the start of the step, off the
@@ -1316,16 +1285,16 @@ class VLAEngine:
         self._actions_bf = self._to_bf16(batch["actions"])
 
     def _segments(self, batch, noise):
-        """[(stream 'M'|'H', fn, wait_key|None, signal_key|None)] for everything after the vision stage."""
+        """[Segment(stream 'M'|'H', fn, wait_key|None, signal_key|None)] for everything after the vision stage."""
         cfg, llm, head = self.cfg, self.llm, self.head
         n_all, nb = cfg.llm.n_layers, cfg.num_blocks
         assert nb <= n_all
         n = self.n_act                                  # layers that reach the loss
         # long chunks at the bottom layers, single layers at the top: the head's last forward chunk and first backward
         # chunk (the serial turn-around) stay short; the backward walks the same ranges top-down
-        fch = self._chunks(n, [4] * max(0, (n - 4) // 4) + [2, 1, 1]) if n >= 8 else self._chunks(n, [1])
+        fch = chunks(n, [4] * max(0, (n - 4) // 4) + [2, 1, 1]) if n >= 8 else chunks(n, [1])
         if os.environ.get("VLA_FWD_CHUNKS"):                  # A/B knob: "4,4,4,4,4,2,1,1"
-            fch = self._chunks(n, [int(x) for x in os.environ["VLA_FWD_CHUNKS"].split(",")])
+            fch = chunks(n, [int(x) for x in os.environ["VLA_FWD_CHUNKS"].split(",")])
         segs = []
 
         def m_begin():
@@ -1381,76 +1350,27 @@ class VLAEngine:
         # one workgroup per CU and 6.5 rounds of gate/up tiles per whole-batch launch, one pipeline measured 25.27-25.34 against
         # 25.61-25.75 ms and the two-pipeline form left the tree in round 4: DESIGN section 5b.)
         for c, (lo, hi) in enumerate(fch):
-            segs.append(("M", m_fwd(c, lo, hi, begin=c == 0), None, ("f", c)))
-            segs.append(("H", h_fwd(c, lo, hi, c == len(fch) - 1), ("f", c), None))
+            segs.append(Segment("M", m_fwd(c, lo, hi, begin=c == 0), None, ("f", c)))
+            segs.append(Segment("H", h_fwd(c, lo, hi, c == len(fch) - 1), ("f", c)))
         for k, (lo, hi) in enumerate(reversed(fch)):
-            segs.append(("H", h_bwd(lo, hi), None, ("b", k)))
-            segs.append(("M", m_bwd(lo, hi, k == 0, k == len(fch) - 1), ("b", k), None))
-        segs.append(("H", head.bwd_end, None, ("end", 0)))      # the caller joins on this event (head gradients final)
+            segs.append(Segment("H", h_bwd(lo, hi), None, ("b", k)))
+            segs.append(Segment("M", m_bwd(lo, hi, k == 0, k == len(fch) - 1), ("b", k)))
+        segs.append(Segment("H", head.bwd_end, None, ("end", 0)))      # the caller joins on this event (head gradients final)
         return segs
 
     def _stream_of(self, name: str, main):
         return main if name == "M" else self.side if name == "H" else self._vstreams[int(name[1:])]
 
-    def _run_segments(self, segs, graphs=None, timeline=None, hooks=None):
-        """Enqueue the segments [(stream 'M'|'H'|'V<j>', fn|None, wait key | [keys] | None, signal key | None)] in order.
-        timeline: optional list that receives (stream, index, start_event, end_event) per segment (timing events).
-        hooks: {segment index: fn(event)} called right after that segment was enqueued, with an event recorded behind it.
-        Returns the dict of recorded events."""
-        main = torch.cuda.current_stream()
-        for name in {sg[0] for sg in segs} - {"M"}:
-            self._stream_of(name, main).wait_stream(main)        # fork (inputs / previous AdamW are ordered before them)
-        ev = {}
-        for k, (st, fn, wait, signal) in enumerate(segs):
-            stream = self._stream_of(st, main)
-            with torch.cuda.stream(stream):
-                for w in ([] if wait is None else wait if isinstance(wait, list) else [wait]):
-                    stream.wait_event(ev[w])
-                if timeline is not None:
-                    t0 = torch.cuda.Event(enable_timing=True)
-                    t0.record(stream)
-                if fn is None:
-                    pass
-                elif graphs is None:
-                    fn()
-                else:
-                    graphs[k].replay()
-                if timeline is not None:
-                    t1 = torch.cuda.Event(enable_timing=True)
-                    t1.record(stream)
-                    timeline.append((st, k, t0, t1))
-                if signal is not None:
-                    ev[signal] = torch.cuda.Event()
-                    ev[signal].record(stream)
-                if hooks is not None and k in hooks:
-                    hev = ev[signal] if signal is not None else torch.cuda.Event()
-                    if signal is None:
-                        hev.record(stream)
-                    hooks[k](hev)
-        return ev
-
-    def _capture_segments(self, segs, pools):
-        """One linear hipGraph per segment, captured on a stream of the segment's kind with that kind's memory pool (graphs
-        sharing a pool replay strictly in capture order on ONE stream, so the allocator's reuse of freed capture-time
-        temporaries stays race-free while the streams overlap)."""
-        graphs = []
-        for st, fn, _, _ in segs:
-            if fn is None:
-                graphs.append(None)
-                continue
-            g = torch.cuda.CUDAGraph()
-            with graph_capture(g, pool=pools.setdefault(st, torch.cuda.graph_pool_handle()),
-                                  stream=self._cap_main if st == "M" else self._stream_of(st, None), capture_error_mode="thread_local"):
-                fn()
-            graphs.append(g)
-        return graphs
+    def _cap_stream(self, name: str):
+        """Capture stream of a segment kind: the "M" graphs replay on the caller's stream and are captured on one of their own."""
+        return self._cap_main if name == "M" else self._stream_of(name, None)
 
     def _fwd_bwd(self, batch, noise, vision: bool = True):
         """Eager run of the two-stream schedule (vision stage first unless the vision graph already ran)."""
         self.executed_steps += 1
         if vision:
             self._vision(batch)
-        torch.cuda.current_stream().wait_event(self._run_segments(self._segments(batch, noise))[("end", 0)])   # join
+        torch.cuda.current_stream().wait_event(schedule.run(self._segments(batch, noise), self._stream_of)[("end", 0)])   # join
         return self._loss3
 
     # Data-parallel schedule of the captured step.  The gradient exchange of step k (one bucketed RCCL all-reduce of the
@@ -1477,28 +1397,24 @@ class VLAEngine:
             self._fwd_bwd(batch, noise)
         torch.cuda.synchronize()
         self.head.dirty = True
-        # one memory pool per stream: graphs sharing a pool are replayed strictly in capture order on ONE stream, so the
-        # allocator's reuse of freed capture-time temporaries stays race-free while the two streams overlap
-        pools = {"V": torch.cuda.graph_pool_handle()}
-        # vision stage: reads the staged pixels of the NEXT batch (stage_next_pixels), writes self.patches
+        # vision stage: reads the staged pixels of the NEXT batch (stage_next_pixels), writes self.patches; a memory pool of its own
         self._next_px = batch["pixel_values"].clone()
         self._px_stage = batch["pixel_values"].clone()
-        self._g_vis = torch.cuda.CUDAGraph()
-        # thread_local: other host threads (the RCCL watchdog of a multi-rank job) may touch the HIP runtime meanwhile
-        with graph_capture(self._g_vis, pool=pools["V"], stream=self.vis_stream, capture_error_mode="thread_local"):
-            self._vision(dict(batch, pixel_values=self._px_stage))
+        self._g_vis = capture_graph(lambda: self._vision(dict(batch, pixel_values=self._px_stage)), torch.cuda.graph_pool_handle(),
+                                    self.vis_stream)
         self._vis_ev = None
         self._segs = self._segments(batch, noise)
-        self._graphs = self._capture_segments(self._segs, pools)
+        self._graphs = schedule.capture(self._segs, {}, self._cap_stream)
         torch.cuda.synchronize()
         self._pending_lr = None
         # the vision stage of step k+1 starts behind this forward segment of step k: it runs under the backward, whose two
         # dependent kernel chains leave most CUs idle.  Default: the third-last forward segment (the last two hold one LLM
         # layer each and are latency-bound with the head trailing them); same-box sweep at B = 32: last 31.52 ms/step,
         # second-last 31.33, third-last 31.14, fourth-last 31.35.  VLA_VIS_AFTER overrides.
-        m_fwd = [k for k, sg in enumerate(self._segs) if sg[0] == "M" and sg[3] is not None and sg[3][0] == "f"]
+        m_fwd = [k for k, sg in enumerate(self._segs) if sg.stream == "M" and sg.signal is not None and sg.signal[0] == "f"]
         # (fourth-last forward segment: 26.51 vs 26.64-26.69 ms for the third-last with the one-pipeline forward, same box)
         self._vis_after = m_fwd[min(len(m_fwd) - 1, max(0, int(os.environ.get("VLA_VIS_AFTER", len(m_fwd) - 4))))]
+        assert self._segs[self._vis_after].signal is not None      # (schedule.run hands after() the event of a signalling segment)
         self._launch_vision()                        # vision stage of the FIRST step (the pixels given to capture)
 
     def stage_next_pixels(self, pixel_values: torch.Tensor):
@@ -1546,8 +1462,11 @@ class VLAEngine:
         self.executed_steps += 1
         self.flush(join=False)
         cur.wait_event(self._vis_ev)           # patches of THIS step (computed during the previous call)
-        self._h_end = self._run_segments(self._segs, self._graphs, getattr(self, "_timeline", None),
-                                         hooks={self._vis_after: lambda ev: self._launch_vision(ev)})[("end", 0)]
+        def after(k, seg, ev):
+            if k == self._vis_after:
+                self._launch_vision(ev)
+        self._h_end = schedule.run(self._segs, self._stream_of, self._graphs, after=after,
+                                   timeline=getattr(self, "_timeline", None))[("end", 0)]
         cur.wait_event(self._px_copied)        # later writes to the staging source are ordered behind the vision copy
         if self.ga > 1:                        # gradient accumulation: join, fold, update only on the boundary micro-step
             cur.wait_event(self._h_end)
@@ -1639,11 +1558,11 @@ class VLAEngine:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             segs = self._predict_segments(batch, noise, loss_of=batch["actions"])
-            self._val_graphs = (self._capture_segments(segs, {}), segs)
+            self._val_graphs = (schedule.capture(segs, {}, self._cap_stream), segs)
             torch.cuda.synchronize()
             self.val_capture_seconds = time.perf_counter() - t0
         graphs, segs = self._val_graphs
         self.head.refresh_forward_operands()
-        ev = self._run_segments(segs, graphs)
+        ev = schedule.run(segs, self._stream_of, graphs)
         torch.cuda.current_stream().wait_event(ev[("end", 0)])
         return self._val_loss3

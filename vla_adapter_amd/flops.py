@@ -73,7 +73,7 @@ def step_flops_per_sample(cfg: VLACfg, L: int = 96, row0: int = 0) -> dict:
 
 
 def source_digest() -> str:
-    """sha256 over the kernel sources and the step schedule (csrc/*.hip, *.h, engine.py, ops.py, trainers.py): stamped into
+    """sha256 over the kernel sources and the step schedule (csrc/*.hip, *.h, engine.py, ops.py, schedule.py, trainers.py): stamped into
     profiles/*_gemm_in_situ.json when a profile is reduced, compared by bench.py - a profile taken from other code is reported
     as stale instead of being quoted as a fresh measurement."""
     import glob
@@ -82,7 +82,7 @@ def source_digest() -> str:
     here = os.path.dirname(os.path.abspath(__file__))
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(here, "csrc", "*.hip")) + glob.glob(os.path.join(here, "csrc", "*.h"))) + \
-        [os.path.join(here, n) for n in ("engine.py", "ops.py", "trainers.py")]
+        [os.path.join(here, n) for n in ("engine.py", "ops.py", "schedule.py", "trainers.py")]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

@@ -38,7 +38,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import engine as E
-from . import ops
+from . import ops, schedule
+from .schedule import Segment, capture_graph, chunks
 from .ops import ACT_GELU, ACT_GELU_TANH, ACT_NONE, ACT_SWIGLU, BF16
 
 rup = E.rup
@@ -522,21 +523,9 @@ class BackboneTrainer:
         # LLM layers per segment: `exchange_layers`, but 2, 1, 1 at the top - the forward -> backward turn-around (last head blocks, loss, first
         # head-backward blocks) is what the LLM backward waits for: with four-layer segments the M stream idled 1.3 ms there (tools/trainer_timeline.py)
         el, na = self.exchange_layers, self.n_active
-        lch = E.VLAEngine._chunks(na, [el] * max(0, (na - 4) // el) + [2, 1, 1]) if na >= 8 and not os.environ.get("VLA_UNIFORM_CHUNKS") else E.VLAEngine._chunks(na, [el])
-        two = self.gstream is not None
+        lch = chunks(na, [el] * max(0, (na - 4) // el) + [2, 1, 1]) if na >= 8 and not os.environ.get("VLA_UNIFORM_CHUNKS") else chunks(na, [el])
         segs = []
-
-        def add(st, fn, wait=None, signal=None, ranges=None):
-            segs.append((st, fn, wait, signal, ranges))
-
-        def grads(after, signal, ranges):
-            """The gradient work the segment signalling `after` has deferred (+ hand-over of the finished ranges)."""
-            if two:
-                add("G", self._flush_work, after, signal, ranges)
-            else:                                   # single stream: nothing was deferred; the ranges are final where the chain stands
-                add("M", None, None, signal, ranges)
-            return signal
-
+        add, grads = self._builders(segs)
         side = self.vstream is not None                 # the second backbone on its own stream (forward and backward)
 
         def f_pre():
@@ -584,21 +573,40 @@ class BackboneTrainer:
             head.bwd_begin(dpred, 0)
         add("H", h_loss, None, None)
         aq_off = head.P.offsets["action_queries"][0]
-        gsig = []
         for k, (lo, hi) in enumerate(reversed(lch)):
             wait = None
             if min(hi, nb) > lo:                    # (layers above the head's last block receive no gradient from it)
                 add("H", lambda lo=lo, hi=hi: [head.bwd_layer(i, self._dHS) for i in range(min(hi, nb) - 1, lo - 1, -1)], None, ("b", k))
                 wait = ("b", k)
             add("M", lambda lo=lo, hi=hi: self._llm_bwd_layers(lo, hi), wait, ("m", k))
-            gsig.append(grads(("m", k), ("g", k), self._ranges("llm", lo, hi - 1)))
+            grads(("m", k), ("g", k), self._ranges("llm", lo, hi - 1))
         add("H", head.bwd_end, None, ("hend", 0), [(head.P.grad, 0, aq_off)])
         add("M", self._mid_backward, None, ("mid", 0))
-        gsig.append(grads(("mid", 0), ("gmid", 0), [(head.P.grad, aq_off, head.P.numel)] + self._ranges("embed") + self._ranges("proj")))
+        grads(("mid", 0), ("gmid", 0), [(head.P.grad, aq_off, head.P.numel)] + self._ranges("embed") + self._ranges("proj"))
+        self._vit_bwd_segments(add, grads, side)
+        if self.trains_vectors:                     # the tail casts the ONE fp32 buffer every piece's bias / norm sums met in
+            add("M", self._end_backward, [sg.signal for sg in segs if sg.stream == "G"], ("end", 0), self._ranges("tail"))
+        return segs
+
+    def _builders(self, segs):
+        """add(kind, fn, wait, signal, ranges) appends a segment to segs; grads(after, signal, ranges) appends the gradient work
+        that the segment signalling `after` has deferred, and the hand-over of the ranges it finished."""
+        def add(st, fn, wait=None, signal=None, ranges=None):
+            segs.append(Segment(st, fn, wait, signal, ranges))
+
+        def grads(after, signal, ranges):
+            if self.gstream is not None:
+                add("G", self._flush_work, after, signal, ranges)
+            else:                                   # single stream: nothing was deferred; the ranges are final where the chain stands
+                add("M", None, None, signal, ranges)
+        return add, grads
+
+    def _vit_bwd_segments(self, add, grads, side: bool):
+        """Backward segments of the vision backbone(s), each followed by its gradient work.  side: the second backbone runs on the
+        "V" stream and the two backbones' segments alternate in the list: both chains start right behind the projector's backward."""
         vsegs = []
-        for j, v in enumerate(self.vits):
-            vch = self._vit_chunks(j)
-            for q, (lo, hi) in enumerate(reversed(vch)):
+        for j in range(len(self.vits)):
+            for q, (lo, hi) in enumerate(reversed(self._vit_chunks(j))):
                 def v_bwd(j=j, lo=lo, hi=hi, first=(q == 0)):
                     if first:
                         self._vit_bwd_begin(j)
@@ -606,16 +614,13 @@ class BackboneTrainer:
                     if lo == 0 and self.trains_vectors:
                         self._vit_bwd_end(j)
                 vsegs.append((j, q, lo, hi, v_bwd))
-        if side:                                    # the two backbones' segments alternate in the list (each followed by its gradient work): both
-            a, b = [x for x in vsegs if x[0] == 0], [x for x in vsegs if x[0] == 1]     # chains start right behind the projector's backward
+        if side:
+            a, b = [x for x in vsegs if x[0] == 0], [x for x in vsegs if x[0] == 1]
             vsegs = [x for pair in zip(a, b) for x in pair] + a[len(b):] + b[len(a):]
         for j, q, lo, hi, v_bwd in vsegs:
             on_side = side and j == 1
             add("V" if on_side else "M", v_bwd, ("mid", 0) if on_side and q == 0 else None, ("v", j, q))
-            gsig.append(grads(("v", j, q), ("gv", j, q), self._ranges("vit", lo, hi - 1, j)))
-        if self.trains_vectors:                     # the tail casts the ONE fp32 buffer every piece's bias / norm sums met in
-            add("M", self._end_backward, [sg for sg in gsig if two], ("end", 0), self._ranges("tail"))
-        return segs
+            grads(("v", j, q), ("gv", j, q), self._ranges("vit", lo, hi - 1, j))
 
     # ---- token cross-entropy objective: the native trainer of prismatic/training/strategies/base_strategy.py:257-417 ----
     # PrismaticVLM.forward(..., labels=) -> HF shifted causal-LM loss (prismatic/models/vlms/prismatic.py:312-481), loss.backward().
@@ -627,19 +632,9 @@ class BackboneTrainer:
         eng, cfg, llm = self.eng, self.cfg, self.llm
         n, D, V = cfg.llm.n_layers, cfg.llm.d, cfg.llm.vocab
         assert getattr(llm, "lm_head", None) is None, "token-CE training: tied lm_head only (Qwen2.5-0.5B / 1.5B tie_word_embeddings)"
-        lch = E.VLAEngine._chunks(n, [self.exchange_layers])
-        two = self.gstream is not None
+        lch = chunks(n, [self.exchange_layers])
         segs = []
-
-        def add(st, fn, wait=None, signal=None, ranges=None):
-            segs.append((st, fn, wait, signal, ranges))
-
-        def grads(after, signal, ranges):
-            if two:
-                add("G", self._flush_work, after, signal, ranges)
-            else:
-                add("M", None, None, signal, ranges)
-            return signal
+        add, grads = self._builders(segs)
 
         def f_front():
             eng._vision_begin(batch)
@@ -680,33 +675,24 @@ class BackboneTrainer:
                 self._defer_tn(self.ce_logits, self.ce_h, self.g_lm)
             ops.copy_rows3d(self.ce_dh, self._dHS[n][0, Np], B, Lm, D, Lm * D, D, S * D, D)
         add("M", f_ce, None, ("ce", 0))
-        gsig = [grads(("ce", 0), ("gce", 0), [])] if self.trains_vectors else []       # (LoRA: lm_head is not adapted - nothing deferred here)
+        if self.trains_vectors:                                      # (LoRA: lm_head is not adapted - nothing deferred here)
+            grads(("ce", 0), ("gce", 0), [])
         for k, (lo, hi) in enumerate(reversed(lch)):
             add("M", lambda lo=lo, hi=hi: self._llm_bwd_layers(lo, hi), None, ("m", k))
-            gsig.append(grads(("m", k), ("g", k), self._ranges("llm", lo, hi - 1)))
+            grads(("m", k), ("g", k), self._ranges("llm", lo, hi - 1))
 
         def f_mid():
             dX0 = self.d_last.view(eng.B, eng.S, D)
             self._embed_backward(dX0)
             self._proj_backward(dX0)
         add("M", f_mid, None, ("mid", 0))
-        gsig.append(grads(("mid", 0), ("gmid", 0), self._ranges("proj")))
-        for j, v in enumerate(self.vits):
-            vch = self._vit_chunks(j)
-            for q, (lo, hi) in enumerate(reversed(vch)):
-                def v_bwd(j=j, lo=lo, hi=hi, first=(q == 0)):
-                    if first:
-                        self._vit_bwd_begin(j)
-                    self._vit_bwd_blocks(j, lo, hi)
-                    if lo == 0 and self.trains_vectors:
-                        self._vit_bwd_end(j)
-                add("M", v_bwd, None, ("v", j, q))
-                gsig.append(grads(("v", j, q), ("gv", j, q), self._ranges("vit", lo, hi - 1, j)))
+        grads(("mid", 0), ("gmid", 0), self._ranges("proj"))
+        self._vit_bwd_segments(add, grads, side=False)
         if self.trains_vectors:
             def f_tail():
                 ops.add_(self.G("llm.embed"), self.g_lm)             # tied weights: lookup gradient + lm_head gradient (one bf16 add, as autograd accumulates)
                 self._end_backward()
-            add("M", f_tail, [sg for sg in gsig if two], ("end", 0), self._ranges("embed") + self._ranges("tail"))
+            add("M", f_tail, [sg.signal for sg in segs if sg.stream == "G"], ("end", 0), self._ranges("embed") + self._ranges("tail"))
         return segs
 
     def set_objective(self, objective: str):
@@ -730,50 +716,22 @@ class BackboneTrainer:
         self._run_work(work)
 
     def _stream(self, name: str, main):
-        return main if name == "M" else ((self.hstream or main) if name == "H" else (self.vstream or main) if name == "V" else (self.gstream or main))
+        return {"H": self.hstream, "G": self.gstream, "V": self.vstream}.get(name) or main
 
     def _run(self, segs, graphs=None, exchange: bool = True, update=None):
-        """Enqueue the segments in order (eagerly, or as replays of their captured graphs); events cross the streams; a segment's
-        finished gradient ranges go to the exchange behind an event of their own.  The caller's stream joins the others at the end.
+        """Enqueue the segments (schedule.run, eagerly or as replays of their captured graphs); a segment's finished gradient ranges
+        go to the exchange behind the event recorded after it.  The caller's stream joins the others at the end.
         update=(lr, betas, eps, wd): AdamW runs RANGE BY RANGE on the gradient stream as soon as a range is final (and exchanged) -
         the backward reads only the W^T copies of a weight, never the parameter itself, so the 15 GB of optimiser traffic of a full
         fine-tune hides under the rest of the backward instead of trailing it (torch's optimizer.step() after loss.backward(),
         vla-scripts/finetune.py:1078-1082: same arithmetic, every use of a parameter in the NEXT forward sees the updated value)."""
-        main = torch.cuda.current_stream()
-        for st in (self.hstream, self.gstream, self.vstream):
-            if st is not None:
-                st.wait_stream(main)                 # fork: inputs / the previous update are ordered before everything
-        ev = {}
-        for k, (st, fn, wait, signal, ranges) in enumerate(segs):
-            stream = self._stream(st, main)
-            with torch.cuda.stream(stream):
-                for w in ([] if wait is None else wait if isinstance(wait, list) else [wait]):
-                    stream.wait_event(ev[w])
-                tl = getattr(self, "_timeline", None)           # (tools/trainer_timeline.py: timing events around every segment)
-                if tl is not None and fn is not None:
-                    t0 = torch.cuda.Event(enable_timing=True)
-                    t0.record(stream)
-                if fn is not None:
-                    if graphs is None:
-                        self._call(st, fn)
-                    elif graphs[k] is not None:
-                        graphs[k].replay()
-                if tl is not None and fn is not None:
-                    t1 = torch.cuda.Event(enable_timing=True)
-                    t1.record(stream)
-                    tl.append((st, k, t0, t1))
-                if signal is not None or ranges:
-                    e = torch.cuda.Event()
-                    e.record(stream)
-                    if signal is not None:
-                        ev[signal] = e
-                    if ranges and exchange:
-                        self._exchange(ranges, after_event=e)
-                    if ranges and update is not None:
-                        self._update_ranges(ranges, e, update, k if graphs is not None else None)
-        for st in (self.hstream, self.gstream, self.vstream):
-            if st is not None:
-                main.wait_stream(st)
+        def after(k, seg, e):
+            if seg.ranges and exchange:
+                self._exchange(seg.ranges, after_event=e)
+            if seg.ranges and update is not None:
+                self._update_ranges(seg.ranges, e, update, k if graphs is not None else None)
+        schedule.run(segs, self._stream, graphs, fork=[st for st in (self.hstream, self.gstream, self.vstream) if st is not None],
+                     join=True, call=self._call, after=after, timeline=getattr(self, "_timeline", None))   # (tools/trainer_timeline.py)
 
     def _call(self, st: str, fn):
         """Run a segment's Python call with its stream kind set (_lane)."""
@@ -782,6 +740,13 @@ class BackboneTrainer:
             fn()
         finally:
             self._lane = "M"
+
+    def _capture(self, segs):
+        """schedule.capture on fresh capture streams, one per stream kind; a kind without a stream of its own (VLA_TRAINER_STREAMS
+        1 / 2) is captured as "M".  -> (graphs, capture streams, memory pools by capture stream)."""
+        caps, pools = {k: torch.cuda.Stream() for k in "MHGV"}, {}
+        graphs = schedule.capture(segs, pools, lambda st: caps[st if self._stream(st, None) is not None else "M"], self._call)
+        return graphs, caps, pools
 
     def _update_ranges(self, ranges, final_event, update, seg_index=None):
         """AdamW over the ranges a segment has finished, then - round 4 - the derived operands of exactly those parameters (W^T copies of
@@ -840,9 +805,9 @@ class BackboneTrainer:
         """The same pieces one after the other on the current stream, gradient work in line (forward() / backward())."""
         g, h, v, self.gstream, self.hstream, self.vstream = self.gstream, self.hstream, self.vstream, None, None, None
         try:
-            for _, fn, _, _, _ in segs:
-                if fn is not None:
-                    fn()
+            for sg in segs:
+                if sg.fn is not None:
+                    sg.fn()
         finally:
             self.gstream, self.hstream, self.vstream = g, h, v
 
@@ -873,7 +838,7 @@ class BackboneTrainer:
         them (1.8 ms behind a seven-block segment in the full fine-tune, tools/trainer_timeline.py)."""
         nbj = len(self.vits[j].blocks)
         last = j == len(self.vits) - 1 and nbj >= 14 and not os.environ.get("VLA_UNIFORM_CHUNKS")
-        return E.VLAEngine._chunks(nbj, [1, 2, 4, self.exchange_blocks] if last else [self.exchange_blocks])
+        return chunks(nbj, [1, 2, 4, self.exchange_blocks] if last else [self.exchange_blocks])
 
     def _end_backward(self):
         pass
@@ -960,14 +925,21 @@ class BackboneTrainer:
     def train_step(self, batch, lr: float, noise=None):
         """One micro-step, launched eagerly on the three streams (with a reducer and no accumulation: every gradient range goes
         to the exchange as soon as it is final); the optimizer steps on every ``ga``-th call."""
+        return self._step(self._segments(batch, noise, 1.0 / self.ga), None, lr)
+
+    def _step(self, segs, graphs, lr: float):
+        """train_step (graphs None: eager, derived operands rebuilt in line) or train_step_graphed (their graphs replayed)."""
         if self.ga == 1 and self.overlap_update:
             self.step_count += 1
-            self._run(self._segments(batch, noise), update=(lr, 0.9, 0.999, 1e-8, 0.01))
-            self._after_update(refresh=True)
-            return self._loss3
-        self._run(self._segments(batch, noise, 1.0 / self.ga), exchange=self.ga == 1)
-        if self._accumulate():
-            self.optimizer_step(lr)
+            self._run(segs, graphs, update=(lr, 0.9, 0.999, 1e-8, 0.01))
+            self._after_update(refresh=graphs is None)
+        else:
+            self._run(segs, graphs, exchange=self.ga == 1)
+            if not self._accumulate():
+                return self._loss3
+            self.optimizer_step(lr, refresh=graphs is None)
+        if graphs is not None and self._g_r is not None:
+            self._g_r.replay()
         return self._loss3
 
     def capture(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None, warmup: int = 2):
@@ -983,20 +955,7 @@ class BackboneTrainer:
         torch.cuda.synchronize()
         self.head.dirty = True                       # the head's own W^T / padded-operand refresh becomes part of its graphs
         self._segs = self._segments(batch, noise, 1.0 / self.ga)
-        # one memory pool and one capture stream per stream kind: graphs sharing a pool are replayed strictly in capture order on
-        # ONE stream, so the allocator's reuse of freed capture-time temporaries stays race-free while the streams overlap
-        pools = {k: torch.cuda.graph_pool_handle() for k in "MHGV"}
-        caps = {k: torch.cuda.Stream() for k in "MHGV"}
-        self._graphs = []
-        for st, fn, _, _, _ in self._segs:
-            if fn is None:
-                self._graphs.append(None)
-                continue
-            kind = st if self._stream(st, None) is not None else "M"      # (single-stream mode: everything is an "M" graph)
-            g = torch.cuda.CUDAGraph()
-            with E.graph_capture(g, pool=pools[kind], stream=caps[kind], capture_error_mode="thread_local"):
-                self._call(st, fn)
-            self._graphs.append(g)
+        self._graphs, caps, pools = self._capture(self._segs)
         # derived operands: per finished range a small graph behind that range's AdamW (overlapped update only), the rest at the step's end
         self._rgraphs, covered, rpool = {}, set(), torch.cuda.graph_pool_handle()
         if self.ga == 1 and self.overlap_update and self._refresh_pieces():
@@ -1006,40 +965,25 @@ class BackboneTrainer:
                 before = set(self._refreshed)
                 fns = self._refresh_pieces_in(ranges)
                 covered |= self._refreshed - before
-                if fns:
-                    g = torch.cuda.CUDAGraph()
-                    with E.graph_capture(g, pool=rpool, stream=caps["G"], capture_error_mode="thread_local"):     # (a pool of their own: they
-                        for f_ in fns:                                                                               #  replay between the G graphs)
-                            f_()
-                    self._rgraphs[k] = g
+                if fns:                              # (a pool of their own: they replay between the G graphs)
+                    self._rgraphs[k] = capture_graph(lambda: [f_() for f_ in fns], rpool, caps["G"])
             self._refreshed = set()
         rest = [f_ for i, (_, _, f_) in enumerate(self._refresh_pieces()) if i not in covered]
         has_extra = type(self)._refresh_extra is not BackboneTrainer._refresh_extra
-        self._g_r = torch.cuda.CUDAGraph() if (not self._rgraphs or rest or has_extra) else None      # (nothing left: LoRA - every pair lies in a range)
-        if self._g_r is not None:
-            with E.graph_capture(self._g_r, pool=pools["M"], stream=caps["M"], capture_error_mode="thread_local"):
-                if self._rgraphs:
-                    for f_ in rest:
-                        f_()
-                    self._refresh_extra()
-                else:
-                    self.refresh()
+
+        def rebuild():
+            if self._rgraphs:
+                for f_ in rest:
+                    f_()
+                self._refresh_extra()
+            else:
+                self.refresh()
+        # (nothing left: LoRA - every pair lies in a range)
+        self._g_r = capture_graph(rebuild, pools[caps["M"]], caps["M"]) if (not self._rgraphs or rest or has_extra) else None
         torch.cuda.synchronize()
 
     def train_step_graphed(self, lr: float):
-        if self.ga == 1 and self.overlap_update:
-            self.step_count += 1
-            self._run(self._segs, self._graphs, update=(lr, 0.9, 0.999, 1e-8, 0.01))
-            self._after_update(refresh=False)
-            if self._g_r is not None:
-                self._g_r.replay()
-            return self._loss3
-        self._run(self._segs, self._graphs, exchange=self.ga == 1)
-        if self._accumulate():
-            self.optimizer_step(lr, refresh=False)
-            if self._g_r is not None:
-                self._g_r.replay()
-        return self._loss3
+        return self._step(self._segs, self._graphs, lr)
 
     # ---- validation pass (vla-scripts/finetune.py:605-685: vla.eval(), torch.no_grad()) --------------------------------------
     # The forward segments of the step (segs[:_n_forward]) in eval mode, then the L1 loss without gradient: no dropout mask, no
@@ -1064,7 +1008,7 @@ class BackboneTrainer:
 
         def h_loss():
             self._val_loss3 = ops.l1_loss(self._pred, self.eng._to_bf16(batch["actions"]), want_grad=False)[0]
-        return segs + [("H", h_loss, None, None, None)]
+        return segs + [Segment("H", h_loss)]
 
     def val_forward(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Eager validation of one batch on the current stream -> f32 [3] (loss, current action, next actions)."""
@@ -1082,18 +1026,7 @@ class BackboneTrainer:
             t0 = time.perf_counter()
             with self._eval_mode():
                 segs = self._val_segments(batch, noise)
-                pools = {k: torch.cuda.graph_pool_handle() for k in "MHGV"}
-                caps = {k: torch.cuda.Stream() for k in "MHGV"}
-                graphs = []
-                for st, fn, _, _, _ in segs:
-                    if fn is None:
-                        graphs.append(None)
-                        continue
-                    kind = st if self._stream(st, None) is not None else "M"
-                    g = torch.cuda.CUDAGraph()
-                    with E.graph_capture(g, pool=pools[kind], stream=caps[kind], capture_error_mode="thread_local"):
-                        self._call(st, fn)
-                    graphs.append(g)
+                graphs = self._capture(segs)[0]
             torch.cuda.synchronize()
             self.val_capture_seconds = time.perf_counter() - t0
             self._val_graphs = (graphs, segs)
