@@ -260,7 +260,6 @@ def test_attention_fwd(ops, B, S, Hq, Hkv, dh, causal, masked):
                           causal, km.to(torch.uint8).to(DEV) if masked else None, want_lse=True)
     hd = lambda t, h: t.float().reshape(B, S, h, dh).transpose(1, 2)
     ref = O.attention(hd(q, Hq), hd(k, Hkv), hd(v, Hkv), causal, km if masked else None, None, True)
-    valid = torch.ones(B, S, dtype=torch.bool) if (causal or not masked) else torch.ones(B, S, dtype=torch.bool)
     check(o, ref.transpose(1, 2).reshape(B, S, Hq * dh), rel=6e-3, mx=3e-2, name=f"attn fwd dh{dh}")
     # log-sum-exp against fp32
     kk, vv = hd(k, Hkv).repeat_interleave(Hq // Hkv, 1), None
