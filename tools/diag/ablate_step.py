@@ -45,13 +45,13 @@ E.LLM._alloc = _alloc_random
 
 
 if what == "rms":
-    E.LLM._rms = lambda self, x, w, out, rstd: None
+    ops.rmsnorm_fwd = lambda x, w, eps, want_rstd=False, out=None, rstd=None: out
 elif what == "ln":
     _ln = ops.layernorm_fwd
 
     def ln(x, w, b, eps, want_stats=False, **kw):
-        if want_stats:
-            return _ln(x, w, b, eps, want_stats=True, **kw)
+        if want_stats or kw.get("stats") is not None:       # (the head's LayerNorms)
+            return _ln(x, w, b, eps, want_stats=want_stats, **kw)
         return x                                              # (ViT blocks: the GEMM reads the un-normalised rows)
     ops.layernorm_fwd = ln
 elif what == "attn":
@@ -63,7 +63,6 @@ elif what == "attn":
             return o, _like("lse", (q.shape[0], Hq, q.shape[1]), torch.float32, q.device)
         return o
     ops.attn_fwd = af
-    E.LLM._attn_fwd = lambda self, q3, i, b0, b1, S: None     # (the LLM's attention output buffer keeps what it held)
 elif what in ("head_fwd", "head_bwd"):
     _attn0 = E.Head._attn
     _filled = set()

@@ -47,9 +47,10 @@ c = llm.cfg; D = c.d; Sq = llm.S
 L = llm.layers[i]
 x = llm.HS[i].view(-1, D)
 pieces = {
-  "rms": lambda: llm._rms(x, L["n1"], llm.nbuf, llm.R1[i]),
+  "rms": lambda: ops.rmsnorm_fwd(x, L["n1"], c.eps, out=llm.nbuf, rstd=llm.R1[i]),
   "qkv": lambda: ops.gemm_nt(llm.nbuf, L["wqkv"], bias=L["bqkv"], out=llm.QKV[i], rope=(1, llm.cos, llm.sin, Sq, c.dh, (c.heads + c.kv_heads) * c.dh)),
-  "attn": lambda: llm._attn_fwd(llm.QKV[i].view(1, Sq, -1), i, 0, 1, Sq),
+  "attn": lambda: ops.attn_fwd(*llm._attn_views(llm.QKV[i].view(1, Sq, -1)), c.heads, c.kv_heads, c.dh, True, llm.kmask,
+                               out=llm.AO[i].view(1, Sq, -1), lse=llm.LSE[i]),
   "o": lambda: ops.gemm_nt(llm.AO[i], L["wo"], residual=x, out=llm.X1[i]),
   "gu": lambda: ops.gemm_nt(llm.nbuf, L["wgu"], act=ops.ACT_SWIGLU, out=llm.GU[i], out2=llm.hbuf),
   "gu(no pre-act store)": lambda: ops.gemm_nt(llm.nbuf, L["wgu"], act=ops.ACT_SWIGLU, out=None, out2=llm.hbuf),

@@ -168,13 +168,94 @@ NAMED_CONFIGS = {"config2": config2, "dinosiglip-0_5b": dinosiglip_05b_config, "
                  "tiny_fused": tiny_fused_config, "tiny_twin": tiny_twin_config, "qwen15b-geometry": qwen15b_geometry_config}
 
 
+# ------------------------------------------------------------------------------------------------ what a Linear does
+class Linear:
+    """What a Linear does on a frozen backbone: y = x W^T + b through the GEMM's fused epilogues, dx = dy W on the kept W^T.  The
+    layer bodies (ViT.block, LLM.fwd_layer / bwd_layer) call ``_lin`` / ``_lin_bwd`` / ``_ln`` / ``_rms`` on the Linear they are
+    given: this one, or a trainer (trainers.BackboneTrainer subclasses it), which adds the weight-gradient or LoRA work.
+
+    fp8: ``Q`` maps a Linear's key ("llm.3.qkv", "vit0.5.fc1") to the OCP e4m3 codes and per-output-channel scales of its weight;
+    such a Linear runs on the fp8 MFMA with its input quantised per row.  A norm whose output feeds one quantises inside the norm
+    kernel (the row is still in registers: bit-identical to norm + quantise) and hands the codes over to the ``_lin`` that follows
+    within the same segment call (``_xq``); anything else is quantised by one pass over it.  Scratch is per shape and per stream
+    kind (``_lane``): one Linear serves each frozen backbone, and the trainers run two kinds at once on different streams."""
+
+    trains_vectors = False       # (trainers: norm / bias / LayerScale gradients)
+    taps = None                  # (trainers' test hook, see BackboneTrainer)
+    keep_norm_out = False        # fp8: the bf16 norm output is written too (a trainer reads it again for a weight gradient)
+    _lane = "M"
+
+    def __init__(self, device):
+        self.dev = device
+        self.fp8 = False
+        self.Q: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._qbuf, self._xq = {}, None
+
+    def _q8_norm(self, x) -> bool:
+        """Does the norm producing rows like x quantise them for the Linear it feeds?"""
+        return self.fp8
+
+    def _qscratch(self, rows: int, cols: int, slot: str):
+        k = (rows, cols, slot, self._lane)
+        b = self._qbuf.get(k)
+        if b is None:
+            b = self._qbuf[k] = (torch.empty(rows, cols, device=self.dev, dtype=torch.uint8), torch.empty(rows, device=self.dev, dtype=torch.float32))
+        return b
+
+    def _hand_over(self, y, q, s_):
+        """Record the norm's quantised output for the next _lin; returns what stands for the norm's output (y, or the codes
+        when the bf16 output is not written)."""
+        h = q if y is None else y
+        self._xq = ((h.data_ptr(), tuple(h.shape)), q, s_)
+        return h
+
+    def _quant(self, x, slot: str):
+        """(codes, scales) of the rows of x: taken from the norm that just produced x, else one pass over x (vla_quant_fp8_rows)."""
+        if self._xq is not None and self._xq[0] == (x.data_ptr(), tuple(x.shape)):
+            hit, self._xq = self._xq, None               # (consumed: the scratch is overwritten by the next norm of this shape)
+            return hit[1], hit[2]
+        q, s_ = self._qscratch(x.shape[0], x.shape[1], slot)
+        return ops.quant_fp8_rows(x, q, s_)
+
+    def _ln(self, x, w, b, y, st, eps):
+        """LayerNorm of the rows of x into y (None: a new tensor) with statistics st (None: not stored) -> its output."""
+        if not self._q8_norm(x):
+            return ops.layernorm_fwd(x, w, b, eps, out=y, stats=st)
+        q, s_ = self._qscratch(x.shape[0], x.shape[1], "n")
+        y = y if self.keep_norm_out else None
+        ops.layernorm_fwd_q8(x, w, b, eps, q, s_, y=y, stats=st)
+        return self._hand_over(y, q, s_)
+
+    def _rms(self, x, w, out, rstd, eps):
+        if not self._q8_norm(x):
+            return ops.rmsnorm_fwd(x, w, eps, out=out, rstd=rstd)
+        q, s_ = self._qscratch(x.shape[0], x.shape[1], "n")
+        ops.rmsnorm_fwd_q8(x, w, eps, q, s_, rstd=rstd, y=out if self.keep_norm_out else None)
+        return self._hand_over(out, q, s_)
+
+    def _lin(self, key, x, W, bias=None, **kw):
+        wq = self.Q.get(key)
+        if wq is not None:
+            xq, xs = self._quant(x, "f")
+            return ops.gemm_nt(xq, wq[0], bias=bias, fp8=(xs, wq[1]), **kw)
+        return ops.gemm_nt(x, W, bias=bias, **kw)
+
+    def _lin_bwd(self, key, dy, x, WT, out=None, swiglu_gu=None, **kw):
+        """dx = dy W (x: the layer's input, for a weight gradient); down_proj (swiglu_gu): dGU = swiglu'(GU) * (dy W_down) in the
+        dX GEMM's epilogue (kw: its gu_group)."""
+        if swiglu_gu is not None:
+            return ops.gemm_swiglu_bwd(dy, WT, swiglu_gu, out=out, **kw)
+        return ops.gemm_nt(dy, WT, out=out)
+
+
 # ------------------------------------------------------------------------------------------------ frozen ViT
 class ViT:
     """timm VisionTransformer forward up to block depth-2, no final norm (modeling_prismatic.py:120-144,196-237;
-    block structure film_vit_wrapper.py:69-75).  Frozen: forward only."""
+    block structure film_vit_wrapper.py:69-75).  Frozen: forward only (the trainers run the same blocks with Linears of their own)."""
 
-    def __init__(self, cfg: ViTCfg, sd: Dict[str, torch.Tensor], device):
-        self.cfg = cfg
+    def __init__(self, cfg: ViTCfg, sd: Dict[str, torch.Tensor], device, j: int = 0):
+        self.cfg, self.key = cfg, f"vit{j}."
+        self.lin = Linear(device)
         d, P = cfg.d, cfg.patch
         g = lambda k: sd[k].to(device=device, dtype=BF16).contiguous()
         self.kpe = rup(3 * P * P, 64)
@@ -207,8 +288,8 @@ class ViT:
             self.blocks.append(blk)
         # ... and, for the FROZEN forward (adapter-only fine-tune, inference), folded into the projections: y = ls * (W x + b) =
         # (ls W) x + ls b - one bf16 rounding point moves (scale applied to the weight instead of to the bf16 output), no extra
-        # kernel on the step.  A trainer of the backbone (LoRA / full fine-tune) calls fold_layerscale(False): ViT.forward then
-        # applies the scale as the reference does (vla_layerscale_fwd), on the weights that are being trained.
+        # kernel on the step.  A trainer of the backbone (LoRA / full fine-tune) calls fold_layerscale(False): the blocks then
+        # apply the scale as the reference does (vla_layerscale_fwd), on the weights that are being trained.
         self.ls_folded = False
         self.fold_layerscale(True)
 
@@ -230,78 +311,79 @@ class ViT:
         """BASELINE configs[4] 'fp8 MFMA weight path', first part: the frozen qkv and fc1 weights as OCP e4m3 with one scale per
         output channel; their inputs come out of LayerNorm already quantised per row (vla_layernorm_fwd_q8), the products run on
         the fp8 MFMA.  proj / fc2 (inputs produced by attention / a GEMM epilogue: no row statistics at hand) stay bf16."""
-        for b in self.blocks:
-            b["wqkv_q"], b["wqkv_s"] = ops.quant_fp8_rows(b["wqkv"])
-            b["w1_q"], b["w1_s"] = ops.quant_fp8_rows(b["w1"])
-        self.fp8 = True
-
-    def _ln_q8(self, x, w, b_):
-        rows, cols = x.shape
-        if getattr(self, "_q8", None) is None or self._q8.shape != (rows, cols):
-            self._q8 = torch.empty(rows, cols, device=x.device, dtype=torch.uint8)
-            self._qs = torch.empty(rows, device=x.device, dtype=torch.float32)
-        return ops.layernorm_fwd_q8(x, w, b_, self.cfg.eps, self._q8, self._qs)
-
-    def forward(self, pixels: torch.Tensor, c0: int, out: torch.Tensor, c_group=None):
-        """pixels [B, C, H, W] (channels c0..c0+2 used) -> writes patch features into ``out`` (a [B*Np, d] window,
-        possibly a column slice of the fused feature buffer)."""
-        cfg = self.cfg
-        B, Np, d, T = pixels.shape[0], cfg.n_patches, cfg.d, cfg.n_patches + cfg.n_prefix
-        cols = ops.im2col_patch(pixels, c0, cfg.patch, self.kpe)
-        if cfg.n_prefix:
-            x = torch.empty(B, T, d, device=pixels.device, dtype=BF16)
-            tmp = ops.gemm_nt(cols, self.wpe, bias=self.bpe, residual=self.pos, res_mod=Np)
-            x[:, cfg.n_prefix:] = tmp.view(B, Np, d)
-            x[:, :cfg.n_prefix] = self.prefix
-            x = x.view(B * T, d)
-        else:
-            x = ops.gemm_nt(cols, self.wpe, bias=self.bpe, residual=self.pos, res_mod=Np)
-        act = ACT_GELU_TANH if cfg.gelu_tanh else ACT_GELU
-        dh = d // cfg.heads
-        nb = len(self.blocks)
-        fp8 = getattr(self, "fp8", False)
         for i, b in enumerate(self.blocks):
-            if fp8:
-                q8, qs = self._ln_q8(x, b["n1w"], b["n1b"])
-                qkv = ops.gemm_nt(q8, b["wqkv_q"], bias=b["bqkv"], fp8=(qs, b["wqkv_s"])).view(B, T, 3 * d)
-            else:
-                h = ops.layernorm_fwd(x, b["n1w"], b["n1b"], cfg.eps)
-                qkv = ops.gemm_nt(h, b["wqkv"], bias=b["bqkv"]).view(B, T, 3 * d)
-            a = ops.attn_fwd(qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], cfg.heads, cfg.heads, dh, False)
-            unf = cfg.layerscale and not self.ls_folded          # scale applied to the bf16 projection output, as the reference does
-            wp, bp, w2, b2 = (b["wproj"], b["bproj"], b["w2"], b["b2"]) if (unf or not cfg.layerscale) else (b["wproj_f"], b["bproj_f"], b["w2_f"], b["b2_f"])
-            if unf:
-                ops.layerscale_fwd(ops.gemm_nt(a.view(B * T, d), wp, bias=bp), b["ls1"], x, out=x)
-            else:
-                ops.gemm_nt(a.view(B * T, d), wp, bias=bp, residual=x, out=x)
-            if fp8:
-                q8, qs = self._ln_q8(x, b["n2w"], b["n2b"])
-                m = ops.gemm_nt(q8, b["w1_q"], bias=b["b1"], act=act, fp8=(qs, b["w1_s"]))
-            else:
-                h = ops.layernorm_fwd(x, b["n2w"], b["n2b"], cfg.eps)
-                m = ops.gemm_nt(h, b["w1"], bias=b["b1"], act=act)
-            if unf:
-                ops.layerscale_fwd(ops.gemm_nt(m, w2, bias=b2), b["ls2"], x, out=x)
-                if i == nb - 1 and cfg.n_prefix == 0:
-                    assert c_group is None
-                    out.copy_(x)
-            elif i == nb - 1 and cfg.n_prefix == 0:
-                ops.gemm_nt(m, w2, bias=b2, residual=x, out=out, c_group=c_group)
-            else:
-                ops.gemm_nt(m, w2, bias=b2, residual=x, out=x)
+            self.lin.Q[f"{self.key}{i}.qkv"] = ops.quant_fp8_rows(b["wqkv"])
+            self.lin.Q[f"{self.key}{i}.fc1"] = ops.quant_fp8_rows(b["w1"])
+        self.lin.fp8 = True
+
+    def forward(self, pixels: torch.Tensor, c0: int, out: Optional[torch.Tensor] = None, lin: Optional[Linear] = None, st=None):
+        """pixels [Bv, C, H, W] (channels c0..c0+2 used) -> the last block's output [Bv * T, d] (prefix tokens included).
+        out: the frozen last block writes its fc2 product straight into it (no prefix tokens: out is then the [Bv * Np, d] patch
+        features).  lin / st: a trainer and its per-block keeps (trainers.BackboneTrainer.V[j])."""
+        cfg = self.cfg
+        lin = self.lin if lin is None else lin
+        Bv, Np, d, T = pixels.shape[0], cfg.n_patches, cfg.d, cfg.n_patches + cfg.n_prefix
+        cols = ops.im2col_patch(pixels, c0, cfg.patch, self.kpe)
+        x = st["X"][0] if st is not None else torch.empty(Bv * T, d, device=pixels.device, dtype=BF16)
         if cfg.n_prefix:
-            assert c_group is None
-            out.view(B, Np, -1).copy_(x.view(B, T, d)[:, cfg.n_prefix:])
-        return out
+            pe = ops.gemm_nt(cols, self.wpe, bias=self.bpe, residual=self.pos, res_mod=Np, out=st["pe"] if st is not None else None)
+            x3 = x.view(Bv, T, d)
+            ops.copy_rows3d(pe, x3[0, cfg.n_prefix:], Bv, Np, d, Np * d, d, T * d, d)
+            ops.copy_rows3d(self.prefix, x3, Bv, cfg.n_prefix, d, 0, d, T * d, d)     # cls + register tokens, broadcast over the batch
+        else:
+            ops.gemm_nt(cols, self.wpe, bias=self.bpe, residual=self.pos, res_mod=Np, out=x)
+        if st is not None:
+            st["cols"] = cols                      # (the patch-embedding weight gradient reads it)
+        nb = len(self.blocks)
+        for i in range(nb):
+            if st is not None:
+                x = self.block(i, x, lin, st, st["X"][i + 1])
+            else:                                  # frozen: the residual stream is updated in place
+                x = self.block(i, x, lin, None, out if i == nb - 1 and out is not None else x)
+        return x
+
+    def block(self, i: int, x: torch.Tensor, lin: Linear, st, x_out: torch.Tensor) -> torch.Tensor:
+        """Block i: x [Bv * T, d] -> x_out.  st: a trainer's per-block keeps (every activation its backward reads; the fc1
+        pre-activation apart from the GELU), None on the frozen path (temporaries; GELU in the fc1 epilogue)."""
+        cfg, b, k = self.cfg, self.blocks[i], f"{self.key}{i}."
+        d, T = cfg.d, cfg.n_patches + cfg.n_prefix
+        Bv = x.shape[0] // T
+        keep = lambda name: st[name][i] if st is not None and name in st else None
+        sfx = "_f" if self.ls_folded else ""       # (folded LayerScale: the scaled projections)
+        # x_mid = x + ls1 * proj(attn(qkv(LN1(x))))
+        h = lin._ln(x, b["n1w"], b["n1b"], keep("H1"), keep("S1"), cfg.eps)
+        qkv = lin._lin(k + "qkv", h, b["wqkv"], b["bqkv"], out=keep("QKV")).view(Bv, T, 3 * d)
+        a = ops.attn_fwd(qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], cfg.heads, cfg.heads, d // cfg.heads, False,
+                         out=st["A"][i].view(Bv, T, d) if st is not None else None, lse=keep("LSE")).view(Bv * T, d)
+        xm = x if st is None else st["Xm"][i]
+        self._residual(lin, k + "proj", a, b["wproj" + sfx], b["bproj" + sfx], b.get("ls1"), x, xm, keep("PA"))
+        # x_out = x_mid + ls2 * fc2(gelu(fc1(LN2(x_mid))))
+        h = lin._ln(xm, b["n2w"], b["n2b"], keep("H2"), keep("S2"), cfg.eps)
+        if st is None:
+            m = lin._lin(k + "fc1", h, b["w1"], b["b1"], act=ACT_GELU_TANH if cfg.gelu_tanh else ACT_GELU)
+        else:
+            m = ops.gelu_fwd(lin._lin(k + "fc1", h, b["w1"], b["b1"], out=st["Mpre"][i]), out=st["Mact"][i])
+        self._residual(lin, k + "fc2", m, b["w2" + sfx], b["b2" + sfx], b.get("ls2"), xm, x_out, keep("PM"))
+        return x_out
+
+    def _residual(self, lin, key, a, w, bias, ls, x, out, pre):
+        """out = x + ls * (a W^T + bias): LayerScale applied to the bf16 product as the reference does (pre: a trainer's slot
+        for the unscaled product), or - folded / none - the residual added in the GEMM's epilogue."""
+        if ls is not None and not self.ls_folded:
+            ops.layerscale_fwd(lin._lin(key, a, w, bias, out=pre), ls, x, out=out)
+        else:
+            lin._lin(key, a, w, bias, out=out, residual=x)
 
 
 # ------------------------------------------------------------------------------------------------ frozen LLM
 class LLM:
     """Qwen2 decoder stack (transformers Qwen2ForCausalLM; reference call site modeling_prismatic.py:644-655),
-    forward with hidden-state taps and explicit dX backward (weights frozen: adapter-only fine-tune)."""
+    forward with hidden-state taps and explicit dX backward (weights frozen: adapter-only fine-tune).  The trainers run the
+    same layer bodies with themselves as the Linear and per-layer slots for what their gradient work reads (keep_per_layer)."""
 
     def __init__(self, cfg: LLMCfg, sd: Dict[str, torch.Tensor], device):
         self.cfg, self.device = cfg, device
+        self.lin = Linear(device)
         D, H, KV, dh, I = cfg.d, cfg.heads, cfg.kv_heads, cfg.dh, cfg.inter
         assert D % 64 == 0 and I % 64 == 0 and (H + 2 * KV) * dh % 64 == 0 and I % 16 == 0
         g = lambda k: sd[k].to(device=device, dtype=BF16).contiguous()
@@ -321,6 +403,15 @@ class LLM:
         self.embed = g("embed_tokens.weight")
         self._buf_key = None
         self.gu_row0 = 0
+        self.per_layer, self.norm_grads = False, False
+        self._flin = self._blin = self.lin
+
+    def keep_per_layer(self, norm_grads: bool):
+        """Training of the layers: the norm / SwiGLU outputs of every layer (N1, N2, Hs) and the dY of every Linear (G_res, G_d1,
+        G_gu, G_qkv; norm_grads: of the two RMSNorms too, G_n1 / G_n2) in slots of their own - the gradient stream reads them any
+        time after the dX chain has moved on (3.4 GB at batch 16)."""
+        self.per_layer, self.norm_grads = True, norm_grads
+        self._buf_key = None
 
     def _alloc(self, B: int, S: int):
         if self._buf_key == (B, S):
@@ -337,8 +428,13 @@ class LLM:
         self.LSE = e(n, B, c.heads, S, dt=torch.float32)
         self.R1, self.R2, self.RF = e(n, M, dt=torch.float32), e(n, M, dt=torch.float32), e(M, dt=torch.float32)
         self.nbuf, self.hbuf = e(M, D), e(M, c.inter)
-        self.q8, self.qs = e(M, D, dt=torch.uint8), e(M, dt=torch.float32)      # fp8 form of the normalised rows (enable_fp8)
-        self.d_a, self.d_b, self.d_h, self.d_gu, self.d_qkv, self.d_n = e(M, D), e(M, D), e(M, c.inter), e(M, 2 * c.inter), e(M, W), e(M, D)
+        self.d_a, self.d_b, self.d_gu, self.d_qkv, self.d_n = e(M, D), e(M, D), e(M, 2 * c.inter), e(M, W), e(M, D)
+        if self.per_layer:
+            self.N1, self.N2, self.Hs = e(n, M, D), e(n, M, D), e(n, M, c.inter)
+            self.G_res, self.G_d1, self.G_gu, self.G_qkv = e(n, M, D), e(n, M, D), e(n, M, 2 * c.inter), e(n, M, W)
+            self.d_last = e(M, D)
+            if self.norm_grads:
+                self.G_n1, self.G_n2 = e(n, M, D), e(n, M, D)
         self.cos, self.sin = ops.rope_half_tables(S, c.dh, c.theta, dev)
         self._buf_key = (B, S)
 
@@ -358,90 +454,60 @@ class LLM:
         if n_run == n:
             self.fwd_final()
 
-    def fwd_begin(self, B: int, S: int, kmask_u8: torch.Tensor, keep_from_row: int = 0):
+    def fwd_begin(self, B: int, S: int, kmask_u8: torch.Tensor, keep_from_row: int = 0, lin: Optional[Linear] = None):
         """keep_from_row: the backward of this forward will only visit the rows >= keep_from_row of every sequence
-        (LLM.backward row0 >= keep_from_row); backward-only tensors skip the rows below it."""
+        (LLM.backward row0 >= keep_from_row); backward-only tensors skip the rows below it.  lin: the Linear the layers of this
+        forward run with (default: the frozen one)."""
         self.kmask, self.B, self.S = kmask_u8, B, S
         self.gu_row0 = keep_from_row
+        self._flin = self.lin if lin is None else lin
 
-    def fwd_layer(self, i: int, b0: int = 0, b1: Optional[int] = None):
-        """Layer i on the samples [b0, b1) of the batch (default: all).  Every op is row- or sample-wise, so disjoint sample
-        ranges can run on different streams (the step schedule pipelines the two halves of the batch)."""
-        c, S = self.cfg, self.S
-        b1 = self.B if b1 is None else b1
-        B, r0, r1 = b1 - b0, b0 * S, b1 * S
-        M, D, H, KV, dh = B * S, c.d, c.heads, c.kv_heads, c.dh
-        L = self.layers[i]
-        x = self.HS[i].view(-1, D)[r0:r1]
-        nbuf, hbuf = self.nbuf[r0:r1], self.hbuf[r0:r1]
-        fp8 = getattr(self, "fp8", False)
-        q8, qs = self.q8[r0:r1], self.qs[r0:r1]
-        qkv = self.QKV[i][r0:r1]
-        # (RMSNorm folded into the neighbouring GEMMs - 47 launches fewer, built and measured SLOWER in round 3 - left the tree in
-        #  round 4: DESIGN section 4, tools/diag/gemm256_pruned_paths.patch)
-        if fp8:
-            ops.rmsnorm_fwd_q8(x, L["n1"], c.eps, q8, qs, rstd=self.R1[i][r0:r1])
-        else:
-            self._rms(x, L["n1"], nbuf, self.R1[i][r0:r1])
-        if fp8 and dh in (64, 128):
-            ops.gemm_nt(q8, L["wqkv_q"], bias=L["bqkv"], out=qkv, rope=(1, self.cos, self.sin, S, dh, (H + KV) * dh), fp8=(qs, L["wqkv_s"]))
-        elif fp8:
-            ops.gemm_nt(q8, L["wqkv_q"], bias=L["bqkv"], out=qkv, fp8=(qs, L["wqkv_s"]))
-            ops.rope_half_(qkv[:, :H * dh], self.cos, self.sin, S, H, dh)
-            ops.rope_half_(qkv[:, H * dh:(H + KV) * dh], self.cos, self.sin, S, KV, dh)
-        elif dh in (64, 128):   # RoPE fused into the projection's epilogue (head dim 128: the 128-row kernel's column map, round 4)
-            ops.gemm_nt(nbuf, L["wqkv"], bias=L["bqkv"], out=qkv, rope=(1, self.cos, self.sin, S, dh, (H + KV) * dh))
-        else:
-            ops.gemm_nt(nbuf, L["wqkv"], bias=L["bqkv"], out=qkv)
-            ops.rope_half_(qkv[:, :H * dh], self.cos, self.sin, S, H, dh)
-            ops.rope_half_(qkv[:, H * dh:(H + KV) * dh], self.cos, self.sin, S, KV, dh)
-        self._attn_fwd(qkv.view(B, S, -1), i, b0, b1, S)
-        x1 = self.X1[i][r0:r1]
-        ops.gemm_nt(self.AO[i][r0:r1], L["wo"], residual=x, out=x1)
-        # the pre-activations are kept for the backward only: rows below the live window are never read again
-        if fp8:
-            ops.rmsnorm_fwd_q8(x1, L["n2"], c.eps, q8, qs, rstd=self.R2[i][r0:r1])
-            ops.gemm_nt(q8, L["wgu_q"], act=ACT_SWIGLU, out=self.GU[i][r0:r1], out2=hbuf,
-                        c_live=(S, self.gu_row0) if self.gu_row0 else None, fp8=(qs, L["wgu_s"]))
-        else:
-            self._rms(x1, L["n2"], nbuf, self.R2[i][r0:r1])
-            ops.gemm_nt(nbuf, L["wgu"], act=ACT_SWIGLU, out=self.GU[i][r0:r1], out2=hbuf,
-                        c_live=(S, self.gu_row0) if self.gu_row0 else None)
-        ops.gemm_nt(hbuf, L["wd"], residual=x1, out=self.HS[self.out_slot(i)].view(-1, D)[r0:r1])
-
-    def fwd_final(self, b0: int = 0, b1: Optional[int] = None):
-        """hidden_states[n] = final RMSNorm of the last layer's output (HF convention)."""
-        n, D, S = self.cfg.n_layers, self.cfg.d, self.S
-        r0, r1 = b0 * S, (self.B if b1 is None else b1) * S
-        self._rms(self.HS[n + 1].view(-1, D)[r0:r1], self.norm, self.HS[n].view(-1, D)[r0:r1], self.RF[r0:r1])
-
-    def enable_fp8(self):
-        """fp8 weight path (see ViT.enable_fp8): the frozen q|k|v and gate/up weights in e4m3, their inputs quantised inside
-        RMSNorm (vla_rmsnorm_fwd_q8); o-proj / down stay bf16.  Forward only: the dX products keep the bf16 W^T."""
-        for L in self.layers:
-            L["wqkv_q"], L["wqkv_s"] = ops.quant_fp8_rows(L["wqkv"])
-            L["wgu_q"], L["wgu_s"] = ops.quant_fp8_rows(L["wgu"])
-        self.fp8 = True
-
-    def _rms(self, x, w, out, rstd):
-        ops.N.check(ops._lib().vla_rmsnorm_fwd(ops._st(), ops._p(x), ops._p(w), ops._p(out), ops._p(rstd), x.shape[0],
-                                               x.shape[1], self.cfg.eps), "rmsnorm_fwd")
+    def _keeps(self, i: int):
+        """(RMSNorm 1 output, RMSNorm 2 output, SwiGLU output) of layer i: per-layer slots, else shared scratch."""
+        return (self.N1[i], self.N2[i], self.Hs[i]) if self.per_layer else (self.nbuf, self.nbuf, self.hbuf)
 
     def _attn_views(self, t3):
         c = self.cfg
         a, b = c.heads * c.dh, (c.heads + c.kv_heads) * c.dh
         return t3[:, :, :a], t3[:, :, a:b], t3[:, :, b:]
 
-    def _attn_fwd(self, q3, i, b0, b1, S):
-        import ctypes as C
-        c = self.cfg
-        q, k, v = self._attn_views(q3)
-        o = self.AO[i].view(self.B, S, -1)[b0:b1]
-        km = self.kmask[b0:b1] if self.kmask is not None else None
-        d = ops._attn_desc(q, k, v, o, self.LSE[i][b0:b1], km, True, c.dh ** -0.5, c.heads, c.kv_heads, c.dh)
-        ops.N.check(ops._lib().vla_attn_fwd(ops._st(), C.byref(d)), "attn_fwd")
+    def fwd_layer(self, i: int):
+        """Layer i over the whole batch."""
+        c, B, S, lin = self.cfg, self.B, self.S, self._flin
+        D, H, KV, dh = c.d, c.heads, c.kv_heads, c.dh
+        L, k = self.layers[i], f"llm.{i}."
+        x, qkv, x1 = self.HS[i].view(-1, D), self.QKV[i], self.X1[i]
+        n1, n2, h = self._keeps(i)
+        # (RMSNorm folded into the neighbouring GEMMs - 47 launches fewer, built and measured SLOWER in round 3 - left the tree in
+        #  round 4: DESIGN section 4, tools/diag/gemm256_pruned_paths.patch)
+        n1 = lin._rms(x, L["n1"], n1, self.R1[i], c.eps)
+        if dh in (64, 128):   # RoPE fused into the projection's epilogue (head dim 128: the 128-row kernel's column map, round 4)
+            lin._lin(k + "qkv", n1, L["wqkv"], L["bqkv"], out=qkv, rope=(1, self.cos, self.sin, S, dh, (H + KV) * dh))
+        else:
+            lin._lin(k + "qkv", n1, L["wqkv"], L["bqkv"], out=qkv)
+            ops.rope_half_(qkv[:, :H * dh], self.cos, self.sin, S, H, dh)
+            ops.rope_half_(qkv[:, H * dh:(H + KV) * dh], self.cos, self.sin, S, KV, dh)
+        ops.attn_fwd(*self._attn_views(qkv.view(B, S, -1)), H, KV, dh, True, self.kmask, out=self.AO[i].view(B, S, -1), lse=self.LSE[i])
+        lin._lin(k + "o", self.AO[i], L["wo"], None, out=x1, residual=x)
+        n2 = lin._rms(x1, L["n2"], n2, self.R2[i], c.eps)
+        # the pre-activations are kept for the backward only: rows below the live window are never read again
+        lin._lin(k + "gu", n2, L["wgu"], None, act=ACT_SWIGLU, out=self.GU[i], out2=h, c_live=(S, self.gu_row0) if self.gu_row0 else None)
+        lin._lin(k + "down", h, L["wd"], None, out=self.HS[self.out_slot(i)].view(-1, D), residual=x1)
 
-    # ---- backward: dX only (frozen weights), restricted to the LIVE rows ------------------------------------------
+    def fwd_final(self):
+        """hidden_states[n] = final RMSNorm of the last layer's output (HF convention)."""
+        n, D = self.cfg.n_layers, self.cfg.d
+        ops.rmsnorm_fwd(self.HS[n + 1].view(-1, D), self.norm, self.cfg.eps, out=self.HS[n].view(-1, D), rstd=self.RF)
+
+    def enable_fp8(self):
+        """fp8 weight path (see ViT.enable_fp8): the frozen q|k|v and gate/up weights in e4m3, their inputs quantised inside
+        RMSNorm (vla_rmsnorm_fwd_q8); o-proj / down stay bf16.  Forward only: the dX products keep the bf16 W^T."""
+        for i, L in enumerate(self.layers):
+            self.lin.Q[f"llm.{i}.qkv"] = ops.quant_fp8_rows(L["wqkv"])
+            self.lin.Q[f"llm.{i}.gu"] = ops.quant_fp8_rows(L["wgu"])
+        self.lin.fp8 = True
+
+    # ---- backward: dX (frozen weights: adapter-only), restricted to the LIVE rows ------------------------------------------
     # The only trainable tensor upstream of the LLM is `action_queries`, spliced in at sequence positions >= r_first
     # (after tok0 + patches + prompt).  Causal attention makes row i of every hidden state a function of the input rows
     # <= i only, so d loss / d inputs_embeds[rows >= r0] depends on d loss / d hidden[rows >= r0] alone, for any
@@ -460,53 +526,70 @@ class LLM:
             self.bwd_layer(i, dHS)
         return self.bwd_result()
 
-    def bwd_begin(self, dHS: torch.Tensor, row0: int = 0, n_run: Optional[int] = None):
+    def bwd_begin(self, dHS: torch.Tensor, row0: Optional[int] = 0, n_run: Optional[int] = None, lin: Optional[Linear] = None):
+        """Gradient w.r.t. the output of the top layer that reached the loss.  row0: the live-row window (any row0 runs the
+        windowed kernels); None: the trainers' whole-sequence backward without a window.  lin: as in fwd_begin."""
         n, S, D = self.cfg.n_layers, self.S, self.cfg.d
         self._n_run = n if n_run is None else n_run
-        assert 0 <= row0 < S and row0 % 32 == 0, "live-row window must start on a multiple of 32"
-        assert row0 >= self.gu_row0, "the forward dropped backward-only rows this window needs"
-        self.r0, self.Rl = row0, S - row0
+        self._blin = lin = self.lin if lin is None else lin
+        if row0 is None:
+            self.r0, self.Rl, self._win = 0, S, None
+        else:
+            assert 0 <= row0 < S and row0 % 32 == 0, "live-row window must start on a multiple of 32"
+            assert row0 >= self.gu_row0, "the forward dropped backward-only rows this window needs"
+            self.r0, self.Rl = row0, S - row0
+            self._win = (self.Rl, S, row0)                    # (rows per sequence, sequence rows, first row)
         Mr = self.B * self.Rl
         assert tuple(dHS.shape[1:]) == (self.B, self.Rl, D)
-        self._win = (self.Rl, S, row0)                        # (rows per sequence, sequence rows, first row)
+        d = (self.G_res[self._n_run - 1] if self.per_layer else self.d_a)[:Mr]
         if self._n_run == n:
-            self._d = ops.rmsnorm_bwd(dHS[n].view(Mr, D), self.HS[n + 1].view(-1, D), self.norm, self.RF, out=self.d_a[:Mr],
-                                      x_rows=self._win)
+            self._d = ops.rmsnorm_bwd(dHS[n].view(Mr, D), self.HS[n + 1].view(-1, D), self.norm, self.RF, out=d, x_rows=self._win)
+            if lin.trains_vectors:
+                ops.rmsnorm_dw(dHS[n].view(Mr, D), self.HS[n + 1].view(-1, D), self.RF, lin.A("llm.norm"))
         else:           # hidden_states[n_run] is a raw layer output (no final norm behind it): its gradient is the head's alone
-            self._d = ops.copy2d(dHS[self._n_run].view(Mr, D), self.d_a[:Mr], Mr, D, D, D)
-        self._other = self.d_b[:Mr]
+            self._d = ops.copy2d(dHS[self._n_run].view(Mr, D), d, Mr, D, D, D)
 
     def bwd_layer(self, i: int, dHS: torch.Tensor):
-        c, B, S, r0, R = self.cfg, self.B, self.S, self.r0, self.Rl
-        n, M, D, H, KV, dh, I = c.n_layers, B * S, c.d, c.heads, c.kv_heads, c.dh, c.inter
-        Mr = B * R
-        L, d, other = self.layers[i], self._d, self._other
+        """dX through layer i: self._d (gradient w.r.t. its output, without the head's share) -> w.r.t. its input.  Per-layer
+        slots: every dY in the layer's own slot and everything that only feeds a parameter gradient handed to the trainer
+        (_lin_bwd, _defer); scratch: one buffer per role, reused by every layer."""
+        c, B, S, r0, R, lin = self.cfg, self.B, self.S, self.r0, self.Rl, self._blin
+        M, D, H, KV, dh, I = B * S, c.d, c.heads, c.kv_heads, c.dh, c.inter
+        Mr, tv, win = B * R, lin.trains_vectors, self._win
+        L, k, d = self.layers[i], f"llm.{i}.", self._d
+        _, n2, h = self._keeps(i)
+        if self.per_layer:
+            d1_out, d_out = self.G_d1[i], (self.G_res[i - 1] if i > 0 else self.d_last)[:Mr]
+            d_gu, d_qkv = self.G_gu[i][:Mr], self.G_qkv[i][:Mr]
+        else:
+            d1_out, d_out, d_gu, d_qkv = self.d_b[:Mr], d, self.d_gu[:Mr], self.d_qkv[:Mr]
         if i < self._n_run - 1:                         # head contribution to the output of layer i (the top layer's came in bwd_begin)
             ops.add_(d, dHS[i + 1].view(Mr, D))
-        gu_live = self.GU[i][r0:]                       # first sequence's window; the others by row-group addressing
-        d_gu, d_n = self.d_gu[:Mr], self.d_n[:Mr]
-        if I % 64 == 0 and not os.environ.get("VLA_NO_FUSED_SWIGLU_BWD"):   # dH GEMM + SwiGLU backward in its epilogue
-            ops.gemm_swiglu_bwd(d, L["wdT"], gu_live, out=d_gu, gu_group=(R, S * 2 * I))
-        else:
-            ops.gemm_nt(d, L["wdT"], out=self.d_h[:Mr])
-            gu_c = self.GU[i].view(B, S, 2 * I)[:, r0:].contiguous().view(Mr, 2 * I) if r0 else self.GU[i]
-            ops.swiglu_bwd(self.d_h[:Mr], gu_c, out=d_gu)
-        ops.gemm_nt(d_gu, L["wguT"], out=d_n)
-        d1 = ops.rmsnorm_bwd(d_n, self.X1[i], L["n2"], self.R2[i], dres=d, out=other, x_rows=self._win)
-        dao = ops.gemm_nt(d1, L["woT"], out=d_n)
-        q, k, v = self._attn_views(self.QKV[i].view(B, S, -1))
-        W = self.QKV.shape[-1]
-        d_qkv = self.d_qkv[:Mr]
-        dq, dk, dv = self._attn_views(d_qkv.view(B, R, W))
-        ops.attn_bwd(dao.view(B, R, -1), q[:, r0:], k, v, self.AO[i].view(B, S, -1)[:, r0:], self.LSE[i], H, KV, dh, True,
+        tap = lin.taps.get(("llm", i)) if lin.taps is not None else None
+        if tap is not None:
+            tap["d_out"] = d.clone()
+        # the first sequence's window of GU; the others by row-group addressing
+        d_gu = lin._lin_bwd(k + "down", d, h, L["wdT"], out=d_gu, swiglu_gu=self.GU[i][r0:], **({"gu_group": (R, S * 2 * I)} if win else {}))
+        d_n = lin._lin_bwd(k + "gu", d_gu, n2, L["wguT"], out=self.G_n2[i] if tv else self.d_n[:Mr])
+        if tv:
+            lin._defer(lambda dy=d_n, x=self.X1[i], r=self.R2[i], acc=lin.A(k + "n2"): ops.rmsnorm_dw(dy, x, r, acc))
+        d1 = ops.rmsnorm_bwd(d_n, self.X1[i], L["n2"], self.R2[i], dres=d, out=d1_out, x_rows=win)
+        dao = lin._lin_bwd(k + "o", d1, self.AO[i], L["woT"], out=self.d_n[:Mr])
+        q, kk, v = self._attn_views(self.QKV[i].view(B, S, -1))
+        dq, dk, dv = self._attn_views(d_qkv.view(B, R, -1))
+        ops.attn_bwd(dao.view(B, R, -1), q[:, r0:], kk, v, self.AO[i].view(B, S, -1)[:, r0:], self.LSE[i], H, KV, dh, True,
                      self.kmask, dq=dq, dk=dk, dv=dv, rope=(self.cos, self.sin) if dh in (64, 128) else None, row0=r0)
         if dh not in (64, 128):
             cs, sn = self.cos[r0:], self.sin[r0:]
             ops.rope_half_(d_qkv[:, :H * dh], cs, sn, R, H, dh, sign=-1)
             ops.rope_half_(d_qkv[:, H * dh:(H + KV) * dh], cs, sn, R, KV, dh, sign=-1)
-        ops.gemm_nt(d_qkv, L["wqkvT"], out=d_n)
-        d_new = ops.rmsnorm_bwd(d_n, self.HS[i].view(M, D), L["n1"], self.R1[i], dres=d1, out=d, x_rows=self._win)
-        self._d, self._other = d_new, d1
+        d_n = lin._lin_bwd(k + "qkv", d_qkv, self._keeps(i)[0], L["wqkvT"], out=self.G_n1[i] if tv else self.d_n[:Mr])
+        if tv:
+            lin._defer(lambda dy=d_qkv, acc=lin.A(k + "bqkv"): ops.colsum_(dy, acc))
+            lin._defer(lambda dy=d_n, x=self.HS[i].view(M, D), r=self.R1[i], acc=lin.A(k + "n1"): ops.rmsnorm_dw(dy, x, r, acc))
+        self._d = ops.rmsnorm_bwd(d_n, self.HS[i].view(M, D), L["n1"], self.R1[i], dres=d1, out=d_out, x_rows=win)
+        if tap is not None:
+            tap["d_in"] = self._d.clone()
 
     def bwd_result(self) -> torch.Tensor:
         return self._d.view(self.B, self.Rl, self.cfg.d)
@@ -784,7 +867,7 @@ class Head:
             ops.gemm_nt(x, P.view("w_x")[i], bias=P.view("b_x")[i], out=self.QKVx[i])
         self._attn(i, fwd=True)
         ops.gemm_nt(self.AOx[i], P.view("w_o")[i], bias=P.view("b_o")[i], residual=x, out=self.O2[i])
-        self._ln(self.O2[i], P.view("ln_w")[i], P.view("ln_b")[i], self.LNo[i], self.stats[i])
+        ops.layernorm_fwd(self.O2[i], P.view("ln_w")[i], P.view("ln_b")[i], 1e-5, out=self.LNo[i], stats=self.stats[i])
         ops.gemm_nt(self.LNo[i], P.view("w_ffn")[i], bias=P.view("b_ffn")[i], act=ACT_RELU, out=self.X[i + 1])
 
     def fwd_end(self) -> torch.Tensor:
@@ -793,12 +876,7 @@ class Head:
         self.pred = ops.gemm_nt(self.xf_ln, P.view("fc2_w"), bias=P.view("fc2_b"))
         return self.pred.view(self.B, self.cfg.chunk, self.cfg.action_dim)
 
-    def _ln(self, x, w, b, y, stats):
-        ops.N.check(ops._lib().vla_layernorm_fwd(ops._st(), ops._p(x), ops._p(w), ops._p(b), ops._p(y), ops._p(stats),
-                                                 x.shape[0], x.shape[1], x.stride(0), y.stride(0), 1e-5), "layernorm_fwd")
-
     def _attn(self, i: int, fwd: bool, dout=None):
-        import ctypes as C
         B, T, D, Ka, Kt, H = self.B, self.cfg.chunk, self.D, self.Ka, self.Kt, self.H
         qkv = self.QKVx[i].view(B, T, 3 * D)
         ka = self.KV_adp[i].view(B, Ka, 2 * D)
@@ -807,9 +885,7 @@ class Head:
         gate = self.P.view("gate")[i]
         out = self.AOx[i].view(B, T, D)
         if fwd:
-            d = ops.head_attn_desc(*args, gate, self.probs[i], out, H)
-            d.ref_softmax = int(self.ref_softmax)
-            ops.N.check(ops._lib().vla_head_attn_fwd(ops._st(), C.byref(d)), "head_attn_fwd")
+            ops.head_attn_fwd(*args, gate, H, self.ref_softmax, out=out, probs=self.probs[i])
         else:
             g = self.dQKVx[i].view(B, T, 3 * D)
             ga = self.dKV_adp[i].view(B, Ka, 2 * D)
@@ -863,10 +939,10 @@ class Head:
         P, D = self.P, self.D
         B, S, Kt, Ka = self.B, self.S, self.Kt, self.Ka
         dff = self.dFF[i]
-        ops.N.check(ops._lib().vla_relu_bwd(ops._st(), ops._p(self.dx), ops._p(self.X[i + 1]), ops._p(dff), self.dx.numel()), "relu_bwd")
+        ops.relu_bwd(self.dx, self.X[i + 1], out=dff)
         d_ln = ops.gemm_nt(dff, self.T["w_ffn"][i])
         do2 = self.dO2[i]
-        self._ln_bwd(d_ln, self.O2[i], P.view("ln_w")[i], self.stats[i], do2, self.ln_dw[i], self.ln_db[i])
+        ops.layernorm_bwd(d_ln, self.O2[i], P.view("ln_w")[i], self.stats[i], self.ln_dw[i], self.ln_db[i], out=do2)
         d_ao = ops.gemm_nt(do2, self.T["w_o"][i])
         self._attn(i, fwd=False, dout=d_ao)          # returns dq / dk already through the RoPE transpose
         self.dx = ops.gemm_nt(self.dQKVx[i], self.T["w_x"][i], residual=do2)
@@ -888,8 +964,7 @@ class Head:
         d_xln = ops.gemm_nt(dy1, self._t(P.view("fc1_w")))
         ops.layernorm_bwd(d_xln, self.x_in, P.view("ln1_w"), self.st1, self.ln1_dw, self.ln1_db, want_dx=False)
         # proprio projector backward (its token's gradient = sum over the blocks)
-        ops.N.check(ops._lib().vla_colsum_bf16(ops._st(), ops._p(self.dh_adp[0, NUM_TOKENS]), ops._p(self.d_pf32), nb, D, B * Ka * D, B,
-                                                Ka * D, D), "colsum(d_pf)")             # [nb, B, D] strided -> sum over the blocks
+        ops.colsum_(self.dh_adp.view(nb, B, Ka, D)[:, :, NUM_TOKENS].transpose(0, 1), self.d_pf32)      # [B, nb, D] strided -> sum over the blocks
         d_pf = ops.cast_f32_bf16(self.d_pf32)
         ops.colsum_(d_pf, self.b_f32["p_fc2_b"])
         self._dw(d_pf, self.pp_act, out=G("p_fc2_w"))
@@ -939,10 +1014,6 @@ class Head:
         """dW[N, K] = dY[R, N]^T . X[R, K] for the small one-off layers."""
         return ops.gemm_tn(dy, x, out=out, split=0)
 
-    def _ln_bwd(self, dy, x, w, stats, dx, dw, db):
-        ops.N.check(ops._lib().vla_layernorm_bwd(ops._st(), ops._p(dy), ops._p(x), ops._p(w), ops._p(stats), ops._p(dx), ops._p(dw),
-                                                 ops._p(db), x.shape[0], x.shape[1], x.stride(0), dy.stride(0), dx.stride(0)), "layernorm_bwd")
-
 
 # ------------------------------------------------------------------------------------------------ whole model
 class VLAEngine:
@@ -952,7 +1023,7 @@ class VLAEngine:
         """weights = dict(vit=[sd...], proj=sd, llm=sd (HF names without 'model.' prefix incl. embed_tokens/norm),
         head=sd, proprio=sd, action_queries=tensor)."""
         self.cfg, self.device = cfg, device
-        self.vits = [ViT(c, sd, device) for c, sd in zip(cfg.vit, weights["vit"])]
+        self.vits = [ViT(c, sd, device, j) for j, (c, sd) in enumerate(zip(cfg.vit, weights["vit"]))]
         self.llm = LLM(cfg.llm, weights["llm"], device)
         self.head = Head(cfg, device)
         self.head.load_state_dicts(weights["head"], weights["proprio"], weights.get("action_queries"))
@@ -1108,8 +1179,7 @@ class VLAEngine:
         # target of sequence row s = multimodal label of row s + 1; the last row has none
         tgt = torch.full((B, S), IGNORE_INDEX, device=self.device, dtype=torch.int64)
         tgt[:, Np:S - 1] = labels[:, 1:]                  # rows Np .. S-2 predict text tokens 1 .. L-1 (row 0 predicts a patch: ignored)
-        out2 = torch.zeros(2, device=self.device, dtype=torch.float32)
-        ops.N.check(ops._lib().vla_token_ce(ops._st(), ops._p(logits), V, ops._p(tgt), B * S, V, ops._p(out2)), "token_ce")
+        out2 = ops.token_ce(logits, tgt, torch.zeros(2, device=self.device, dtype=torch.float32))
         return out2[0] / out2[1], logits
 
     def _vision_and_embed(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -1138,24 +1208,31 @@ class VLAEngine:
         self.B, self.S, self.Np = B, L + Np, Np
 
     def _vision_backbone(self, j: int, batch: Dict[str, torch.Tensor]):
-        """Backbone j over ALL images of the batch in one pass (modeling_prismatic.py:196-237 runs them one by one): image
-        `im` uses channels 3*(im*n_backbones + j) .. +2 and fills feats[:, im*npi:(im+1)*npi, column block of backbone j]."""
-        cfg, vit, px = self.cfg, self.vits[j], batch["pixel_values"]
-        B, Np, nbk, npi = self.B, self.Np, len(cfg.vit), cfg.vit[0].n_patches
-        col = sum(v.cfg.d for v in self.vits[:j])
-        if nbk == 1 and cfg.n_img == 1:
-            vit.forward(px, 0, self.feats.view(B * Np, -1))
-            return
+        """Backbone j over ALL images of the batch in one pass (modeling_prismatic.py:196-237 runs them one by one) -> its
+        column block of feats.  One backbone, one image, no prefix tokens: the last block writes the features in place."""
+        vit = self.vits[j]
+        direct = len(self.vits) == 1 and self.cfg.n_img == 1 and vit.cfg.n_prefix == 0
+        x = vit.forward(*self._stacked_pixels(j, batch["pixel_values"]), out=self.feats.view(self.B * self.Np, -1) if direct else None)
+        if not direct:
+            self._scatter_feats(j, x)
+
+    def _stacked_pixels(self, j: int, px: torch.Tensor):
+        """Images of backbone j stacked along the batch: ([n_img * B, C, H, W] tensor, first channel).  Image `im` uses channels
+        3*(im*n_backbones + j) .. +2."""
+        cfg, nbk = self.cfg, len(self.cfg.vit)
         if cfg.n_img == 1:
-            stacked, c0 = px, 3 * j
-        else:          # [n_img * B, 3, H, W]: the images of one backbone stacked along the batch
-            stacked = torch.cat([px[:, 3 * (im * nbk + j):3 * (im * nbk + j) + 3] for im in range(cfg.n_img)], 0).contiguous()
-            c0 = 0
-        tmp = torch.empty(cfg.n_img * B * npi, vit.cfg.d, device=self.device, dtype=BF16)
-        vit.forward(stacked, c0, tmp)
-        t4 = tmp.view(cfg.n_img, B, npi, vit.cfg.d)
+            return px, 3 * j
+        return torch.cat([px[:, 3 * (im * nbk + j):3 * (im * nbk + j) + 3] for im in range(cfg.n_img)], 0).contiguous(), 0
+
+    def _scatter_feats(self, j: int, x: torch.Tensor):
+        """Patch features of backbone j (its last block's output [n_img * B * T, d]; prefix tokens dropped, no final norm) ->
+        feats[:, im*npi:(im+1)*npi, column block of backbone j] for every image im."""
+        cfg, vc, B, feats = self.cfg, self.vits[j].cfg, self.B, self.feats
+        npi, T, d, vis = vc.n_patches, vc.n_patches + vc.n_prefix, vc.d, cfg.vis_dim
+        col = sum(v.cfg.d for v in self.vits[:j])
+        x3 = x.view(-1, T, d)
         for im in range(cfg.n_img):
-            self.feats[:, im * npi:(im + 1) * npi, col:col + vit.cfg.d] = t4[im]
+            ops.copy_rows3d(x3[im * B, vc.n_prefix:], feats[0, im * npi:, col:], B, npi, d, T * d, d, feats.shape[1] * vis, vis)
 
     def _vision_project(self):
         """PrismaticProjector (modeling_prismatic.py:261-273) -> self.patches."""

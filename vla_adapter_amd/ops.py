@@ -342,36 +342,40 @@ def transpose(x: torch.Tensor, ld_out: Optional[int] = None, out: Optional[torch
     return out
 
 
-def layernorm_fwd(x, w, b, eps: float, want_stats: bool = False):
+def layernorm_fwd(x, w, b, eps: float, want_stats: bool = False, out=None, stats=None):
+    """out / stats: [rows, cols] bf16 / [rows, 2] f32 destinations (default: new tensors; stats only with want_stats)."""
     _chk_bf16(x, w, b)
     cols = x.shape[-1]
     x2 = x.reshape(-1, cols)
     assert x2.stride(-1) == 1
-    y = torch.empty_like(x2)
-    stats = torch.empty(x2.shape[0], 2, device=x.device, dtype=torch.float32) if want_stats else None
+    y = torch.empty_like(x2) if out is None else out
+    if want_stats and stats is None:
+        stats = torch.empty(x2.shape[0], 2, device=x.device, dtype=torch.float32)
     N.check(_lib().vla_layernorm_fwd(_st(), _p(x2), _p(w), _p(b), _p(y), _p(stats), x2.shape[0], cols, x2.stride(0),
                                      y.stride(0), eps), "layernorm_fwd")
     return (y.view(x.shape), stats) if want_stats else y.view(x.shape)
 
 
 def layernorm_bwd(dy, x, w, stats, dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None,
-                  want_dx: bool = True):
+                  want_dx: bool = True, out=None):
     _chk_bf16(dy, x, w)
     cols = x.shape[-1]
     x2, dy2 = x.reshape(-1, cols), dy.reshape(-1, cols)
-    dx = torch.empty_like(x2) if want_dx else None
+    dx = out if out is not None else torch.empty_like(x2) if want_dx else None
     N.check(_lib().vla_layernorm_bwd(_st(), _p(dy2), _p(x2), _p(w), _p(stats), _p(dx), _p(dw), _p(db), x2.shape[0], cols,
                                      x2.stride(0), dy2.stride(0), dx.stride(0) if dx is not None else cols), "layernorm_bwd")
     return dx.view(x.shape) if dx is not None else None
 
 
-def rmsnorm_fwd(x, w, eps: float, want_rstd: bool = False, out=None):
+def rmsnorm_fwd(x, w, eps: float, want_rstd: bool = False, out=None, rstd=None):
+    """rstd: f32 [rows] destination of the reciprocal RMS (default: a new tensor with want_rstd, else not stored)."""
     _chk_bf16(x, w)
     cols = x.shape[-1]
     assert x.is_contiguous()
     rows = x.numel() // cols
     y = torch.empty_like(x) if out is None else out
-    rstd = torch.empty(rows, device=x.device, dtype=torch.float32) if want_rstd else None
+    if want_rstd and rstd is None:
+        rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
     N.check(_lib().vla_rmsnorm_fwd(_st(), _p(x), _p(w), _p(y), _p(rstd), rows, cols, eps), "rmsnorm_fwd")
     return (y, rstd) if want_rstd else y
 
@@ -416,6 +420,13 @@ def rmsnorm_bwd(dy, x, w, rstd, dres=None, out=None, x_rows=None):
     return dx
 
 
+def rmsnorm_dw(dy, x, rstd, acc_f32):
+    """acc_f32 [cols] += sum over the rows of dy * x * rstd (the RMSNorm weight gradient; dy / x [rows, cols] contiguous)."""
+    rows, cols = dy.shape
+    N.check(_lib().vla_rmsnorm_dw(_st(), _p(dy), _p(x), _p(rstd), _p(acc_f32), rows, cols), "rmsnorm_dw")
+    return acc_f32
+
+
 def _attn_desc(q, k, v, o, lse, kmask, causal, scale, Hq, Hkv, dh):
     """q [B,Sq,>=Hq*dh], k/v [B,Sk,>=Hkv*dh] views (last-dim stride 1), o [B,Sq,Hq*dh]."""
     d = N.AttnDesc()
@@ -430,14 +441,16 @@ def _attn_desc(q, k, v, o, lse, kmask, causal, scale, Hq, Hkv, dh):
 
 
 def attn_fwd(q, k, v, Hq: int, Hkv: int, dh: int, causal: bool, kmask=None, scale: Optional[float] = None,
-             want_lse: bool = False):
+             want_lse: bool = False, out=None, lse=None):
+    """out [B, Sq, Hq*dh] / lse f32 [B, Hq, Sq]: destinations (default: new tensors; lse only with want_lse)."""
     _chk_bf16(q, k, v)
     assert q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1
     B, Sq = q.shape[:2]
     if kmask is not None:
         assert kmask.dtype == torch.uint8 and kmask.is_contiguous() and tuple(kmask.shape) == (B, k.shape[1])
-    o = torch.empty(B, Sq, Hq * dh, device=q.device, dtype=BF16)
-    lse = torch.empty(B, Hq, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    o = torch.empty(B, Sq, Hq * dh, device=q.device, dtype=BF16) if out is None else out
+    if want_lse and lse is None:
+        lse = torch.empty(B, Hq, Sq, device=q.device, dtype=torch.float32)
     d = _attn_desc(q, k, v, o, lse, kmask, causal, scale if scale is not None else dh ** -0.5, Hq, Hkv, dh)
     N.check(_lib().vla_attn_fwd(_st(), C.byref(d)), "attn_fwd")
     return (o, lse) if want_lse else o
@@ -562,20 +575,21 @@ def add_(a, b):
     return a
 
 
-def gelu_fwd(x):
-    y = torch.empty_like(x)
+def gelu_fwd(x, out=None):
+    y = torch.empty_like(x) if out is None else out
     N.check(_lib().vla_gelu_fwd(_st(), _p(x), _p(y), x.numel()), "gelu_fwd")
     return y
 
 
-def gelu_bwd(dy, x):
-    dx = torch.empty_like(x)
+def gelu_bwd(dy, x, out=None):
+    """out may be dy itself (in place)."""
+    dx = torch.empty_like(x) if out is None else out
     N.check(_lib().vla_gelu_bwd(_st(), _p(dy), _p(x), _p(dx), x.numel()), "gelu_bwd")
     return dx
 
 
-def relu_bwd(dy, y):
-    dx = torch.empty_like(y)
+def relu_bwd(dy, y, out=None):
+    dx = torch.empty_like(y) if out is None else out
     N.check(_lib().vla_relu_bwd(_st(), _p(dy), _p(y), _p(dx), y.numel()), "relu_bwd")
     return dx
 
@@ -625,15 +639,16 @@ def head_attn_desc(q, ks, vs, ka, va, kt, vt, gate, probs, out, H: int):
     return d
 
 
-def head_attn_fwd(q, ks, vs, ka, va, kt, vt, gate, H: int = 8, ref_softmax: bool = False):
-    """q/ks/vs [B,T,D*], ka/va [B,Ka,D*], kt/vt [B,Kt,D*] (views, last stride 1) -> out [B,T,D], probs f32.
-    ref_softmax: weights rounded to bf16 after normalisation, as ATen's bf16 softmax emits them (two passes over the keys)."""
+def head_attn_fwd(q, ks, vs, ka, va, kt, vt, gate, H: int = 8, ref_softmax: bool = False, out=None, probs=None):
+    """q/ks/vs [B,T,D*], ka/va [B,Ka,D*], kt/vt [B,Kt,D*] (views, last stride 1) -> out [B,T,D], probs f32 [B,H,T,T+Ka+Kt]
+    (given or new).  ref_softmax: weights rounded to bf16 after normalisation, as ATen's bf16 softmax emits them (two passes
+    over the keys)."""
     _chk_bf16(q, ks, vs, ka, va, kt, vt, gate)
     B, T = q.shape[:2]
     D = q.shape[-1]
     Nn = T + ka.shape[1] + kt.shape[1]
-    out = torch.empty(B, T, D, device=q.device, dtype=BF16)
-    probs = torch.empty(B, H, T, Nn, device=q.device, dtype=torch.float32)
+    out = torch.empty(B, T, D, device=q.device, dtype=BF16) if out is None else out
+    probs = torch.empty(B, H, T, Nn, device=q.device, dtype=torch.float32) if probs is None else probs
     d = head_attn_desc(q, ks, vs, ka, va, kt, vt, gate, probs, out, H)
     d.ref_softmax = int(ref_softmax)
     N.check(_lib().vla_head_attn_fwd(_st(), C.byref(d)), "head_attn_fwd")
@@ -736,6 +751,31 @@ def zero_(t: torch.Tensor):
 
 def head_index_prep(pos1, pos0, cnt0, gather, scatter, guard, B: int, S: int, Np: int, row0: int):
     N.check(_lib().vla_head_index_prep(_st(), _p(pos1), _p(pos0), _p(cnt0), _p(gather), _p(scatter), _p(guard), B, S, Np, row0), "head_index_prep")
+
+
+def embed_grad(dx, ids, qidx, out, Np: int):
+    """Token-embedding gradient: out [V, D] += the rows of dx [B, L + Np, D] that hold a looked-up token (ids [B, L]; qidx: the
+    action-query slots, which read no table row)."""
+    B, L = ids.shape
+    V, D = out.shape
+    N.check(_lib().vla_embed_grad(_st(), _p(dx), _p(ids), _p(qidx), _p(out), B, L, Np, D, V), "embed_grad")
+    return out
+
+
+def token_ce(logits, tgt, out_f32):
+    """out_f32[0] += sum of logsumexp(logits) - logits[tgt], out_f32[1] += count, over the rows of logits [rows, V] whose target
+    (tgt int64 [rows]) is not IGNORE_INDEX."""
+    V = logits.shape[-1]
+    N.check(_lib().vla_token_ce(_st(), _p(logits), V, _p(tgt), logits.numel() // V, V, _p(out_f32)), "token_ce")
+    return out_f32
+
+
+def token_ce_bwd(logits, tgt, sums_f32, gscale: float, out):
+    """d loss / d logits = gscale (softmax - onehot) / count (sums_f32 from token_ce); out may be logits itself (in place)."""
+    V = logits.shape[-1]
+    N.check(_lib().vla_token_ce_bwd(_st(), _p(logits), V, _p(tgt), logits.numel() // V, V, _p(sums_f32), gscale, _p(out), V),
+            "token_ce_bwd")
+    return out
 
 
 def add_scalar_f32_(x: torch.Tensor, s: torch.Tensor):

@@ -29,7 +29,6 @@ biases, the token embedding.  The action head, the proprio projector and the act
 from __future__ import annotations
 
 import contextlib
-import ctypes as C
 import math
 import os
 import time
@@ -40,7 +39,7 @@ import torch
 from . import engine as E
 from . import ops, schedule
 from .schedule import Segment, capture_graph, chunks
-from .ops import ACT_GELU, ACT_GELU_TANH, ACT_NONE, ACT_SWIGLU, BF16
+from .ops import BF16
 
 rup = E.rup
 
@@ -134,20 +133,24 @@ class _Slot:
             setattr(self.holder, self.key, t)
 
 
-class BackboneTrainer:
-    """Training forward / backward through ViT(s) -> projector -> Qwen2 stack -> action head, shared by both modes."""
+class BackboneTrainer(E.Linear):
+    """Training forward / backward through ViT(s) -> projector -> Qwen2 stack -> action head, shared by both modes.  The layers are
+    the engine's own (ViT.forward / block, LLM.fwd_layer / bwd_layer), run with the trainer as their Linear."""
 
     mode = "?"
+    keep_norm_out = True         # (LoRA fp8: the bf16 norm outputs feed the adapter products and their gradients)
 
     def __init__(self, eng: E.VLAEngine):
         cfg = eng.cfg
         assert not getattr(eng, "fp8_frozen", False), "engine.enable_fp8_frozen() is the adapter-only forward's opt-in; LoRA has its own (LoRAFinetune(fp8=True))"
-        self.eng, self.cfg, self.dev = eng, cfg, eng.device
+        super().__init__(eng.device)
+        self.eng, self.cfg = eng, cfg
         self.vits, self.llm, self.head = eng.vits, eng.llm, eng.head
         for v in self.vits:
             assert not v.cfg.gelu_tanh, "tanh-GELU backward is not built (no backbone of the reference uses it)"
             v.fold_layerscale(False)                 # LayerScale acts as its own (trainable or frozen) parameter from here on
         eng.full_llm_backward = True
+        self.llm.keep_per_layer(self.trains_vectors)
         self.step_count = 0
         self._key = None
         # test hook: {("llm", i) | ("vit", j, i): {}} -> the backward fills "d_out" (gradient w.r.t. the layer's output) and "d_in"
@@ -179,13 +182,7 @@ class BackboneTrainer:
         # streams (eagerly: the segment's stream; captured: the kind's capture stream, whose graphs replay on that same stream)
         self._lane = "M"
 
-    # ---- mode hooks ---------------------------------------------------------------------------------------------
-    def _lin(self, key, x, W, bias=None, **kw):
-        raise NotImplementedError
-
-    def _lin_bwd(self, key, dy, x, WT, out=None, swiglu_gu=None):
-        raise NotImplementedError
-
+    # ---- mode hooks (besides the Linear's _lin / _lin_bwd) ---------------------------------------------------------
     trains_vectors = False       # norms / biases / LayerScale / pos-embed / prefix tokens / patch embedding / token embedding
 
     def A(self, name):
@@ -216,83 +213,17 @@ class BackboneTrainer:
             if vc.n_prefix:
                 st["pe"] = e(Bv * vc.n_patches, d)
             self.V.append(st)
-        c = cfg.llm
-        n, D, I = c.n_layers, c.d, c.inter
-        M = B * S
-        self.N1, self.N2, self.Hs = e(n, M, D), e(n, M, D), e(n, M, I)
-        W_ = (c.heads + 2 * c.kv_heads) * c.dh
-        # per-layer dY of the four Linears (residual-stream gradient = dY of down_proj, d1 = dY of o_proj): 3.4 GB at batch 16
-        self.G_res, self.G_d1, self.G_gu, self.G_qkv = e(n, M, D), e(n, M, D), e(n, M, 2 * I), e(n, M, W_)
-        self.d_last = e(M, D)
-        if self.trains_vectors:       # dY of the two RMSNorms per layer: their weight gradients run on the gradient stream too (0.5 GB)
-            self.G_n1, self.G_n2 = e(n, M, D), e(n, M, D)
+        self.llm._alloc(B, S)          # (per-layer activations and dY of the LLM: LLM.keep_per_layer)
         self.dfeats = e(B * cfg.n_patches, cfg.vis_dim)
-        self.dp = e(B * cfg.n_patches, D)
+        self.dp = e(B * cfg.n_patches, cfg.llm.d)
         self.pj = {}
         self._key = (B, S)
 
     # ---- forward ------------------------------------------------------------------------------------------------
-    def _ln(self, x, w, b, y, st, eps):
-        d = x.shape[1]
-        ops.N.check(ops._lib().vla_layernorm_fwd(ops._st(), ops._p(x), ops._p(w), ops._p(b), ops._p(y), ops._p(st), x.shape[0], d, d, d, eps), "layernorm_fwd")
-
-    def _rms(self, x, w, out, rstd):
-        self.llm._rms(x, w, out, rstd)
-
-    def _ln_bwd(self, dy, x, w, st, dx, dw, db):
-        d = x.shape[1]
-        ops.N.check(ops._lib().vla_layernorm_bwd(ops._st(), ops._p(dy), ops._p(x), ops._p(w), ops._p(st), ops._p(dx), ops._p(dw), ops._p(db),
-                                                 x.shape[0], d, d, d, d), "layernorm_bwd")
-
-    def _stacked_pixels(self, j: int, px: torch.Tensor):
-        """Images of backbone j stacked along the batch: ([n_img * B, C, H, W] tensor, first channel) - engine._vision_backbone."""
-        cfg, nbk = self.cfg, len(self.cfg.vit)
-        if cfg.n_img == 1:
-            return px, 3 * j
-        return torch.cat([px[:, 3 * (im * nbk + j):3 * (im * nbk + j) + 3] for im in range(cfg.n_img)], 0).contiguous(), 0
-
     def _vit_forward(self, j: int, px: torch.Tensor):
-        v, st, cfg = self.vits[j], self.V[j], self.cfg
-        vc = v.cfg
-        stacked, c0 = self._stacked_pixels(j, px)
-        Bv, Np, T, d = stacked.shape[0], vc.n_patches, vc.n_patches + vc.n_prefix, vc.d
-        X = st["X"]
-        st["cols"] = ops.im2col_patch(stacked, c0, vc.patch, v.kpe)
-        if vc.n_prefix:
-            ops.gemm_nt(st["cols"], v.wpe, bias=v.bpe, residual=v.pos, res_mod=Np, out=st["pe"])
-            x3 = X[0].view(Bv, T, d)
-            ops.copy_rows3d(st["pe"], x3[0, vc.n_prefix:], Bv, Np, d, Np * d, d, T * d, d)
-            ops.copy_rows3d(v.prefix, x3, Bv, vc.n_prefix, d, 0, d, T * d, d)               # cls + register tokens, broadcast over the batch
-        else:
-            ops.gemm_nt(st["cols"], v.wpe, bias=v.bpe, residual=v.pos, res_mod=Np, out=X[0])
-        dh = d // vc.heads
-        for i, b in enumerate(v.blocks):
-            x, k = X[i], f"vit{j}.{i}."
-            self._ln(x, b["n1w"], b["n1b"], st["H1"][i], st["S1"][i], vc.eps)
-            qkv = self._lin(k + "qkv", st["H1"][i], b["wqkv"], b["bqkv"], out=st["QKV"][i]).view(Bv, T, 3 * d)
-            dsc = ops._attn_desc(qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], st["A"][i].view(Bv, T, d), st["LSE"][i], None, False,
-                                 dh ** -0.5, vc.heads, vc.heads, dh)
-            ops.N.check(ops._lib().vla_attn_fwd(ops._st(), C.byref(dsc)), "attn_fwd")
-            if vc.layerscale:
-                self._lin(k + "proj", st["A"][i], b["wproj"], b["bproj"], out=st["PA"][i])
-                ops.layerscale_fwd(st["PA"][i], b["ls1"], x, out=st["Xm"][i])
-            else:
-                self._lin(k + "proj", st["A"][i], b["wproj"], b["bproj"], out=st["Xm"][i], residual=x)
-            xm = st["Xm"][i]
-            self._ln(xm, b["n2w"], b["n2b"], st["H2"][i], st["S2"][i], vc.eps)
-            self._lin(k + "fc1", st["H2"][i], b["w1"], b["b1"], out=st["Mpre"][i])          # pre-activation kept for the GELU backward
-            ops.N.check(ops._lib().vla_gelu_fwd(ops._st(), ops._p(st["Mpre"][i]), ops._p(st["Mact"][i]), st["Mpre"][i].numel()), "gelu_fwd")
-            if vc.layerscale:
-                self._lin(k + "fc2", st["Mact"][i], b["w2"], b["b2"], out=st["PM"][i])
-                ops.layerscale_fwd(st["PM"][i], b["ls2"], xm, out=X[i + 1])
-            else:
-                self._lin(k + "fc2", st["Mact"][i], b["w2"], b["b2"], out=X[i + 1], residual=xm)
-        # patch features (prefix tokens dropped, no final norm) -> this backbone's column block of the fused feature buffer
-        feats, B, npi = self.eng.feats, self.eng.B, vc.n_patches
-        vis, col = cfg.vis_dim, sum(u.cfg.d for u in self.vits[:j])
-        out3 = X[len(v.blocks)].view(Bv, T, d)
-        for im in range(cfg.n_img):
-            ops.copy_rows3d(out3[im * B, vc.n_prefix:], feats[0, im * npi:, col:], B, npi, d, T * d, d, feats.shape[1] * vis, vis)
+        """Backbone j with its per-block activations kept in V[j] -> its column block of the engine's feature buffer."""
+        eng = self.eng
+        eng._scatter_feats(j, self.vits[j].forward(*eng._stacked_pixels(j, px), lin=self, st=self.V[j]))
 
     def _proj_forward(self):
         eng, cfg, pj = self.eng, self.cfg, self.eng.proj
@@ -310,80 +241,27 @@ class BackboneTrainer:
             self._lin("proj.fc2", P["act1"], pj["fc2.weight"], pj["fc2.bias"], out=dst)
 
     def _llm_fwd_layers(self, lo: int, hi: int):
-        llm, c = self.llm, self.cfg.llm
-        B, S = self.eng.B, self.eng.S
-        D, H, KV, dh = c.d, c.heads, c.kv_heads, c.dh
+        llm = self.llm
         for i in range(lo, hi):
-            L = llm.layers[i]
-            x, k = llm.HS[i].view(-1, D), f"llm.{i}."
-            self._rms(x, L["n1"], self.N1[i], llm.R1[i])
-            qkv = llm.QKV[i]
-            if dh in (64, 128):   # RoPE in the projection's epilogue (the LoRA delta is already inside the accumulator)
-                self._lin(k + "qkv", self.N1[i], L["wqkv"], L["bqkv"], out=qkv, rope=(1, llm.cos, llm.sin, S, dh, (H + KV) * dh))
-            else:
-                self._lin(k + "qkv", self.N1[i], L["wqkv"], L["bqkv"], out=qkv)
-                ops.rope_half_(qkv[:, :H * dh], llm.cos, llm.sin, S, H, dh)
-                ops.rope_half_(qkv[:, H * dh:(H + KV) * dh], llm.cos, llm.sin, S, KV, dh)
-            llm._attn_fwd(qkv.view(B, S, -1), i, 0, B, S)
-            x1 = llm.X1[i]
-            self._lin(k + "o", llm.AO[i], L["wo"], None, out=x1, residual=x)
-            self._rms(x1, L["n2"], self.N2[i], llm.R2[i])
-            self._lin(k + "gu", self.N2[i], L["wgu"], None, act=ACT_SWIGLU, out=llm.GU[i], out2=self.Hs[i])
-            self._lin(k + "down", self.Hs[i], L["wd"], None, out=llm.HS[llm.out_slot(i)].view(-1, D), residual=x1)
-        if hi == c.n_layers:
+            llm.fwd_layer(i)
+        if hi == self.cfg.llm.n_layers:
             llm.fwd_final()
 
     # ---- backward pieces (stateless between calls: every gradient that crosses a piece boundary lives in a per-layer slot) -----
     def _llm_bwd_layers(self, lo: int, hi: int):
-        """dX chain through layers hi-1 .. lo.  Everything that only feeds a parameter gradient (dW / LoRA-pair TN products, bias
-        column sums) is handed to _defer / _defer_tn and runs on the gradient stream."""
-        llm, c, B, S = self.llm, self.cfg.llm, self.eng.B, self.eng.S
-        n, D, H, KV, dh, I = c.n_layers, c.d, c.heads, c.kv_heads, c.dh, c.inter
-        M = B * S
-        lib, st, p = ops._lib(), ops._st, ops._p
-        tv, dHS = self.trains_vectors, self._dHS
-        if hi == n:                                        # backward of the final norm into the top layer's slot
-            ops.rmsnorm_bwd(dHS[n].view(M, D), llm.HS[n + 1].view(M, D), llm.norm, llm.RF, out=self.G_res[n - 1])
-            if tv:
-                ops.N.check(lib.vla_rmsnorm_dw(st(), p(dHS[n].view(M, D)), p(llm.HS[n + 1].view(M, D)), p(llm.RF), p(self.A("llm.norm")), M, D), "rmsnorm_dw")
+        """dX chain through layers hi-1 .. lo (LLM.bwd_layer with the trainer as its Linear).  Everything that only feeds a parameter
+        gradient (dW / LoRA-pair TN products, bias column sums, RMSNorm weight sums) is handed to _defer / _defer_tn and runs on the
+        gradient stream."""
+        llm = self.llm
+        if hi == self.n_active:                            # backward of the final norm (or the head's gradient) into the top layer's slot
+            llm.bwd_begin(self._dHS, None, self.n_active, lin=self)
         for i in range(hi - 1, lo - 1, -1):
-            L, k = llm.layers[i], f"llm.{i}."
-            d = self.G_res[i]
-            if i == self.n_active - 1 and i < n - 1:       # top ACTIVE layer below dead ones: its output gradient is the head's alone
-                ops.copy2d(dHS[i + 1].view(M, D), d, M, D, D, D)
-            elif i < n - 1:
-                ops.add_(d, dHS[i + 1].view(M, D))
-            tap = self.taps.get(("llm", i)) if self.taps is not None else None
-            if tap is not None:
-                tap["d_out"] = d.clone()
-            d_gu = self._lin_bwd(k + "down", d, self.Hs[i], L["wdT"], out=self.G_gu[i], swiglu_gu=llm.GU[i])
-            d_n = self._lin_bwd(k + "gu", d_gu, self.N2[i], L["wguT"], out=self.G_n2[i] if tv else llm.d_n[:M])
-            if tv:
-                self._defer(lambda dy=d_n, x=llm.X1[i], r=llm.R2[i], acc=self.A(k + "n2"):
-                            ops.N.check(ops._lib().vla_rmsnorm_dw(ops._st(), ops._p(dy), ops._p(x), ops._p(r), ops._p(acc), M, D), "rmsnorm_dw"))
-            d1 = ops.rmsnorm_bwd(d_n, llm.X1[i], L["n2"], llm.R2[i], dres=d, out=self.G_d1[i])
-            dao = self._lin_bwd(k + "o", d1, llm.AO[i], L["woT"], out=llm.d_n[:M])
-            q, kk, v = llm._attn_views(llm.QKV[i].view(B, S, -1))
-            d_qkv = self.G_qkv[i]
-            dq, dk, dv = llm._attn_views(d_qkv.view(B, S, -1))
-            ops.attn_bwd(dao.view(B, S, -1), q, kk, v, llm.AO[i].view(B, S, -1), llm.LSE[i], H, KV, dh, True, llm.kmask, dq=dq, dk=dk, dv=dv,
-                         rope=(llm.cos, llm.sin) if dh in (64, 128) else None)
-            if dh not in (64, 128):
-                ops.rope_half_(d_qkv[:, :H * dh], llm.cos, llm.sin, S, H, dh, sign=-1)
-                ops.rope_half_(d_qkv[:, H * dh:(H + KV) * dh], llm.cos, llm.sin, S, KV, dh, sign=-1)
-            d_n = self._lin_bwd(k + "qkv", d_qkv, self.N1[i], L["wqkvT"], out=self.G_n1[i] if tv else llm.d_n[:M])
-            if tv:
-                self._defer(lambda dy=d_qkv, acc=self.A(k + "bqkv"): ops.colsum_(dy, acc))
-                self._defer(lambda dy=d_n, x=llm.HS[i].view(M, D), r=llm.R1[i], acc=self.A(k + "n1"):
-                            ops.N.check(ops._lib().vla_rmsnorm_dw(ops._st(), ops._p(dy), ops._p(x), ops._p(r), ops._p(acc), M, D), "rmsnorm_dw"))
-            d = ops.rmsnorm_bwd(d_n, llm.HS[i].view(M, D), L["n1"], llm.R1[i], dres=d1, out=self.G_res[i - 1] if i > 0 else self.d_last)
-            if tap is not None:
-                tap["d_in"] = d.clone()
+            llm.bwd_layer(i, self._dHS)
 
     def _mid_backward(self):
         """Between the LLM and the vision backward: action-query gradient, token-embedding gradient, projector."""
         eng, head = self.eng, self.head
-        dX0 = self.d_last.view(eng.B, eng.S, self.cfg.llm.d)          # gradient w.r.t. inputs_embeds
+        dX0 = self.llm.d_last.view(eng.B, eng.S, self.cfg.llm.d)      # gradient w.r.t. inputs_embeds
         dq = ops.action_query_grad(dX0, eng.pos0, eng.Np, 0)
         ops.cast_f32_bf16(dq, out=head.P.g("action_queries"))
         self._embed_backward(dX0)
@@ -453,12 +331,12 @@ class BackboneTrainer:
             if tv:
                 cs(dh_, a("b2"))
             dm = self._lin_bwd(k + "fc2", dh_, st["Mact"][i], b["w2T"], out=st["G_pre"][i])
-            ops.N.check(ops._lib().vla_gelu_bwd(ops._st(), ops._p(dm), ops._p(st["Mpre"][i]), ops._p(dm), dm.numel()), "gelu_bwd")   # in place
+            ops.gelu_bwd(dm, st["Mpre"][i], out=dm)        # in place
             dpre = dm
             if tv:
                 cs(dpre, a("b1"))
             dh2 = self._lin_bwd(k + "fc1", dpre, st["H2"][i], b["w1T"], out=st["g_d"])
-            self._ln_bwd(dh2, st["Xm"][i], b["n2w"], st["S2"][i], dxm, a("n2w"), a("n2b"))
+            ops.layernorm_bwd(dh2, st["Xm"][i], b["n2w"], st["S2"][i], a("n2w"), a("n2b"), out=dxm)
             ops.add_(dxm, dx)                            # residual
             # x_mid = x_in + ls1 * proj(attn(qkv(LN1(x_in))))
             da_ = ops.layerscale_bwd(dxm, st["PA"][i] if tv else None, b["ls1"], a("ls1"), out=st["G_proj"][i]) if ls else dxm
@@ -476,7 +354,7 @@ class BackboneTrainer:
             if i == 0 and not tv:
                 return                                   # below block 0 everything is frozen (Conv2d patch embedding, pos_embed, tokens)
             dxi = self._vit_grad_slots(j, i - 1)[0] if i > 0 else st["dxa"]
-            self._ln_bwd(dh1, st["X"][i], b["n1w"], st["S1"][i], dxi, a("n1w"), a("n1b"))
+            ops.layernorm_bwd(dh1, st["X"][i], b["n1w"], st["S1"][i], a("n1w"), a("n1b"), out=dxi)
             ops.add_(dxi, dxm)
             if tap is not None:
                 tap["d_in"] = dxi.clone()
@@ -488,17 +366,15 @@ class BackboneTrainer:
         npi, T, d = vc.n_patches, vc.n_patches + vc.n_prefix, vc.d
         Bv = self.eng.B * cfg.n_img
         dx = st["dxa"]
-        lib, p = ops._lib(), ops._p
         if vc.n_prefix:
-            dx3 = dx.view(Bv, T, d)
             dpe = st["pe"]
-            ops.copy_rows3d(dx3[0, vc.n_prefix:], dpe, Bv, npi, d, T * d, d, npi * d, d)
-            ops.N.check(lib.vla_colsum_bf16(ops._st(), p(dx), p(self.A(f"vit{j}.prefix")), Bv, vc.n_prefix * d, T * d, 1, 0, 0), "colsum(prefix)")
+            ops.copy_rows3d(dx.view(Bv, T, d)[0, vc.n_prefix:], dpe, Bv, npi, d, T * d, d, npi * d, d)
+            ops.colsum_(dx.view(Bv, T * d)[:, :vc.n_prefix * d], self.A(f"vit{j}.prefix"))      # sum over the batch
         else:
             dpe = dx
         self._defer_tn(dpe, st["cols"], self.G(f"vit{j}.wpe"))
         ops.colsum_(dpe, self.A(f"vit{j}.bpe"))
-        ops.N.check(lib.vla_colsum_bf16(ops._st(), p(dpe), p(self.A(f"vit{j}.pos")), Bv, npi * d, npi * d, 1, 0, 0), "colsum(pos)")   # sum over the batch
+        ops.colsum_(dpe.view(Bv, npi * d), self.A(f"vit{j}.pos"))                               # sum over the batch
 
     # ---- the step as a list of single-stream segments ---------------------------------------------------------------
     # Three streams.  "M": vision, LLM forward, the dX chain of the backward.  "H": the action head - 3 % of the FLOPs but a chain
@@ -543,7 +419,7 @@ class BackboneTrainer:
             self._proj_forward()
             self._mm = eng._embed(batch)
             self._batch = batch
-            llm.fwd_begin(eng.B, eng.S, self._mm, 0)
+            llm.fwd_begin(eng.B, eng.S, self._mm, 0, lin=self)
             if not self._evaluating:                # (the validation forward has no backward)
                 self._begin_backward()              # (fp32 accumulators / sparse embedding gradient: zero before anything adds to them)
                 self._dHS = eng._dhs(0)             # zeroed hidden-state gradients: the head's backward scatters into them
@@ -645,7 +521,7 @@ class BackboneTrainer:
             self._proj_forward()
             self._mm = eng._embed(batch, action_queries=False)
             self._batch = batch
-            llm.fwd_begin(eng.B, eng.S, self._mm, 0)
+            llm.fwd_begin(eng.B, eng.S, self._mm, 0, lin=self)
             self._begin_backward()
             self._dHS = eng._dhs(0)
         add("M", f_front, None, ("front", 0))
@@ -665,11 +541,10 @@ class BackboneTrainer:
             ops.gemm_nt(self.ce_h, llm.embed, out=self.ce_logits, split_k=0)
             tgt = self._ce_tgt = batch["labels"][:, 1:].contiguous().view(-1)
             ops.zero_(self.ce_out)
-            lib, st, p = ops._lib(), ops._st, ops._p
-            ops.N.check(lib.vla_token_ce(st(), p(self.ce_logits), V, p(tgt), B * Lm, V, p(self.ce_out)), "token_ce")
+            ops.token_ce(self.ce_logits, tgt, self.ce_out)
             loss = self.ce_out[0:1] / self.ce_out[1:2]
             self._loss3 = torch.cat([loss, loss, loss])              # (same three-slot shape the L1 path logs)
-            ops.N.check(lib.vla_token_ce_bwd(st(), p(self.ce_logits), V, p(tgt), B * Lm, V, p(self.ce_out), gscale, p(self.ce_logits), V), "token_ce_bwd")
+            ops.token_ce_bwd(self.ce_logits, tgt, self.ce_out, gscale, out=self.ce_logits)
             ops.gemm_nt(self.ce_logits, self.lmT, out=self.ce_dh, split_k=0)                      # d hidden = dlogits . W_lm
             if self.trains_vectors:                                  # d lm_head = dlogits^T . hidden, added to the tied table's gradient in the tail
                 self._defer_tn(self.ce_logits, self.ce_h, self.g_lm)
@@ -682,7 +557,7 @@ class BackboneTrainer:
             grads(("m", k), ("g", k), self._ranges("llm", lo, hi - 1))
 
         def f_mid():
-            dX0 = self.d_last.view(eng.B, eng.S, D)
+            dX0 = self.llm.d_last.view(eng.B, eng.S, D)
             self._embed_backward(dX0)
             self._proj_backward(dX0)
         add("M", f_mid, None, ("mid", 0))
@@ -1173,22 +1048,16 @@ class FullFinetune(BackboneTrainer):
     def _refresh_extra(self):
         self._refresh_objective()
 
-    # ---- the Linear of this mode
-    def _lin(self, key, x, W, bias=None, **kw):
-        return ops.gemm_nt(x, W, bias=bias, **kw)
-
+    # ---- the Linear of this mode: the frozen one's forward (E.Linear._lin); backward adds the weight gradient
     def _lin_bwd(self, key, dy, x, WT, out=None, swiglu_gu=None):
         """dx = dy W on the chain; dW = dy^T x (TN GEMM on dy and x as they lie) handed to the gradient stream: dy is the layer's
         persistent dY slot, x a saved activation - both stay untouched until the next step."""
         self._defer_tn(dy, x, self.G(self._gname(key)))
-        if swiglu_gu is not None:            # down_proj: dGU = swiglu'(GU) * (dy W_down) in the dX GEMM's epilogue
-            return ops.gemm_swiglu_bwd(dy, WT, swiglu_gu, out=out)
-        return ops.gemm_nt(dy, WT, out=out)
+        return super()._lin_bwd(key, dy, x, WT, out=out, swiglu_gu=swiglu_gu)
 
     def _embed_backward(self, dX0):
-        ids, q0, G, B, Np = self._batch["input_ids"], self.eng.qidx0, self.G("llm.embed"), self.eng.B, self.eng.Np
-        self._defer(lambda: ops.N.check(ops._lib().vla_embed_grad(ops._st(), ops._p(dX0), ops._p(ids), ops._p(q0), ops._p(G), B, ids.shape[1], Np,
-                                                                  self.cfg.llm.d, self.cfg.llm.vocab), "embed_grad"))      # gradient-only: off the dX chain
+        ids, q0, G, Np = self._batch["input_ids"], self.eng.qidx0, self.G("llm.embed"), self.eng.Np
+        self._defer(lambda: ops.embed_grad(dX0, ids, q0, G, Np))      # gradient-only: off the dX chain
 
     def _adam_ranges(self):
         na, n = self.n_active, self.cfg.llm.n_layers
@@ -1335,8 +1204,7 @@ class LoRAFinetune(BackboneTrainer):
                     b[k + "T"] = ops.transpose(b[k])
         self.projT = {k: ops.transpose(w) for k, w in eng.proj.items() if k.endswith("weight")}
         self.T, self.DT = {}, {}              # t = 2 x A^T per LoRA Linear (kept for dB), dt = 2 dy B scratch per shape
-        self.Q, self.QT = {}, {}              # fp8: key -> (e4m3 codes, fp32 scales) of W [out, in] / of W^T [in, out]
-        self._qbuf, self._xq = {}, None       # row-quantised activations: scratch per shape; (data_ptr, codes, scales) of the last norm output
+        self.QT = {}                          # fp8: key -> (e4m3 codes, fp32 scales) of W^T [in, out] (self.Q: of W [out, in])
         if self.fp8:
             for key in L:
                 holder, wk = self._base(key)
@@ -1376,7 +1244,7 @@ class LoRAFinetune(BackboneTrainer):
             return self.projT[rest[0] + ".weight"]
         return self.llm.layers[int(rest[0])][{"qkv": "wqkvT", "o": "woT", "gu": "wguT", "down": "wdT"}[rest[1]]]
 
-    # ---- fp8: row-quantised activations
+    # ---- fp8: row-quantised activations (E.Linear: norm -> quantise hand-over, scratch per shape and stream kind)
     # Scratch is keyed by the stream kind as well as the shape: with two vision backbones of the same token count and width (DINOv2-L +
     # CLIP-L, tiny_twin_config) the "V" backbone and the "M" chain quantise / drop rows of the same shape AT THE SAME TIME on two
     # streams, and a buffer shared between them is a data race (no error, slightly wrong gradients).  Cost: one extra set of per-shape
@@ -1384,34 +1252,8 @@ class LoRAFinetune(BackboneTrainer):
     # apart, G and H never call these.  The norm -> quantise hand-over (_xq) needs no key: the host sets it in _ln / _rms and consumes
     # it in the _lin that follows within the SAME segment call (a norm's output feeds the next Linear of its block), so it never
     # crosses from one stream's segment to another's; a left-over entry only matches the very tensor it was made for.
-    def _qscratch(self, rows: int, cols: int, slot: str):
-        k = (rows, cols, slot, self._lane)
-        b = self._qbuf.get(k)
-        if b is None:
-            b = self._qbuf[k] = (torch.empty(rows, cols, device=self.dev, dtype=torch.uint8), torch.empty(rows, device=self.dev, dtype=torch.float32))
-        return b
-
-    def _quant(self, x, slot: str):
-        """(codes, scales) of the rows of x: taken from the norm that just produced x, else one pass over x (vla_quant_fp8_rows)."""
-        if self._xq is not None and self._xq[0] == (x.data_ptr(), tuple(x.shape)):
-            hit, self._xq = self._xq, None               # (consumed: the scratch is overwritten by the next norm of this shape)
-            return hit[1], hit[2]
-        q, s_ = self._qscratch(x.shape[0], x.shape[1], slot)
-        return ops.quant_fp8_rows(x, q, s_)
-
-    def _ln(self, x, w, b, y, st, eps):
-        if not self.fp8 or x.shape[1] % 128:
-            return super()._ln(x, w, b, y, st, eps)
-        q, s_ = self._qscratch(x.shape[0], x.shape[1], "n")
-        ops.layernorm_fwd_q8(x, w, b, eps, q, s_, y=y, stats=st)          # the row is still in registers: bit-identical to norm + quantise
-        self._xq = ((y.data_ptr(), tuple(y.shape)), q, s_)
-
-    def _rms(self, x, w, out, rstd):
-        if not self.fp8 or x.shape[1] % 128:
-            return super()._rms(x, w, out, rstd)
-        q, s_ = self._qscratch(x.shape[0], x.shape[1], "n")
-        ops.rmsnorm_fwd_q8(x, w, self.cfg.llm.eps, q, s_, rstd=rstd, y=out)
-        self._xq = ((out.data_ptr(), tuple(out.shape)), q, s_)
+    def _q8_norm(self, x) -> bool:
+        return self.fp8 and x.shape[1] % 128 == 0          # (the Linear it feeds has an e4m3 weight: Q)
 
     def _alloc(self, B, S):
         if self._key != (B, S):
