@@ -35,8 +35,9 @@ extern "C" {
  *      fp8 = 1 may be combined with the K extension (and, in that form, with the SwiGLU-backward epilogue).
  *   6  round 4: new entry points vla_gemm_latency_hint, vla_dropout_bf16, vla_dropout_bwd_add_bf16, vla_inc_i32 (no layout change).
  *   7  new entry points vla_augment_slab_floats, vla_augment_stats, vla_augment_apply (no layout change).
+ *   8  vla_gemm_nt_plan and vla_gemm_tn_plan (kernel ids VLA_KERNEL_*) replace vla_gemm_uses_256; the latency hint is per thread.
  * A binder checks vla_version() AND vla_desc_size() against its own struct definitions before the first call. */
-#define VLA_ABI_VERSION 7
+#define VLA_ABI_VERSION 8
 int vla_version(void);
 /* sizeof() of the descriptor structs as this library was compiled: which = 0 vla_gemm_desc, 1 vla_attn_desc, 2 vla_head_attn_desc,
  * 3 vla_gemm_tn_desc; -1 for an unknown index.  A caller whose struct is shorter would make the library read past its end. */
@@ -98,19 +99,36 @@ typedef struct vla_gemm_desc {
   const void* A2; const void* B2; int K2, lda2, ldb2;
 } vla_gemm_desc;
 
+/* Kernel ids of the routing plans below: the instantiation a GEMM launch runs (its RoPE, fp8, K-extension and SwiGLU variants follow
+ * from the descriptor). */
+enum {
+  VLA_KERNEL_NT_SKINNY = 0,       /* + tile 0..6: gemm_skinny.hip, (16 MT) x (16 NT) tiles, MT x NT = 1x1 1x2 2x2 1x4 2x4 4x4 4x6 */
+  VLA_KERNEL_NT_64x128_S6 = 8,    /* gemm.hip 64 x 128 tiles, six-stage operand ring (latency hint) */
+  VLA_KERNEL_NT_128x128_S4 = 9,   /* gemm.hip 128 x 128, four-stage ring (latency hint) */
+  VLA_KERNEL_NT_128x128 = 10,     /* gemm.hip 128 x 128, two-stage ring, 8 waves */
+  VLA_KERNEL_NT_128x64 = 11,      /* gemm.hip 128 x 64, 4 waves */
+  VLA_KERNEL_NT_256 = 12,         /* gemm256.hip 256 x 256, one workgroup per CU */
+  VLA_KERNEL_TN_128 = 16,         /* gemm_tn.hip 128 x 128 */
+  VLA_KERNEL_TN_256 = 17          /* gemm_tn.hip 256 x 256 */
+};
+/* Host-side routing of vla_gemm_bf16_nt (the launch calls the same function): the kernel id it runs `desc` on, VLA_ERR_ARG for an
+ * empty problem.  latency < 0: the calling thread's vla_gemm_latency_hint, else that hint; num_cus <= 0: the current device's CUs.
+ * *split (optional): with desc->split_k > 1 the K slices that run (fewer when the slices do not divide K); otherwise the automatic slice
+ * count for split_k (1 = leave the product unsplit) - a caller that sets it, with a workspace, plans again for the kernel.  Reads the
+ * test overrides VLA_GEMM_TILE, VLA_NO_SKINNY, VLA_NO_SMALL_ROWS and VLA_NO_SPLITK like the launch does. */
+int vla_gemm_nt_plan(const vla_gemm_desc* desc /* host */, int latency, int num_cus, int* split /* host */);
+/* Hint for vla_gemm_bf16_nt and vla_attn_fwd, per calling thread, read when a product is launched (= when a hipGraph is captured, on the
+ * capturing thread): on = 1 says the following products run on an otherwise idle chip and are bound by the latency of a launch, not by
+ * throughput - the batch-1 predict_action of modeling_prismatic.py:892-972 / openvla_utils.py:737-825 (every product there is at most one
+ * workgroup per CU and took 17-22 us whatever its size: one K-tile in flight per workgroup).  Under the hint: launches of at most one
+ * workgroup per CU use a deeper operand ring (bit-identical results); products of at most 512 rows run on gemm_skinny.hip's small tiles
+ * with the contraction split over a workgroup's four waves, few-tile long-K products take an uneven split-K, and vla_attn_fwd launches of
+ * fewer workgroups than half the CUs split the KEYS over the waves - these three are the same arithmetic in another fp32 association
+ * (results agree to rounding; in a training step a product's bits must not depend on the batch size, hence the hint).  on = 0 clears it,
+ * on < 0 only queries.  Returns the previous value. */
+int vla_gemm_latency_hint(int on);
 /* 1 when every operand row a 256-row tile of this problem can touch lies below 4 GiB from its base (the 256 x 256 kernel keeps
  * 32-bit per-lane byte offsets; larger operands are routed to the 128-row kernel, which uses 64-bit pointers).  Host arithmetic. */
-/* 1 when vla_gemm_bf16_nt would run this descriptor on the 256 x 256 kernel (the routing is shape- and device-dependent). */
-int vla_gemm_uses_256(const vla_gemm_desc* desc);
-/* Process-wide hint for vla_gemm_bf16_nt, read when a product is launched (= when a hipGraph is captured): on = 1 says the following
- * products run on an otherwise idle chip and are bound by the latency of a launch, not by throughput - the batch-1 predict_action of
- * modeling_prismatic.py:892-972 / openvla_utils.py:737-825 (every product there is at most one workgroup per CU and took 17-22 us
- * whatever its size: one K-tile in flight per workgroup).  Under the hint: launches of at most one workgroup per CU use a deeper operand
- * ring (bit-identical results); products of at most 512 rows run on gemm_skinny.hip's small tiles with the contraction split over a
- * workgroup's four waves, and vla_attn_fwd launches of fewer workgroups than half the CUs split the KEYS over the waves - both the same
- * arithmetic in another fp32 association (results agree to rounding; in a training step a product's bits must not depend on the batch
- * size, hence the hint).  on = 0 clears it, on < 0 only queries.  Returns the previous value. */
-int vla_gemm_latency_hint(int on);
 int vla_gemm256_extent_ok(const vla_gemm_desc* desc /* host */);
 
 /* ---------------------------------------------------------------- TN GEMM (weight gradients) */
@@ -128,7 +146,7 @@ typedef struct vla_gemm_tn_desc {
   /* column groups on A (0 = plain): column c of the product's N1 axis is column (c / g) * stride + c % g of A (g % 8 == 0): the
    * gate (or up) columns of a gate/up-interleaved dY */
   int a_col_group, a_col_group_stride;
-  /* split of the contraction (0/1 = off): `split` slices of M as extra blocks, fp32 planes in ws [batch, split, N1, N2] (device,
+  /* split of the contraction (0/1 = off): up to `split` K-tile aligned slices of M (none left empty) as extra blocks, fp32 planes in ws [batch, split, N1, N2] (device,
    * no initialisation needed), summed by a second kernel - for few-tile long-M products (LoRA pairs) */
   int split; float* ws;
 } vla_gemm_tn_desc;
@@ -137,6 +155,11 @@ typedef struct vla_gemm_tn_desc {
  * Linear in the full fine-tune (:846-849) - on dY and X as the backward / forward left them (no operand transposes).
  * N1 % 8 == 0, N2 % 8 == 0, lda / ldb % 8 == 0; M arbitrary. */
 int vla_gemm_bf16_tn(void* stream, const vla_gemm_tn_desc* desc /* host */);
+/* Host-side routing of vla_gemm_bf16_tn (the launch calls the same function): VLA_KERNEL_TN_128 or _256, VLA_ERR_ARG for an empty
+ * problem; num_cus <= 0: the current device's CUs.  *split (optional): with desc->split > 1 the slices that run (fewer when a slice would
+ * be empty); otherwise the automatic split for few-tile long-M products (1 = none) - set it, with a workspace, and plan again.  Reads
+ * VLA_TN_TILE (128 / 256: force a tile) like the launch does. */
+int vla_gemm_tn_plan(const vla_gemm_tn_desc* desc /* host */, int num_cus, int* split /* host */);
 /* GROUPED form: `count` (1 .. 48) independent TN products as ONE launch over the concatenated tile list - the weight gradients of
  * several Linears / layers, which torch.autograd computes one GEMM at a time (vla-scripts/finetune.py:1039-1042).  A single dW
  * product is 49 ... 532 tiles on a chip with 512 workgroup slots and leaves up to half of it idle in its tail round; a whole

@@ -65,9 +65,9 @@ def test_augment_settings_map_to_the_kernel_arguments():
     assert p.shape == (2, 9) and p[0, 1] == p[0, 2] == (np.float32(1) - side) / np.float32(2) and p[1, 3] == p[0, 1] + side
 
 
-def test_library_exports_the_augment_entry_points_at_abi_7(lib):
+def test_library_exports_the_augment_entry_points_at_abi_8(lib):
     from vla_adapter_amd import native
-    assert lib.vla_version() == native.ABI_VERSION == 7
+    assert lib.vla_version() == native.ABI_VERSION == 8          # (the augment entry points arrived in ABI 7)
     for name in ("vla_augment_slab_floats", "vla_augment_stats", "vla_augment_apply"):
         assert name in native.ABI_SYMBOLS and hasattr(lib, name)
     # 224 x 224: 28 units of 8 pixels per row, 224 rows -> 25 chunks of 256 units per image, 3 channel sums each

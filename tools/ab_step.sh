@@ -2,7 +2,5 @@
 run() { env "$@" timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-full-backward --no-probe 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$*', d['ms_per_step'])"; }
 run A=persistent-tickets
 run VLA_GEMM256_GRID=0
-run VLA_GEMM256_STATIC=1
 run A=persistent-tickets
 run VLA_GEMM256_GRID=0
-run VLA_GEMM256_STATIC=1

@@ -725,16 +725,11 @@ extern "C" int vla_attn_fwd(void* stream, const vla_attn_desc* d) {
   dim3 grid((p.Sq + 127) / 128, p.Hq, p.B);
   hipStream_t st = (hipStream_t)stream;
   // the batch-1 pass (caller's latency hint): fewer workgroups than half the CUs -> 32-query workgroups whose waves split the keys
-  if (vla_gemm_latency_hint(-1) > 0 && (p.dh == 64 || p.dh == 72) && (long long)grid.x * grid.y * grid.z * 2 <= vla_num_cus() &&
-      !getenv("VLA_NO_ATTN_SPLIT")) {
+  if (vla_gemm_latency_hint(-1) > 0 && (p.dh == 64 || p.dh == 72) && (long long)grid.x * grid.y * grid.z * 2 <= vla_num_cus()) {
     const dim3 g2((p.Sq + 31) / 32, p.Hq, p.B);
     const int dv = (p.dh + 31) / 32 * 32;
     const size_t lds = (size_t)4 * 32 * (dv + 8) * 2 + 2 * 4 * 32 * 4 + (size_t)4 * 32 * (dv + 1) * 4;
-    static bool split_attr = false;
-    if (!split_attr) {
-      (void)hipFuncSetAttribute((const void*)attn_fwd_split_kernel<72>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      split_attr = true;
-    }
+    if (int rc = vla_lds_limit<attn_fwd_split_kernel<72>>(96 * 1024, "attn_fwd_split_kernel")) return rc;
     if (p.dh == 64) hipLaunchKernelGGL(attn_fwd_split_kernel<64>, g2, dim3(256), lds, st, p);
     else hipLaunchKernelGGL(attn_fwd_split_kernel<72>, g2, dim3(256), lds, st, p);
     VLA_CHECK_LAUNCH("attn_fwd(split)");
@@ -769,14 +764,11 @@ extern "C" int vla_attn_bwd(void* stream, const vla_attn_desc* d) {
   }
   const int ld = ((p.dh + 31) / 32 * 32 + 8);
   const size_t lds = (size_t)grp * KT * (2 * 32 * ld * 2 + 256) + (p.dh > 72 ? (size_t)KT * 2 * 32 * ld * 2 : 0);   // (+ the K / V images at dh 128)
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<72>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
   VLA_REQUIRE(lds <= 160 * 1024, "attn_bwd: LDS budget exceeded");
+  rc = p.dh == 64 ? vla_lds_limit<attn_bwd_dkv_kernel<64>>(160 * 1024, "attn_bwd_dkv_kernel")
+       : p.dh == 72 ? vla_lds_limit<attn_bwd_dkv_kernel<72>>(160 * 1024, "attn_bwd_dkv_kernel")
+                    : vla_lds_limit<attn_bwd_dkv_kernel<128>>(160 * 1024, "attn_bwd_dkv_kernel");
+  if (rc) return rc;
   if (p.dh == 64) {
     hipLaunchKernelGGL(attn_bwd_dq_kernel<64>, gq, dim3(256), 0, st, p);
     hipLaunchKernelGGL(attn_bwd_dkv_kernel<64>, gk, dim3(64 * grp * KT), lds, st, p, grp, KT);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 typedef unsigned short bf16_t;  // raw bf16 storage
 typedef __attribute__((ext_vector_type(8))) short bf16x8;     // MFMA A/B fragment (8 bf16 = 4 VGPR)
@@ -23,6 +24,18 @@ extern "C" void vla_set_error(const char* msg);
       return VLA_ERR_ARG;                 \
     }                                     \
   } while (0)
+
+// Lift KERNEL's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) to `bytes`, once per kernel: the call runs in a
+// thread-safe static initialiser, and its refusal is returned (VLA_ERR_LAUNCH, the kernel named in vla_last_error) on every launch.
+template <auto KERNEL>
+int vla_lds_limit(int bytes, const char* name) {
+  static const hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) return VLA_OK;
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: setting %d bytes of dynamic LDS failed (%s)", name, bytes, hipGetErrorString(e));
+  vla_set_error(msg);
+  return VLA_ERR_LAUNCH;
+}
 
 #define VLA_CHECK_LAUNCH(name)                          \
   do {                                                  \

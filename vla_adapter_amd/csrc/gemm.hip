@@ -17,12 +17,12 @@
 //   * operands are swapped at the MFMA (A-operand := B rows) so each lane owns 4 consecutive n of one row m: the
 //     epilogue stages the wave's tile through LDS and stores whole row segments with 16-B lanes;
 //   * XCD-aware bijective tile order (T1).
-// Three instantiations: 256x128 (8 waves, 3 stages, 144 KiB LDS, 1 block/CU) for the large GEMMs, 128x128 (4 waves,
-// 2 stages, 2 blocks/CU) and 128x64 (4 waves, 2 stages, 48 KiB, 3 blocks/CU) - the host picks per problem by a
-// wave-quantisation model (a 616-tile problem on 512 slots wastes 40 % of the machine with 128x128 tiles).
+// Tiles: 128x128 (8 waves, 2 stages, 2 blocks/CU), 128x64 (4 waves, 2 stages, 48 KiB, 3 blocks/CU) and, under the latency hint,
+// 128x128 on a four-stage and 64x128 on a six-stage ring; large products go to gemm256.hip, small outputs to gemm_skinny.hip.
+// plan_nt below picks one per call.
 //
 // Epilogue rounding points follow the reference under bf16 autocast: bf16(acc+bias) -> act -> bf16 -> (+residual) -> bf16.
-#include <atomic>
+#include <algorithm>
 #include "common.h"
 #include "gemm_params.h"
 #include "../../include/vla_native.h"
@@ -557,63 +557,6 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
   }
 }
 
-// Pick the tile per problem.  Calibrated on MI355X (tools/bench_kernels.py, round 1):
-//  * 256x256 (8 waves of 64x128, 1 block/CU) only pays on huge squares (8192^3: 1201 vs 1093 TF/s); 256x128x3-stage
-//    is kept as a forced option (VLA_GEMM_TILE=1);
-//  * 128x128 with EIGHT waves (2x4 waves of 64x32, 2 blocks/CU = 16 waves/CU): the K-loop is latency/barrier bound
-//    (rocprofv3 PMC: SQ_WAIT_ANY 30-40 %, MFMA busy ~41 % with 4 waves), so more resident waves win over operand
-//    reuse per wave: +5..+40 % over the 4-wave 64x64 geometry on every hot shape;
-//  * 128x64 (4 waves, 3 blocks/CU) only for problems smaller than one round of tiles (the M=256 head GEMMs).
-struct TileChoice { int bm, bn; };
-// When the 256 x 256 8-phase kernel (one workgroup per CU) is chosen automatically: problems with at least a chip-full of
-// its tiles' worth of work in both dimensions.  VLA_GEMM_TILE=6 forces it, VLA_NO_GEMM256 disables it.
-inline bool use_256(int M, int N, int K, int batch, int act) {
-  static const bool off = getenv("VLA_NO_GEMM256") != nullptr;
-  if (off) return false;
-  const long long tiles = (long long)((M + 255) / 256) * ((N + 255) / 256) * batch;
-  // the SwiGLU-backward epilogue streams GU in and dGU out (4 N bytes per row against 2 K of operands: as long as a short K
-  // loop, HBM-bound on the full sequence): the 128-row kernel's second resident workgroup overlaps it with the other one's
-  // K loop (live rows, M = 2048: 38 vs 44 us; full sequence, M = 11264: 166 vs 191 us)
-  if (act == VLA_ACT_SWIGLU_BWD) return false;
-  // a GELU epilogue (10 us of VALU per round of tiles) with a thin tail round (ViT fc1: 544 tiles = two rounds + 32) is the one
-  // large shape the 128-row kernel still wins isolated (96 vs 106-114 us: its second resident workgroup computes under the
-  // first one's epilogue); on the step the two routings tie (25.25-25.34 vs 25.29-25.32 ms)
-  const int ncu = vla_num_cus();
-  if ((act == VLA_ACT_GELU || act == VLA_ACT_GELU_TANH) && tiles > ncu && (tiles % ncu) != 0 && (tiles % ncu) * 4 < ncu) return false;
-  // Rounds model (round 3, tools/bench_tiles_b16.py): a 256 x 256 tile is four 128 x 128 tiles of work on one CU; the 128-row kernel
-  // keeps two workgroups per CU and reaches ~0.87 of the 256-row kernel's per-CU rate.  Cost in units of "one 128 x 128 tile at
-  // the 256-row kernel's rate":  rounds256 x 4  against  rounds128 x 2 / 0.87.  Reproduces every measured winner of the batch-32
-  // step (gate/up, down, o, q|k|v, ViT qkv / proj / fc2, task K/V -> 256) and of the batch-16 shapes of the LoRA / full steps, where
-  // the round-2 threshold (>= 96 tiles) sent two shapes the wrong way: LLM q|k|v 5632 x 1152 (110 tiles = 0.43 round: 25.2 vs
-  // 17.3 us) and ViT fc1 / dX fc2 4096 x 4352 (272 tiles = 1.06 rounds: 58.3 vs 47.8 us).
-  const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128) * batch;
-  const double est256 = (double)((tiles + ncu - 1) / ncu) * 4.0, est128 = (double)((t128 + 2 * ncu - 1) / (2 * ncu)) * (2.0 / 0.87);
-  return M >= 1024 && N >= 768 && K >= 256 && est256 < est128;
-}
-inline TileChoice choose_tile(int M, int N, int K, int force, int rope_mode, int batch = 1, int split = 1, int act = 0) {
-  // rotate_half RoPE is fused in both kernels (bit-identical).  The LLM's q|k|v projection goes to the 256-row kernel when it
-  // fills most of the chip with its tiles (whole-batch launch, M = 11264: 220 tiles, 26.64-26.69 vs 26.84-26.85 ms on the step,
-  // same box); the half-batch launches of the two-pipeline forward (110 tiles) measured 26.10-26.20 vs 26.07-26.10 and stay
-  // on the 128-row kernel.  VLA_NO_ROPE256 switches it off.
-  static const bool no_rope256 = getenv("VLA_NO_ROPE256") != nullptr;
-  if (split == 1) {     // (both RoPE conventions are fused in both kernels)
-    if (force == 6) return {256, 257};   // 256 x 256 two-phase kernel (gemm256.hip)
-    const long long t256 = (long long)((M + 255) / 256) * ((N + 255) / 256) * batch;
-    if (force == 0 && (rope_mode == 0 || (!no_rope256 && t256 >= 192)) && use_256(M, N, K, batch, act)) return {256, 257};
-  }
-  if (rope_mode == 1) return {128, 128};   // rotate_half: 8 waves, each owning 16 columns of both halves of one head
-  if (force == 2) return {128, 128};
-  if (force == 3) return {128, 64};
-  // In situ (whole training step, same-box A/B) the 8-wave 128x128 geometry beats the narrow tile on every shape of
-  // the step, including the M=256 head GEMMs that overlap the LLM on the side stream (48.5 vs 49.5 vs 52.0 ms/step
-  // for always-square / mixed / always-narrow); the narrow tile stays available through VLA_GEMM_TILE=3.
-  // Exception: long-K problems that fill less than half the chip with square tiles (the live-row gate/up dX GEMM:
-  // M 2048, N 896, K 9728 -> 112 tiles): the narrow tile doubles the number of K loops in flight.
-  const long long tiles = (long long)((M + 127) / 128) * ((N + 127) / 128) * batch;
-  if (tiles <= 128 && K >= 4096 && N % 64 == 0) return TileChoice{128, 64};
-  return TileChoice{128, 128};
-}
-
 // split-K second pass: C = bf16(bf16(act(bf16(sum_z ws[z] * alpha + bias))) + R); 4 columns per thread
 __global__ void splitk_finalize_kernel(const float* __restrict__ ws, const bf16_t* __restrict__ bias, const bf16_t* __restrict__ R,
                                        bf16_t* __restrict__ C, int M, int N, int ldc, int ldr, int act, float alpha, int split, int vec) {
@@ -661,18 +604,225 @@ __global__ void splitk_finalize_kernel(const float* __restrict__ ws, const bf16_
 }
 
 template <int BM, int BN, int STAGES, int ROPE, int WN = 2, bool F8 = false, bool EXT = false>
-int launch(const GemmP& p0, int M, int N, int batch, hipStream_t st) {
+int launch(const GemmP& p0, int nb, hipStream_t st) {
   using C = Cfg<BM, BN, STAGES, WN>;
+  if (int rc = vla_lds_limit<gemm_nt_kernel<BM, BN, STAGES, ROPE, WN, F8, EXT>>(C::LDS_BYTES, "gemm_nt_kernel")) return rc;
   GemmP p = p0;
-  p.tiles_n = (N + BN - 1) / BN;
-  p.ntiles = ((M + BM - 1) / BM) * p.tiles_n;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<BM, BN, STAGES, ROPE, WN, F8, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    attr_set = true;
+  p.tiles_n = (p.N + BN - 1) / BN;
+  p.ntiles = ((p.M + BM - 1) / BM) * p.tiles_n;
+  hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, STAGES, ROPE, WN, F8, EXT>), dim3(p.ntiles, 1, nb), dim3(C::NTHREADS), C::LDS_BYTES, st, p);
+  return VLA_OK;
+}
+
+// The gemm.hip launch of a plan.  ROPE 3 is the SwiGLU-backward epilogue; the deep rings and the 128 x 64 tile exist only for the
+// plain bf16 forms (128 x 64: not with rotate_half), so only the instantiations a plan can select are compiled.
+template <int ROPE, bool F8 = false, bool EXT = false>
+int launch_nt(int kernel, const GemmP& p, int nb, hipStream_t st) {
+  if constexpr (!F8 && !EXT && ROPE != 3) {
+    if (kernel == VLA_KERNEL_NT_64x128_S6) return launch<64, 128, 6, ROPE, 4>(p, nb, st);
+    if (kernel == VLA_KERNEL_NT_128x128_S4) return launch<128, 128, 4, ROPE, 4>(p, nb, st);
+    if constexpr (ROPE != 1)
+      if (kernel == VLA_KERNEL_NT_128x64) return launch<128, 64, 2, ROPE>(p, nb, st);
   }
-  hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, STAGES, ROPE, WN, F8, EXT>), dim3(p.ntiles, 1, batch), dim3(C::NTHREADS), C::LDS_BYTES, st, p);
-  return 0;
+  return launch<128, 128, 2, ROPE, 4, F8, EXT>(p, nb, st);     // 8 waves (2x4) of 64x32
+}
+
+// ---------------------------------------------------------------- routing: one plan per call
+// Test / benchmarking overrides, read once per call (tests flip them in the middle of a process):
+//   VLA_GEMM_TILE=2|3|6   force 128x128 (8 waves) | 128x64 | 256x256; any non-zero value also keeps the product off gemm_skinny.hip
+//   VLA_NO_SKINNY, VLA_NO_SMALL_ROWS   keep every / the <= 512-row products off gemm_skinny.hip
+//   VLA_NO_SPLITK         no automatic split-K
+//   VLA_GEMM256_GRID=n    workgroups of the persistent 256x256 kernel (default one per CU, 0 = one per tile)
+struct NtOverrides {
+  int tile;
+  bool no_skinny, no_small_rows, no_splitk, grid_set;
+  long long grid;
+};
+NtOverrides nt_overrides() {
+  const char* tile = getenv("VLA_GEMM_TILE");
+  const char* nsk = getenv("VLA_NO_SPLITK");
+  const char* grid = getenv("VLA_GEMM256_GRID");
+  return {tile ? atoi(tile) : 0, getenv("VLA_NO_SKINNY") != nullptr, getenv("VLA_NO_SMALL_ROWS") != nullptr, nsk && *nsk,
+          grid != nullptr, grid ? atoll(grid) : 0};
+}
+
+// Caller's hint (per thread, read at launch = at graph capture): the following products run on an otherwise idle chip and are bound
+// by latency, not throughput (batch-1 predict_action).  It selects the deep operand rings (bit-identical), gemm_skinny.hip's short-M
+// tiles, the uneven split-K and the key-split attention (these three change the fp32 association).
+thread_local int g_latency_hint = 0;
+
+// When the 256 x 256 8-phase kernel (one workgroup per CU) is chosen automatically: problems with at least a chip-full of
+// its tiles' worth of work in both dimensions.
+bool use_256(int M, int N, int K, int batch, int act, int ncu) {
+  const long long tiles = (long long)((M + 255) / 256) * ((N + 255) / 256) * batch;
+  // the SwiGLU-backward epilogue streams GU in and dGU out (4 N bytes per row against 2 K of operands: as long as a short K
+  // loop, HBM-bound on the full sequence): the 128-row kernel's second resident workgroup overlaps it with the other one's
+  // K loop (live rows, M = 2048: 38 vs 44 us; full sequence, M = 11264: 166 vs 191 us)
+  if (act == VLA_ACT_SWIGLU_BWD) return false;
+  // a GELU epilogue (10 us of VALU per round of tiles) with a thin tail round (ViT fc1: 544 tiles = two rounds + 32) is the one
+  // large shape the 128-row kernel still wins isolated (96 vs 106-114 us: its second resident workgroup computes under the
+  // first one's epilogue); on the step the two routings tie (25.25-25.34 vs 25.29-25.32 ms)
+  if ((act == VLA_ACT_GELU || act == VLA_ACT_GELU_TANH) && tiles > ncu && (tiles % ncu) != 0 && (tiles % ncu) * 4 < ncu) return false;
+  // Rounds model (round 3, tools/bench_tiles_b16.py): a 256 x 256 tile is four 128 x 128 tiles of work on one CU; the 128-row kernel
+  // keeps two workgroups per CU and reaches ~0.87 of the 256-row kernel's per-CU rate.  Cost in units of "one 128 x 128 tile at
+  // the 256-row kernel's rate":  rounds256 x 4  against  rounds128 x 2 / 0.87.  Reproduces every measured winner of the batch-32
+  // step (gate/up, down, o, q|k|v, ViT qkv / proj / fc2, task K/V -> 256) and of the batch-16 shapes of the LoRA / full steps, where
+  // the round-2 threshold (>= 96 tiles) sent two shapes the wrong way: LLM q|k|v 5632 x 1152 (110 tiles = 0.43 round: 25.2 vs
+  // 17.3 us) and ViT fc1 / dX fc2 4096 x 4352 (272 tiles = 1.06 rounds: 58.3 vs 47.8 us).
+  const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128) * batch;
+  const double est256 = (double)((tiles + ncu - 1) / ncu) * 4.0, est128 = (double)((t128 + 2 * ncu - 1) / (2 * ncu)) * (2.0 / 0.87);
+  return M >= 1024 && N >= 768 && K >= 256 && est256 < est128;
+}
+
+// gemm_skinny.hip's tile for a small-output product, -1 when it is not one: (a) tall-skinny, N = 64 / 128 / 192 and M >= 1024 (the LoRA
+// t / dt products), or (b) under the latency hint M <= 512 (the batch-1 pass); K < 2048, bias / activation / residual / RoPE epilogue.
+// Contractions of 2048 and more stay on the 128-row tiles with split-K (measured, tools/diag/bench_skinny.py: with K cut into slices here
+// as well, 64-row tiles pull twice the operand rows per output and lose - dt of gate/up, K = 9728: 57.7 vs 32.1 us; t of down 22.8 vs 20.0).
+int skinny_tile(const vla_gemm_desc* d, bool latency, int ncu, bool no_small_rows) {
+  const bool tall = (d->N == 64 || d->N == 128 || d->N == 192) && d->M >= 1024;                         // (a)
+  // (b) only under the caller's latency hint (the batch-1 pass): in a training step the head's products are off the critical path (measured:
+  // no change of the step), and a product's bits would depend on its row count - the live-row backward equals the full one bit for bit
+  // because every row is computed by the same instruction sequence whatever M is (tests/test_engine_gpu.py)
+  const bool shortm = latency && d->M <= 512 && d->N % 16 == 0 && d->K >= 512 && !no_small_rows;
+  if (!(tall || shortm) || d->K % 128 != 0 || d->K >= 2048 || d->ldc % 8 != 0 || ((uintptr_t)d->C & 15) != 0) return -1;
+  if (!(d->act == VLA_ACT_NONE || d->act == VLA_ACT_GELU || d->act == VLA_ACT_RELU || d->act == VLA_ACT_GELU_TANH)) return -1;
+  if (d->bias && ((uintptr_t)d->bias & 15) != 0) return -1;
+  if (d->R && (d->ldr % 8 != 0 || ((uintptr_t)d->R & 15) != 0)) return -1;
+  if ((d->rope_mode == 1 && (d->rope_dh != 64 || d->rope_cols % 64 != 0 || tall)) ||
+      (d->rope_mode == 2 && (d->rope_dh % 8 != 0 || d->rope_cols % 8 != 0 || (((uintptr_t)d->rope_cos | (uintptr_t)d->rope_sin) & 15) != 0)))
+    return -1;
+  // Tile: what a CU has to pull through its L1 is (tile rows + tile columns) x K operand rows per workgroup, times the workgroups it gets -
+  // minimised over the instantiated tiles (every CU busy, as few rows each as possible; ties: the larger tile)
+  int best = -1;
+  long long best_cost = 0;
+  for (int t = 0; t < SKINNY_TILES; ++t) {
+    const int tm = 16 * SKINNY_TILE[t][0], tn = 16 * SKINNY_TILE[t][1];
+    if (tall && d->N % tn != 0) continue;
+    if (d->rope_mode == 1 && tn != 64) continue;              // rotate_half: both halves of a head inside one tile row
+    const long long wgs = (long long)((d->M + tm - 1) / tm) * ((d->N + tn - 1) / tn), cost = (long long)(tm + tn) * ((wgs + ncu - 1) / ncu);
+    if (best < 0 || cost < best_cost || (cost == best_cost && t > best)) best = t, best_cost = cost;
+  }
+  // (b) only for tiles up to 32 x 64 (96 operand rows per workgroup): measured in the batch-1 pass (profiles/r04_prof_predict_summary.txt, us under
+  // the profiler, this kernel vs gemm.hip's 64 x 128 six-stage ring): 16 x 16 tiles 5.1 vs 10.6 (the head's 8-row products), 32 x 32 6.6 vs 12,
+  // 32 x 64 8.9-10.4 vs 12.7-12.9 (LLM o, ViT proj) - but 64 x 64 13.3 vs 12.3 (ViT q|k|v) and 64 x 96 17.3 vs 13.4 (ViT fc1): with 128+ operand
+  // rows per workgroup the LDS-DMA ring keeps more bytes in flight than register fragments at one or two waves per SIMD do
+  if (!tall && best_cost > 96) return -1;
+  return best;
+}
+
+// K extension on the 256 x 256 kernel (round 4; bf16 operands): the routing of the plain product over K + K2, provided the extension's rows
+// are addressable like the main operands' (32-bit per-lane byte offsets, no row groups on A) and the epilogue is one the kernel has
+// (plain / activation / residual / rotate_half at head dim 64 / SwiGLU forward).
+bool ext_on_256(const vla_gemm_desc* d, int force, int ncu) {
+  if (d->fp8 || d->batch != 1 || d->split_k > 1 || d->act == VLA_ACT_SWIGLU_BWD || d->rope_mode == 2 || d->a_group != 0 ||
+      (d->rope_mode == 1 && d->rope_dh != 64) || !vla_gemm256_extent_ok(d))
+    return false;
+  const unsigned long long ra = (unsigned long long)((d->M + 255) / 256) * 256, rb = (unsigned long long)((d->N + 255) / 256) * 256;
+  if ((ra * d->lda2 + d->K2) * 2 >= (1ull << 32) || (rb * d->ldb2 + d->K2) * 2 >= (1ull << 32)) return false;
+  if (force != 0) return force == 6;
+  const long long t256 = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256);
+  if (d->rope_mode == 1 && t256 < 192) return false;
+  return use_256(d->M, d->N, d->K + d->K2, 1, d->act, ncu);
+}
+
+struct NtPlan { int kernel, split; };
+
+// The kernel and the K-slice count of a validated descriptor.  Calibrated on MI355X (tools/bench_kernels.py, tools/bench_tiles_b16.py):
+//  * 256x256 (gemm256.hip, one workgroup per CU) for chip-filling products by the rounds model of use_256;
+//  * 128x128 with EIGHT waves (2x4 waves of 64x32, 2 blocks/CU = 16 waves/CU) otherwise: the K-loop is latency/barrier bound
+//    (rocprofv3 PMC: SQ_WAIT_ANY 30-40 %, MFMA busy ~41 % with 4 waves), so more resident waves win over operand reuse per wave;
+//  * 128x64 (4 waves, 3 blocks/CU) only for long-K problems that fill less than half the chip with square tiles;
+//  * under the latency hint, launches of at most one workgroup per CU on deeper operand rings; small outputs on gemm_skinny.hip.
+NtPlan plan_nt(const vla_gemm_desc* d, bool latency, int ncu, const NtOverrides& ov) {
+  const int force = ov.tile, kt = d->K / BK;
+  // split-K: slices of ceil(K-tiles / split_k) K-tiles; when that does not divide, the last slice is shorter and fewer slices may be needed
+  const int asked = d->split_k > 1 ? d->split_k : 1, per = (kt + asked - 1) / asked, split = (kt + per - 1) / per;
+  // small-output products (the LoRA t / dt products; the action head's Linears on 8 x B rows; the batch-1 pass)
+  if (force == 0 && !ov.no_skinny && d->batch == 1 && split == 1 && d->a_group == 0 && d->c_group == 0 && d->r_group == 0 &&
+      d->res_mod == 0 && d->c_live_mod == 0 && !d->fp8 && d->K2 == 0 && d->C) {
+    const int t = skinny_tile(d, latency, ncu, ov.no_small_rows);
+    if (t >= 0) return {VLA_KERNEL_NT_SKINNY + t, 1};
+  }
+  const bool fits256 = vla_gemm256_extent_ok(d) != 0;     // operands of 4 GiB and more: the 64-bit-pointer 128-row kernel
+  if (d->K2 > 0) return {!d->fp8 && ext_on_256(d, force, ncu) ? VLA_KERNEL_NT_256 : VLA_KERNEL_NT_128x128, 1};
+  if (d->fp8) {
+    // e4m3 operands.  With the K loop halved, the 256 x 256 kernel's per-tile costs weigh twice as much: on the step's shapes the
+    // 128-row kernel (two workgroups per CU, one's epilogue under the other's K loop) is as fast or faster (gate/up 162 vs 162 us,
+    // down 62 vs 70, ViT fc1 63 vs 87), on big squares the 256-row kernel wins (8192^3: 2503 vs 2108 TF/s) - it takes those.
+    const bool big = force == 6 || (force == 0 && d->M >= 4096 && d->N >= 4096 && d->K >= 4096);
+    return {big && d->c_group == 0 && d->r_group == 0 && fits256 && !(d->rope_mode == 1 && d->rope_dh != 64) ? VLA_KERNEL_NT_256
+                                                                                                              : VLA_KERNEL_NT_128x128, 1};
+  }
+  const int nb = asked > 1 ? asked : d->batch;       // (the tile rules see the requested slice count)
+  bool square = false;
+  if (asked == 1) {
+    // rotate_half RoPE: the LLM's q|k|v projection goes to the 256-row kernel when it fills most of the chip with its tiles (whole-batch
+    // launch, M = 11264: 220 tiles, 26.64-26.69 vs 26.84-26.85 ms on the step, same box); the half-batch launches of the two-pipeline
+    // forward (110 tiles) measured 26.10-26.20 vs 26.07-26.10 and stay on the 128-row kernel.
+    const long long t256 = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) * nb;
+    if (force == 6 || (force == 0 && (d->rope_mode == 0 || t256 >= 192) && use_256(d->M, d->N, d->K, nb, d->act, ncu))) {
+      // interleaved RoPE on the 256-row kernel: the plain epilogue without residual (the head's K|V projections); rotate_half at head
+      // dim 128: the 128-row kernel's column map (one head per 128-column tile), the 256-row kernel's is built on 64-wide heads
+      if (fits256 && !(d->rope_mode == 2 && (d->R || d->act != VLA_ACT_NONE)) && !(d->rope_mode == 1 && d->rope_dh != 64))
+        return {VLA_KERNEL_NT_256, 1};
+      square = true;          // (refused: the 128-row square tile)
+    }
+  }
+  if (d->act == VLA_ACT_SWIGLU_BWD) return {VLA_KERNEL_NT_128x128, split};
+  // In situ (whole training step, same-box A/B) the 8-wave 128x128 geometry beats the narrow tile on every shape of the step,
+  // including the M=256 head GEMMs that overlap the LLM on the side stream (48.5 vs 49.5 vs 52.0 ms/step for always-square / mixed /
+  // always-narrow).  Exception: long-K problems that fill less than half the chip with square tiles (the live-row gate/up dX GEMM:
+  // M 2048, N 896, K 9728 -> 112 tiles): the narrow tile doubles the number of K loops in flight.
+  const long long tiles = (long long)((d->M + 127) / 128) * ((d->N + 127) / 128) * nb;
+  const bool narrow = !square && d->rope_mode != 1 && force != 2 && (force == 3 || (tiles <= 128 && d->K / asked >= 4096 && d->N % 64 == 0));
+  if (narrow) return {VLA_KERNEL_NT_128x64, split};
+  // Launches of at most one workgroup per CU (batch-1 inference: every product; the training step: the action head's x-chain) are
+  // bound by the LATENCY of a K-tile, not by bandwidth: with the two-stage ring one K-tile is in flight per workgroup and every tile
+  // costs a full trip to HBM (~1.2 us against 0.2 us of MFMAs: 17-22 us for ANY product of the batch-1 pass, K = 896-1152, whatever its
+  // size).  They run on a four-stage ring (128 KiB of LDS: the CU is theirs anyway), three K-tiles in flight - or, when even 64-row tiles
+  // leave CUs idle, on 64 x 128 tiles with a six-stage ring (144 KiB, five in flight, twice the workgroups: what such a launch can keep
+  // in flight is workgroups x ring bytes) -, the same K order and MFMA sequence: bit-identical (test_gemm_deep_ring_bit_identical).
+  // Only under the latency hint: in the training step the same launches share the chip with two other streams' kernels, and a 128-KiB
+  // workgroup waits for a whole CU's LDS where the 64-KiB one slips in beside another (step 24.13 -> 24.44 ms same box with the deep
+  // ring on every sub-round launch).
+  if (latency && per >= 4) {
+    const int runs = split > 1 ? split : d->batch;
+    const long long wgs = (long long)((d->M + 127) / 128) * ((d->N + 127) / 128) * runs, wgs64 = (long long)((d->M + 63) / 64) * ((d->N + 127) / 128) * runs;
+    if (wgs64 <= ncu) return {VLA_KERNEL_NT_64x128_S6, split};     // 64-row tiles, six stages: twice the workgroups, five K-tiles in flight
+    if (wgs <= ncu) return {VLA_KERNEL_NT_128x128_S4, split};      // 128-row tiles, four stages
+  }
+  return {VLA_KERNEL_NT_128x128, split};
+}
+
+// The automatic split-K of a product the caller lets the library split (few-tile long-K problems: batch-1 inference, the live-row
+// backward's M = B*64 GEMM over K = 2I).  The K loop of a tile is serial, so a problem with fewer tiles than the chip has workgroup slots
+// (two per CU) runs at the latency of ONE long loop on part of the CUs; K slices meet in an fp32 workspace and are summed by
+// splitk_finalize_kernel.  1 = do not split.
+int auto_split_k(const vla_gemm_desc* d, bool latency, int ncu, const NtOverrides& ov) {
+  const bool plain = !d->fp8 && d->K2 == 0 && d->batch == 1 && !d->bias_post_round && d->C && d->a_group == 0 && d->c_group == 0 &&
+                     d->r_group == 0 && d->rope_mode == 0 && d->c_live_mod == 0 && d->res_mod == 0 && d->N % 4 == 0 &&
+                     (d->act == VLA_ACT_NONE || d->act == VLA_ACT_GELU || d->act == VLA_ACT_RELU || d->act == VLA_ACT_GELU_TANH);
+  if (!plain || d->K < 2048 || ov.no_splitk) return 1;
+  const long long tiles = (long long)((d->M + 127) / 128) * ((d->N + 127) / 128), t64 = (long long)((d->M + 63) / 64) * ((d->N + 127) / 128);
+  // the batch-1 pass (latency hint): as many K slices as give every CU one 64 x 128 workgroup, >= 4 K-tiles each (the slices need not
+  // divide K: the last one is shorter) - ViT fc2 256 x 1152 x 4352: 7 slices of 10 K-tiles on 252 workgroups instead of 4 on 144
+  if (latency && t64 * 2 <= ncu) return (int)std::max(2LL, std::min({ncu / t64, (long long)(d->K / BK) / 4, 16LL}));
+  if (tiles > ncu) return 1;
+  for (int sk = 8; sk >= 2; sk /= 2)          // even slices of >= 512, at most two workgroups per CU
+    if (tiles * sk <= 2 * ncu && d->K % (BK * sk) == 0 && d->K / sk >= 512) return sk;
+  return 1;
+}
+
+// second pass of a split-K product: the `split` fp32 planes of d->ws summed in order, then alpha / bias / activation / residual / rounding
+int splitk_finalize(const vla_gemm_desc* d, int split, hipStream_t st) {
+  const long long total = (long long)d->M * d->N / 4;
+  const unsigned nblk = (unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  hipLaunchKernelGGL(splitk_finalize_kernel, dim3(nblk), dim3(256), 0, st, (const float*)d->ws, (const bf16_t*)d->bias,
+                     (const bf16_t*)d->R, (bf16_t*)d->C, d->M, d->N, d->ldc, d->ldr, d->act, d->alpha == 0.f ? 1.f : d->alpha, split,
+                     (d->ldc % 4 == 0 && ((uintptr_t)d->C & 7) == 0 && (!d->R || (d->ldr % 4 == 0 && ((uintptr_t)d->R & 7) == 0)) &&
+                      (!d->bias || ((uintptr_t)d->bias & 7) == 0)) ? 1 : 0);
+  VLA_CHECK_LAUNCH("gemm_splitk_finalize");
+  return VLA_OK;
 }
 
 }  // namespace
@@ -690,62 +840,20 @@ extern "C" int vla_gemm256_extent_ok(const vla_gemm_desc* d) {
   return (offA + d->K) * EB < lim && (offB + d->K) * EB < lim;
 }
 
-// Caller's hint (process-wide, read at launch = at graph capture): the following products run on an otherwise idle chip and are bound
-// by latency, not throughput (batch-1 predict_action).  Selects kernels only - results are bit-identical either way.
-static std::atomic<int> g_latency_hint{0};
 extern "C" int vla_gemm_latency_hint(int on) {
-  return on < 0 ? g_latency_hint.load(std::memory_order_relaxed) : g_latency_hint.exchange(on ? 1 : 0, std::memory_order_relaxed);
+  const int prev = g_latency_hint;
+  if (on >= 0) g_latency_hint = on ? 1 : 0;
+  return prev;
 }
 
-// The tile choice of vla_gemm_bf16_nt for a descriptor (shared with the predicate below).
-static TileChoice route(const vla_gemm_desc* d) {
-  const int split = d->split_k > 1 ? d->split_k : 1;
-  const char* e = getenv("VLA_GEMM_TILE");     // 0/unset auto, 2: 128x128, 3: 128x64, 6: 256x256  (test / benchmarking aid)
-  TileChoice tc = choose_tile(d->M, d->N, d->K / split, e ? atoi(e) : 0, d->rope_mode, split > 1 ? split : d->batch, split, d->act);
-  if (tc.bm == 256 && tc.bn == 257 && !vla_gemm256_extent_ok(d)) tc = TileChoice{128, 128};   // operands of 4 GiB and more: 64-bit-pointer kernel
-  // interleaved RoPE on the 256-row kernel: the plain epilogue without residual (the head's K|V projections) - anything else keeps gemm.hip's
-  if (tc.bm == 256 && tc.bn == 257 && d->rope_mode == 2 && (d->R || d->act != VLA_ACT_NONE || d->fp8)) tc = TileChoice{128, 128};
-  // rotate_half at head dim 128: the 128-row kernel's column map (one head per 128-column tile); the 256-row kernel's is built on 64-wide heads
-  if (tc.bm == 256 && tc.bn == 257 && d->rope_mode == 1 && d->rope_dh != 64) tc = TileChoice{128, 128};
-  return tc;
-}
-
-// K extension on the 256 x 256 kernel (round 4; bf16 operands): the routing of the plain product over K + K2, provided the extension's rows
-// are addressable like the main operands' (32-bit per-lane byte offsets, no row groups on A) and the epilogue is one the kernel has
-// (plain / activation / residual / rotate_half at head dim 64 / SwiGLU forward).
-static bool ext_on_256(const vla_gemm_desc* d) {
-  if (d->K2 <= 0 || d->fp8 || d->batch != 1 || d->split_k > 1 || d->act == VLA_ACT_SWIGLU_BWD || d->rope_mode == 2 || d->a_group != 0 ||
-      (d->rope_mode == 1 && d->rope_dh != 64) || !vla_gemm256_extent_ok(d))
-    return false;
-  const unsigned long long ra = (unsigned long long)((d->M + 255) / 256) * 256, rb = (unsigned long long)((d->N + 255) / 256) * 256;
-  if ((ra * d->lda2 + d->K2) * 2 >= (1ull << 32) || (rb * d->ldb2 + d->K2) * 2 >= (1ull << 32)) return false;
-  const char* e = getenv("VLA_GEMM_TILE");
-  const int force = e ? atoi(e) : 0;
-  if (force == 6) return true;
-  if (force != 0) return false;
-  const long long t256 = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256);
-  static const bool no_rope256 = getenv("VLA_NO_ROPE256") != nullptr;
-  if (d->rope_mode == 1 && (no_rope256 || t256 < 192)) return false;
-  return use_256(d->M, d->N, d->K + d->K2, 1, d->act);
-}
-
-extern "C" int vla_gemm_uses_256(const vla_gemm_desc* d) {
-  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->fp8 || d->split_k > 1) return 0;
-  if (d->K2 > 0) return ext_on_256(d) ? 1 : 0;
-  const TileChoice tc = route(d);
-  return tc.bm == 256 && tc.bn == 257 ? 1 : 0;
-}
-
-// second pass of a split-K product: the `split` fp32 planes of d->ws summed in order, then alpha / bias / activation / residual / rounding
-static int splitk_finalize(const vla_gemm_desc* d, int split, hipStream_t st) {
-  const long long total = (long long)d->M * d->N / 4;
-  const unsigned nblk = (unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(splitk_finalize_kernel, dim3(nblk), dim3(256), 0, st, (const float*)d->ws, (const bf16_t*)d->bias,
-                     (const bf16_t*)d->R, (bf16_t*)d->C, d->M, d->N, d->ldc, d->ldr, d->act, d->alpha == 0.f ? 1.f : d->alpha, split,
-                     (d->ldc % 4 == 0 && ((uintptr_t)d->C & 7) == 0 && (!d->R || (d->ldr % 4 == 0 && ((uintptr_t)d->R & 7) == 0)) &&
-                      (!d->bias || ((uintptr_t)d->bias & 7) == 0)) ? 1 : 0);
-  VLA_CHECK_LAUNCH("gemm_splitk_finalize");
-  return VLA_OK;
+extern "C" int vla_gemm_nt_plan(const vla_gemm_desc* d, int latency, int num_cus, int* split) {
+  if (!d || d->M <= 0 || d->N <= 0 || d->K < BK || d->batch <= 0) return VLA_ERR_ARG;
+  const bool lat = latency < 0 ? g_latency_hint > 0 : latency > 0;
+  const int ncu = num_cus > 0 ? num_cus : vla_num_cus();
+  const NtOverrides ov = nt_overrides();
+  const NtPlan pl = plan_nt(d, lat, ncu, ov);
+  if (split) *split = d->split_k > 1 ? pl.split : auto_split_k(d, lat, ncu, ov);
+  return pl.kernel;
 }
 
 extern "C" int vla_gemm_bf16_nt(void* stream, const vla_gemm_desc* d) {
@@ -777,6 +885,37 @@ extern "C" int vla_gemm_bf16_nt(void* stream, const vla_gemm_desc* d) {
   VLA_REQUIRE(d->a_group >= 0 && d->c_group >= 0 && d->a_group_stride % 8 == 0 &&
                   (d->c_group == 0 || d->ldc % 8 != 0 || d->c_group_stride % 8 == 0),
               "gemm: row-group strides must keep 16-B alignment");
+  const bool split_k = d->split_k > 1;
+  VLA_REQUIRE(d->bias_post_round == 0 || (d->bias_post_round == 1 && d->bias && d->rope_mode != 1 && !split_k && d->act == VLA_ACT_NONE),
+              "gemm: bias_post_round needs a bias and a plain epilogue (no rotate_half rope / split-K / activation)");
+  if (split_k) {
+    VLA_REQUIRE(d->ws && d->batch == 1 && d->rope_mode == 0 && d->c_group == 0 && d->r_group == 0 &&
+                    d->res_mod == 0 && d->c_live_mod == 0 && d->C &&
+                    (d->act == VLA_ACT_NONE || d->act == VLA_ACT_GELU || d->act == VLA_ACT_RELU || d->act == VLA_ACT_GELU_TANH),
+                "gemm: split_k needs an fp32 workspace [split_k, M, N], batch 1 and a plain epilogue");
+    VLA_REQUIRE(d->N % 4 == 0 && ((uintptr_t)d->ws & 15) == 0, "gemm: split_k needs N % 4 == 0 and a 16-B aligned workspace");
+  }
+  VLA_REQUIRE(d->c_live_mod >= 0 && d->c_live_from >= 0 && (d->c_live_mod == 0 || d->c_live_from < d->c_live_mod),
+              "gemm: c_live_from must lie inside c_live_mod");
+  VLA_REQUIRE(d->r_group >= 0 && d->r_group_stride % 8 == 0 && (d->r_group == 0 || d->res_mod == 0),
+              "gemm: r_group stride must keep 16-B alignment; r_group and res_mod are exclusive");
+  if (d->K2 != 0)
+    VLA_REQUIRE(d->K2 > 0 && d->K2 % BK == 0 && d->A2 && d->B2 && d->lda2 % 8 == 0 && d->ldb2 % 8 == 0 && (((uintptr_t)d->A2 | (uintptr_t)d->B2) & 15) == 0 &&
+                    d->batch == 1 && !split_k && d->rope_mode != 2,
+                "gemm: the K extension needs A2 / B2 (bf16, 16-B aligned rows, K2 % 64 == 0), batch 1, no split-K / interleaved RoPE");
+  if (d->rope_mode != 0) {
+    VLA_REQUIRE(d->rope_mode == 1 || d->rope_mode == 2, "gemm: rope_mode 0/1/2");
+    VLA_REQUIRE(d->rope_cos && d->rope_sin && d->rope_T > 0 && d->rope_dh > 0 && d->rope_dh % 4 == 0 && d->rope_cols % 64 == 0 &&
+                    (((uintptr_t)d->rope_cos | (uintptr_t)d->rope_sin) & 15) == 0 && d->act != VLA_ACT_SWIGLU,
+                "gemm: bad rope arguments");
+    if (d->rope_mode == 1) VLA_REQUIRE(d->rope_dh == 64 || (d->rope_dh == 128 && d->N % 128 == 0 && d->rope_cols % 128 == 0),
+                                       "gemm: fused rotate_half RoPE needs head dim 64, or 128 with N and rope_cols multiples of 128");
+  }
+
+  const NtOverrides ov = nt_overrides();
+  const int ncu = vla_num_cus();
+  const NtPlan pl = plan_nt(d, g_latency_hint > 0, ncu, ov);
+
   GemmP p;
   p.A = (const bf16_t*)d->A; p.B = (const bf16_t*)d->B; p.C = (bf16_t*)d->C;
   p.bias = (const bf16_t*)d->bias; p.R = (const bf16_t*)d->R; p.C2 = (bf16_t*)d->C2;
@@ -788,120 +927,43 @@ extern "C" int vla_gemm_bf16_nt(void* stream, const vla_gemm_desc* d) {
   p.gA = d->a_group; p.sgA = d->a_group_stride; p.gC = d->c_group; p.sgC = d->c_group_stride;
   p.gR = d->r_group; p.sgR = d->r_group_stride;
   p.c_live_mod = d->c_live_mod; p.c_live_from = d->c_live_from;
-  int split = d->split_k > 1 ? d->split_k : 1;     // (split-K below may lower it: uneven slices)
   p.bias_post = d->bias_post_round;
-  VLA_REQUIRE(d->bias_post_round == 0 || (d->bias_post_round == 1 && d->bias && d->rope_mode != 1 && split == 1 && d->act == VLA_ACT_NONE),
-              "gemm: bias_post_round needs a bias and a plain epilogue (no rotate_half rope / split-K / activation)");
   p.ws = nullptr; p.Ktot = 0;
-  if (split > 1) {
-    VLA_REQUIRE(d->ws && d->batch == 1 && d->rope_mode == 0 && d->c_group == 0 && d->r_group == 0 &&
-                    d->res_mod == 0 && d->c_live_mod == 0 && d->C &&
-                    (d->act == VLA_ACT_NONE || d->act == VLA_ACT_GELU || d->act == VLA_ACT_RELU || d->act == VLA_ACT_GELU_TANH),
-                "gemm: split_k needs an fp32 workspace [split_k, M, N], batch 1 and a plain epilogue");
-    VLA_REQUIRE(d->N % 4 == 0 && ((uintptr_t)d->ws & 15) == 0, "gemm: split_k needs N % 4 == 0 and a 16-B aligned workspace");
-    // slices of ceil(K-tiles / split_k) K-tiles; when that does not divide, the last slice is shorter and fewer slices may be needed
-    const int kt = d->K / BK, per = (kt + split - 1) / split;
-    split = (kt + per - 1) / per;
+  if (split_k) {
+    const int kt = d->K / BK;
     p.ws = d->ws;
-    p.K = per * BK;                // every z slice owns `per` K-tiles of the contraction (the last one what is left of Ktot)
+    p.K = (kt + pl.split - 1) / pl.split * BK;   // every z slice owns that many K-tiles of the contraction (the last one what is left of Ktot)
     p.Ktot = d->K;
     p.sA = p.sB = p.K;             // ... starting that many elements further along the rows of A and B
     p.bias = nullptr; p.R = nullptr;
   }
-  VLA_REQUIRE(d->c_live_mod >= 0 && d->c_live_from >= 0 && (d->c_live_mod == 0 || d->c_live_from < d->c_live_mod),
-              "gemm: c_live_from must lie inside c_live_mod");
-  VLA_REQUIRE(d->r_group >= 0 && d->r_group_stride % 8 == 0 && (d->r_group == 0 || d->res_mod == 0),
-              "gemm: r_group stride must keep 16-B alignment; r_group and res_mod are exclusive");
   p.rope_mode = d->rope_mode; p.rope_T = d->rope_T; p.rope_dh = d->rope_dh; p.rope_cols = d->rope_cols;
   p.rope_cos = d->rope_cos; p.rope_sin = d->rope_sin;
   p.scaleA = d->fp8 ? d->a_scale : nullptr; p.scaleB = d->fp8 ? d->b_scale : nullptr;
   p.A2 = (const bf16_t*)d->A2; p.B2 = (const bf16_t*)d->B2; p.K2 = d->K2; p.lda2 = d->lda2; p.ldb2 = d->ldb2;
-  if (d->K2 != 0)
-    VLA_REQUIRE(d->K2 > 0 && d->K2 % BK == 0 && d->A2 && d->B2 && d->lda2 % 8 == 0 && d->ldb2 % 8 == 0 && (((uintptr_t)d->A2 | (uintptr_t)d->B2) & 15) == 0 &&
-                    d->batch == 1 && split == 1 && d->rope_mode != 2,
-                "gemm: the K extension needs A2 / B2 (bf16, 16-B aligned rows, K2 % 64 == 0), batch 1, no split-K / interleaved RoPE");
-  if (d->rope_mode != 0) {
-    VLA_REQUIRE(d->rope_mode == 1 || d->rope_mode == 2, "gemm: rope_mode 0/1/2");
-    VLA_REQUIRE(d->rope_cos && d->rope_sin && d->rope_T > 0 && d->rope_dh > 0 && d->rope_dh % 4 == 0 && d->rope_cols % 64 == 0 &&
-                    (((uintptr_t)d->rope_cos | (uintptr_t)d->rope_sin) & 15) == 0 && d->act != VLA_ACT_SWIGLU,
-                "gemm: bad rope arguments");
-    if (d->rope_mode == 1) VLA_REQUIRE(d->rope_dh == 64 || (d->rope_dh == 128 && d->N % 128 == 0 && d->rope_cols % 128 == 0),
-                                       "gemm: fused rotate_half RoPE needs head dim 64, or 128 with N and rope_cols multiples of 128");
-  }
-  const char* e = getenv("VLA_GEMM_TILE");
-  {   // small-output products (the LoRA t / dt products; the action head's Linears on 8 x B rows; the batch-1 pass): gemm_skinny.hip
-    const bool simple = d->batch == 1 && split == 1 && d->a_group == 0 && d->c_group == 0 && d->r_group == 0 && d->res_mod == 0 && d->c_live_mod == 0 &&
-                        !d->fp8 && d->K2 == 0 && d->C && !(e && atoi(e) != 0);
-    if (vla_gemm_skinny_try(p, simple, g_latency_hint.load(std::memory_order_relaxed) > 0, (hipStream_t)stream)) {
-      VLA_CHECK_LAUNCH("gemm_bf16_nt(skinny)");
-      return VLA_OK;
-    }
-  }
-  const TileChoice tc = route(d);
-  const bool fits256 = vla_gemm256_extent_ok(d) != 0;
-  if (d->K2 > 0) {                 // K extension: the 128-row kernel, or - bf16, chip-filling shapes - the 256-row kernel's EXT instantiations
-    hipStream_t sx = (hipStream_t)stream;
-    if (d->fp8) {                  // e4m3 base operands, bf16 extension: the scales meet the accumulator between the two contractions
-      if (d->act == VLA_ACT_SWIGLU_BWD) launch<128, 128, 2, 3, 4, true, true>(p, d->M, d->N, 1, sx);
-      else if (d->rope_mode == 1) launch<128, 128, 2, 1, 4, true, true>(p, d->M, d->N, 1, sx);
-      else launch<128, 128, 2, 0, 4, true, true>(p, d->M, d->N, 1, sx);
-    } else if (ext_on_256(d)) vla_gemm256_launch(p, d->act == VLA_ACT_SWIGLU ? 1 : 0, 1, sx);     // (p.K2 > 0: the EXT instantiations)
-    else if (d->act == VLA_ACT_SWIGLU_BWD) launch<128, 128, 2, 3, 4, false, true>(p, d->M, d->N, 1, sx);
-    else if (d->rope_mode == 1) launch<128, 128, 2, 1, 4, false, true>(p, d->M, d->N, 1, sx);
-    else launch<128, 128, 2, 0, 4, false, true>(p, d->M, d->N, 1, sx);
-    VLA_CHECK_LAUNCH("gemm_bf16_nt(ext)");
-    return VLA_OK;
-  }
+
   hipStream_t st = (hipStream_t)stream;
-  if (d->fp8) {
-    // e4m3 operands.  With the K loop halved, the 256 x 256 kernel's per-tile costs weigh twice as much: on the step's shapes the
-    // 128-row kernel (two workgroups per CU, one's epilogue under the other's K loop) is as fast or faster (gate/up 162 vs 162 us,
-    // down 62 vs 70, ViT fc1 63 vs 87), on big squares the 256-row kernel wins (8192^3: 2503 vs 2108 TF/s) - it takes those.
-    const int force = e ? atoi(e) : 0;
-    if ((force == 6 || (force == 0 && d->M >= 4096 && d->N >= 4096 && d->K >= 4096)) && d->c_group == 0 && d->r_group == 0 && fits256 &&
-        !(d->rope_mode == 1 && d->rope_dh != 64))
-      vla_gemm256_launch(p, d->act == VLA_ACT_SWIGLU ? 1 : 0, 1, st);
-    else if (d->rope_mode == 1) launch<128, 128, 2, 1, 4, true>(p, d->M, d->N, 1, st);
-    else launch<128, 128, 2, 0, 4, true>(p, d->M, d->N, 1, st);
-    VLA_CHECK_LAUNCH("gemm_fp8_nt");
-    return VLA_OK;
-  }
-  if (tc.bm == 256 && tc.bn == 257) {          // 256 x 256 staggered 8-phase kernel (gemm256.hip)
-    const int epi = d->act == VLA_ACT_SWIGLU ? 1 : d->act == VLA_ACT_SWIGLU_BWD ? 2 : 0;
+  const int nb = pl.split > 1 ? pl.split : d->batch;
+  const int rope = d->act == VLA_ACT_SWIGLU_BWD ? 3 : d->rope_mode;
+  int rc;
+  if (pl.kernel < VLA_KERNEL_NT_SKINNY + SKINNY_TILES) rc = vla_gemm_skinny_launch(p, pl.kernel - VLA_KERNEL_NT_SKINNY, st);
+  else if (pl.kernel == VLA_KERNEL_NT_256)
     // (a column peel of the tail round - the last column tiles on the 128-row kernel behind this launch - turned ViT fc1's 105 us into
     //  ~80 isolated and cost 0.1 ms on the step: the other streams already fill the tail round.  tools/diag/gemm256_pruned_paths.patch)
-    vla_gemm256_launch(p, epi, d->batch, st);
-  } else if (d->act == VLA_ACT_SWIGLU_BWD) launch<128, 128, 2, 3, 4>(p, d->M, d->N, d->batch, st);
-  else {
-    // Launches of at most one workgroup per CU (batch-1 inference: every product; the training step: the action head's x-chain) are
-    // bound by the LATENCY of a K-tile, not by bandwidth: with the two-stage ring one K-tile is in flight per workgroup and every tile
-    // costs a full trip to HBM (~1.2 us against 0.2 us of MFMAs: 17-22 us for ANY product of the batch-1 pass, K = 896-1152, whatever its
-    // size).  They run on a four-stage ring (128 KiB of LDS: the CU is theirs anyway), three K-tiles in flight - or, when even 64-row tiles
-    // leave CUs idle, on 64 x 128 tiles with a six-stage ring (144 KiB, five in flight, twice the workgroups: what such a launch can keep
-    // in flight is workgroups x ring bytes) -, the same K order and MFMA sequence: bit-identical (test_gemm_deep_ring_bit_identical).
-    // Only under vla_gemm_latency_hint(1): in the training step the same launches share the chip with two other streams' kernels, and a 128-KiB workgroup waits for a whole CU's LDS where the 64-KiB one
-    // slips in beside another (step 24.13 -> 24.44 ms same box with the deep ring on every sub-round launch).  VLA_NO_DEEP_RING=1: two
-    // stages everywhere (A/B aid).
-    const int nb = split > 1 ? split : d->batch;
-    const long long wgs = (long long)((d->M + 127) / 128) * ((d->N + 127) / 128) * nb, wgs64 = (long long)((d->M + 63) / 64) * ((d->N + 127) / 128) * nb;
-    const bool lat = g_latency_hint.load(std::memory_order_relaxed) > 0 && tc.bn == 128 && p.K / BK >= 4 && !getenv("VLA_NO_DEEP_RING");
-    const bool deep64 = lat && wgs64 <= vla_num_cus();            // 64-row tiles, six stages (144 KiB): twice the workgroups, five K-tiles in flight
-    const bool deep = lat && !deep64 && wgs <= vla_num_cus();     // 128-row tiles, four stages (128 KiB)
-    if (d->rope_mode == 1) {               // 8 waves, rotation pairs inside a lane
-      if (deep64) launch<64, 128, 6, 1, 4>(p, d->M, d->N, nb, st);
-      else if (deep) launch<128, 128, 4, 1, 4>(p, d->M, d->N, nb, st);
-      else launch<128, 128, 2, 1, 4>(p, d->M, d->N, nb, st);
-    } else if (d->rope_mode == 2) {
-      if (deep64) launch<64, 128, 6, 2, 4>(p, d->M, d->N, nb, st);
-      else if (deep) launch<128, 128, 4, 2, 4>(p, d->M, d->N, nb, st);
-      else if (tc.bn == 128) launch<128, 128, 2, 2, 4>(p, d->M, d->N, nb, st);
-      else launch<128, 64, 2, 2>(p, d->M, d->N, nb, st);
-    } else if (deep64) launch<64, 128, 6, 0, 4>(p, d->M, d->N, nb, st);
-    else if (deep) launch<128, 128, 4, 0, 4>(p, d->M, d->N, nb, st);
-    else if (tc.bn == 128) launch<128, 128, 2, 0, 4>(p, d->M, d->N, nb, st);   // 8 waves (2x4) of 64x32
-    else launch<128, 64, 2, 0>(p, d->M, d->N, nb, st);
-  }
+    rc = vla_gemm256_launch(p, d->act == VLA_ACT_SWIGLU ? 1 : d->act == VLA_ACT_SWIGLU_BWD ? 2 : 0, d->batch, ov.grid_set ? ov.grid : ncu, st);
+  else if (d->K2 > 0 && d->fp8)    // e4m3 base operands, bf16 extension: the scales meet the accumulator between the two contractions
+    rc = rope == 3 ? launch_nt<3, true, true>(pl.kernel, p, nb, st) : rope == 1 ? launch_nt<1, true, true>(pl.kernel, p, nb, st)
+                                                                                : launch_nt<0, true, true>(pl.kernel, p, nb, st);
+  else if (d->K2 > 0)
+    rc = rope == 3 ? launch_nt<3, false, true>(pl.kernel, p, nb, st) : rope == 1 ? launch_nt<1, false, true>(pl.kernel, p, nb, st)
+                                                                                 : launch_nt<0, false, true>(pl.kernel, p, nb, st);
+  else if (d->fp8) rc = rope == 1 ? launch_nt<1, true>(pl.kernel, p, nb, st) : launch_nt<0, true>(pl.kernel, p, nb, st);
+  else if (rope == 3) rc = launch_nt<3>(pl.kernel, p, nb, st);
+  else if (rope == 2) rc = launch_nt<2>(pl.kernel, p, nb, st);
+  else if (rope == 1) rc = launch_nt<1>(pl.kernel, p, nb, st);
+  else rc = launch_nt<0>(pl.kernel, p, nb, st);
+  if (rc) return rc;
   VLA_CHECK_LAUNCH("gemm_bf16_nt");
-  if (split > 1) return splitk_finalize(d, split, st);
+  if (pl.split > 1) return splitk_finalize(d, pl.split, st);
   return VLA_OK;
 }

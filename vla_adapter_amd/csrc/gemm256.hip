@@ -763,49 +763,40 @@ int num_cus() {
 }
 
 template <int EPI, bool F8 = false, bool RES = true, bool R2 = false, bool EXT = false>
-int launch256(const GemmP& p0, int batch, hipStream_t st) {
+int launch256(const GemmP& p0, int batch, long long grid, hipStream_t st) {
+  if (int rc = vla_lds_limit<gemm256_kernel<EPI, F8, RES, R2, EXT>>(LDS_BYTES, "gemm256_kernel")) return rc;
   GemmP p = p0;
   p.tiles_n = (p.N + 255) / 256;
   p.ntiles = ((p.M + 255) / 256) * p.tiles_n;
   p.batch = batch;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI, F8, RES, R2, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_set = true;
-  }
-  // one workgroup per CU walks the tiles (VLA_GEMM256_GRID overrides the workgroup count: 0 = one workgroup per tile)
-  const char* ge = getenv("VLA_GEMM256_GRID");      // (read per launch: the A/B tool flips it in one process)
   const long long total = (long long)p.ntiles * batch;
+  if (grid <= 0 || grid > total) grid = total;
   // Free de-phasing of a partial last round (kernel: start of the walk).  Every workgroup has the same work per tile, so all 256
   // epilogues burst their stores into the fabric in the same few microseconds and wait for it; the workgroups that walk one tile
   // fewer have a tile's time to spare, and starting them late by half a tile puts their bursts between those of the others.
   // Same box: gate/up 203 -> 196 us, d->dh 97 -> 95, exact-round launches unchanged, step -0.15 ... -0.2 ms.  (A delay for EVERY
   // group of workgroups - not only those with slack - shortens the epilogues by what the delay costs: measured, no gain.)
-  // VLA_GEMM256_STAGGER = percent of the estimated tile time (default 50, 0 = off; read per launch for the A/B tools).
-  const char* se = getenv("VLA_GEMM256_STAGGER");
-  long long grid = ge ? atoll(ge) : num_cus();
-  if (grid <= 0 || grid > total) grid = total;
   p.stagger = 0;
   if (total > grid && total % grid != 0) {
     const long long tile_cycles = (long long)((p.K + (EXT ? p.K2 : 0)) / BK) * 2128 + 13000;       // K loop + what surrounds it (stamped: DESIGN section 4)
-    p.stagger = (int)(tile_cycles * (se != nullptr ? atoi(se) : 50) / 100 / 1024);
+    p.stagger = (int)(tile_cycles / 2 / 1024);                                                        // half a tile, in units of 1024 cycles
   }
   hipLaunchKernelGGL((gemm256_kernel<EPI, F8, RES, R2, EXT>), dim3((unsigned)grid), dim3(512), LDS_BYTES, st, p);
-  return 0;
+  return VLA_OK;
 }
 
 }  // namespace
 
 int vla_num_cus() { return num_cus(); }
 
-int vla_gemm256_launch(const GemmP& p, int epi, int batch, hipStream_t st) {
+int vla_gemm256_launch(const GemmP& p, int epi, int batch, long long grid, hipStream_t st) {
   if (p.K2 > 0) {                    // K extension (host: bf16, batch 1, plain / residual / rotate_half or SwiGLU-forward epilogue)
-    if (epi == 1) return launch256<1, false, true, false, true>(p, 1, st);
-    return p.R ? launch256<0, false, true, false, true>(p, 1, st) : launch256<0, false, false, false, true>(p, 1, st);
+    if (epi == 1) return launch256<1, false, true, false, true>(p, 1, grid, st);
+    return p.R ? launch256<0, false, true, false, true>(p, 1, grid, st) : launch256<0, false, false, false, true>(p, 1, grid, st);
   }
-  if (p.scaleA != nullptr) return epi == 1 ? launch256<1, true>(p, batch, st) : launch256<0, true>(p, batch, st);     // fp8 operands
-  if (p.rope_mode == 2) return launch256<0, false, false, true>(p, batch, st);     // (host: plain epilogue, no residual)
-  if (epi == 1) return launch256<1>(p, batch, st);
-  if (epi == 2) return launch256<2>(p, batch, st);
-  return p.R ? launch256<0, false, true>(p, batch, st) : launch256<0, false, false>(p, batch, st);
+  if (p.scaleA != nullptr) return epi == 1 ? launch256<1, true>(p, batch, grid, st) : launch256<0, true>(p, batch, grid, st);     // fp8 operands
+  if (p.rope_mode == 2) return launch256<0, false, false, true>(p, batch, grid, st);     // (host: plain epilogue, no residual)
+  if (epi == 1) return launch256<1>(p, batch, grid, st);
+  if (epi == 2) return launch256<2>(p, batch, grid, st);
+  return p.R ? launch256<0, false, true>(p, batch, grid, st) : launch256<0, false, false>(p, batch, grid, st);
 }

@@ -22,9 +22,12 @@ struct GemmP {
   const bf16_t* A2; const bf16_t* B2; int K2, lda2, ldb2;   // K extension (gemm.hip EXT): C = epilogue(A . B^T + A2 . B2^T)
 };
 
-// gemm256.hip: 256x256x64 tile, 8 waves, staggered 8-phase schedule.  epi: 0 plain, 1 SwiGLU forward, 2 SwiGLU backward.
-int vla_gemm256_launch(const GemmP& p, int epi, int batch, hipStream_t st);
-// gemm_skinny.hip: small-output products (tall-skinny N = 64 / 128 / 192, or - under the latency hint - M <= 512; K < 2048; bias / activation / residual /
-// interleaved-RoPE epilogue): 1 = launched there, 0 = not its shape.  `p` must be completely filled.
-int vla_gemm_skinny_try(const GemmP& p, bool simple_addressing, bool latency_hint, hipStream_t st);
+// gemm256.hip: 256x256x64 tile, 8 waves, staggered 8-phase schedule.  epi: 0 plain, 1 SwiGLU forward, 2 SwiGLU backward.  `grid`:
+// workgroups walking the tiles (<= 0 or more than the tiles: one per tile).
+int vla_gemm256_launch(const GemmP& p, int epi, int batch, long long grid, hipStream_t st);
+// gemm_skinny.hip: small-output products on (16 MT) x (16 NT) tiles, four waves splitting K; `tile` indexes SKINNY_TILE (gemm.hip's
+// plan picks it).  `p` must be completely filled.
+constexpr int SKINNY_TILES = 7;
+constexpr int SKINNY_TILE[SKINNY_TILES][2] = {{1, 1}, {1, 2}, {2, 2}, {1, 4}, {2, 4}, {4, 4}, {4, 6}};   // {MT, NT}
+int vla_gemm_skinny_launch(const GemmP& p, int tile, hipStream_t st);
 int vla_num_cus();      // compute units of the current device (cached)

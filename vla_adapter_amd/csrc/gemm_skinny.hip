@@ -151,60 +151,24 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmP p) {
 }
 
 template <int MT, int NT, int U>
-void launch_skinny(const GemmP& p, hipStream_t st) {
+int launch_skinny(const GemmP& p, hipStream_t st) {
   constexpr int LDS = 4 * 16 * MT * (16 * NT + 4) * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_skinny_kernel<MT, NT, U>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
+  if (int rc = vla_lds_limit<gemm_skinny_kernel<MT, NT, U>>(LDS, "gemm_skinny_kernel")) return rc;
   hipLaunchKernelGGL((gemm_skinny_kernel<MT, NT, U>), dim3((p.M + 16 * MT - 1) / (16 * MT), (p.N + 16 * NT - 1) / (16 * NT)), dim3(256), LDS, st, p);
+  return VLA_OK;
 }
 
 }  // namespace
 
-// Host-side predicate + launch (called from vla_gemm_bf16_nt after its argument checks, `p` completely filled): 1 = launched here,
-// 0 = not this kernel's shape / epilogue.  latency_hint: vla_gemm_latency_hint is set.  simple_addressing: batch 1, no split-K, no row groups / res_mod / c_live, no K extension, bf16.
-// Contractions of 2048 and more stay on the 128-row tiles with split-K (measured, tools/diag/bench_skinny.py: with K cut into slices here
-// as well, 64-row tiles pull twice the operand rows per output and lose - dt of gate/up, K = 9728: 57.7 vs 32.1 us; t of down 22.8 vs 20.0).
-int vla_gemm_skinny_try(const GemmP& p, bool simple_addressing, bool latency_hint, hipStream_t st) {
-  if (getenv("VLA_NO_SKINNY") || !simple_addressing) return 0;
-  const bool tall = (p.N == 64 || p.N == 128 || p.N == 192) && p.M >= 1024;                         // (a)
-  // (b) only under the caller's latency hint (the batch-1 pass): in a training step the head's products are off the critical path (measured:
-  // no change of the step), and a product's bits would depend on its row count - the live-row backward equals the full one bit for bit
-  // because every row is computed by the same instruction sequence whatever M is (tests/test_engine_gpu.py)
-  const bool shortm = latency_hint && p.M <= 512 && p.N % 16 == 0 && p.K >= 512 && !getenv("VLA_NO_SMALL_ROWS");
-  if (!(tall || shortm) || p.K % 128 != 0 || p.K >= 2048 || p.ldc % 8 != 0 || ((uintptr_t)p.C & 15) != 0) return 0;
-  if (!(p.act == VLA_ACT_NONE || p.act == VLA_ACT_GELU || p.act == VLA_ACT_RELU || p.act == VLA_ACT_GELU_TANH)) return 0;
-  if (p.bias && ((uintptr_t)p.bias & 15) != 0) return 0;
-  if (p.R && (p.ldr % 8 != 0 || ((uintptr_t)p.R & 15) != 0)) return 0;
-  if ((p.rope_mode == 1 && (p.rope_dh != 64 || p.rope_cols % 64 != 0 || tall)) || (p.rope_mode == 2 && (p.rope_dh % 8 != 0 || p.rope_cols % 8 != 0 || (((uintptr_t)p.rope_cos | (uintptr_t)p.rope_sin) & 15) != 0))) return 0;
-  // Tile: what a CU has to pull through its L1 is (tile rows + tile columns) x K operand rows per workgroup, times the workgroups it gets -
-  // minimised over the instantiated tiles (every CU busy, as few rows each as possible; ties: the larger tile)
-  static const int TL[7][2] = {{1, 1}, {1, 2}, {2, 2}, {1, 4}, {2, 4}, {4, 4}, {4, 6}};
-  const int ncu = vla_num_cus();
-  int best = -1;
-  long long best_cost = 0;
-  for (int t = 0; t < 7; ++t) {
-    const int tm = 16 * TL[t][0], tn = 16 * TL[t][1];
-    if (tall && p.N % tn != 0) continue;
-    if (p.rope_mode == 1 && tn != 64) continue;              // rotate_half: both halves of a head inside one tile row
-    const long long wgs = (long long)((p.M + tm - 1) / tm) * ((p.N + tn - 1) / tn), cost = (long long)(tm + tn) * ((wgs + ncu - 1) / ncu);
-    if (best < 0 || cost < best_cost || (cost == best_cost && t > best)) best = t, best_cost = cost;
+// Launch on SKINNY_TILE[tile] (called from vla_gemm_bf16_nt after its argument checks; the eligibility is gemm.hip's skinny_tile).
+int vla_gemm_skinny_launch(const GemmP& p, int tile, hipStream_t st) {
+  switch (tile) {
+    case 0: return launch_skinny<1, 1, 8>(p, st);
+    case 1: return launch_skinny<1, 2, 6>(p, st);
+    case 2: return launch_skinny<2, 2, 6>(p, st);
+    case 3: return launch_skinny<1, 4, 4>(p, st);
+    case 4: return launch_skinny<2, 4, 4>(p, st);
+    case 5: return launch_skinny<4, 4, 3>(p, st);
+    default: return launch_skinny<4, 6, 2>(p, st);
   }
-  // (b) only for tiles up to 32 x 64 (96 operand rows per workgroup): measured in the batch-1 pass (profiles/r04_prof_predict_summary.txt, us under
-  // the profiler, this kernel vs gemm.hip's 64 x 128 six-stage ring): 16 x 16 tiles 5.1 vs 10.6 (the head's 8-row products), 32 x 32 6.6 vs 12,
-  // 32 x 64 8.9-10.4 vs 12.7-12.9 (LLM o, ViT proj) - but 64 x 64 13.3 vs 12.3 (ViT q|k|v) and 64 x 96 17.3 vs 13.4 (ViT fc1): with 128+ operand
-  // rows per workgroup the LDS-DMA ring keeps more bytes in flight than register fragments at one or two waves per SIMD do
-  if (!tall && best_cost > 96) return 0;
-  switch (best) {
-    case 0: launch_skinny<1, 1, 8>(p, st); break;
-    case 1: launch_skinny<1, 2, 6>(p, st); break;
-    case 2: launch_skinny<2, 2, 6>(p, st); break;
-    case 3: launch_skinny<1, 4, 4>(p, st); break;
-    case 4: launch_skinny<2, 4, 4>(p, st); break;
-    case 5: launch_skinny<4, 4, 3>(p, st); break;
-    default: launch_skinny<4, 6, 2>(p, st); break;
-  }
-  return 1;
 }

@@ -20,7 +20,9 @@
 //     group): X = the first Kt rows of every sequence of a [B, S, D] hidden state, read in place;
 //   * column groups on A (column c at (c / g) * stride + c % g): the gate or the up columns of an interleaved dGU;
 //   * split over the contraction (blockIdx.z slices, fp32 planes + a finalize pass) for few-tile long-M products.
+#include <algorithm>
 #include "common.h"
+#include "gemm_params.h"
 #include "../../include/vla_native.h"
 
 namespace {
@@ -472,7 +474,7 @@ __global__ __launch_bounds__(512) void gemm_tn256_grouped_kernel(TnGroup G) {
 // amortise its prologue - when the launch (a batch, or a whole group) brings at least half a round of such tiles: one 256-tile
 // is ~130 us of K loop at 88 K-tiles, a launch of 20 of them leaves the chip to the tile's latency (tools/bench_tn.py: 5632 x
 // 1152 x 896 alone 86 us on 128-tiles, 142 us on 256-tiles; the four-layer group 848 -> 705 us).  VLA_TN_TILE=128 / 256 forces
-// one (read per launch for the A/B tools).
+// one (read once per call: tests flip it in the middle of a process).
 constexpr int TN256_MIN_TILES = 128;
 int tn_forced() {
   const char* e = getenv("VLA_TN_TILE");
@@ -480,12 +482,26 @@ int tn_forced() {
 }
 bool tn_eligible_256(int M, int N1, int N2, int split) { return split <= 1 && M >= 1024 && N1 >= 192 && N2 >= 192; }
 long long tn_tiles_256(int N1, int N2) { return (long long)((N1 + 255) / 256) * ((N2 + 255) / 256); }
-bool tn_use_256(int M, int N1, int N2, int split, int batch) {
-  if (split > 1) return false;
-  const int f = tn_forced();
-  if (f == 128) return false;
-  if (f == 256) return true;
-  return tn_eligible_256(M, N1, N2, split) && tn_tiles_256(N1, N2) * batch >= TN256_MIN_TILES;
+
+// Slices of the contraction: `asked` cut into K-tile aligned slices (row groups stay intact), as few as leave none empty.
+int tn_slices(int M, int asked) {
+  if (asked <= 1) return 1;
+  const int per = ((M + asked - 1) / asked + TBK - 1) / TBK * TBK;
+  return (M + per - 1) / per;
+}
+struct TnPlan { int kernel, split; };
+// d->split > 1: those slices (normalised).  Otherwise the automatic split - few-tile long-M products (the LoRA pairs): up to two
+// workgroups per CU, slices of >= 256 rows, at most 16 - when `auto_split`, else none.
+TnPlan plan_tn(const vla_gemm_tn_desc* d, int ncu, int forced, bool auto_split) {
+  int asked = d->split;
+  if (asked <= 1 && auto_split) {
+    const long long tiles = (long long)((d->N1 + 127) / 128) * ((d->N2 + 127) / 128) * d->batch;
+    asked = tiles * 2 <= ncu && d->M >= 1024 ? (int)std::max(1LL, std::min({16LL, 2 * ncu / tiles, (long long)d->M / 256})) : 1;
+  }
+  const int split = tn_slices(d->M, asked);
+  const bool on256 = split <= 1 && forced != 128 &&
+                     (forced == 256 || (tn_eligible_256(d->M, d->N1, d->N2, split) && tn_tiles_256(d->N1, d->N2) * d->batch >= TN256_MIN_TILES));
+  return {on256 ? VLA_KERNEL_TN_256 : VLA_KERNEL_TN_128, split};
 }
 
 // second pass of the contraction split: C = bf16(bf16(alpha * sum_s ws[b][s]) + R); 4 columns per thread
@@ -526,7 +542,8 @@ extern "C" int vla_gemm_bf16_tn(void* stream, const vla_gemm_tn_desc* d) {
                   (d->a_col_group == 0 || d->a_col_group_stride >= d->a_col_group),
               "gemm_tn: column groups on A must be multiples of 8 columns");
   if (d->R) VLA_REQUIRE(((uintptr_t)d->R & 7) == 0 && d->ldr % 4 == 0 && d->sR % 4 == 0, "gemm_tn: R must be 8-B aligned");
-  const int split = d->split > 1 ? d->split : 1;
+  const TnPlan pl = plan_tn(d, vla_num_cus(), tn_forced(), false);
+  const int split = pl.split;
   if (split > 1)
     VLA_REQUIRE(d->ws && ((uintptr_t)d->ws & 15) == 0 && d->N2 % 4 == 0, "gemm_tn: split needs an fp32 workspace [batch, split, N1, N2]");
   TnP p;
@@ -541,21 +558,16 @@ extern "C" int vla_gemm_bf16_tn(void* stream, const vla_gemm_tn_desc* d) {
   p.ntiles = ((d->N1 + 127) / 128) * p.tiles_n2;
   p.split = split;
   p.mslice = split > 1 ? ((d->M + split - 1) / split + TBK - 1) / TBK * TBK : d->M;       // K-tile aligned slices (groups stay intact)
-  VLA_REQUIRE((long long)p.mslice * (split - 1) < d->M, "gemm_tn: split leaves an empty contraction slice (lower it)");
   hipStream_t st = (hipStream_t)stream;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_tn256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS);
-    attr_set = true;
-  }
-  if (tn_use_256(d->M, d->N1, d->N2, split, d->batch)) {
+  if (pl.kernel == VLA_KERNEL_TN_256) {
+    if (int rc = vla_lds_limit<gemm_tn256_kernel>(T2_LDS, "gemm_tn256_kernel")) return rc;
     p.tiles_n2 = (d->N2 + 255) / 256;
     p.ntiles = ((d->N1 + 255) / 256) * p.tiles_n2;
     hipLaunchKernelGGL(gemm_tn256_kernel, dim3(p.ntiles, 1, d->batch), dim3(512), T2_LDS, st, p);
     VLA_CHECK_LAUNCH("gemm_bf16_tn (256)");
     return VLA_OK;
   }
+  if (int rc = vla_lds_limit<gemm_tn_kernel>(LDS_BYTES, "gemm_tn_kernel")) return rc;
   hipLaunchKernelGGL(gemm_tn_kernel, dim3(p.ntiles, 1, d->batch * split), dim3(512), LDS_BYTES, st, p);
   VLA_CHECK_LAUNCH("gemm_bf16_tn");
   if (split > 1) {
@@ -597,19 +609,25 @@ extern "C" int vla_gemm_bf16_tn_grouped(void* stream, const vla_gemm_tn_desc* de
     total[k] += ((d->N1 + tile - 1) / tile) * g.tiles_n2;
     ++cnt[k];
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_tn256_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS);
-    attr_set = true;
-  }
   for (int k = 1; k >= 0; --k) {       // the long 256-tile products first: the short ones fill their tail
     if (cnt[k] == 0) continue;
     G[k].start[cnt[k]] = total[k];
     G[k].count = cnt[k]; G[k].total = total[k];
-    if (k == 1) hipLaunchKernelGGL(gemm_tn256_grouped_kernel, dim3(total[k]), dim3(512), T2_LDS, (hipStream_t)stream, G[k]);
-    else hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(total[k]), dim3(512), LDS_BYTES, (hipStream_t)stream, G[k]);
+    if (k == 1) {
+      if (int rc = vla_lds_limit<gemm_tn256_grouped_kernel>(T2_LDS, "gemm_tn256_grouped_kernel")) return rc;
+      hipLaunchKernelGGL(gemm_tn256_grouped_kernel, dim3(total[k]), dim3(512), T2_LDS, (hipStream_t)stream, G[k]);
+    } else {
+      if (int rc = vla_lds_limit<gemm_tn_grouped_kernel>(LDS_BYTES, "gemm_tn_grouped_kernel")) return rc;
+      hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(total[k]), dim3(512), LDS_BYTES, (hipStream_t)stream, G[k]);
+    }
     VLA_CHECK_LAUNCH("gemm_bf16_tn_grouped");
   }
   return VLA_OK;
+}
+
+extern "C" int vla_gemm_tn_plan(const vla_gemm_tn_desc* d, int num_cus, int* split) {
+  if (!d || d->M <= 0 || d->N1 <= 0 || d->N2 <= 0 || d->batch <= 0) return VLA_ERR_ARG;
+  const int ncu = num_cus > 0 ? num_cus : vla_num_cus(), forced = tn_forced();
+  if (split) *split = plan_tn(d, ncu, forced, true).split;
+  return plan_tn(d, ncu, forced, false).kernel;
 }

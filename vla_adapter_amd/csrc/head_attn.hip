@@ -255,7 +255,7 @@ extern "C" int vla_head_attn_fwd(void* stream, const vla_head_attn_desc* d) {
   int rc = fill(p, d, false);
   if (rc) return rc;
   if (head_attn_mfma_supported(p) && !getenv("VLA_HEAD_ATTN_VALU")) {
-    head_attn_mfma_fwd(p, (hipStream_t)stream);
+    if (int rc = head_attn_mfma_fwd(p, (hipStream_t)stream)) return rc;
     VLA_CHECK_LAUNCH("head_attn_fwd(mfma)");
     return VLA_OK;
   }
@@ -274,7 +274,7 @@ extern "C" int vla_head_attn_bwd(void* stream, const vla_head_attn_desc* d) {
   if (rc) return rc;
   if (head_attn_mfma_supported(p) && !getenv("VLA_HEAD_ATTN_VALU")) {
     VLA_REQUIRE(p.out, "head_attn_bwd: the MFMA path needs the forward output (desc.out)");
-    head_attn_mfma_bwd(p, (hipStream_t)stream);
+    if (int rc = head_attn_mfma_bwd(p, (hipStream_t)stream)) return rc;
     VLA_CHECK_LAUNCH("head_attn_bwd(mfma)");
     return VLA_OK;
   }
@@ -282,11 +282,7 @@ extern "C" int vla_head_attn_bwd(void* stream, const vla_head_attn_desc* d) {
   const int N = p.T + p.Ka + p.Kt;
   const size_t lds = (size_t)(2 * TQ * p.dh + 3 * TQ * N + 64) * sizeof(float);
   VLA_REQUIRE(lds <= 160 * 1024, "head_attn_bwd: key count too large for LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)head_attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  if (int rc = vla_lds_limit<head_attn_bwd_kernel>(160 * 1024, "head_attn_bwd_kernel")) return rc;
   hipLaunchKernelGGL(head_attn_bwd_kernel, dim3(p.B * p.H), dim3(256), lds, (hipStream_t)stream, p);
   VLA_CHECK_LAUNCH("head_attn_bwd");
   if (p.rope_cos) {   // VALU fallback: apply the RoPE transpose with the stand-alone kernel (same contract as the MFMA path)

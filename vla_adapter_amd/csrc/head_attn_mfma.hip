@@ -843,38 +843,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void h
 }
 
 template <int D>
-void launch_fwd(const HP& p, hipStream_t st) {
-  const size_t lds = 4 * HG<D>::WAVE_BYTES;
-  if (p.ref_softmax) hipLaunchKernelGGL(head_fwd_mfma_ref<D>, dim3(p.B * p.H), dim3(256), lds, st, p);
-  else hipLaunchKernelGGL(head_fwd_mfma<D>, dim3(p.B * p.H), dim3(256), lds, st, p);
+int launch_fwd(const HP& p, hipStream_t st) {
+  constexpr int lds = 4 * HG<D>::WAVE_BYTES;
+  if (p.ref_softmax) {
+    if (int rc = vla_lds_limit<head_fwd_mfma_ref<D>>(lds, "head_fwd_mfma_ref")) return rc;
+    hipLaunchKernelGGL(head_fwd_mfma_ref<D>, dim3(p.B * p.H), dim3(256), lds, st, p);
+  } else {
+    if (int rc = vla_lds_limit<head_fwd_mfma<D>>(lds, "head_fwd_mfma")) return rc;
+    hipLaunchKernelGGL(head_fwd_mfma<D>, dim3(p.B * p.H), dim3(256), lds, st, p);
+  }
+  return VLA_OK;
 }
 template <int D>
-void launch_bwd(const HP& p, hipStream_t st) {
+int launch_bwd(const HP& p, hipStream_t st) {
   const int ntile = (p.T + p.Ka + p.Kt + 31) / 32;
   const long long need = (long long)p.B * p.H * ntile * ((long long)p.T * D + 1);
   if (p.ws != nullptr && p.ws_floats >= need && !getenv("VLA_HEAD_BWD_COMBINED")) {     // tile-uniform form (needs the workspace)
+    if (int rc = vla_lds_limit<head_bwd_tiles<D>>(4 * 33 * HG<D>::LD + 256 + 4 * HG<D>::TILE * 2, "head_bwd_tiles")) return rc;
     float* ws_gate = p.ws + (long long)p.B * p.H * ntile * p.T * D;
     const size_t lds2 = (size_t)4 * (p.T + 1) * HG<D>::LD + 256 + (size_t)4 * HG<D>::TILE * 2;
     hipLaunchKernelGGL(head_bwd_tiles<D>, dim3(p.B * p.H * ((ntile + 3) / 4)), dim3(256), lds2, st, p, p.ws, ws_gate);
     hipLaunchKernelGGL(head_dq_reduce<D>, dim3(p.B * p.H), dim3(256), 0, st, p, (const float*)p.ws, (const float*)ws_gate);
-    return;
+    return VLA_OK;
   }
-  const size_t lds = 4 * HG<D>::WAVE_BYTES;
+  constexpr int lds = 4 * HG<D>::WAVE_BYTES;
+  if (int rc = vla_lds_limit<head_bwd_mfma<D>>(lds, "head_bwd_mfma")) return rc;
   const int ndq = (p.B * p.H + 3) / 4, ndkv = (p.B * p.H * ntile + 3) / 4;
   hipLaunchKernelGGL(head_bwd_mfma<D>, dim3(ndq + ndkv), dim3(256), lds, st, p, ndq);
-}
-template <int D>
-void set_attrs() {
-  (void)hipFuncSetAttribute((const void*)head_fwd_mfma<D>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * HG<D>::WAVE_BYTES);
-  (void)hipFuncSetAttribute((const void*)head_fwd_mfma_ref<D>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * HG<D>::WAVE_BYTES);
-  (void)hipFuncSetAttribute((const void*)head_bwd_mfma<D>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * HG<D>::WAVE_BYTES);
-  (void)hipFuncSetAttribute((const void*)head_bwd_tiles<D>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 33 * HG<D>::LD + 256 + 4 * HG<D>::TILE * 2);
-}
-void set_all_attrs() {
-  static bool done = false;
-  if (done) return;
-  set_attrs<16>(); set_attrs<32>(); set_attrs<64>(); set_attrs<112>(); set_attrs<128>(); set_attrs<192>();
-  done = true;
+  return VLA_OK;
 }
 
 }  // namespace
@@ -884,25 +880,23 @@ bool head_attn_mfma_supported(const HP& p) {
          (long long)p.T * (p.T + p.Ka + p.Kt) >= 2 * p.T;   // probs slab must hold LSE + delta
 }
 
-void head_attn_mfma_fwd(const HP& p, hipStream_t st) {
-  set_all_attrs();
+int head_attn_mfma_fwd(const HP& p, hipStream_t st) {
   switch (p.dh) {
-    case 16: launch_fwd<16>(p, st); break;
-    case 32: launch_fwd<32>(p, st); break;
-    case 64: launch_fwd<64>(p, st); break;
-    case 112: launch_fwd<112>(p, st); break;
-    case 192: launch_fwd<192>(p, st); break;      // Qwen2.5-1.5B: d 1536 / 8 heads (BASELINE configs[4])
-    default: launch_fwd<128>(p, st); break;
+    case 16: return launch_fwd<16>(p, st);
+    case 32: return launch_fwd<32>(p, st);
+    case 64: return launch_fwd<64>(p, st);
+    case 112: return launch_fwd<112>(p, st);
+    case 192: return launch_fwd<192>(p, st);      // Qwen2.5-1.5B: d 1536 / 8 heads (BASELINE configs[4])
+    default: return launch_fwd<128>(p, st);
   }
 }
-void head_attn_mfma_bwd(const HP& p, hipStream_t st) {
-  set_all_attrs();
+int head_attn_mfma_bwd(const HP& p, hipStream_t st) {
   switch (p.dh) {
-    case 16: launch_bwd<16>(p, st); break;
-    case 32: launch_bwd<32>(p, st); break;
-    case 64: launch_bwd<64>(p, st); break;
-    case 112: launch_bwd<112>(p, st); break;
-    case 192: launch_bwd<192>(p, st); break;
-    default: launch_bwd<128>(p, st); break;
+    case 16: return launch_bwd<16>(p, st);
+    case 32: return launch_bwd<32>(p, st);
+    case 64: return launch_bwd<64>(p, st);
+    case 112: return launch_bwd<112>(p, st);
+    case 192: return launch_bwd<192>(p, st);
+    default: return launch_bwd<128>(p, st);
   }
 }

@@ -13,5 +13,5 @@ struct HP {
 };
 
 bool head_attn_mfma_supported(const HP& p);
-void head_attn_mfma_fwd(const HP& p, hipStream_t st);
-void head_attn_mfma_bwd(const HP& p, hipStream_t st);
+int head_attn_mfma_fwd(const HP& p, hipStream_t st);      // 0, or the error of the kernel's LDS attribute
+int head_attn_mfma_bwd(const HP& p, hipStream_t st);

@@ -1099,11 +1099,14 @@ class VLAEngine:
         self._ensure_streams()
         if key not in cache:
             static = {k: v.clone() for k, v in batch.items()}
-            for _ in range(2):                       # allocate buffers / set kernel attributes outside the capture
-                self.forward(static, None)
-            torch.cuda.synchronize()
-            segs = self._predict_segments(static)
-            with ops.latency_hint():                 # sub-chip launches on an idle chip: the deep-ring GEMM (bit-identical; baked into the graphs)
+            # sub-chip launches on an idle chip (ops.latency_hint: deep-ring GEMMs, short-M skinny tiles, uneven split-K, key-split
+            # attention - baked into the graphs).  The warm-up runs under the hint too, so that every kernel the graphs use has been
+            # launched, its LDS attribute set and its split-K workspace allocated before the capture.
+            with ops.latency_hint():
+                for _ in range(2):
+                    self.forward(static, None)
+                torch.cuda.synchronize()
+                segs = self._predict_segments(static)
                 graphs = schedule.capture(segs, {}, self._cap_stream)
             torch.cuda.synchronize()
             cache[key] = (graphs, static, segs)

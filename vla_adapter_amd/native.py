@@ -12,7 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = (os.environ.get("VLA_NATIVE_LIB") or None) or os.path.join(_HERE, "libvla_native.so")   # override: same-box A/B of two builds
 
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_TANH, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 7          # include/vla_native.h: VLA_ABI_VERSION
+# kernel ids of vla_gemm_nt_plan / vla_gemm_tn_plan (include/vla_native.h: VLA_KERNEL_*)
+KERNEL_NT_SKINNY, KERNEL_NT_64x128_S6, KERNEL_NT_128x128_S4, KERNEL_NT_128x128, KERNEL_NT_128x64, KERNEL_NT_256 = 0, 8, 9, 10, 11, 12
+KERNEL_TN_128, KERNEL_TN_256 = 16, 17
+ABI_VERSION = 8          # include/vla_native.h: VLA_ABI_VERSION
 
 
 class NativeLibraryMissing(ImportError):
@@ -76,7 +79,8 @@ _PROTOS = {
     "vla_version": ([], _I),
     "vla_desc_size": ([_I], _I),
     "vla_gemm256_extent_ok": ([C.POINTER(GemmDesc)], _I),
-    "vla_gemm_uses_256": ([C.POINTER(GemmDesc)], _I),
+    "vla_gemm_nt_plan": ([C.POINTER(GemmDesc), _I, _I, C.POINTER(C.c_int)], _I),
+    "vla_gemm_tn_plan": ([C.POINTER(GemmTnDesc), _I, C.POINTER(C.c_int)], _I),
     "vla_gemm_latency_hint": ([C.c_int], _I),
     "vla_gemm_bf16_tn": ([_P, C.POINTER(GemmTnDesc)], _I),
     "vla_gemm_bf16_tn_grouped": ([_P, C.POINTER(GemmTnDesc), _I], _I),

@@ -6,7 +6,6 @@ Every function launches on ``torch.cuda.current_stream()`` and raises on failure
 from __future__ import annotations
 
 import ctypes as C
-import os
 import math
 from typing import Optional, Tuple
 
@@ -103,10 +102,6 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, *, bias=None, residual=None, res_m
         assert cos_t.shape[1] == (dh // 2 if mode == 1 else dh)
         d.rope_mode, d.rope_T, d.rope_dh, d.rope_cols = mode, T, dh, ncols
         d.rope_cos, d.rope_sin = cos_t.data_ptr(), sin_t.data_ptr()
-    # split-K for few-tile long-K problems (batch-1 inference, and the live-row backward's M = B*64 GEMM over K = 2I): the
-    # K loop of a tile is serial, so a problem with fewer tiles than the chip has workgroup slots (2 x 256) runs at the
-    # latency of ONE long loop on part of the CUs; K slices meet in a per-stream fp32 workspace and are summed by
-    # splitk_finalize_kernel
     if fp8 is not None:
         sa, sb = fp8
         assert sa.dtype == torch.float32 and sb.dtype == torch.float32 and sa.numel() == M and sb.numel() == Nn and sa.is_contiguous() and sb.is_contiguous()
@@ -121,37 +116,30 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, *, bias=None, residual=None, res_m
     if bias_post_round:          # C = bf16(bf16(A.B^T) + bias): torch CPU Linear on a strided bf16 input (vla_native.h)
         assert bias is not None
         d.bias_post_round = 1
-    plain = (not bias_post_round and not batched and act in (ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_TANH) and out is not None and a_group is None
-             and c_group is None and r_group is None and rope is None and c_live is None and res_mod == 0 and Nn % 4 == 0)
-    if split_k is None:
-        split_k = 0
-        tiles = ((M + 127) // 128) * ((Nn + 127) // 128)
-        t64 = ((M + 63) // 64) * ((Nn + 127) // 128)
-        if (plain and K >= 2048 and t64 * 2 <= 256 and not os.environ.get("VLA_NO_SPLITK") and not os.environ.get("VLA_NO_SPLITK_UNEVEN")
-                and _lib().vla_gemm_latency_hint(-1) > 0):
-            # the batch-1 pass (latency hint): as many K slices as give every CU one 64 x 128 workgroup, >= 4 K-tiles each (the slices need
-            # not divide K: the last one is shorter) - ViT fc2 256 x 1152 x 4352: 7 slices of 10 K-tiles on 252 workgroups instead of 4 on 144
-            split_k = max(2, min(256 // t64, (K // 64) // 4, 16))
-        elif plain and K >= 2048 and tiles <= 256 and not os.environ.get("VLA_NO_SPLITK"):
-            cap = 512                                                   # workgroup slots a split may fill (two per CU)
-            for sk in (8, 4, 2):
-                if tiles * sk <= cap and K % (64 * sk) == 0 and K // sk >= 512:
-                    split_k = sk
-                    break
-    if split_k > 1:
-        assert plain, "split-K needs a plain epilogue"
+    if split_k is None and not batched and K >= 2048:    # (shorter contractions and batched products never split)
+        split_k = _nt_plan(d)[1]
+    if split_k and split_k > 1:
         d.split_k, d.ws = split_k, _splitk_ws(split_k * M * Nn, a.device).data_ptr()
     if query_256:
-        return bool(_lib().vla_gemm_uses_256(C.byref(d)))
+        return _nt_plan(d)[0] == N.KERNEL_NT_256
     N.check(_lib().vla_gemm_bf16_nt(_st(), C.byref(d)), "gemm_bf16_nt")
     if act == ACT_SWIGLU:
         return out, out2
     return out
 
 
+def _nt_plan(d) -> Tuple[int, int]:
+    """(kernel id, K slices) of vla_gemm_nt_plan for a descriptor: the library's routing, as the launch will run it."""
+    split = C.c_int(0)
+    kernel = _lib().vla_gemm_nt_plan(C.byref(d), -1, 0, C.byref(split))
+    N.check(min(kernel, 0), "gemm_nt_plan")
+    return kernel, split.value
+
+
 class latency_hint:
-    """``with ops.latency_hint():`` - the products launched (or captured into a hipGraph) inside run on an otherwise idle chip and are
-    latency-bound (batch-1 predict_action): vla_gemm_latency_hint(1) for the block.  Kernel selection only, bit-identical results."""
+    """``with ops.latency_hint():`` - the products launched (or captured into a hipGraph) by this thread inside run on an otherwise idle
+    chip and are latency-bound (batch-1 predict_action): vla_gemm_latency_hint(1) for the block.  Kernel selection: the deep operand rings
+    are bit-identical; the short-M skinny tiles, the uneven split-K and the key-split attention change the fp32 association."""
 
     def __enter__(self):
         self.prev = _lib().vla_gemm_latency_hint(1)
@@ -251,15 +239,11 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, *, out: Optional[torch.Tensor] = N
         d.a_group, d.a_group_stride = a_group
     if b_group is not None:
         d.b_group, d.b_group_stride = b_group
-    if split is None:
-        split = 0
-        tiles = ((N1 + 127) // 128) * ((N2 + 127) // 128) * nb
-        if tiles <= 128 and M >= 1024:
-            split = max(1, min(16, 512 // tiles, M // 256))
-    if split > 1:
-        per = ((M + split - 1) // split + 63) // 64 * 64
-        split = (M + per - 1) // per                  # no empty slice
-    if split > 1:
+    if split is None and M >= 1024:                   # (shorter contractions never split)
+        split_c = C.c_int(0)
+        N.check(min(_lib().vla_gemm_tn_plan(C.byref(d), 0, C.byref(split_c)), 0), "gemm_tn_plan")
+        split = split_c.value
+    if split and split > 1:
         key = (torch.cuda.current_stream().cuda_stream, str(a.device))
         need = nb * split * N1 * N2
         ws = _TN_WS.get(key)
