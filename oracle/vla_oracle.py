@@ -16,7 +16,9 @@ Qwen2 (the reference's pinned fork is absent) and writes ``tests/golden/*.npz``;
 checks this file against them.  Rows a1, a7, a8, a9, a10 are therefore pinned by reference code run here;
 a5 is pinned by installed-transformers Qwen2 (third-party, version differs from the reference's pin);
 a3 (ViT; timm absent) is pinned by third-party stand-ins too since round 4: installed transformers' SiglipVisionModel and
-Dinov2WithRegistersModel (tools/make_golden_vit.py).  a2, a4, a6, a11 (VLM glue, LoRA from peft: not importable) are **parity unpinned**
+Dinov2WithRegistersModel (tools/make_golden_vit.py).  a2, a4, a6 (VLM glue) and the batch-1 predict_action restatement are pinned
+by the reference's own modeling_prismatic.py forward / predict_action and finetune.py's run_forward_pass, run in fp32 with the
+stand-ins above (tools/make_golden_vla.py -> tests/golden/vla_*.npz).  a11 (LoRA from peft: not importable) is **parity unpinned**
 - restated from the reference text and checked only for self-consistency; the fp8 registry restates the NATIVE build's arithmetic
 (the reference has no fp8 code).  token_ce is pinned like a5: against the loss / logits of installed transformers'
 Qwen2ForCausalLM (tools/make_golden_ce.py -> tests/golden/qwen2_tiny_ce.npz) and torch's cross_entropy.
@@ -35,6 +37,7 @@ import torch.nn.functional as F  # only: erf-GELU / softmax primitives used as a
 
 IGNORE_INDEX = -100                 # prismatic/vla/constants.py:11
 ACTION_TOKEN_BEGIN_IDX = 151386     # prismatic/vla/constants.py:13
+STOP_INDEX = 2                      # prismatic/vla/constants.py:14
 NUM_TOKENS = 64                     # prismatic/vla/constants.py:15
 ACTION_DIM = 7                      # prismatic/vla/constants.py:28-33 (LIBERO)
 NUM_ACTIONS_CHUNK = 8
@@ -271,7 +274,7 @@ def vit_block(x, p: Dict[str, torch.Tensor], pre: str, cfg: Dict, emu=False):
 
 
 # ----------------------------------------------------------------------------------------------
-# a4  projector (modeling_prismatic.py:242-273).  PARITY UNPINNED (glue not importable: top-level timm).
+# a4  projector (modeling_prismatic.py:242-273).  Pinned by tests/golden/vla_*.npz (tools/make_golden_vla.py).
 # ----------------------------------------------------------------------------------------------
 def projector(x, p: Dict[str, torch.Tensor], fused: bool, emu=False):
     h = gelu(linear(x, p["fc1.weight"], p["fc1.bias"], emu), emu)
@@ -624,6 +627,19 @@ def lr_at(step: int, base_lr: float, warmup_steps: float = 0.1, decay_at: int = 
     return base_lr * (gamma if step >= decay_at else 1.0)
 
 
+def vision_features(px, vit_w: List[Dict[str, torch.Tensor]], cfg: Dict, emu=False):
+    """PrismaticVisionBackbone.forward (modeling_prismatic.py:196-237): pixels [B, 3 * n_backbones * n_img, H, W] -> [B, Np * n_img,
+    sum of widths].  Per image, channels [0, 3) go to the featurizer and [3, 6) to the fused featurizer; features concatenated
+    [featurizer | fused] along the width, images along the patches."""
+    n_img, nb = cfg["n_img"], len(cfg["vit"])
+    feats = []
+    for im in range(n_img):
+        chans = px[:, im * 3 * nb:(im + 1) * 3 * nb]
+        f = [vit_forward(chans[:, 3 * j:3 * j + 3], vit_w[j], cfg["vit"][j], emu) for j in range(nb)]
+        feats.append(torch.cat(f, dim=2))
+    return torch.cat(feats, dim=1)
+
+
 # ----------------------------------------------------------------------------------------------
 # Composite: the whole fine-tune forward of run_forward_pass (finetune.py:288-447) on the oracle pieces.
 # ----------------------------------------------------------------------------------------------
@@ -631,14 +647,7 @@ def vla_forward(batch: Dict[str, torch.Tensor], W: Dict[str, Dict[str, torch.Ten
                 noise: Optional[torch.Tensor] = None):
     """-> dict(pred [B,8,7], loss, hidden_states, mlhs).  ``W`` = dict(vit=[..one dict per backbone..],
     proj, llm, embed, action_queries, head, proprio); cfg = dict(vit=[...], fused, llm, n_img, pro)."""
-    px = batch["pixel_values"]
-    n_img, nb = cfg["n_img"], len(cfg["vit"])
-    feats = []
-    for im in range(n_img):                                        # modeling_prismatic.py:206-237
-        chans = px[:, im * 3 * nb:(im + 1) * 3 * nb]
-        f = [vit_forward(chans[:, 3 * j:3 * j + 3], W["vit"][j], cfg["vit"][j], emu) for j in range(nb)]
-        feats.append(torch.cat(f, dim=2))
-    patches = projector(torch.cat(feats, dim=1), W["proj"], cfg["fused"], emu)
+    patches = projector(vision_features(batch["pixel_values"], W["vit"], cfg, emu), W["proj"], cfg["fused"], emu)
     mm, mm_mask = embed_splice(batch["input_ids"], batch["labels"], batch["attention_mask"],
                                W["embed"], W["action_queries"], patches)
     hs = qwen2_forward(mm, mm_mask, W["llm"], cfg["llm"], emu)
@@ -648,3 +657,38 @@ def vla_forward(batch: Dict[str, torch.Tensor], W: Dict[str, Dict[str, torch.Ten
                                noise, emu, cfg.get("num_blocks", 24))
     loss = l1_loss(pred, batch["actions"], emu)
     return dict(pred=pred, loss=loss, hidden_states=hs, mlhs=mlhs, patches=patches)
+
+
+def prepare_predict_inputs(input_ids, attention_mask):
+    """_prepare_input_for_action_prediction + _prepare_labels_for_action_prediction (modeling_prismatic.py:748-784) -> (ids, mask,
+    labels): the prompt ids, 64 placeholder ids (1) and the stop id; the mask extended with ones; IGNORE_INDEX over the prompt,
+    an action id over the placeholders, the stop id last."""
+    B, L0 = input_ids.shape
+    ids = torch.cat([input_ids, torch.ones(B, NUM_TOKENS, dtype=input_ids.dtype),
+                     torch.full((B, 1), STOP_INDEX, dtype=input_ids.dtype)], dim=1)
+    am = torch.cat([attention_mask.bool(), torch.ones(B, ids.shape[1] - L0, dtype=torch.bool)], dim=1)
+    labels = torch.full_like(ids, IGNORE_INDEX)
+    labels[:, L0:] = ACTION_TOKEN_BEGIN_IDX + 1
+    labels[:, -1] = STOP_INDEX
+    return ids, am, labels
+
+
+def predict_action_batch1(input_ids, attention_mask, pixels, proprio, W, cfg: Dict, action_stats: Dict, emu=False):
+    """OpenVLAForActionPrediction.predict_action with the L1 regression head, batch 1, phase Inference (modeling_prismatic.py:892-972):
+    the batch of prepare_predict_inputs; the fine-tune forward on that batch; the
+    returned hidden states are the last state's rows [NUM_PATCHES + NUM_PROMPT_TOKENS, +64) with NUM_PROMPT_TOKENS = prompt
+    length - 1 (:855, :927); q01 / q99 un-normalisation where the stats' mask is set (:786-805).
+    -> (un-normalised actions [chunk, action_dim] float64 ndarray, normalised [1, chunk, action_dim], hidden [1, 1, 64, D])."""
+    import numpy as np
+    L0 = input_ids.shape[1]
+    assert input_ids.shape[0] == 1
+    ids, am, labels = prepare_predict_inputs(input_ids, attention_mask)
+    batch = dict(input_ids=ids, labels=labels, attention_mask=am, pixel_values=pixels, proprio=proprio.reshape(1, -1),
+                 actions=torch.zeros(1, NUM_ACTIONS_CHUNK, ACTION_DIM))
+    out = vla_forward(batch, W, cfg, emu)
+    s0 = out["patches"].shape[1] + L0 - 1
+    hid = out["hidden_states"][-1][:, s0:s0 + NUM_TOKENS].reshape(1, 1, NUM_TOKENS, -1)
+    norm = out["pred"].detach().reshape(NUM_ACTIONS_CHUNK, ACTION_DIM).double().numpy()
+    lo, hi = np.array(action_stats["q01"]), np.array(action_stats["q99"])
+    mask = np.array(action_stats.get("mask", np.ones_like(lo, dtype=bool)))
+    return np.where(mask, 0.5 * (norm + 1) * (hi - lo + 1e-8) + lo, norm), out["pred"], hid

@@ -183,18 +183,17 @@ def test_predict_action_batch1_inference_matches_oracle():
     # oracle on the same prepared inputs
     pids, pam, plab = OpenVLAForActionPrediction.prepare_inference_inputs(ids, torch.ones_like(ids, dtype=torch.bool))
     assert pids.shape[1] == 19 + 65 and int((plab > K.ACTION_TOKEN_BEGIN_IDX).sum()) == 64 and int(plab[0, -1]) == K.STOP_INDEX
+    opids, opam, oplab = O.prepare_predict_inputs(ids, torch.ones_like(ids, dtype=torch.bool))
+    assert torch.equal(pids, opids) and torch.equal(pam.bool(), opam) and torch.equal(plab, oplab)
     f = lambda sd: {k: v.float().cpu() for k, v in sd.items()}
     llm = f(W["llm"])
     OW = dict(vit=[f(s) for s in W["vit"]], proj=f(W["proj"]), llm=llm, embed=llm["embed_tokens.weight"],
               action_queries=W["action_queries"].float().cpu(), head=f(W["head"]), proprio=f(W["proprio"]))
     ocfg = dict(vit=[v.as_oracle() for v in cfg.vit], fused=cfg.fused, llm=cfg.llm.as_oracle(), n_img=cfg.n_img, pro=cfg.pro,
                 num_blocks=cfg.num_blocks)
-    cb = dict(input_ids=pids, labels=plab, attention_mask=pam.bool(), pixel_values=px.to(BF).float(),
-              proprio=torch.tensor(proprio).to(BF).float()[None], actions=torch.zeros(1, cfg.chunk, 7))
-    ref = O.vla_forward(cb, OW, ocfg, emu=True, noise=None)["pred"].reshape(cfg.chunk, 7).to(BF).float().numpy()
-    st = stats["libero_object"]["action"]
-    lo, hi, mk = np.array(st["q01"]), np.array(st["q99"]), np.array(st["mask"])
-    ref_un = np.where(mk, 0.5 * (ref + 1) * (hi - lo + 1e-8) + lo, ref)
+    # the batch-1 restatement pinned to the reference's own predict_action by tests/test_oracle_golden.py (tests/golden/vla_*.npz)
+    ref_un, _, _ = O.predict_action_batch1(ids, torch.ones_like(ids, dtype=torch.bool), px.to(BF).float(),
+                                           torch.tensor(proprio).to(BF).float(), OW, ocfg, stats["libero_object"]["action"], emu=True)
     err = np.linalg.norm(act - ref_un) / np.linalg.norm(ref_un)
     assert err < 2e-2, err
     assert np.allclose(act[:, 6], vla.engine._pred_out.float().cpu().numpy()[0, :, 6])      # masked dim stays normalised

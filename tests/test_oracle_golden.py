@@ -287,3 +287,99 @@ def test_resize_restatement_is_bit_exact_against_pillow(H, W, oh, ow):
     ref = np.asarray(Image.fromarray(img).resize((ow, oh), resample=Image.BICUBIC))
     got = O.resize_bicubic_u8(img, oh, ow)
     assert got.shape == ref.shape and np.array_equal(got, ref), f"max |diff| {np.abs(got.astype(int) - ref.astype(int)).max()}"
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The multimodal glue (rows a2, a4, a6 and batch-1 predict_action) against the reference's OWN run: tools/make_golden_vla.py
+# executes OpenVLAForActionPrediction.forward / predict_action and finetune.py's run_forward_pass in fp32 on seeded weights
+# (tests/vla_golden.py; transformers stand-ins for Qwen2 and the two ViTs).  Both sides are fp32 with different operation orders:
+# VLA_REL is the max-norm relative bound for values, VLA_GRAD_REL for gradients (measured: see the comment at their definition).
+# Hidden states are compared at the positions the multimodal attention mask keeps.
+# ------------------------------------------------------------------------------------------------------------------
+VLA_CASES = ["fused1", "fused2", "siglip"]
+VLA_REL, VLA_GRAD_REL = 2e-5, 2e-4
+
+
+def _vla_fixture(name):
+    import sys
+    sys.path.insert(0, os.path.dirname(__file__))
+    import vla_golden as VG
+    cfg, W, batch, pred_in, z = VG.fixture(name)
+    return VG, cfg, W, batch, pred_in, z
+
+
+@pytest.mark.parametrize("name", VLA_CASES)
+def test_vla_forward_matches_the_reference_run(name):
+    """oracle.vla_forward (emu=False) = the reference's run_forward_pass on the same weights and batch: projector features, every
+    hidden state, the regrouped multi-layer states, the actions, loss_value and both L1 metrics; after backward, the kept gradients
+    element by element, the norm of every gradient and the row norms of the embedding table's."""
+    VG, cfg, W, batch, _, z = _vla_fixture(name)
+    torch.set_num_threads(min(8, os.cpu_count() or 1))
+    OW = VG.oracle_weights(W, requires_grad=True)
+    out = O.vla_forward(batch, OW, VG.oracle_cfg(cfg), emu=False)
+    hs, valid = VG.hidden_states(z), z["mm_mask"].bool()
+    close(out["patches"], z["patches"], VLA_REL)
+    assert len(out["hidden_states"]) == len(hs)
+    for i, (a, b) in enumerate(zip(out["hidden_states"], hs)):
+        close(a[valid], b[valid], VLA_REL)
+    close(out["mlhs"], VG.regroup_from_rows(hs, z["rows"]), VLA_REL)
+    close(out["pred"], z["pred"], VLA_REL)
+    m = O.l1_metrics(out["pred"], batch["actions"])
+    got = [out["loss"].item(), m["curr_action_l1_loss"].item(), m["next_actions_l1_loss"].item()]
+    assert np.allclose(got, z["metrics"].numpy(), rtol=VLA_REL, atol=0), (got, z["metrics"].tolist())
+    out["loss"].backward()
+    for k in VG.grad_keys(z):
+        g = VG.oracle_grad(OW, k)
+        close(g[:z["g." + k].shape[0]], z["g." + k], VLA_GRAD_REL)
+    for k in VG.norm_keys(z):
+        g = VG.oracle_grad(OW, k)
+        assert g is not None, f"{k}: the reference has a gradient, the oracle none"
+        ref = float(z["gn." + k])
+        assert abs(g.double().norm().item() - ref) <= VLA_GRAD_REL * ref + 1e-12, (k, g.norm().item(), ref)
+    close(OW["llm"]["embed_tokens.weight"].grad.norm(dim=1), z["grow.language_model.model.embed_tokens.weight"], VLA_GRAD_REL)
+
+
+@pytest.mark.parametrize("name", VLA_CASES)
+def test_vla_glue_pieces_match_the_reference_run(name):
+    """Each piece on the reference's own intermediate values: the vision split / concatenation (fused, two images) against the
+    projector's input, the projector against its output, embed_splice against hidden_states[0] and the multimodal attention mask
+    (bit for bit: index ops only), regroup_hidden_states against the reference's regroup (bit for bit)."""
+    VG, cfg, W, batch, _, z = _vla_fixture(name)
+    f32 = lambda d: {k: v.float() for k, v in d.items()}
+    ocfg = VG.oracle_cfg(cfg)
+    close(O.vision_features(batch["pixel_values"], [f32(s) for s in W["vit"]], ocfg), z["vis"], VLA_REL)
+    close(O.projector(z["vis"], f32(W["proj"]), cfg.fused), z["patches"], VLA_REL)
+    hs = VG.hidden_states(z)
+    mm, mm_mask = O.embed_splice(batch["input_ids"], batch["labels"], batch["attention_mask"], W["llm"]["embed_tokens.weight"].float(),
+                                 W["action_queries"].float(), z["patches"])
+    assert torch.equal(mm, hs[0]), "embed_splice differs from the reference's inputs_embeds"
+    assert torch.equal(mm_mask, z["mm_mask"].bool()), "multimodal attention mask differs from the reference's"
+    assert torch.equal(O.regroup_hidden_states(hs, batch["labels"], cfg.n_patches), VG.regroup_from_rows(hs, z["rows"]))
+
+
+@pytest.mark.parametrize("name", VLA_CASES)
+def test_predict_action_restatement_matches_the_reference(name):
+    """oracle.predict_action_batch1 = the reference's predict_action (placeholder + stop ids, fake labels, the
+    NUM_PATCHES + NUM_PROMPT_TOKENS slice, un-normalisation with the gripper left normalised by the mask).  The prepared batch is
+    compared exactly, the oracle's and modeling_prismatic.prepare_inference_inputs' both: the stop token sits after every action
+    position, so under causal attention leaving it out changes no output, only the prepared inputs."""
+    VG, cfg, W, batch, (ids, px, proprio), z = _vla_fixture(name)
+    am = torch.ones_like(ids, dtype=torch.bool)
+    # the prepared batch, exactly: ids + 64 placeholders + stop id, extended mask, fake labels; the oracle's and the package's
+    from vla_adapter_amd.modeling_prismatic import OpenVLAForActionPrediction
+    for who, (pids, pam, plab) in (("oracle", O.prepare_predict_inputs(ids, am)),
+                                   ("modeling_prismatic", OpenVLAForActionPrediction.prepare_inference_inputs(ids, am))):
+        assert torch.equal(pids, z["p.input_ids"]), f"{who}: prepared input ids differ from the reference's"
+        assert torch.equal(pam.bool(), z["p.attention_mask"].bool()), f"{who}: prepared attention mask differs from the reference's"
+        assert torch.equal(plab, z["p.labels"]), f"{who}: fake labels differ from the reference's"
+    pids, pam, plab = O.prepare_predict_inputs(ids, am)
+    _, mm_mask = O.embed_splice(pids, plab, pam, W["llm"]["embed_tokens.weight"].float(), W["action_queries"].float(),
+                                torch.zeros(1, cfg.n_patches, cfg.llm.d))
+    assert torch.equal(mm_mask, z["p.mm_mask"].bool()), "multimodal attention mask of the predict call differs from the reference's"
+    OW = VG.oracle_weights(W)
+    act, norm, hid = O.predict_action_batch1(ids, am, px, torch.from_numpy(proprio), OW,
+                                             VG.oracle_cfg(cfg), VG.NORM_STATS["golden"]["action"])
+    close(norm.reshape(z["p.normalized"].shape), z["p.normalized"], VLA_REL)
+    close(hid, z["p.hidden"], VLA_REL)
+    close(torch.from_numpy(act), z["p.actions"], VLA_REL)
+    assert np.array_equal(act[:, 6], norm.reshape(-1, 7)[:, 6].double().numpy()), "the masked gripper dimension stays normalised"

@@ -1,6 +1,10 @@
 """Seeded synthetic weights and batches: there is no network for checkpoints or datasets, so
 the benchmark, smoke test and parity tests use random-init weights of the exact architecture and synthetic batches
-with the collator's contract (prismatic/util/data_utils.py:165-172).  State-dict key names are the reference's."""
+with the collator's contract (prismatic/util/data_utils.py:165-172).  State-dict key names are the reference's.
+
+The reference-run fixtures tests/golden/vla_*.npz are built on these draws (tests/vla_golden.py regenerates their weights and
+batches from seeds and checks a digest): a change to the order, shape or scale of any draw here means regenerating them with
+tools/make_golden_vla.py, which needs the reference checkout."""
 from __future__ import annotations
 
 from typing import Dict
