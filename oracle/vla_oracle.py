@@ -18,8 +18,8 @@ a5 is pinned by installed-transformers Qwen2 (third-party, version differs from 
 a3 (ViT; timm absent) is pinned by third-party stand-ins too since round 4: installed transformers' SiglipVisionModel and
 Dinov2WithRegistersModel (tools/make_golden_vit.py).  a2, a4, a6 (VLM glue) and the batch-1 predict_action restatement are pinned
 by the reference's own modeling_prismatic.py forward / predict_action and finetune.py's run_forward_pass, run in fp32 with the
-stand-ins above (tools/make_golden_vla.py -> tests/golden/vla_*.npz).  a11 (LoRA from peft: not importable) is **parity unpinned**
-- restated from the reference text and checked only for self-consistency; the fp8 registry restates the NATIVE build's arithmetic
+stand-ins above (tools/make_golden_vla.py -> tests/golden/vla_*.npz).  a11 (LoRA; peft is not importable) is pinned
+through the full-weight gradient: the same run with W_eff = W + 2 B A (tests/golden/vla_lora_*.npz; peft's bf16 rounding order stays unpinned); the fp8 registry restates the NATIVE build's arithmetic
 (the reference has no fp8 code).  token_ce is pinned like a5: against the loss / logits of installed transformers'
 Qwen2ForCausalLM (tools/make_golden_ce.py -> tests/golden/qwen2_tiny_ce.npz) and torch's cross_entropy.
 
@@ -139,7 +139,7 @@ def fake_quant_e4m3_rows(t):
     return q * torch.where(a > 0, a / 448.0, torch.ones_like(a))
 
 
-# LoRA registry (a11, parity unpinned: peft absent): id(base weight tensor) -> (A [r, in], B [out, r], alpha / r).  Tests fill it
+# LoRA registry (a11, pinned through the full-weight gradient: tests/test_oracle_golden.py): id(base weight tensor) -> (A [r, in], B [out, r], alpha / r).  Tests fill it
 # to evaluate the LoRA-wrapped model (vla-scripts/finetune.py:832-844) through the unchanged restated forward.
 LORA: Dict[int, Tuple[torch.Tensor, torch.Tensor, float]] = {}
 LORA_FUSED = False     # True: restate the native build's single-rounding evaluation instead of peft's module-by-module one
@@ -592,7 +592,7 @@ def token_ce(hidden_last, lm_head, labels, num_patches: int, emu=False):
 
 
 # ----------------------------------------------------------------------------------------------
-# a11  LoRA linear (peft LoraConfig r, alpha=2r; finetune.py:832-844).  PARITY UNPINNED (peft absent).
+# a11  LoRA linear (peft LoraConfig r, alpha=2r; finetune.py:832-844).  Pinned via W_eff = W + 2 B A (test_oracle_golden.py).
 # ----------------------------------------------------------------------------------------------
 def lora_linear(x, w, b, A, Bm, scale: float, emu=False):
     return rnd(linear(x, w, b, emu) + rnd(linear(linear(x, A, None, emu), Bm, None, emu) * scale, emu), emu)

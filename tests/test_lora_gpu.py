@@ -1,6 +1,6 @@
 """LoRA fine-tune (vla-scripts/finetune.py:832-844) against autograd through the oracle with peft's Linear semantics
 (oracle.LORA registry): forward and the gradients of the A / B pairs of every kind of target, under the fp32-truth budget.
-PARITY UNPINNED (peft is not importable here)."""
+The reference's own run pins LoRA through the full-weight gradient in tests/test_lora_golden_gpu.py."""
 import os
 import sys
 

@@ -383,3 +383,89 @@ def test_predict_action_restatement_matches_the_reference(name):
     close(hid, z["p.hidden"], VLA_REL)
     close(torch.from_numpy(act), z["p.actions"], VLA_REL)
     assert np.array_equal(act[:, 6], norm.reshape(-1, 7)[:, 6].double().numpy()), "the masked gripper dimension stays normalised"
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# LoRA (a11) against the reference's own run through the full-weight gradient: tools/make_golden_vla.py runs run_forward_pass with
+# W_eff = W + 2 B A in every Linear peft's "all-linear" wraps and stores dA = 2 B^T dW_eff, dB = 2 dW_eff A^T (float64 from the
+# run's fp32 weight gradients).  oracle.lora_linear's registry is the yardstick of every LoRA GPU test: pinned here in fp32, in
+# peft's module-by-module form and in the native build's fused form (LORA_FUSED), at the tolerances of the glue pins above.
+# ------------------------------------------------------------------------------------------------------------------
+LORA_CASES = ["lora_fused1_r8", "lora_siglip_r8", "lora_fused2_r64", "lora_siglip_b0"]
+
+
+@pytest.mark.parametrize("fused", [False, True], ids=["peft_form", "fused_form"])
+@pytest.mark.parametrize("name", LORA_CASES)
+def test_oracle_lora_matches_the_reference_run(name, fused):
+    """oracle.vla_forward with the adapters registered (scale 2) = the reference's run on W_eff: projector output, every hidden
+    state, the regroup, the actions, loss_value and the L1 metrics; after backward, every adapter gradient (kept rows and norm), the
+    gradients of the head, the proprio projector and the action queries.  The adapted set is every Linear of the VLM but lm_head;
+    modules no forward reaches (the ViTs' last block) get no gradient on either side; with B = 0, dA is exactly zero."""
+    import sys
+    sys.path.insert(0, os.path.dirname(__file__))
+    import vla_golden as VG
+    cfg, W, batch, r, AB, z = VG.lora_fixture(name)
+    torch.set_num_threads(min(8, os.cpu_count() or 1))
+    assert [m for m, _ in VG.lora_targets(cfg, W)] == z["lora_modules"].tolist(), "adapted set differs from the reference's"
+    OW = VG.oracle_weights(W, requires_grad=True)
+    O.LORA.clear()
+    leaves = VG.oracle_lora(OW, AB, requires_grad=True)
+    O.LORA_FUSED = fused
+    try:
+        out = O.vla_forward(batch, OW, VG.oracle_cfg(cfg), emu=False)
+        out["loss"].backward()
+    finally:
+        O.LORA.clear()
+        O.LORA_FUSED = False
+    hs, valid = VG.hidden_states(z), z["mm_mask"].bool()
+    close(out["patches"].detach(), z["patches"], VLA_REL)
+    for a, b in zip(out["hidden_states"], hs):
+        close(a.detach()[valid], b[valid], VLA_REL)
+    close(out["mlhs"].detach(), VG.regroup_from_rows(hs, z["rows"]), VLA_REL)
+    close(out["pred"].detach(), z["pred"], VLA_REL)
+    m = O.l1_metrics(out["pred"].detach(), batch["actions"])
+    got = [out["loss"].item(), m["curr_action_l1_loss"].item(), m["next_actions_l1_loss"].item()]
+    assert np.allclose(got, z["metrics"].numpy(), rtol=VLA_REL, atol=0), (got, z["metrics"].tolist())
+    dead = set(z["lora_dead"].tolist())
+    for mod, (a, b) in leaves.items():
+        if mod in dead:
+            assert a.grad is None or not a.grad.any(), f"{mod}: no forward reaches it, yet its A has a gradient"
+            continue
+        for which, g in (("A", a.grad), ("B", b.grad)):
+            k = VG.lora_key(mod, which)
+            close(g[VG.lora_rows(g.shape[0])], z["g." + k], VLA_GRAD_REL)
+            ref = float(z["gn." + k])
+            assert abs(g.double().norm().item() - ref) <= VLA_GRAD_REL * ref + 1e-12, (k, g.norm().item(), ref)
+        if not AB[mod][1].any():
+            assert not a.grad.any() and float(z["gn." + VG.lora_key(mod, "A")]) == 0.0, f"{mod}: B = 0, so dA = 2 B^T dW_eff = 0"
+    for k in (k for k in VG.norm_keys(z) if k.startswith(("head.", "proprio.", "action_queries"))):
+        g = VG.oracle_grad(OW, k)
+        if "g." + k in z:
+            close(g[:z["g." + k].shape[0]], z["g." + k], VLA_GRAD_REL)
+        assert abs(g.double().norm().item() - float(z["gn." + k])) <= VLA_GRAD_REL * float(z["gn." + k]) + 1e-12, k
+
+
+@pytest.mark.parametrize("name", ["lora_fused1_r8", "lora_fused2_r64"])
+def test_offline_lora_merge_matches_the_reference_w_eff(name):
+    """checkpoints.merge_lora_into_state_dict (merge_and_unload of merge_lora_weights_and_save.py) on the bf16 base and the saved
+    adapter = the fixture's W_eff within ONE bf16 rounding per element; the same merge with the scale 1 or with the gate / up
+    adapters exchanged is rejected."""
+    import sys
+    sys.path.insert(0, os.path.dirname(__file__))
+    import vla_golden as VG
+    from vla_adapter_amd import checkpoints as CK
+    cfg, W, batch, r, AB, z = VG.lora_fixture(name)
+    base = {k: v.to(torch.bfloat16) for k, v in VG.reference_state_dict(W, cfg).items()}
+    adapter = {VG.lora_key(m, w): t.to(torch.bfloat16) for m, (A, B) in AB.items() for w, t in (("A", A), ("B", B))}
+    swapped = dict(adapter)
+    g, u = "language_model.model.layers.1.mlp.gate_proj", "language_model.model.layers.1.mlp.up_proj"
+    for w in "AB":
+        swapped[VG.lora_key(g, w)], swapped[VG.lora_key(u, w)] = adapter[VG.lora_key(u, w)], adapter[VG.lora_key(g, w)]
+    for tag, ad, scale, ok in (("merge", adapter, None, True), ("scale 1", adapter, 1.0, False), ("gate / up exchanged", swapped, None, False)):
+        merged = CK.merge_lora_into_state_dict(base, ad, scaling=scale)
+        worst = 0.0
+        for mod in VG.MERGED:
+            lo = VG.merged_rows(cfg, mod)
+            worst = max(worst, VG.half_ulp_excess(merged[mod + ".weight"][lo:lo + VG.MERGED_ROWS], z["merged." + mod]))
+        print(f"{name} {tag}: max |merged - W_eff| / half a bf16 ulp = {worst:.3f}")
+        assert (worst <= 1.0) == ok, (tag, worst)

@@ -138,3 +138,122 @@ def oracle_grad(OW, name):
             return d[name[len(pre):]].grad
     assert name == "action_queries.weight", f"no oracle tensor behind {name}"
     return OW["action_queries"].grad
+
+
+# ---------------------------------------------------------------------------------------------- LoRA on the same geometries
+# peft LoraConfig(r, lora_alpha=2r, target_modules="all-linear") (vla-scripts/finetune.py:832-844) computes y = W x + b + 2 B(A x):
+# in exact arithmetic the plain Linear with W_eff = W + 2 B A.  tools/make_golden_vla.py runs the reference's glue with W_eff in every
+# adapted Linear and derives the adapter gradients from that run's weight gradient: dA = 2 B^T dW_eff, dB = 2 dW_eff A^T.
+# name -> (geometry case, rank, seed of A and B, B scale: 0 is the state right after init_lora_weights="gaussian")
+LORA_CASES = {
+    "lora_fused1_r8": ("fused1", 8, 41, 1.0),       # rank 8: zero-padded to 64 in the native build (the padding path)
+    "lora_siglip_r8": ("siglip", 8, 42, 1.0),       # the original (non-Pro) head block
+    "lora_fused2_r64": ("fused2", 64, 43, 1.0),     # two images, rank 64 (no padding)
+    "lora_siglip_b0": ("siglip", 8, 44, 0.0),       # B = 0: the wrapped model is the base model, dA = 0 exactly
+}
+LORA_SCALE = 2.0                                    # lora_alpha / r
+# B ~ N(0, (B_STD sqrt(r))^2) and A ~ N(0, (1/r)^2): |2 B A| ~ 2 B_STD |W| / 0.05 ~ 0.3 |W| for the std-0.05 weights of case()
+B_STD = 0.0075
+# rows of W_eff kept for the merge check (merge_and_unload's result): module -> first row
+MERGED_ROWS = 16
+LORA_ROWS = 4        # adapter gradients kept element by element: 4 rows of every dA [r, in] and dB [out, r], spread over the rows
+
+
+def lora_rows(n):
+    """The rows of an n-row adapter gradient the fixture keeps (dB: across q | k | v and every projection)."""
+    return slice(0, None, max(1, n // LORA_ROWS))
+MERGED = {"projector.fc1": 0, "language_model.model.layers.0.self_attn.k_proj": 0, "language_model.model.layers.1.mlp.up_proj": 0,
+          "vision_backbone.featurizer.blocks.0.attn.qkv": None}          # None: the first rows of the k block
+
+
+def lora_targets(cfg, W):
+    """[(module name under the reference's layout, base weight tensor of W)] for every Linear of the VLM that "all-linear" wraps:
+    each ViT block's attn.qkv / attn.proj / mlp.fc1 / mlp.fc2 (timm names; the last block too, which no forward reaches), the
+    projector's fc layers, each LLM layer's seven projections; not lm_head (the output embedding)."""
+    out = []
+    for pre, w in zip(("vision_backbone.featurizer.", "vision_backbone.fused_featurizer."), W["vit"]):
+        for i in range(len([k for k in w if k.endswith(".attn.qkv.weight")])):
+            out += [(f"{pre}blocks.{i}.{n}", w[f"blocks.{i}.{n}.weight"]) for n in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")]
+    out += [(f"projector.{k[:-7]}", v) for k, v in W["proj"].items() if k.endswith(".weight")]
+    for i in range(cfg.llm.n_layers):
+        out += [(f"language_model.model.layers.{i}.{n}", W["llm"][f"layers.{i}.{n}.weight"]) for n in (
+            "self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")]
+    return out
+
+
+def lora_case(name):
+    """-> (cfg, W, batch, predict inputs, rank, AB): the geometry case's weights and batch, and per adapted module (A [r, in], B [out, r])
+    drawn from the case's seed, bf16-representable fp32 (the native trainer holds them in bf16)."""
+    geo, r, seed, bscale = LORA_CASES[name]
+    cfg, W, batch, pred_in = case(geo)
+    g = torch.Generator().manual_seed(seed)
+    AB = {}
+    for mod, w in lora_targets(cfg, W):
+        A = bf16(torch.randn(r, w.shape[1], generator=g) / r)                                  # init_lora_weights="gaussian"
+        AB[mod] = (A, bf16(torch.randn(w.shape[0], r, generator=g) * (B_STD * r ** 0.5 * bscale)))
+    return cfg, W, batch, pred_in, r, AB
+
+
+def effective_weights(W, AB):
+    """W with W_eff = W + 2 B A (float64, then fp32) in every adapted Linear: what a peft Linear computes, as one plain Linear."""
+    We = dict(W, vit=[dict(w) for w in W["vit"]], proj=dict(W["proj"]), llm=dict(W["llm"]))
+    groups = {"vision_backbone.featurizer.": We["vit"][0], "projector.": We["proj"], "language_model.model.": We["llm"]}
+    if len(We["vit"]) > 1:
+        groups["vision_backbone.fused_featurizer."] = We["vit"][1]
+    for mod, (A, B) in AB.items():
+        pre = next(p for p in groups if mod.startswith(p))
+        k = mod[len(pre):] + ".weight"
+        groups[pre][k] = (groups[pre][k].double() + LORA_SCALE * (B.double() @ A.double())).float()
+    return We
+
+
+def lora_digest(cfg, W, batch, predict, AB):
+    h = hashlib.sha256(digest(cfg, W, batch, predict).encode())
+    for k in sorted(AB):
+        for t in AB[k]:
+            h.update(k.encode())
+            h.update(np.ascontiguousarray(t.numpy()).tobytes())
+    return h.hexdigest()
+
+
+def lora_key(mod, which):
+    """peft's saved adapter key (lora_adapter/adapter_model.safetensors): which in ("A", "B")."""
+    return f"base_model.model.{mod}.lora_{which}.weight"
+
+
+def lora_fixture(name):
+    """(cfg, W, batch, rank, AB, fixture) with the fixture's targets in the batch; fails if the seeds drifted."""
+    cfg, W, batch, pred_in, r, AB = lora_case(name)
+    z = load(name)
+    assert str(z["digest"]) == lora_digest(cfg, W, batch, pred_in, AB), f"vla_{name}: regenerated inputs differ from the fixture's"
+    batch["actions"] = z["actions"].clone()
+    return cfg, W, batch, r, AB, z
+
+
+def merged_rows(cfg, mod):
+    """First row of the kept W_eff slice of MERGED's module."""
+    lo = MERGED[mod]
+    return cfg.vit[0].d if lo is None else lo
+
+
+def oracle_lora(OW, AB, requires_grad=False):
+    """Register AB with the oracle (oracle.LORA: id of the base weight leaf -> (A, B, 2)); returns {module: (A, B)} as fresh fp32
+    leaves.  The caller clears O.LORA."""
+    from oracle import vla_oracle as O
+    groups = {"vision_backbone.featurizer.": OW["vit"][0], "vision_backbone.fused_featurizer.": OW["vit"][-1], "projector.": OW["proj"],
+              "language_model.model.": OW["llm"]}
+    leaves = {}
+    for mod, (A, B) in AB.items():
+        pre = next(p for p in groups if mod.startswith(p))
+        a, b = (t.float().clone().requires_grad_(requires_grad) for t in (A, B))
+        O.LORA[id(groups[pre][mod[len(pre):] + ".weight"])] = (a, b, LORA_SCALE)
+        leaves[mod] = (a, b)
+    return leaves
+
+
+def half_ulp_excess(got, ref):
+    """max over elements of |got - ref| / (half a bf16 ulp at ref): <= 1 when got is ONE rounding to bf16 of an fp32 value of ref
+    (plus fp32 slack of 2^-20 relative)."""
+    ref = ref.double()
+    e = torch.floor(torch.log2(ref.abs().clamp_min(2.0 ** -126)))
+    return ((got.double() - ref).abs() / (2.0 ** (e - 8) + 2.0 ** -20 * ref.abs())).max().item()

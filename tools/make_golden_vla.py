@@ -31,6 +31,12 @@ head, proprio projector, projector, action queries, LLM layer 0 and ViT block 0 
 slices of matrices above 16384 elements), the norm of every parameter's gradient and the row norms of the embedding table's;
 one batch-1 predict_action call: its prepared ids, attention mask, fake labels and multimodal mask, un-normalised and normalised
 actions and actions_hidden_states.
+
+vla_lora_*.npz (tests/vla_golden.LORA_CASES): the same run with W_eff = W + 2 B A in every Linear peft's target_modules="all-linear"
+wraps (adapted_modules: every nn.Linear of the VLM but get_output_embeddings()), A and B drawn from seeds; stored: the forward taps,
+loss and metrics as above, per adapted module dA = 2 B^T dW_eff and dB = 2 dW_eff A^T (float64 from the run's fp32 weight gradients;
+4 rows each and the norm), the gradients of the head, proprio projector and action queries, 16 rows of W_eff of a few Linears, the
+adapted module list, the modules no forward reaches, and the trainable parameter names under peft (finetune.py:832-844).
     python tools/make_golden_vla.py [--ref PATH]
 """
 import argparse
@@ -57,6 +63,7 @@ import vla_golden as VG  # noqa: E402
 FULL = 16384          # gradients kept whole up to this many elements, else their first ROWS rows
 ROWS = 8
 CASE_SEEDS = {"fused1": 101, "fused2": 102, "siglip": 103}      # target placement
+LORA_SEEDS = {"lora_fused1_r8": 111, "lora_siglip_r8": 113, "lora_fused2_r64": 112, "lora_siglip_b0": 114}
 
 
 class _Fp32Torch(types.ModuleType):
@@ -180,7 +187,9 @@ def vit_stand_in(c, w):
             out.setdefault(t, []).append(g.reshape(-1, *w[t].shape[1:]) if rows is not None else g.reshape(w[t].shape))
         return {t: torch.cat(v, 0) for t, v in out.items()}
 
-    return Featurizer(m, c), timm_grads
+    f = Featurizer(m, c)
+    f.timm_modules = {"hf." + h[:-7]: t[:-7] for t, h, _ in pairs if t.endswith(".weight")}      # HF module -> timm module
+    return f, timm_grads
 
 
 def qwen2(cfg, w):
@@ -245,9 +254,10 @@ def _tap_head(head, taps, key):
     head.predict_action = predict_action
 
 
-def run_case(name, R, rfp):
-    cfg, W, batch, (pids, ppx, pprop) = VG.case(name)
-    Np, n = cfg.n_patches, cfg.llm.n_layers
+def train_run(R, rfp, cfg, W, batch, seed):
+    """The reference's run_forward_pass on W: a no-grad pass that places the targets (seed), then the pass with loss.backward().
+    -> (targets, taps, metrics, (vla, head, pp, ViT gradient getters))."""
+    Np = cfg.n_patches
 
     def one_pass(actions, grad):
         vla, head, pp, vit_grads = build_reference(R, cfg, W)
@@ -264,17 +274,17 @@ def run_case(name, R, rfp):
         return taps, metrics, (vla, head, pp, vit_grads)
 
     taps0, _, _ = one_pass(torch.zeros(batch["actions"].shape), False)
-    g = torch.Generator().manual_seed(CASE_SEEDS[name])
+    g = torch.Generator().manual_seed(seed)
     sign = torch.randint(0, 2, taps0["pred"].shape, generator=g) * 2 - 1
     actions = VG.bf16(taps0["pred"] + sign * (0.1 + 0.4 * torch.rand(taps0["pred"].shape, generator=g)))
-    taps, metrics, (vla, head, pp, vit_grads) = one_pass(actions, True)
+    return (actions,) + one_pass(actions, True)
 
-    out = dict(digest=np.array(VG.digest(cfg, W, batch, (pids, ppx, pprop))), actions=actions.numpy(),
-               input_ids=batch["input_ids"].numpy(), labels=batch["labels"].numpy(), attention_mask=batch["attention_mask"].numpy(),
-               vis=taps["vis"].numpy(), patches=taps["patches"].numpy(), mm_mask=taps["mm_mask"].to(torch.uint8).numpy(),
-               pred=taps["pred"].numpy(), n_states=np.array(len(taps["hs"])),
-               metrics=np.array([metrics["loss_value"], metrics["curr_action_l1_loss"], metrics["next_actions_l1_loss"]], np.float64))
-    assert torch.equal(taps["pf"], taps["patches"]) and len(taps["hs"]) == n + 1
+
+def forward_record(cfg, taps):
+    """The forward taps every fixture keeps: projector input / output, multimodal mask, actions, the regroup as row indices."""
+    out = dict(vis=taps["vis"].numpy(), patches=taps["patches"].numpy(), mm_mask=taps["mm_mask"].to(torch.uint8).numpy(),
+               pred=taps["pred"].numpy(), n_states=np.array(len(taps["hs"])))
+    assert torch.equal(taps["pf"], taps["patches"]) and len(taps["hs"]) == cfg.llm.n_layers + 1
     # the regroup as row indices: each regrouped state is one row of the hidden states (index ops only, exact copies)
     hs, mlhs = taps["hs"], taps["mlhs"]
     B = hs[0].shape[0]
@@ -283,13 +293,30 @@ def run_case(name, R, rfp):
     rows = eq.float().argmax(-1)
     assert torch.equal(VG.regroup_from_rows(hs, rows), mlhs)
     out["rows"] = rows.to(torch.int16).numpy()
-    # gradients under the reference's state-dict names
+    return out
+
+
+def named_gradients(vla, head, pp, vit_grads):
+    """Every gradient of the run under the reference's state-dict names (ViTs in timm layout)."""
     named = {}
     for pre, fn in zip(("vision_backbone.featurizer.", "vision_backbone.fused_featurizer."), vit_grads):
         named.update({pre + k: v for k, v in fn().items()})
     for mod, pre in ((vla.projector, "projector."), (vla.language_model.model, "language_model.model."), (head, "head."), (pp, "proprio.")):
         named.update({pre + k: p.grad for k, p in mod.named_parameters() if p.grad is not None})
     named["action_queries.weight"] = vla.action_queries.weight.grad
+    return named
+
+
+def run_case(name, R, rfp):
+    cfg, W, batch, (pids, ppx, pprop) = VG.case(name)
+    actions, taps, metrics, (vla, head, pp, vit_grads) = train_run(R, rfp, cfg, W, batch, CASE_SEEDS[name])
+    out = dict(digest=np.array(VG.digest(cfg, W, batch, (pids, ppx, pprop))), actions=actions.numpy(),
+               input_ids=batch["input_ids"].numpy(), labels=batch["labels"].numpy(), attention_mask=batch["attention_mask"].numpy(),
+               metrics=np.array([metrics["loss_value"], metrics["curr_action_l1_loss"], metrics["next_actions_l1_loss"]], np.float64))
+    out.update(forward_record(cfg, taps))
+    hs = taps["hs"]
+    # gradients under the reference's state-dict names
+    named = named_gradients(vla, head, pp, vit_grads)
     keep = lambda k: k.startswith(("head.", "proprio.", "projector.", "action_queries")) or ".layers.0." in k or ".blocks.0." in k
     for k, v in named.items():
         out["gn." + k] = np.array(v.double().norm().item())
@@ -323,6 +350,60 @@ def run_case(name, R, rfp):
     return out, {f"hs.{i}": h.numpy() for i, h in enumerate(hs)}
 
 
+def adapted_modules(vla):
+    """peft's target_modules="all-linear" on the built VLM: every nn.Linear but get_output_embeddings(), under the reference's
+    module names (the ViT stand-ins' HF q / k / v map to timm's one fused attn.qkv)."""
+    out_emb, names = vla.get_output_embeddings(), []
+    for n, m in vla.named_modules():
+        if not isinstance(m, nn.Linear) or m is out_emb:
+            continue
+        for pre in ("vision_backbone.featurizer.", "vision_backbone.fused_featurizer."):
+            if n.startswith(pre):
+                n = pre + vla.get_submodule(pre[:-1]).timm_modules[n[len(pre):]]
+        if n not in names:
+            names.append(n)
+    return names
+
+
+def run_lora_case(name, R, rfp):
+    """The reference's run with W_eff = W + 2 B A in every adapted Linear; adapter gradients from its fp32 weight gradients."""
+    cfg, W, batch, pred_in, r, AB = VG.lora_case(name)
+    We = VG.effective_weights(W, AB)
+    actions, taps, metrics, (vla, head, pp, vit_grads) = train_run(R, rfp, cfg, We, batch, LORA_SEEDS[name])
+    mods = adapted_modules(vla)
+    assert mods == [m for m, _ in VG.lora_targets(cfg, W)], "the adapted set differs from tests/vla_golden.lora_targets"
+    out = dict(digest=np.array(VG.lora_digest(cfg, W, batch, pred_in, AB)), actions=actions.numpy(),
+               metrics=np.array([metrics["loss_value"], metrics["curr_action_l1_loss"], metrics["next_actions_l1_loss"]], np.float64))
+    out.update(forward_record(cfg, taps))
+    del out["vis"]
+    named = named_gradients(vla, head, pp, vit_grads)
+    dead = [m for m in mods if m + ".weight" not in named]             # no forward reaches them (the ViTs' last block)
+    assert all(".blocks." in m for m in dead), dead
+    for m in mods:
+        if m in dead:
+            continue
+        A, B = (t.double() for t in AB[m])
+        dW = named[m + ".weight"].double()
+        for which, g in (("A", VG.LORA_SCALE * B.t() @ dW), ("B", VG.LORA_SCALE * dW @ A.t())):
+            k = VG.lora_key(m, which)
+            out["gn." + k] = np.array(g.norm().item())
+            out["g." + k] = g[VG.lora_rows(g.shape[0])].float().numpy()
+    # the parameters that train outside the adapters: the action head, the proprio projector (modules of their own) and the
+    # action queries (finetune.py:841-843)
+    for k, v in named.items():
+        if k.startswith(("head.", "proprio.", "action_queries")):
+            out["gn." + k] = np.array(v.double().norm().item())
+            out["g." + k] = (v if v.numel() <= FULL else v[:ROWS]).numpy()
+    for m in VG.MERGED:                                                 # what merge_and_unload writes (fp32 here)
+        lo = VG.merged_rows(cfg, m)
+        w = dict(VG.lora_targets(cfg, We))[m]
+        out["merged." + m] = w[lo:lo + VG.MERGED_ROWS].numpy()
+    out["lora_modules"], out["lora_dead"] = np.array(mods), np.array(dead)
+    out["trainable"] = np.array([f"base_model.model.{m}.lora_{w}.default.weight" for m in mods for w in "AB"]
+                                + ["base_model.model.action_queries.weight"])
+    return out, {f"hs.{i}": h.numpy() for i, h in enumerate(taps["hs"])}
+
+
 def save(path, arrays):
     """np.savez_compressed with fixed zip timestamps: the same arrays give the same file."""
     with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
@@ -335,14 +416,14 @@ def save(path, arrays):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--only", nargs="*", default=list(VG.CASES))
+    ap.add_argument("--only", nargs="*", default=list(VG.CASES) + list(VG.LORA_CASES))
     args = ap.parse_args()
     torch.set_num_threads(1)                  # one summation order: the same fixture on every run
     R = import_reference(args.ref)
     rfp = extract_run_forward_pass(args.ref, R)
     R["modeling_prismatic"].torch = R["action_heads"].torch = F32      # the fp32 run (module docstring)
     for name in args.only:
-        out, hs = run_case(name, R, rfp)
+        out, hs = (run_lora_case if name in VG.LORA_CASES else run_case)(name, R, rfp)
         save(os.path.join(VG.GOLDEN, f"vla_{name}.npz"), out)
         save(os.path.join(VG.GOLDEN, f"vla_{name}_hs.npz"), hs)
         print(name, [os.path.getsize(os.path.join(VG.GOLDEN, f"vla_{name}{s}.npz")) for s in ("", "_hs")], "bytes;",

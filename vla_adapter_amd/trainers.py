@@ -18,7 +18,8 @@ Linear does with its weight (the ``_lin`` / ``_lin_bwd`` pair):
          bias / RoPE / SwiGLU / residual epilogue and no read-modify-write pass over y exists.  Backward alike:
          dt = 2 dy B_blk (skinny), dx = [dy | dt] . [W^T | A_cat^T]^T, dA_cat = dt^T x and dB_j = dy_j^T t_j as TN GEMMs.
          One rounding of y instead of peft's three (base output, branch, sum): closer to the fp32 result than the reference's
-         own bf16 arithmetic; the oracle's LORA_FUSED switch restates it.  PARITY UNPINNED either way (peft is not importable).
+         own bf16 arithmetic; the oracle's LORA_FUSED switch restates it.  Pinned to the reference's own run through the full-weight
+         gradient (W_eff = W + 2 B A; tests/test_lora_golden_gpu.py); peft's own bf16 rounding order and dropout masks stay unpinned.
          Parameters are stored per pair under peft's names in one flat buffer; a fused base Linear (q|k|v, gate/up) carries
          several pairs: A_cat is a view of adjacent A's, B_blk the dense block matrix (rebuilt after every update).
          Ranks are zero-padded to a multiple of 64 (the GEMM's K granule); padding has zero value and zero gradient.
