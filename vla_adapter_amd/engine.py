@@ -22,7 +22,6 @@ from __future__ import annotations
 
 import math
 import os
-import time
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -30,7 +29,7 @@ import torch
 
 from . import ops, schedule
 from .ops import ACT_GELU, ACT_GELU_TANH, ACT_NONE, ACT_RELU, ACT_SWIGLU, BF16
-from .schedule import Segment, capture_graph, chunks
+from .schedule import Segment, capture_graph, chunks, turnaround_chunks
 
 NUM_TOKENS = 64          # prismatic/vla/constants.py:15
 IGNORE_INDEX = -100
@@ -38,6 +37,12 @@ IGNORE_INDEX = -100
 
 def rup(n: int, m: int) -> int:
     return (n + m - 1) // m * m
+
+
+def copy_flat(dst: torch.Tensor, src: torch.Tensor):
+    """dst <- src, contiguous tensors of one size, by the native copy (no ATen / runtime copy kernel on the step)."""
+    n = src.numel()
+    ops.copy2d(src, dst, 1, n, n, n)
 
 
 # ------------------------------------------------------------------------------------------------ configs
@@ -446,12 +451,14 @@ class LLM:
     def forward(self, B: int, S: int, kmask_u8: torch.Tensor, keep_from_row: int = 0, n_run: Optional[int] = None):
         """HS[0] must already hold inputs_embeds [B,S,D].  Fills HS[1..n] (HF hidden_states semantics).  n_run < n_layers: only the
         first n_run layers (hidden_states[1..n_run]: all the action head reads when it has fewer blocks than the LLM has layers)."""
-        n = self.cfg.n_layers
-        n_run = n if n_run is None else n_run
         self.fwd_begin(B, S, kmask_u8, keep_from_row)
-        for i in range(n_run):
+        self.fwd_layers(0, self.cfg.n_layers if n_run is None else n_run)
+
+    def fwd_layers(self, lo: int, hi: int):
+        """Layers lo .. hi - 1, and behind the top layer the final norm."""
+        for i in range(lo, hi):
             self.fwd_layer(i)
-        if n_run == n:
+        if hi == self.cfg.n_layers:
             self.fwd_final()
 
     def fwd_begin(self, B: int, S: int, kmask_u8: torch.Tensor, keep_from_row: int = 0, lin: Optional[Linear] = None):
@@ -655,6 +662,7 @@ class Head:
         self.pfc1_pad = z(D, 64)                   # proprio fc1 weight zero-padded to K=64
         self.dirty = True
         self._key = None
+        self._prep_key = None    # (B, S, Np, row0) of the last prep_backward()
         self.rope_tab = None     # f32 [max(T, Ka, Kt), dh] cos/sin tables (positions restart per segment: one table serves all)
         # attention weights rounded to bf16 AFTER normalisation, as the reference's bf16 softmax emits them (action_heads.py:397): a second
         # pass over the keys (vla_head_attn_desc.ref_softmax).  Off by default: +N us per block on a chain the step's turn-around waits
@@ -921,7 +929,7 @@ class Head:
         cfg, P, nb = self.cfg, self.P, self.nb
         R, Da = self.R, cfg.action_dim
         self.row0 = row0
-        assert getattr(self, "_prep_key", None) == (self.B, self.S, self.Np, row0), "prep_backward() first"
+        assert self._prep_key == (self.B, self.S, self.Np, row0), "prep_backward() first"
         self.refresh_transposes()                                  # W^T operands of the dX products (stale after AdamW)
         ops.zero_(self.acc32)                                      # every fp32 gradient accumulator in one fill
         dp = dpred.reshape(R, Da)
@@ -1036,13 +1044,19 @@ class VLAEngine:
         self.full_llm_backward = bool(int(os.environ.get("VLA_FULL_LLM_BWD", "0")))
         self._row0 = None          # frozen by capture(); None = derive from every batch (one host sync)
         self.reducer = None        # ddp.FlatGradReducer when world_size > 1
-        self.ga, self._micro, self._gacc = 1, 0, None     # gradient accumulation (set_grad_accumulation)
+        self._accum = schedule.GradAccumulator(copy_flat, ops.add_)      # gradient accumulation (set_grad_accumulation)
         self.executed_steps = 0    # forward+backward passes enqueued so far (eager, pipelined or replayed): profile bookkeeping
         # LLM layers above the head's last block (Qwen2.5-1.5B: 28 layers, 24 blocks - action_heads.py:117-118 reads hidden_states[1..24])
         # never reach the loss or the predicted actions: the training step and predict() run the first n_act layers only, as the
         # LoRA / full trainers do; forward_vlm() - the API twin that RETURNS every hidden state - runs them all
         self.n_act = min(cfg.llm.n_layers, cfg.num_blocks)
         self.fp8_frozen = False
+        self.side = None           # head stream: the streams are created on first use (_ensure_streams)
+        self._vis_bufs = {}        # (feats, patches) per (batch, patches): captured graphs keep their addresses
+        self._predict_graphs, self._val_graphs = {}, None      # predict(): (graphs, static batch, segments) per input shape; val_step_graphed()
+        self._timeline = None      # a list collects (kind, index, start, end) events of every segment run (tools/*_timeline.py)
+        # captured step (capture()): its graphs, the vision graph, events of the vision stage in flight / of its pixel copy, pending update, exchange events
+        self._graphs = self._g_vis = self._vis_ev = self._px_copied = self._pending_lr = self._reduced = None
         if os.environ.get("VLA_FP8_FROZEN"):
             self.enable_fp8_frozen()
 
@@ -1060,25 +1074,12 @@ class VLAEngine:
         autograd accumulates ``.grad``), one optimizer step per n.  The data-parallel exchange runs on the boundary
         micro-step only (the reference's DDP all-reduces on every one; same result, n-1 exchanges saved).  Call before
         capture(): the captured loss kernel carries the 1/n."""
-        assert n >= 1 and getattr(self, "_graphs", None) is None, "set_grad_accumulation() before capture()"
-        self.ga, self._micro = int(n), 0
-        self._gacc = torch.zeros_like(self.head.P.grad) if n > 1 else None
+        assert n >= 1 and self._graphs is None, "set_grad_accumulation() before capture()"
+        self._accum.reset(n, [self.head.P.grad])
 
-    def _accumulate(self) -> bool:
-        """Fold the micro-step's gradient into the accumulator; True on the boundary micro-step (P.grad then holds the sum)."""
-        if self.ga == 1:
-            return True
-        G = self.head.P.grad
-        if self._micro == 0:
-            self._gacc.copy_(G)
-        else:
-            ops.add_(self._gacc, G)
-        self._micro += 1
-        if self._micro < self.ga:
-            return False
-        self._micro = 0
-        G.copy_(self._gacc)
-        return True
+    @property
+    def ga(self) -> int:
+        return self._accum.ga
 
     def forward(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None, for_training: bool = False):
         """VLM forward + action head (finetune.py:336-411) -> predicted actions [B, chunk, 7]."""
@@ -1093,7 +1094,7 @@ class VLAEngine:
         the LLM on the caller's stream with the action head trailing it on the head stream; each segment is a linear
         hipGraph captured on first use of an input shape and replayed on static input buffers afterwards."""
         key = (tuple(batch["input_ids"].shape), tuple(batch["pixel_values"].shape), batch["pixel_values"].dtype)
-        cache = self.__dict__.setdefault("_predict_graphs", {})
+        cache = self._predict_graphs
         if os.environ.get("VLA_PREDICT_EAGER"):
             return self.forward(batch, None)
         self._ensure_streams()
@@ -1114,47 +1115,32 @@ class VLAEngine:
         for k, v in batch.items():
             static[k].copy_(v)
         self.head.refresh_forward_operands()     # parameters may have changed since the capture (no-op when fresh)
-        ev = schedule.run(segs, self._stream_of, graphs, timeline=getattr(self, "_timeline", None))
+        ev = schedule.run(segs, self._stream_of, graphs, timeline=self._timeline)
         torch.cuda.current_stream().wait_event(ev[("end", 0)])
         return self._pred_out
 
     def _predict_segments(self, batch, noise: Optional[torch.Tensor] = None, loss_of: Optional[torch.Tensor] = None):
         """Forward-only segments (predict()).  noise: the head's input perturbation (phase "Training"); loss_of: actions whose L1
         loss against the prediction ends the last head segment (-> self._val_loss3: the validation pass)."""
-        cfg, llm, head = self.cfg, self.llm, self.head
-        n, nb = cfg.llm.n_layers, cfg.num_blocks
+        llm, head = self.llm, self.head
         self._vision_begin(batch)                                 # host-side bookkeeping only
-        n_all, n = n, self.n_act                                  # (layers above the head's last block do not reach the actions)
         segs = [Segment(f"V{j}", (lambda j=j: self._vision_backbone(j, batch)), None, ("v", j)) for j in range(len(self.vits))]
-        ch = chunks(n, [6] * max(0, (n - 6) // 6) + [4, 2]) if n >= 12 else chunks(n, [1])   # few launches: the caller blocks on every call
+        # (layers above the head's last block do not reach the actions; few launches: the caller blocks on every call)
+        ch = turnaround_chunks(self.n_act, 6, [4, 2], 1)
 
-        def m_fwd(c, lo, hi):
-            def fn():
-                if c == 0:
-                    self._vision_project()
-                    llm.fwd_begin(self.B, self.S, self._embed(batch), 0)
-                for i in range(lo, hi):
-                    llm.fwd_layer(i)
-                if hi == n_all:
-                    llm.fwd_final()
-            return fn
+        def llm_fwd(c, lo, hi):
+            if c == 0:
+                self._vision_project()
+                llm.fwd_begin(self.B, self.S, self._embed(batch), 0)
+            llm.fwd_layers(lo, hi)
 
-        def h_fwd(c, lo, hi, last):
-            def fn():
-                if c == 0:
-                    head.fwd_begin(llm.HS, self.pos1, batch["proprio"], self.Np, noise)
-                for i in range(lo, min(hi, nb)):
-                    head.fwd_layer(i)
-                if last:
-                    self._pred_out = head.fwd_end()
-                    if loss_of is not None:
-                        self._val_loss3 = ops.l1_loss(self._pred_out, self._to_bf16(loss_of), want_grad=False)[0]
-            return fn
+        def at_end():
+            self._pred_out = head.fwd_end()
+            if loss_of is not None:
+                self._val_loss3 = ops.l1_loss(self._pred_out, self._to_bf16(loss_of), want_grad=False)[0]
 
-        for c, (lo, hi) in enumerate(ch):
-            segs.append(Segment("M", m_fwd(c, lo, hi), [("v", j) for j in range(len(self.vits))] if c == 0 else None, ("f", c)))
-            segs.append(Segment("H", h_fwd(c, lo, hi, c == len(ch) - 1), ("f", c), ("end", 0) if c == len(ch) - 1 else None))
-        return segs
+        return segs + schedule.pipeline_forward(head, ch, llm_fwd, lambda: (llm.HS, self.pos1, batch["proprio"], self.Np, noise), at_end,
+                                                wait=[sg.signal for sg in segs], signal=("end", 0))
 
     # modeling_prismatic.py:596-655 (multimodal forward): fills llm.HS with the n+1 hidden states
     def forward_vlm(self, batch: Dict[str, torch.Tensor], for_training: bool = False, action_queries: bool = True):
@@ -1203,7 +1189,7 @@ class VLAEngine:
         B, L = batch["input_ids"].shape
         Np = cfg.n_patches
         self.llm._alloc(B, L + Np)
-        bufs = self.__dict__.setdefault("_vis_bufs", {})     # one pair per batch size: captured graphs keep their addresses
+        bufs = self._vis_bufs
         if (B, Np) not in bufs:
             bufs[(B, Np)] = (torch.empty(B, Np, cfg.vis_dim, device=self.device, dtype=BF16),
                              torch.empty(B, Np, cfg.llm.d, device=self.device, dtype=BF16))
@@ -1332,7 +1318,7 @@ class VLAEngine:
         self.executed_steps += 1
         pred = self.forward(batch, noise, for_training=True)
         loss3 = self.loss_and_backward(pred, batch["actions"], 1.0 / self.ga, exchange=self.ga == 1)
-        if self._accumulate():
+        if self._accum.fold():
             if self.ga > 1 and self.reducer is not None:
                 self.reducer.reduce_async(self.head.P.grad, 0, None)
             self.optimizer_step(lr)
@@ -1344,11 +1330,9 @@ class VLAEngine:
     # of the LLM backward (which needs dHS[i+1] from block i).  The head's kernels fill the idle CUs / tile-quantisation
     # tails of the LLM's large GEMMs instead of serialising with them.
     #
-    # The step is cut into SEGMENTS, each living on exactly one stream ("M": vision/LLM, "H": head), which schedule.run
-    # enqueues and schedule.capture turns into one linear hipGraph each.  Layer chunks are short next to the
-    # forward->backward turn-around (little pipeline fill/drain) and longer elsewhere (fewer graph launches).
+    # The step is a list of single-stream segments ("M": vision / LLM, "H": head) built, run and captured by schedule.py.
     def _ensure_streams(self):
-        if getattr(self, "side", None) is None:
+        if self.side is None:
             self.side = torch.cuda.Stream()            # head stream (a high-priority stream measured 0.7 % slower on the step in round 1)
             self._cap_main = torch.cuda.Stream()       # capture stream of the "M" graphs (replayed on the current stream)
             self.vis_stream = torch.cuda.Stream()      # vision stage of the NEXT step (fills the backward's idle CUs)
@@ -1366,77 +1350,40 @@ class VLAEngine:
 
     def _segments(self, batch, noise):
         """[Segment(stream 'M'|'H', fn, wait_key|None, signal_key|None)] for everything after the vision stage."""
-        cfg, llm, head = self.cfg, self.llm, self.head
-        n_all, nb = cfg.llm.n_layers, cfg.num_blocks
-        assert nb <= n_all
+        llm, head = self.llm, self.head
         n = self.n_act                                  # layers that reach the loss
-        # long chunks at the bottom layers, single layers at the top: the head's last forward chunk and first backward
-        # chunk (the serial turn-around) stay short; the backward walks the same ranges top-down
-        fch = chunks(n, [4] * max(0, (n - 4) // 4) + [2, 1, 1]) if n >= 8 else chunks(n, [1])
+        fch = turnaround_chunks(n, 4, [2, 1, 1], 1)           # (the backward walks the same ranges top-down)
         if os.environ.get("VLA_FWD_CHUNKS"):                  # A/B knob: "4,4,4,4,4,2,1,1"
             fch = chunks(n, [int(x) for x in os.environ["VLA_FWD_CHUNKS"].split(",")])
-        segs = []
 
-        def m_begin():
-            mm = self._embed(batch)
-            self._prep_backward(batch)
-            llm.fwd_begin(self.B, self.S, mm, self._row0_used)
+        def llm_fwd(c, lo, hi):
+            if c == 0:
+                mm = self._embed(batch)
+                self._prep_backward(batch)
+                llm.fwd_begin(self.B, self.S, mm, self._row0_used)
+            llm.fwd_layers(lo, hi)
 
-        def m_fwd(c, lo, hi, begin=False):
-            def fn():
-                if begin:
-                    m_begin()
-                for i in range(lo, hi):
-                    llm.fwd_layer(i)
-                if hi == n_all:
-                    llm.fwd_final()
-            return fn
+        def turn_around():
+            pred = head.fwd_end()
+            self._loss3, dpred = ops.l1_loss(pred, self._actions_bf, True, 1.0 / self.ga)
+            if self._guard is not None:
+                ops.add_scalar_f32_(self._loss3, self._guard)
+            head.bwd_begin(dpred, self._row0_used)
 
-        def h_fwd(c, lo, hi, last):
-            def fn():
-                if c == 0:
-                    head.fwd_begin(llm.HS, self.pos1, batch["proprio"], self.Np, noise)
-                    head.refresh_transposes()        # (the W^T operands of the head's backward: rebuilt here, beside the LLM forward, instead of
-                                                     #  at bwd_begin - 0.13 ms on the forward -> backward turn-around that the LLM backward waits for: step -0.09 ms same box)
-                for i in range(lo, min(hi, nb)):
-                    head.fwd_layer(i)
-                if last:
-                    pred = head.fwd_end()
-                    self._loss3, dpred = ops.l1_loss(pred, self._actions_bf, True, 1.0 / self.ga)
-                    if self._guard is not None:
-                        ops.add_scalar_f32_(self._loss3, self._guard)
-                    head.bwd_begin(dpred, self._row0_used)
-            return fn
+        def llm_bwd(k, lo, hi):
+            if k == 0:
+                llm.bwd_begin(self._dHS, self._row0_used, n)
+            for i in range(hi - 1, lo - 1, -1):
+                llm.bwd_layer(i, self._dHS)
+            if k == len(fch) - 1:
+                dq = ops.action_query_grad(llm.bwd_result().contiguous(), self.pos0, self.Np, self._row0_used)
+                ops.cast_f32_bf16(dq, out=head.P.g("action_queries"))
 
-        def h_bwd(lo, hi):
-            def fn():
-                for i in range(min(hi, nb) - 1, lo - 1, -1):
-                    head.bwd_layer(i, self._dHS)
-            return fn
-
-        def m_bwd(lo, hi, first, last):
-            def fn():
-                if first:
-                    llm.bwd_begin(self._dHS, self._row0_used, n)
-                for i in range(hi - 1, lo - 1, -1):
-                    llm.bwd_layer(i, self._dHS)
-                if last:
-                    dq = ops.action_query_grad(llm.bwd_result().contiguous(), self.pos0, self.Np, self._row0_used)
-                    ops.cast_f32_bf16(dq, out=head.P.g("action_queries"))
-            return fn
-
-        # ONE whole-batch forward pipeline.  (Round 1 ran the forward as two half-batch pipelines on two streams - with the 128-row
-        # GEMM, two workgroups per CU, the chains filled each other's tail rounds: -0.5 ms.  With the persistent 256 x 256 kernel,
-        # one workgroup per CU and 6.5 rounds of gate/up tiles per whole-batch launch, one pipeline measured 25.27-25.34 against
-        # 25.61-25.75 ms and the two-pipeline form left the tree in round 4: DESIGN section 5b.)
-        for c, (lo, hi) in enumerate(fch):
-            segs.append(Segment("M", m_fwd(c, lo, hi, begin=c == 0), None, ("f", c)))
-            segs.append(Segment("H", h_fwd(c, lo, hi, c == len(fch) - 1), ("f", c)))
-        for k, (lo, hi) in enumerate(reversed(fch)):
-            segs.append(Segment("H", h_bwd(lo, hi), None, ("b", k)))
-            segs.append(Segment("M", m_bwd(lo, hi, k == 0, k == len(fch) - 1), ("b", k)))
-        segs.append(Segment("H", head.bwd_end, None, ("end", 0)))      # the caller joins on this event (head gradients final)
-        return segs
+        # ONE whole-batch forward pipeline (round 1's two half-batch pipelines left the tree in round 4: DESIGN section 5b)
+        return (schedule.pipeline_forward(head, fch, llm_fwd, lambda: (llm.HS, self.pos1, batch["proprio"], self.Np, noise), turn_around,
+                                          refresh=True)
+                + schedule.pipeline_backward(head, fch, llm_bwd, lambda: self._dHS)
+                + [Segment("H", head.bwd_end, None, ("end", 0))])      # the caller joins on this event (head gradients final)
 
     def _stream_of(self, name: str, main):
         return main if name == "M" else self.side if name == "H" else self._vstreams[int(name[1:])]
@@ -1500,7 +1447,7 @@ class VLAEngine:
     def stage_next_pixels(self, pixel_values: torch.Tensor):
         """Captured mode: pixels of the batch AFTER the one the next train_step_graphed() call trains on (its vision stage
         runs during that call).  Without staging, the pixels given to capture() are reused."""
-        if getattr(self, "_px_copied", None) is not None:
+        if self._px_copied is not None:
             torch.cuda.current_stream().wait_event(self._px_copied)   # the vision stream has taken its copy of the old pixels
         self._next_px.copy_(pixel_values)
 
@@ -1511,13 +1458,12 @@ class VLAEngine:
             V.wait_event(after_event)           # self.patches of the running step has been consumed (_embed)
         else:
             V.wait_stream(cur)
-        tl = getattr(self, "_timeline", None)
+        tl = self._timeline
         with torch.cuda.stream(V):
             if tl is not None:
                 t0 = torch.cuda.Event(enable_timing=True)
                 t0.record(V)
-            n = self._next_px.numel()
-            ops.copy2d(self._next_px, self._px_stage, 1, n, n, n)     # (native copy: no ATen / runtime copy kernel on the step)
+            copy_flat(self._px_stage, self._next_px)
             self._px_copied = torch.cuda.Event()
             self._px_copied.record(V)
             self._g_vis.replay()
@@ -1546,11 +1492,11 @@ class VLAEngine:
             if k == self._vis_after:
                 self._launch_vision(ev)
         self._h_end = schedule.run(self._segs, self._stream_of, self._graphs, after=after,
-                                   timeline=getattr(self, "_timeline", None))[("end", 0)]
+                                   timeline=self._timeline)[("end", 0)]
         cur.wait_event(self._px_copied)        # later writes to the staging source are ordered behind the vision copy
         if self.ga > 1:                        # gradient accumulation: join, fold, update only on the boundary micro-step
             cur.wait_event(self._h_end)
-            if not self._accumulate():
+            if not self._accum.fold():
                 return self._loss3
             self._h_end = torch.cuda.Event()
             self._h_end.record(cur)            # the summed gradient is final on the current stream
@@ -1574,7 +1520,7 @@ class VLAEngine:
         runs beside the first LLM forward segment instead of in front of it.  ``join`` (default) makes the current stream
         wait for the head-stream half too, so that callers may read any parameter afterwards (checkpoints, evaluation);
         the captured step passes False: its head segments run on the head stream anyway."""
-        if getattr(self, "_pending_lr", None) is None:
+        if self._pending_lr is None:
             return
         lr, self._pending_lr = self._pending_lr, None
         cur, P = torch.cuda.current_stream(), self.head.P
@@ -1583,7 +1529,7 @@ class VLAEngine:
         self.step_count += 1
         gscale = 1.0
         if self.reducer is not None:
-            ev_aq, ev_head = getattr(self, "_reduced", None) or (None, None)
+            ev_aq, ev_head = self._reduced or (None, None)
             if ev_aq is not None and ev_head is not None:
                 cur.wait_event(ev_aq)                 # the LLM stream needs the action queries only ...
                 self.side.wait_event(ev_head)         # ... the 437 MB head exchange is joined by the head stream
@@ -1613,13 +1559,13 @@ class VLAEngine:
         """Before a sweep: apply the pending update, order the sweep behind the in-flight vision stage, refresh the head's
         forward operands (the captured validation graphs do not carry that refresh)."""
         self.flush()
-        if getattr(self, "_vis_ev", None) is not None:
+        if self._vis_ev is not None:
             torch.cuda.current_stream().wait_event(self._vis_ev)
         self.head.refresh_forward_operands()
 
     def end_validation(self):
         """After a sweep: recompute the next training batch's patches (captured step only)."""
-        if getattr(self, "_g_vis", None) is not None:
+        if self._g_vis is not None:
             self._launch_vision()
 
     def val_forward(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1632,17 +1578,12 @@ class VLAEngine:
         segments of predict() ending in the L1 loss, captured on the first call.  No ops.latency_hint(): its GEMM variant
         changes the fp32 association, and the values must be the eager forward's."""
         self._ensure_streams()
-        if getattr(self, "_val_graphs", None) is None:
-            for _ in range(2):                       # allocate buffers / set kernel attributes outside the capture
-                self.val_forward(batch, noise)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
+
+        def make():
             segs = self._predict_segments(batch, noise, loss_of=batch["actions"])
-            self._val_graphs = (schedule.capture(segs, {}, self._cap_stream), segs)
-            torch.cuda.synchronize()
-            self.val_capture_seconds = time.perf_counter() - t0
-        graphs, segs = self._val_graphs
-        self.head.refresh_forward_operands()
-        ev = schedule.run(segs, self._stream_of, graphs)
-        torch.cuda.current_stream().wait_event(ev[("end", 0)])
-        return self._val_loss3
+            return schedule.capture(segs, {}, self._cap_stream), segs
+
+        def replay(graphs, segs):
+            self.head.refresh_forward_operands()
+            torch.cuda.current_stream().wait_event(schedule.run(segs, self._stream_of, graphs)[("end", 0)])
+        return schedule.captured_validation(self, batch, noise, make, replay)

@@ -4,13 +4,19 @@ A step is a list of single-stream segments, ordered so that every event is recor
 a Python call under its stream; captured, every segment is its own single-stream (linear) hipGraph replayed on that stream, and
 the cross-stream edges are plain hipEvents between graph launches.  (One multi-stream hipGraph of the whole step was measured to
 serialise the two backward chains in the runtime's graph executor - rocprofv3 trace, tools/timeline.py: LLM backward started only
-after the head backward's last kernel - so the overlap is not left to it.)  engine.VLAEngine builds the adapter-only step and
-batch-1 predict() as such lists, trainers.BackboneTrainer the LoRA / full fine-tune step; both run and capture them here.
+after the head backward's last kernel - so the overlap is not left to it.)
+
+The part every step shares - the LLM in layer chunks on "M" with the action head trailing it on "H", and the head's backward
+running ahead of the LLM's over the reversed chunks - is built here, once: turnaround_chunks() cuts the layers, pipeline_forward()
+and pipeline_backward() return the two halves.  engine.VLAEngine (adapter-only step, predict(), validation) and
+trainers.BackboneTrainer (LoRA / full fine-tune step) supply the calls that are theirs, put their own segments (vision, gradient
+hand-overs) around the halves, and run and capture the lists here; they share GradAccumulator and captured_validation() too.
 """
 from __future__ import annotations
 
 import contextlib
 import gc
+import time
 from typing import Any, Callable, List, NamedTuple, Optional, Tuple
 
 import torch
@@ -34,6 +40,98 @@ def chunks(n: int, sizes) -> List[Tuple[int, int]]:
         out.append((lo, min(n, lo + sz)))
         lo, k = out[-1][1], k + 1
     return out
+
+
+def turnaround_chunks(n: int, body: int, tail, short: int) -> List[Tuple[int, int]]:
+    """Layer ranges with `body`-layer chunks at the bottom and the short `tail` sizes at the top: the head's last forward chunk
+    and first backward chunk - the serial forward -> backward turn-around - stay short, the rest costs few segments.  Stacks
+    too shallow for two tails get uniform `short`-layer chunks."""
+    t = sum(tail)
+    return chunks(n, [body] * max(0, (n - t) // body) + list(tail)) if n >= 2 * t else chunks(n, [short])
+
+
+def pipeline_forward(head, ch, llm_fwd, head_args, at_end, *, wait=None, signal=None, refresh: bool = False) -> List[Segment]:
+    """Forward half of the LLM-and-head pipeline: per chunk c = [lo, hi) of ``ch`` an "M" segment running llm_fwd(c, lo, hi) and
+    signalling ("f", c), and an "H" segment behind it with the head's blocks lo .. min(hi, head.nb) - 1 (block i reads hidden
+    state i + 1).  The first "H" segment begins with head.fwd_begin(*head_args()) and, with ``refresh``, head.refresh_transposes() (the
+    W^T operands of the head's backward, rebuilt beside the LLM forward instead of on the turn-around, which the LLM backward
+    waits for: -0.09 ms on the adapter step, same box); the last one ends with at_end().  wait: of the first "M" segment; signal:
+    of the last "H" segment."""
+    segs = []
+    for c, (lo, hi) in enumerate(ch):
+        def h_fwd(c=c, lo=lo, hi=hi):
+            if c == 0:
+                head.fwd_begin(*head_args())
+                if refresh:
+                    head.refresh_transposes()
+            for i in range(lo, min(hi, head.nb)):
+                head.fwd_layer(i)
+            if c == len(ch) - 1:
+                at_end()
+        segs.append(Segment("M", lambda c=c, lo=lo, hi=hi: llm_fwd(c, lo, hi), wait if c == 0 else None, ("f", c)))
+        segs.append(Segment("H", h_fwd, ("f", c), signal if c == len(ch) - 1 else None))
+    return segs
+
+
+def pipeline_backward(head, ch, llm_bwd, dhs, handover=None) -> List[Segment]:
+    """Backward half: over the reversed chunks, k = 0 at the top, an "H" segment running head.bwd_layer(i, dhs()) from block
+    min(hi, head.nb) - 1 down to lo and signalling ("b", k), and an "M" segment behind it running llm_bwd(k, lo, hi).  A chunk above
+    the head's last block receives no gradient from it: no "H" segment, and its "M" segment waits for nothing.  handover(k, lo,
+    hi) -> the segment that follows chunk k's "M" segment (the trainers' gradient work), which then signals ("m", k)."""
+    segs = []
+    for k, (lo, hi) in enumerate(reversed(ch)):
+        wait = None
+        if min(hi, head.nb) > lo:
+            segs.append(Segment("H", lambda lo=lo, hi=hi: [head.bwd_layer(i, dhs()) for i in range(min(hi, head.nb) - 1, lo - 1, -1)], None, ("b", k)))
+            wait = ("b", k)
+        segs.append(Segment("M", lambda k=k, lo=lo, hi=hi: llm_bwd(k, lo, hi), wait, ("m", k) if handover else None))
+        if handover:
+            segs.append(handover(k, lo, hi))
+    return segs
+
+
+class GradAccumulator:
+    """Gradient accumulation over ``ga`` micro-steps (vla-scripts/finetune.py:1039-1042, 1078-1082): one accumulator per flat
+    gradient buffer, summed in the buffers' own precision as autograd accumulates ``.grad``.  copy(dst, src) and add(dst, src)
+    are the caller's kernels."""
+
+    def __init__(self, copy, add):
+        self.ga, self._micro, self._copy, self._add, self._pairs = 1, 0, copy, add, []
+
+    def reset(self, ga: int, grads):
+        self.ga, self._micro = int(ga), 0
+        self._pairs = [(torch.zeros_like(g), g) for g in grads] if ga > 1 else []
+
+    def fold(self) -> bool:
+        """Fold the micro-step's gradients into the accumulators; True on the boundary micro-step (the gradient buffers then hold
+        the sums).  ga == 1: nothing to do."""
+        if self.ga == 1:
+            return True
+        for acc, g in self._pairs:
+            (self._copy if self._micro == 0 else self._add)(acc, g)
+        self._micro += 1
+        if self._micro < self.ga:
+            return False
+        self._micro = 0
+        for acc, g in self._pairs:
+            self._copy(g, acc)
+        return True
+
+
+def captured_validation(model, batch, noise, make, replay):
+    """val_step_graphed of an engine / trainer: on the first call two eager model.val_forward() (every buffer allocated and
+    kernel attribute set outside the capture), then make() -> (graphs, segs), timed into model.val_capture_seconds and kept;
+    every call replay(graphs, segs) -> model._val_loss3."""
+    if model._val_graphs is None:
+        for _ in range(2):
+            model.val_forward(batch, noise)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        model._val_graphs = make()
+        torch.cuda.synchronize()
+        model.val_capture_seconds = time.perf_counter() - t0
+    replay(*model._val_graphs)
+    return model._val_loss3
 
 
 @contextlib.contextmanager

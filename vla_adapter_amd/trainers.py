@@ -32,14 +32,13 @@ from __future__ import annotations
 import contextlib
 import math
 import os
-import time
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import engine as E
 from . import ops, schedule
-from .schedule import Segment, capture_graph, chunks
+from .schedule import Segment, capture_graph, chunks, turnaround_chunks
 from .ops import BF16
 
 rup = E.rup
@@ -162,7 +161,7 @@ class BackboneTrainer(E.Linear):
         # of bf16 gradients at the 0.5B geometry: large messages for the point-to-point xGMI links) / `exchange_blocks` ViT blocks
         self.exchange_layers, self.exchange_blocks = 4, 7
         self.n_active = min(cfg.llm.n_layers, cfg.num_blocks)      # LLM layers that reach the loss (see _segments)
-        self.ga, self._micro, self._gacc = 1, 0, None             # gradient accumulation (set_grad_accumulation)
+        self._accum = schedule.GradAccumulator(E.copy_flat, ops.add_)      # gradient accumulation (set_grad_accumulation)
         self.objective = "l1"
         self.overlap_update = not os.environ.get("VLA_NO_UPDATE_OVERLAP")      # AdamW range by range under the backward (_run)
         # Streams of the step schedule (_segments): the caller's stream carries the dX chain, `gstream` everything that only feeds a
@@ -178,6 +177,10 @@ class BackboneTrainer(E.Linear):
         self._deferred = []
         self._refreshed, self._rgraphs = set(), {}      # derived operands rebuilt behind a range's AdamW in this step; their graphs (captured step)
         self._evaluating, self._val_graphs = False, None     # validation forward (val_forward / val_step_graphed)
+        self._graphs = None      # the captured step (capture())
+        self._timeline = None    # a list collects (kind, index, start, end) events of every segment run (tools/trainer_timeline.py)
+        self._ce_key = None      # (B, S) of the token-CE objective's buffers
+        self._pieces = None      # _refresh_pieces() of the mode, built on first use
         # stream kind ("M" | "H" | "G" | "V") of the segment whose Python call is running: per-shape scratch of the mode (LoRA's fp8
         # row-quantised activations, lora_dropout's u / h) is kept per kind, because two kinds run at the same time on different
         # streams (eagerly: the segment's stream; captured: the kind's capture stream, whose graphs replay on that same stream)
@@ -240,13 +243,6 @@ class BackboneTrainer(E.Linear):
             self._lin("proj.fc3", P["act2"], pj["fc3.weight"], pj["fc3.bias"], out=dst)
         else:
             self._lin("proj.fc2", P["act1"], pj["fc2.weight"], pj["fc2.bias"], out=dst)
-
-    def _llm_fwd_layers(self, lo: int, hi: int):
-        llm = self.llm
-        for i in range(lo, hi):
-            llm.fwd_layer(i)
-        if hi == self.cfg.llm.n_layers:
-            llm.fwd_final()
 
     # ---- backward pieces (stateless between calls: every gradient that crosses a piece boundary lives in a per-layer slot) -----
     def _llm_bwd_layers(self, lo: int, hi: int):
@@ -392,7 +388,6 @@ class BackboneTrainer(E.Linear):
         if self.objective == "token_ce":
             return self._segments_ce(batch, gscale)
         eng, cfg, llm, head = self.eng, self.cfg, self.llm, self.head
-        n, nb = cfg.llm.n_layers, cfg.num_blocks
         # LLM layers above the head's last block (Qwen2.5-1.5B: 28 layers, 24 head blocks - action_heads.py:117-118 reads
         # hidden_states[1..24]) never reach the loss: the reference computes them and throws the result away; autograd hands their
         # parameters all-zero gradients, so AdamW moves them by the weight-decay factor 1 - lr wd alone, which a bf16 parameter does
@@ -400,7 +395,7 @@ class BackboneTrainer(E.Linear):
         # LLM layers per segment: `exchange_layers`, but 2, 1, 1 at the top - the forward -> backward turn-around (last head blocks, loss, first
         # head-backward blocks) is what the LLM backward waits for: with four-layer segments the M stream idled 1.3 ms there (tools/trainer_timeline.py)
         el, na = self.exchange_layers, self.n_active
-        lch = chunks(na, [el] * max(0, (na - 4) // el) + [2, 1, 1]) if na >= 8 and not os.environ.get("VLA_UNIFORM_CHUNKS") else chunks(na, [el])
+        lch = chunks(na, [el]) if os.environ.get("VLA_UNIFORM_CHUNKS") else turnaround_chunks(na, el, [2, 1, 1], el)
         segs = []
         add, grads = self._builders(segs)
         side = self.vstream is not None                 # the second backbone on its own stream (forward and backward)
@@ -429,18 +424,11 @@ class BackboneTrainer(E.Linear):
             add("V", lambda: self._vit_forward(1, batch["pixel_values"]), ("pre", 0), ("vf", 1))
         add("M", f_front, None, None)
         add("M", f_front2, ("vf", 1) if side else None, ("front", 0))
-        for c, (lo, hi) in enumerate(lch):
-            add("M", lambda lo=lo, hi=hi: self._llm_fwd_layers(lo, hi), None, ("f", c))
 
-            def h_fwd(c=c, lo=lo, hi=hi):
-                if c == 0:
-                    head.fwd_begin(llm.HS, eng.pos1, batch["proprio"], eng.Np, noise)
-                    head.refresh_transposes()        # (W^T operands of the head's backward: beside the LLM forward, not on the turn-around)
-                for i in range(lo, min(hi, nb)):
-                    head.fwd_layer(i)
-                if c == len(lch) - 1:
-                    self._pred = head.fwd_end()
-            add("H", h_fwd, ("f", c), None)
+        def fwd_end():
+            self._pred = head.fwd_end()
+        segs += schedule.pipeline_forward(head, lch, lambda c, lo, hi: llm.fwd_layers(lo, hi),
+                                          lambda: (llm.HS, eng.pos1, batch["proprio"], eng.Np, noise), fwd_end, refresh=True)
         self._n_forward = len(segs)                 # forward() = these; backward() = the rest
 
         def h_loss():
@@ -450,13 +438,8 @@ class BackboneTrainer(E.Linear):
             head.bwd_begin(dpred, 0)
         add("H", h_loss, None, None)
         aq_off = head.P.offsets["action_queries"][0]
-        for k, (lo, hi) in enumerate(reversed(lch)):
-            wait = None
-            if min(hi, nb) > lo:                    # (layers above the head's last block receive no gradient from it)
-                add("H", lambda lo=lo, hi=hi: [head.bwd_layer(i, self._dHS) for i in range(min(hi, nb) - 1, lo - 1, -1)], None, ("b", k))
-                wait = ("b", k)
-            add("M", lambda lo=lo, hi=hi: self._llm_bwd_layers(lo, hi), wait, ("m", k))
-            grads(("m", k), ("g", k), self._ranges("llm", lo, hi - 1))
+        segs += schedule.pipeline_backward(head, lch, lambda k, lo, hi: self._llm_bwd_layers(lo, hi), lambda: self._dHS,
+                                           lambda k, lo, hi: self._grads(("m", k), ("g", k), self._ranges("llm", lo, hi - 1)))
         add("H", head.bwd_end, None, ("hend", 0), [(head.P.grad, 0, aq_off)])
         add("M", self._mid_backward, None, ("mid", 0))
         grads(("mid", 0), ("gmid", 0), [(head.P.grad, aq_off, head.P.numel)] + self._ranges("embed") + self._ranges("proj"))
@@ -465,18 +448,17 @@ class BackboneTrainer(E.Linear):
             add("M", self._end_backward, [sg.signal for sg in segs if sg.stream == "G"], ("end", 0), self._ranges("tail"))
         return segs
 
+    def _grads(self, after, signal, ranges) -> Segment:
+        """The gradient work that the segment signalling `after` has deferred, and the hand-over of the ranges it finished."""
+        if self.gstream is not None:
+            return Segment("G", self._flush_work, after, signal, ranges)
+        return Segment("M", None, None, signal, ranges)     # single stream: nothing was deferred; the ranges are final where the chain stands
+
     def _builders(self, segs):
-        """add(kind, fn, wait, signal, ranges) appends a segment to segs; grads(after, signal, ranges) appends the gradient work
-        that the segment signalling `after` has deferred, and the hand-over of the ranges it finished."""
+        """add(kind, fn, wait, signal, ranges) appends a segment to segs; grads(after, signal, ranges) appends _grads(...)."""
         def add(st, fn, wait=None, signal=None, ranges=None):
             segs.append(Segment(st, fn, wait, signal, ranges))
-
-        def grads(after, signal, ranges):
-            if self.gstream is not None:
-                add("G", self._flush_work, after, signal, ranges)
-            else:                                   # single stream: nothing was deferred; the ranges are final where the chain stands
-                add("M", None, None, signal, ranges)
-        return add, grads
+        return add, lambda after, signal, ranges: segs.append(self._grads(after, signal, ranges))
 
     def _vit_bwd_segments(self, add, grads, side: bool):
         """Backward segments of the vision backbone(s), each followed by its gradient work.  side: the second backbone runs on the
@@ -527,13 +509,13 @@ class BackboneTrainer(E.Linear):
             self._dHS = eng._dhs(0)
         add("M", f_front, None, ("front", 0))
         for c, (lo, hi) in enumerate(lch):
-            add("M", lambda lo=lo, hi=hi: self._llm_fwd_layers(lo, hi), None, ("f", c))
+            add("M", lambda lo=lo, hi=hi: llm.fwd_layers(lo, hi), None, ("f", c))
         self._n_forward = len(segs)
 
         def f_ce():
             B, S, Np = eng.B, eng.S, eng.Np
             Lm = S - Np - 1                                          # text rows that predict a token: sequence rows Np .. S - 2
-            if getattr(self, "_ce_key", None) != (B, S):
+            if self._ce_key != (B, S):
                 e = lambda *sh, dt=BF16: torch.empty(*sh, device=self.dev, dtype=dt)
                 self.ce_h, self.ce_dh, self.ce_logits = e(B * Lm, D), e(B * Lm, D), e(B * Lm, V)
                 self.ce_out = torch.zeros(2, device=self.dev, dtype=torch.float32)
@@ -574,7 +556,7 @@ class BackboneTrainer(E.Linear):
     def set_objective(self, objective: str):
         """"l1" (default: action head + L1 regression, vla-scripts/finetune.py) or "token_ce" (the native VLM / VLA trainer's token
         cross-entropy, base_strategy.py:257-417).  Before capture()."""
-        assert objective in ("l1", "token_ce") and getattr(self, "_graphs", None) is None
+        assert objective in ("l1", "token_ce") and self._graphs is None
         self.objective = objective
         if objective == "token_ce":
             self.n_active = self.cfg.llm.n_layers                    # every layer and the final norm reach this loss
@@ -607,7 +589,7 @@ class BackboneTrainer(E.Linear):
             if seg.ranges and update is not None:
                 self._update_ranges(seg.ranges, e, update, k if graphs is not None else None)
         schedule.run(segs, self._stream, graphs, fork=[st for st in (self.hstream, self.gstream, self.vstream) if st is not None],
-                     join=True, call=self._call, after=after, timeline=getattr(self, "_timeline", None))   # (tools/trainer_timeline.py)
+                     join=True, call=self._call, after=after, timeline=self._timeline)   # (tools/trainer_timeline.py)
 
     def _call(self, st: str, fn):
         """Run a segment's Python call with its stream kind set (_lane)."""
@@ -767,36 +749,13 @@ class BackboneTrainer(E.Linear):
 
     # ---- update / capture ----------------------------------------------------------------------------------------------
     def set_grad_accumulation(self, n: int):
-        """vla-scripts/finetune.py:1039-1042, 1078-1082: loss / n on every micro-batch, gradients summed over n micro-batches (in
-        bf16, as autograd accumulates ``.grad``), one optimizer step per n.  The data-parallel exchange then runs once, on the
-        summed gradient of the boundary micro-step (the reference's DDP all-reduces on every micro-step: same result).  Call
-        before capture(): the captured loss kernel carries the 1 / n."""
-        assert n >= 1 and getattr(self, "_graphs", None) is None, "set_grad_accumulation() before capture()"
-        self.ga, self._micro = int(n), 0
-        self._gacc = (torch.zeros_like(self.P.grad), torch.zeros_like(self.head.P.grad)) if n > 1 else None
+        """As VLAEngine.set_grad_accumulation, over both flat gradient buffers; the data-parallel exchange runs once, on the sums (_step)."""
+        assert n >= 1 and self._graphs is None, "set_grad_accumulation() before capture()"
+        self._accum.reset(n, [self.P.grad, self.head.P.grad])
 
-    def _accumulate(self) -> bool:
-        """Fold the micro-step's gradients into the accumulators; True on the boundary micro-step (the grad buffers then hold the sums)."""
-        if self.ga == 1:
-            return True
-        for acc, g in zip(self._gacc, (self.P.grad, self.head.P.grad)):
-            if self._micro == 0:
-                n = g.numel()
-                ops.copy2d(g, acc, 1, n, n, n)
-            else:
-                ops.add_(acc, g)
-        self._micro += 1
-        if self._micro < self.ga:
-            return False
-        self._micro = 0
-        for acc, g in zip(self._gacc, (self.P.grad, self.head.P.grad)):
-            n = g.numel()
-            ops.copy2d(acc, g, 1, n, n, n)
-        red = self.eng.reducer
-        if red is not None:                          # one exchange, of the sums
-            red.reduce_async(self.P.grad, 0, None)
-            red.reduce_async(self.head.P.grad, 0, None)
-        return True
+    @property
+    def ga(self) -> int:
+        return self._accum.ga
 
     def train_step(self, batch, lr: float, noise=None):
         """One micro-step, launched eagerly on the three streams (with a reducer and no accumulation: every gradient range goes
@@ -811,8 +770,12 @@ class BackboneTrainer(E.Linear):
             self._after_update(refresh=graphs is None)
         else:
             self._run(segs, graphs, exchange=self.ga == 1)
-            if not self._accumulate():
+            if not self._accum.fold():
                 return self._loss3
+            red = self.eng.reducer
+            if self.ga > 1 and red is not None:      # one exchange, of the sums
+                red.reduce_async(self.P.grad, 0, None)
+                red.reduce_async(self.head.P.grad, 0, None)
             self.optimizer_step(lr, refresh=graphs is None)
         if graphs is not None and self._g_r is not None:
             self._g_r.replay()
@@ -895,20 +858,11 @@ class BackboneTrainer(E.Linear):
     def val_step_graphed(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Captured validation of the static ``batch`` / ``noise`` buffers (copy each batch INTO them first): one linear hipGraph
         per forward segment on the step's streams, captured on the first call into memory pools of their own."""
-        if self._val_graphs is None:
-            for _ in range(2):                       # allocate buffers / set kernel attributes outside the capture
-                self.val_forward(batch, noise)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
+        def make():
             with self._eval_mode():
                 segs = self._val_segments(batch, noise)
-                graphs = self._capture(segs)[0]
-            torch.cuda.synchronize()
-            self.val_capture_seconds = time.perf_counter() - t0
-            self._val_graphs = (graphs, segs)
-        graphs, segs = self._val_graphs
-        self._run(segs, graphs, exchange=False)
-        return self._val_loss3
+                return self._capture(segs)[0], segs
+        return schedule.captured_validation(self, batch, noise, make, lambda graphs, segs: self._run(segs, graphs, exchange=False))
 
     def _after_update(self, refresh: bool):
         if self.eng.reducer is not None:
@@ -1027,7 +981,7 @@ class FullFinetune(BackboneTrainer):
 
     def _refresh_pieces(self):
         """One piece per weight matrix: its W^T copy (the flat offsets of the matrix in self.P)."""
-        if getattr(self, "_pieces", None) is None:
+        if self._pieces is None:
             out = []
 
             def add(name, holder, k):
@@ -1224,7 +1178,7 @@ class LoRAFinetune(BackboneTrainer):
 
     def _refresh_pieces(self):
         """One piece per wrapped Linear: B_blk, A_cat^T, B_blk^T from its pairs (adjacent in the flat buffer: first A to last B)."""
-        if getattr(self, "_pieces", None) is None:
+        if self._pieces is None:
             out = []
             for l in self.L.values():
                 lo = self.P.offsets[f"{l.name}.{l.projs[0][0]}.lora_A"][0]
