@@ -9,6 +9,8 @@ typedef __attribute__((ext_vector_type(8))) short bf16x8;     // MFMA A/B fragme
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;      // 16x16 accumulator
 typedef __attribute__((ext_vector_type(16))) float f32x16;    // 32x32 accumulator
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;   // 16 B of packed bf16 that stay four plain registers
+typedef __attribute__((ext_vector_type(8))) int v8i_f8;       // the 32-byte fp8 MFMA operand
 
 #define VLA_OK 0
 #define VLA_ERR_ARG (-1)       // bad shape / alignment / null pointer
@@ -59,6 +61,26 @@ __device__ __forceinline__ unsigned pack2(float lo, float hi) {   // ONE v_cvt_p
   return __builtin_bit_cast(unsigned, b);
 }
 
+// ---- packed bf16: a 32-bit word holds two values, the lower-indexed one in bits 0..15.  The ONE spelling of the unpack.
+__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+__device__ __forceinline__ void unpack4(const uint2& u, float (&f)[4]) {
+  f[0] = bf_lo(u.x); f[1] = bf_hi(u.x); f[2] = bf_lo(u.y); f[3] = bf_hi(u.y);
+}
+__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
+  const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    f[2 * k] = bf_lo(w[k]);
+    f[2 * k + 1] = bf_hi(w[k]);
+  }
+}
+template <class V>   // four floats behind operator[] (float[4], f32x4)
+__device__ __forceinline__ uint2 pack4(const V& f) { return uint2{pack2(f[0], f[1]), pack2(f[2], f[3])}; }
+__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+  return uint4{pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7])};
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -99,7 +121,6 @@ __device__ __forceinline__ float gelu_tanh(float x) {
   const float u2 = x * __builtin_fmaf(x * x, 0.044715f * 1.5957691216057308f, 1.5957691216057308f);   // 2u
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u2 * -1.4426950408889634f));
 }
-__device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
 
 // Zero `bytes` (a multiple of 16, 16-B aligned) of LDS with 16-B stores, strided over `n` threads.  The attention kernels cleared
 // their tile images with one ds_write_b16 per element: 136 stores per lane and tile pair in the head kernels - 8.3k of
@@ -112,6 +133,40 @@ __device__ __forceinline__ void lds_zero16(void* p, int bytes, int idx, int n) {
 __device__ __forceinline__ void glds16(const void* gptr, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gptr,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+// The same copy issued from inline asm: 16 B per lane from (wave-uniform base + per-lane 32-bit byte offset) to LDS address `dst`
+// (+ lane * 16).  Hidden from hipcc on purpose: beside a builtin global_load_lds it drains vmcnt(0) before every ordinary
+// load, every ds_write that might alias the DMA target and every reuse of a loaded register - i.e. all through an epilogue
+// that runs under the next tile's K-tile 0.  Its completion is counted by hand (the s_waitcnt statements of the callers); M0 is
+// saved and restored in the same statement (it is compiler-reserved).
+__device__ __forceinline__ void glds16s(const char* base, unsigned voff, unsigned dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
+}
+
+// two 16-B fragment reads -> the 32-byte fp8 MFMA operand
+__device__ __forceinline__ v8i_f8 cat8(bf16x8 lo, bf16x8 hi) {
+  typedef float f32x8 __attribute__((ext_vector_type(8)));
+  const f32x4 l = __builtin_bit_cast(f32x4, lo), h = __builtin_bit_cast(f32x4, hi);
+  return __builtin_bit_cast(v8i_f8, f32x8{l[0], l[1], l[2], l[3], h[0], h[1], h[2], h[3]});
+}
+
+// raw s_barrier that the scheduler moves nothing across (the hand-scheduled phases of the 256-row kernels)
+#define VLA_BARRIER()                      \
+  do {                                     \
+    __builtin_amdgcn_sched_barrier(0);     \
+    __builtin_amdgcn_s_barrier();          \
+    asm volatile("" ::: "memory");         \
+    __builtin_amdgcn_sched_barrier(0);     \
+  } while (0)
+
+// XCD-aware bijective order over `nwg` workgroups: workgroups b and b + 8 share an XCD (round-robin dispatch); every XCD gets a
+// contiguous run of the tile list, so neighbouring tiles (same operand panel) hit the same L2
+__device__ __forceinline__ int xcd_order(int bid, int nwg) {
+  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
 // ---------------------------------------------------------------- column reductions with a fixed summation order

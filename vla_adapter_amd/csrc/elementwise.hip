@@ -1,21 +1,9 @@
 // HBM-bound glue kernels of the fine-tune hot path (gfx950): im2col, action masks, embedding splice, gathers,
 // RoPE (both conventions), SwiGLU backward, transposes, casts, L1 loss, AdamW.  All bf16 traffic is 16 B per lane.
-#include "common.h"
-#include "../../include/vla_native.h"
+#include "gemm_epilogue.h"
 
 namespace {
 
-__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(w[k] << 16);
-    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  return uint4{pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7])};
-}
 inline unsigned nblk(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // ---------------------------------------------------------------- im2col for the PxP/P patch-embed conv
@@ -161,12 +149,13 @@ __global__ void swiglu_bwd_kernel(const bf16_t* __restrict__ dh, const bf16_t* _
     unpack8(*reinterpret_cast<const uint4*>(dh + m * I + c), d);
     unpack8(*reinterpret_cast<const uint4*>(gu + go), g);
     unpack8(*reinterpret_cast<const uint4*>(gu + go + 16), u);
+    // (mirrors swiglu_bwd of gemm_epilogue.h with the sigmoid by an exact division and du as d (g sg): this stand-alone pass keeps
+    //  its own bits)
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float sg = 1.f / (1.f + __expf(-g[k]));
-      const float sl = g[k] * sg;
-      du[k] = d[k] * sl;
-      dg[k] = d[k] * u[k] * (sg * (1.f + g[k] * (1.f - sg)));
+      du[k] = d[k] * (g[k] * sg);
+      dg[k] = d[k] * u[k] * silu_grad(g[k], sg);
     }
     *reinterpret_cast<uint4*>(dgu + go) = pack8(dg);
     *reinterpret_cast<uint4*>(dgu + go + 16) = pack8(du);
@@ -272,8 +261,8 @@ __global__ void rope_half_kernel(bf16_t* __restrict__ x, const float* __restrict
     bf16_t* p = x + r * ldx + hh * dh + d;
     const float a = bf2f(p[0]), b = bf2f(p[half]);
     const float c = ct[pos * half + d], s = sign * st[pos * half + d];
-    p[0] = f2bf(rbf(a * c) + rbf(-b * s));
-    p[half] = f2bf(rbf(b * c) + rbf(a * s));
+    p[0] = f2bf(rope_rot_a(a, b, c, s));
+    p[half] = f2bf(rope_rot_b(a, b, c, s));
   }
 }
 
@@ -294,8 +283,8 @@ __global__ void rope_inter_kernel(bf16_t* __restrict__ x, const float* __restric
     const float ca = ct[pos * dh + 2 * d], cb = ct[pos * dh + 2 * d + 1];
     const float sa = st[pos * dh + 2 * d], sb = st[pos * dh + 2 * d + 1];
     if (mode == 0) {
-      p[0] = f2bf(rbf(a * ca) + rbf(-b * sa));
-      p[1] = f2bf(rbf(b * cb) + rbf(a * sb));
+      p[0] = f2bf(rope_rot_a(a, b, ca, sa));
+      p[1] = f2bf(rope_rot_b(a, b, cb, sb));
     } else {
       p[0] = f2bf(a * ca + b * sb);
       p[1] = f2bf(b * cb - a * sa);
@@ -321,8 +310,8 @@ __global__ void rope_inter_vec_kernel(bf16_t* __restrict__ x, const float* __res
     for (int k = 0; k < 8; k += 2) {
       const float a = f[k], b = f[k + 1];
       if (mode == 0) {
-        o[k] = rbf(a * cc[k]) + rbf(-b * ss[k]);
-        o[k + 1] = rbf(b * cc[k + 1]) + rbf(a * ss[k + 1]);
+        o[k] = rope_rot_a(a, b, cc[k], ss[k]);
+        o[k + 1] = rope_rot_b(a, b, cc[k + 1], ss[k + 1]);
       } else {
         o[k] = a * cc[k] + b * ss[k + 1];
         o[k + 1] = b * cc[k + 1] - a * ss[k];
@@ -398,8 +387,8 @@ __global__ void adamw_vec8_kernel(uint4* __restrict__ p, const void* __restrict_
       const unsigned t[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        gr[2 * k] = bf2f((bf16_t)(t[k] & 0xffff));
-        gr[2 * k + 1] = bf2f((bf16_t)(t[k] >> 16));
+        gr[2 * k] = bf_lo(t[k]);
+        gr[2 * k + 1] = bf_hi(t[k]);
       }
       if (gscale != 1.f) {
 #pragma unroll
@@ -410,9 +399,9 @@ __global__ void adamw_vec8_kernel(uint4* __restrict__ p, const void* __restrict_
     unsigned po[4], mo[4], vo[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      float p0 = bf2f((bf16_t)(pw[k] & 0xffff)), p1 = bf2f((bf16_t)(pw[k] >> 16));
-      float m0 = bf2f((bf16_t)(mw[k] & 0xffff)), m1 = bf2f((bf16_t)(mw[k] >> 16));
-      float v0 = bf2f((bf16_t)(vw[k] & 0xffff)), v1 = bf2f((bf16_t)(vw[k] >> 16));
+      float p0 = bf_lo(pw[k]), p1 = bf_hi(pw[k]);
+      float m0 = bf_lo(mw[k]), m1 = bf_hi(mw[k]);
+      float v0 = bf_lo(vw[k]), v1 = bf_hi(vw[k]);
       adamw_one(p0, gr[2 * k], m0, v0, decay, omb1, beta2, omb2, bc2_sqrt, eps, neg_step);
       adamw_one(p1, gr[2 * k + 1], m1, v1, decay, omb1, beta2, omb2, bc2_sqrt, eps, neg_step);
       po[k] = pack2(p0, p1); mo[k] = pack2(m0, m1); vo[k] = pack2(v0, v1);
@@ -686,7 +675,7 @@ __global__ void quant_fp8_rows_kernel(const bf16_t* __restrict__ x, unsigned cha
     const uint4 v = *reinterpret_cast<const uint4*>(xr + c);
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) amax = fmaxf(amax, fmaxf(fabsf(bf2f((bf16_t)(w[k] & 0xffff))), fabsf(bf2f((bf16_t)(w[k] >> 16)))));
+    for (int k = 0; k < 4; ++k) amax = fmaxf(amax, fmaxf(fabsf(bf_lo(w[k])), fabsf(bf_hi(w[k]))));
   }
   amax = wave_max(amax);
   // (IEEE divisions, one per row: with the approximate form a value that sits one ulp above a rounding tie lands below it)
@@ -697,10 +686,10 @@ __global__ void quant_fp8_rows_kernel(const bf16_t* __restrict__ x, unsigned cha
     const uint4 v = *reinterpret_cast<const uint4*>(xr + c);
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
     int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f((bf16_t)(w[0] & 0xffff)) * inv, bf2f((bf16_t)(w[0] >> 16)) * inv, lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f((bf16_t)(w[1] & 0xffff)) * inv, bf2f((bf16_t)(w[1] >> 16)) * inv, lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f((bf16_t)(w[2] & 0xffff)) * inv, bf2f((bf16_t)(w[2] >> 16)) * inv, hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f((bf16_t)(w[3] & 0xffff)) * inv, bf2f((bf16_t)(w[3] >> 16)) * inv, hi, true);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf_lo(w[0]) * inv, bf_hi(w[0]) * inv, lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf_lo(w[1]) * inv, bf_hi(w[1]) * inv, lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf_lo(w[2]) * inv, bf_hi(w[2]) * inv, hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf_lo(w[3]) * inv, bf_hi(w[3]) * inv, hi, true);
     *reinterpret_cast<uint2*>(qr + c) = uint2{(unsigned)lo, (unsigned)hi};
   }
 }
@@ -799,8 +788,8 @@ __global__ void dropout_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict_
     for (int k = 0; k < 4; ++k) {
       const unsigned long long h = k < 2 ? h0 : h1;
       const bool k0 = ((unsigned)(h >> (32 * (k & 1))) & 0xffffu) >= thr, k1 = ((unsigned)(h >> (32 * (k & 1) + 16)) & 0xffffu) >= thr;
-      const float a = k0 ? rbf(bf2f((bf16_t)(xw[k] & 0xffff)) * scale) : 0.f, b = k1 ? rbf(bf2f((bf16_t)(xw[k] >> 16)) * scale) : 0.f;
-      if (ADD) yw[k] = pack2(bf2f((bf16_t)(yw[k] & 0xffff)) + a, bf2f((bf16_t)(yw[k] >> 16)) + b);
+      const float a = k0 ? rbf(bf_lo(xw[k]) * scale) : 0.f, b = k1 ? rbf(bf_hi(xw[k]) * scale) : 0.f;
+      if (ADD) yw[k] = pack2(bf_lo(yw[k]) + a, bf_hi(yw[k]) + b);
       else yw[k] = pack2(a, b);
     }
     *reinterpret_cast<uint4*>(y + r * ldy + c) = uint4{yw[0], yw[1], yw[2], yw[3]};
@@ -957,7 +946,7 @@ __global__ __launch_bounds__(256) void token_ce_kernel(const bf16_t* __restrict_
       const uint4 v = *reinterpret_cast<const uint4*>(x + c);
       const unsigned u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) m = fmaxf(m, fmaxf(bf2f((bf16_t)(u[k] & 0xffff)), bf2f((bf16_t)(u[k] >> 16))));
+      for (int k = 0; k < 4; ++k) m = fmaxf(m, fmaxf(bf_lo(u[k]), bf_hi(u[k])));
     } else {
       for (int k = c; k < V; ++k) m = fmaxf(m, bf2f(x[k]));
     }
@@ -973,7 +962,7 @@ __global__ __launch_bounds__(256) void token_ce_kernel(const bf16_t* __restrict_
       const uint4 v = *reinterpret_cast<const uint4*>(x + c);
       const unsigned u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) s += __expf(bf2f((bf16_t)(u[k] & 0xffff)) - m) + __expf(bf2f((bf16_t)(u[k] >> 16)) - m);
+      for (int k = 0; k < 4; ++k) s += __expf(bf_lo(u[k]) - m) + __expf(bf_hi(u[k]) - m);
     } else {
       for (int k = c; k < V; ++k) s += __expf(bf2f(x[k]) - m);
     }
@@ -1023,7 +1012,7 @@ __global__ __launch_bounds__(256) void token_ce_bwd_kernel(const bf16_t* __restr
       const uint4 v = *reinterpret_cast<const uint4*>(x + c);
       const unsigned u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) m = fmaxf(m, fmaxf(bf2f((bf16_t)(u[k] & 0xffff)), bf2f((bf16_t)(u[k] >> 16))));
+      for (int k = 0; k < 4; ++k) m = fmaxf(m, fmaxf(bf_lo(u[k]), bf_hi(u[k])));
     } else {
       for (int k = c; k < V; ++k) m = fmaxf(m, bf2f(x[k]));
     }
@@ -1039,7 +1028,7 @@ __global__ __launch_bounds__(256) void token_ce_bwd_kernel(const bf16_t* __restr
       const uint4 v = *reinterpret_cast<const uint4*>(x + c);
       const unsigned u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) s += __expf(bf2f((bf16_t)(u[k] & 0xffff)) - m) + __expf(bf2f((bf16_t)(u[k] >> 16)) - m);
+      for (int k = 0; k < 4; ++k) s += __expf(bf_lo(u[k]) - m) + __expf(bf_hi(u[k]) - m);
     } else {
       for (int k = c; k < V; ++k) s += __expf(bf2f(x[k]) - m);
     }
@@ -1056,8 +1045,8 @@ __global__ __launch_bounds__(256) void token_ce_bwd_kernel(const bf16_t* __restr
       unsigned o[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float p0 = __expf(bf2f((bf16_t)(u[k] & 0xffff)) - m) * inv - (c + 2 * k == lab ? 1.f : 0.f);
-        const float p1 = __expf(bf2f((bf16_t)(u[k] >> 16)) - m) * inv - (c + 2 * k + 1 == lab ? 1.f : 0.f);
+        const float p0 = __expf(bf_lo(u[k]) - m) * inv - (c + 2 * k == lab ? 1.f : 0.f);
+        const float p1 = __expf(bf_hi(u[k]) - m) * inv - (c + 2 * k + 1 == lab ? 1.f : 0.f);
         o[k] = pack2(p0 * sc, p1 * sc);
       }
       *reinterpret_cast<uint4*>(y + c) = uint4{o[0], o[1], o[2], o[3]};
@@ -1080,7 +1069,7 @@ extern "C" int vla_token_ce_bwd(void* stream, const void* logits, long long ld_l
 
 
 // ---------------------------------------------------------------- SwiGLU forward on interleaved pre-activations (LoRA path)
-// h[m, 16t + c] = bf16(bf16(silu(g)) * u), g = GU[m, 32t + c], u = GU[m, 32t + 16 + c]: the product the fused GEMM epilogue forms;
+// h[m, 16t + c] = bf16(bf16(silu(g)) * u), g = GU[m, 32t + c], u = GU[m, 32t + 16 + c]: swiglu_h, the fused GEMM epilogue's own;
 // stand-alone because LoRA adds its low-rank deltas to the gate / up pre-activations BEFORE the activation (peft wraps each
 // nn.Linear: vla-scripts/finetune.py:832-844).  8 h columns per thread.
 __global__ void swiglu_fwd_kernel(const bf16_t* __restrict__ gu, bf16_t* __restrict__ h, long long nch, int I) {
@@ -1089,16 +1078,12 @@ __global__ void swiglu_fwd_kernel(const bf16_t* __restrict__ gu, bf16_t* __restr
     const long long m = e / I;
     const int c = (int)(e - m * I);                  // column in [0, I), multiple of 8
     const bf16_t* row = gu + m * 2 * I + (c >> 4) * 32 + (c & 15);
-    const uint4 gv = *reinterpret_cast<const uint4*>(row), uv = *reinterpret_cast<const uint4*>(row + 16);
-    const unsigned ga[4] = {gv.x, gv.y, gv.z, gv.w}, ua[4] = {uv.x, uv.y, uv.z, uv.w};
-    unsigned o[4];
+    float g[8], u[8], o[8];
+    unpack8(*reinterpret_cast<const uint4*>(row), g);
+    unpack8(*reinterpret_cast<const uint4*>(row + 16), u);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float g0 = bf2f((bf16_t)(ga[k] & 0xffff)), g1 = bf2f((bf16_t)(ga[k] >> 16));
-      const float u0 = bf2f((bf16_t)(ua[k] & 0xffff)), u1 = bf2f((bf16_t)(ua[k] >> 16));
-      o[k] = pack2(rbf(g0 * __builtin_amdgcn_rcpf(1.0f + __expf(-g0))) * u0, rbf(g1 * __builtin_amdgcn_rcpf(1.0f + __expf(-g1))) * u1);
-    }
-    *reinterpret_cast<uint4*>(h + e) = uint4{o[0], o[1], o[2], o[3]};
+    for (int k = 0; k < 8; ++k) o[k] = swiglu_h(g[k], u[k]);
+    *reinterpret_cast<uint4*>(h + e) = pack8(o);
   }
 }
 

@@ -23,16 +23,16 @@
 //
 // Epilogue rounding points follow the reference under bf16 autocast: bf16(acc+bias) -> act -> bf16 -> (+residual) -> bf16.
 #include <algorithm>
-#include "common.h"
+#include "gemm_epilogue.h"
 #include "gemm_params.h"
-#include "../../include/vla_native.h"
 
 namespace {
 
 constexpr int BK = 64;
 constexpr int EPI_PAD = 16;  // bytes of padding per staged epilogue row (keeps 16-B alignment, spreads banks)
 
-
+// Per-element activation of the split-K finalize pass, on the ROUNDED linear value: the Act* functors of gemm_epilogue.h with the
+// roundings written out (open-coded: dispatched through epi_with_act, splitk_finalize_kernel's SGPR count moves)
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {
     case VLA_ACT_GELU: return rbf(gelu_erf(v));
@@ -40,13 +40,6 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     case VLA_ACT_GELU_TANH: return rbf(gelu_tanh(v));
     default: return v;
   }
-}
-
-typedef int v8i_f8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ v8i_f8 cat8(bf16x8 lo, bf16x8 hi) {          // two 16-B fragment reads -> the 32-byte fp8 operand
-  typedef float f32x8 __attribute__((ext_vector_type(8)));
-  const f32x4 l = __builtin_bit_cast(f32x4, lo), h = __builtin_bit_cast(f32x4, hi);
-  return __builtin_bit_cast(v8i_f8, f32x8{l[0], l[1], l[2], l[3], h[0], h[1], h[2], h[3]});
 }
 
 template <int BM, int BN, int STAGES, int WN = 2>
@@ -89,11 +82,7 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid / WN, wc = wid - wr * WN;
 
-  // XCD-aware bijective remap: blocks b and b+8 share an XCD (round-robin dispatch); give each XCD a
-  // contiguous run of tiles so neighbouring tiles (same A row-panel) hit the same L2.
-  const int nwg = p.ntiles, bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int swz = xcd_order(blockIdx.x, p.ntiles);         // every XCD a contiguous run of tiles
   // group-M order inside the XCD's run: GM row-panels x all column tiles, row index fastest, so the ~32-64 tiles an
   // XCD has in flight form a GM x (32/GM) patch whose A panels stay in that XCD's 4 MiB L2 while B tiles stream once
   // (row-major order re-streamed every B tile from beyond L2 for every row panel: 44 x 17 MB for the gate/up GEMM).
@@ -119,7 +108,7 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
     const int pc = wid * C::PPW + i;                      // wave-uniform
     if (pc < BM / 8) {
       const int ra = min(m0 + pc * 8 + (lane >> 3), p.M - 1);
-      pp[i] = Ab + (p.gA > 0 ? (long long)(ra / p.gA) * p.sgA + (long long)(ra % p.gA) * p.lda : (long long)ra * p.lda) * EB + kc;
+      pp[i] = Ab + grouped_row(ra, p.gA, p.sgA, p.lda) * EB + kc;
     } else {
       const int rb = min(n0 + (pc - BM / 8) * 8 + (lane >> 3), p.N - 1);
       pp[i] = Bb + (long long)rb * p.ldb * EB + kc;
@@ -184,8 +173,8 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
       const int n = n0 + cbase(ni) + lq * 4;
       if (bvec && n + 3 < p.N) {
         const uint2 b2 = *reinterpret_cast<const uint2*>(bias + n);
-        bv[ni][0] = bf2f((bf16_t)(b2.x & 0xffff)); bv[ni][1] = bf2f((bf16_t)(b2.x >> 16));
-        bv[ni][2] = bf2f((bf16_t)(b2.y & 0xffff)); bv[ni][3] = bf2f((bf16_t)(b2.y >> 16));
+        bv[ni][0] = bf_lo(b2.x); bv[ni][1] = bf_hi(b2.x);
+        bv[ni][2] = bf_lo(b2.y); bv[ni][3] = bf_hi(b2.y);
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) bv[ni][j] = (bias && n + j < p.N) ? bf2f(bias[n + j]) : 0.f;
@@ -315,7 +304,6 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
     // the first is used (row clamped, no per-element condition), staged in the wave's LDS region and overwritten IN PLACE by dGU
     // (same interleaved layout).  The former per-lane 8-B gathers (16 rows x 32 B per load instruction, each behind its own
     // bounds branch and wait) made this epilogue as long as the K loop of the live-row backward's M = 2048 GEMM.
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     u32x4 gin[2][NIT];
 #pragma unroll
     for (int half = 0; half < 2; ++half)
@@ -323,8 +311,7 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
       for (int it = 0; it < NIT; ++it) {
         const int row = it * RPP2 + lane / CH2, ch = lane % CH2;
         const int m = min(wm0 + half * 32 + row, p.M - 1);
-        const long long ro = p.gR > 0 ? (long long)(m / p.gR) * p.sgR + (long long)(m % p.gR) * p.ldr : (long long)m * p.ldr;
-        gin[half][it] = *reinterpret_cast<const u32x4*>(GU + ro + 2 * wn0 + ch * 8);
+        gin[half][it] = *reinterpret_cast<const u32x4*>(GU + grouped_row(m, p.gR, p.sgR, p.ldr) + 2 * wn0 + ch * 8);
       }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -339,20 +326,13 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
 #pragma unroll
         for (int ni = 0; ni < C::NT; ++ni) {
           char* rowp = reg2 + (mh * 16 + lr) * ROWB + (ni * 32 + lq * 4) * 2;
-          const uint2 gv = *reinterpret_cast<const uint2*>(rowp);
-          const uint2 uv = *reinterpret_cast<const uint2*>(rowp + 32);
-          const float gg[4] = {bf2f((bf16_t)(gv.x & 0xffff)), bf2f((bf16_t)(gv.x >> 16)), bf2f((bf16_t)(gv.y & 0xffff)), bf2f((bf16_t)(gv.y >> 16))};
-          const float uu[4] = {bf2f((bf16_t)(uv.x & 0xffff)), bf2f((bf16_t)(uv.x >> 16)), bf2f((bf16_t)(uv.y & 0xffff)), bf2f((bf16_t)(uv.y >> 16))};
-          float dg[4], du[4];
+          float gg[4], uu[4], dg[4], du[4];
+          unpack4(*reinterpret_cast<const uint2*>(rowp), gg);
+          unpack4(*reinterpret_cast<const uint2*>(rowp + 32), uu);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float d = rbf(acc[ni][mi][j] * p.alpha);
-            const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-gg[j]));
-            du[j] = d * gg[j] * sg;
-            dg[j] = d * uu[j] * (sg * (1.0f + gg[j] * (1.0f - sg)));
-          }
-          *reinterpret_cast<uint2*>(rowp) = uint2{pack2(dg[0], dg[1]), pack2(dg[2], dg[3])};
-          *reinterpret_cast<uint2*>(rowp + 32) = uint2{pack2(du[0], du[1]), pack2(du[2], du[3])};
+          for (int j = 0; j < 4; ++j) swiglu_bwd(rbf(acc[ni][mi][j] * p.alpha), gg[j], uu[j], dg[j], du[j]);
+          *reinterpret_cast<uint2*>(rowp) = pack4(dg);
+          *reinterpret_cast<uint2*>(rowp + 32) = pack4(du);
         }
       }
 #pragma unroll
@@ -376,25 +356,20 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
         float h[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float g = rbf(acc[2 * pr][mi][j] * p.alpha + bv[2 * pr][j]);
-          const float u = rbf(acc[2 * pr + 1][mi][j] * p.alpha + bv[2 * pr + 1][j]);
+          const float g = rbf(epi_linear(acc[2 * pr][mi][j], p.alpha, bv[2 * pr][j]));
+          const float u = rbf(epi_linear(acc[2 * pr + 1][mi][j], p.alpha, bv[2 * pr + 1][j]));
           acc[2 * pr][mi][j] = g;
           acc[2 * pr + 1][mi][j] = u;
-          h[j] = rbf(g * __builtin_amdgcn_rcpf(1.0f + __expf(-g))) * u;
+          h[j] = swiglu_h(g, u);
         }
         const int hc = (wn0 >> 1) + pr * 16 + lq * 4;
-        if (m < p.M && hc + 3 < (p.N >> 1)) {
-          uint2 o = {pack2(h[0], h[1]), pack2(h[2], h[3])};
-          *reinterpret_cast<uint2*>(C2 + (long long)m * p.ldc2 + hc) = o;
-        }
+        if (m < p.M && hc + 3 < (p.N >> 1)) *reinterpret_cast<uint2*>(C2 + (long long)m * p.ldc2 + hc) = pack4(h);
       }
     if (p.C == nullptr) return;
   } else {
-    // alpha, bias, activation on the bf16-rounded linear output (the reference's Linear emits bf16 before the activation
-    // module; the activation's own bf16 rounding is the pack into the staging tile below).  The activation is resolved
-    // OUTSIDE the element loops: a per-element switch cost 5 us on the ViT fc1 GEMM even for ReLU.
+    // alpha, bias, activation (gemm_epilogue.h; the activation's own bf16 rounding is the pack into the staging tile below)
     float alpha = p.alpha;
-    if (p.bias_post) {                        // bf16(bf16(alpha acc) + bias): torch CPU Linear on a strided input
+    if (p.bias_post) {                        // epi_linear<true>, its rounding taken in a pass of its own
 #pragma unroll
       for (int ni = 0; ni < C::NT; ++ni)
 #pragma unroll
@@ -409,29 +384,26 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[ni][mi][j] = fn(acc[ni][mi][j] * alpha + bv[ni][j]);
+          for (int j = 0; j < 4; ++j) acc[ni][mi][j] = fn(epi_linear(acc[ni][mi][j], alpha, bv[ni][j]));
     };
-    if (p.act == VLA_ACT_GELU) finish([](float v) { return gelu_erf(rbf(v)); });
-    else if (p.act == VLA_ACT_RELU) finish([](float v) { return fmaxf(v, 0.f); });
-    else if (p.act == VLA_ACT_GELU_TANH) finish([](float v) { return gelu_tanh(rbf(v)); });
-    else finish([](float v) { return v; });
+    epi_with_act(p.act, finish);
     // ---- fused rotary embedding on the projected q/k columns (saves a full read+write pass per projection)
     if (ROPE != 0 && n0 + cbase(0) < p.rope_cols) {
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
         const int pos = min(wm0 + mi * 16 + lr, p.M - 1) % p.rope_T;
         if (ROPE == 2) {
-          // action_heads.py:125-146: pairs (2i, 2i+1), cos/sin tables of cat([f, f]) (different frequency per lane of a pair)
+          // interleaved: the partners are neighbours inside the lane's four columns
 #pragma unroll
           for (int ni = 0; ni < C::NT; ++ni) {
             const int d = (wn0 + ni * 16 + lq * 4) % p.rope_dh;
             const float4 c = *reinterpret_cast<const float4*>(p.rope_cos + (long long)pos * p.rope_dh + d);
             const float4 sn = *reinterpret_cast<const float4*>(p.rope_sin + (long long)pos * p.rope_dh + d);
             const float x0 = rbf(acc[ni][mi][0]), x1 = rbf(acc[ni][mi][1]), x2 = rbf(acc[ni][mi][2]), x3 = rbf(acc[ni][mi][3]);
-            acc[ni][mi][0] = rbf(x0 * c.x) + rbf(-x1 * sn.x);
-            acc[ni][mi][1] = rbf(x1 * c.y) + rbf(x0 * sn.y);
-            acc[ni][mi][2] = rbf(x2 * c.z) + rbf(-x3 * sn.z);
-            acc[ni][mi][3] = rbf(x3 * c.w) + rbf(x2 * sn.w);
+            acc[ni][mi][0] = rope_rot_a(x0, x1, c.x, sn.x);
+            acc[ni][mi][1] = rope_rot_b(x0, x1, c.y, sn.y);
+            acc[ni][mi][2] = rope_rot_a(x2, x3, c.z, sn.z);
+            acc[ni][mi][3] = rope_rot_b(x2, x3, c.w, sn.w);
           }
         } else if (ROPE == 1 && C::NT == 4) {
           // HF rotate_half, head dim 64 == this wave's 64 columns: d <-> d+32 are tiles ni and ni+2 of the same lane
@@ -439,28 +411,16 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni) {
             const int d = ni * 16 + lq * 4;
-            const float4 c = *reinterpret_cast<const float4*>(p.rope_cos + (long long)pos * half + d);
-            const float4 sn = *reinterpret_cast<const float4*>(p.rope_sin + (long long)pos * half + d);
-            const float cc[4] = {c.x, c.y, c.z, c.w}, ss[4] = {sn.x, sn.y, sn.z, sn.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const float a = rbf(acc[ni][mi][j]), b = rbf(acc[ni + 2][mi][j]);
-              acc[ni][mi][j] = rbf(a * cc[j]) + rbf(-b * ss[j]);
-              acc[ni + 2][mi][j] = rbf(b * cc[j]) + rbf(a * ss[j]);
-            }
+            const f32x4 c = *reinterpret_cast<const f32x4*>(p.rope_cos + (long long)pos * half + d);
+            const f32x4 sn = *reinterpret_cast<const f32x4*>(p.rope_sin + (long long)pos * half + d);
+            rope_half<4>(acc[ni][mi], acc[ni + 2][mi], c, sn);
           }
         } else if (ROPE == 1 && C::NT == 2) {
           // same rotation on the permuted 8-wave layout: n tile 0 holds head columns d = 16 (wc & 1) + 4 lq + j, tile 1 d + 32
           const int half = p.rope_dh >> 1, d = (wide ? wc * 16 : (wc & 1) * 16) + lq * 4;
-          const float4 c = *reinterpret_cast<const float4*>(p.rope_cos + (long long)pos * half + d);
-          const float4 sn = *reinterpret_cast<const float4*>(p.rope_sin + (long long)pos * half + d);
-          const float cc[4] = {c.x, c.y, c.z, c.w}, ss[4] = {sn.x, sn.y, sn.z, sn.w};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float a = rbf(acc[0][mi][j]), b = rbf(acc[1][mi][j]);
-            acc[0][mi][j] = rbf(a * cc[j]) + rbf(-b * ss[j]);
-            acc[1][mi][j] = rbf(b * cc[j]) + rbf(a * ss[j]);
-          }
+          const f32x4 c = *reinterpret_cast<const f32x4*>(p.rope_cos + (long long)pos * half + d);
+          const f32x4 sn = *reinterpret_cast<const f32x4*>(p.rope_sin + (long long)pos * half + d);
+          rope_half<4>(acc[0][mi], acc[1][mi], c, sn);
         }
       }
     }
@@ -480,8 +440,7 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
 #pragma unroll
       for (int mh = 0; mh < MIH; ++mh) {
         const int mi = half * MIH + mh;
-        uint2 o = {pack2(acc[ni][mi][0], acc[ni][mi][1]), pack2(acc[ni][mi][2], acc[ni][mi][3])};
-        *reinterpret_cast<uint2*>(reg + (mh * 16 + lr) * C::EPI_STRIDE + (ni * 16 + lq * 4) * 2) = o;
+        *reinterpret_cast<uint2*>(reg + (mh * 16 + lr) * C::EPI_STRIDE + (ni * 16 + lq * 4) * 2) = pack4(acc[ni][mi]);
       }
     // The common case - the wave's rows and columns all inside C, 16-B aligned rows, plain row addressing - without a branch
     // per row segment, the residual segments all requested before the first is added (as in gemm256.hip: in the general loop
@@ -494,7 +453,6 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
         const int row0 = lane / CH, ch = lane % CH;
         const int n = n0 + cbase(ch >> 1) + (ch & 1) * 8;
         if (Rb) {
-          typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
           u32x4 rv[NIT];
 #pragma unroll
           for (int it = 0; it < NIT; ++it) rv[it] = *reinterpret_cast<const u32x4*>(Rb + (long long)(wmh + it * RPP + row0) * p.ldr + n);
@@ -502,12 +460,7 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
           for (int it = 0; it < NIT; ++it) {
             const int row = it * RPP + row0;
             const uint4 v = *reinterpret_cast<const uint4*>(reg + row * C::EPI_STRIDE + ch * 16);
-            const unsigned a[4] = {v.x, v.y, v.z, v.w};
-            unsigned o[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              o[k] = pack2(bf2f((bf16_t)(a[k] & 0xffff)) + bf2f((bf16_t)(rv[it][k] & 0xffff)), bf2f((bf16_t)(a[k] >> 16)) + bf2f((bf16_t)(rv[it][k] >> 16)));
-            *reinterpret_cast<uint4*>(Cb + (long long)(wmh + row) * p.ldc + n) = uint4{o[0], o[1], o[2], o[3]};
+            *reinterpret_cast<uint4*>(Cb + (long long)(wmh + row) * p.ldc + n) = add_packed8(v, rv[it]);
           }
         } else {
 #pragma unroll
@@ -525,29 +478,18 @@ void gemm_nt_kernel(GemmP p) {                                   //  workgroups 
       const int m = wm0 + half * C::EPI_ROWS + row, n = n0 + cbase(ch >> 1) + (ch & 1) * 8;
       uint4 v = *reinterpret_cast<const uint4*>(reg + row * C::EPI_STRIDE + ch * 16);
       if (m >= p.M || n >= p.N) continue;
-      if (p.c_live_mod > 0 && (m % p.c_live_mod) < p.c_live_from) continue;   // row never read again (live-row backward)
-      const long long roff = p.res_mod > 0 ? (long long)(m % p.res_mod) * p.ldr
-                             : p.gR > 0 ? (long long)(m / p.gR) * p.sgR + (long long)(m % p.gR) * p.ldr : (long long)m * p.ldr;
-      const long long crow = p.gC > 0 ? (long long)(m / p.gC) * p.sgC + (long long)(m % p.gC) * p.ldc : (long long)m * p.ldc;
+      if (!row_live(m, p.c_live_mod, p.c_live_from)) continue;              // row never read again (live-row backward)
+      const long long roff = residual_row(m, p.res_mod, p.gR, p.sgR, p.ldr);
+      const long long crow = grouped_row(m, p.gC, p.sgC, p.ldc);
       if (vec_ok && n + 8 <= p.N) {
-        if (Rb) {
-          const uint4 rv = *reinterpret_cast<const uint4*>(Rb + roff + n);
-          const unsigned a[4] = {v.x, v.y, v.z, v.w};
-          const unsigned b[4] = {rv.x, rv.y, rv.z, rv.w};
-          unsigned o[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            o[k] = pack2(bf2f((bf16_t)(a[k] & 0xffff)) + bf2f((bf16_t)(b[k] & 0xffff)),
-                         bf2f((bf16_t)(a[k] >> 16)) + bf2f((bf16_t)(b[k] >> 16)));
-          v = uint4{o[0], o[1], o[2], o[3]};
-        }
+        if (Rb) v = add_packed8(v, *reinterpret_cast<const uint4*>(Rb + roff + n));
         *reinterpret_cast<uint4*>(Cb + crow + n) = v;
       } else {
-        const unsigned wv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
+        const unsigned wv[4] = {v.x, v.y, v.z, v.w};          // (store_tail8 of gemm_epilogue.h, open-coded: the call changes the SGPR count
+#pragma unroll                                                 //  of the interleaved-RoPE instantiations)
         for (int k = 0; k < 8; ++k) {
           if (n + k < p.N) {
-            float f = bf2f((bf16_t)((k & 1) ? (wv[k >> 1] >> 16) : (wv[k >> 1] & 0xffffu)));
+            float f = (k & 1) ? bf_hi(wv[k >> 1]) : bf_lo(wv[k >> 1]);
             if (Rb) f += bf2f(Rb[roff + n + k]);
             Cb[crow + n + k] = f2bf(f);
           }
@@ -584,18 +526,18 @@ __global__ void splitk_finalize_kernel(const float* __restrict__ ws, const bf16_
 #pragma unroll
     for (int z = 1; z < 8; ++z) a += pv[z];                   // (same order as the rolled sum; absent planes add +0)
     for (int z = 8; z < split; ++z) a += *reinterpret_cast<const f32x4*>(ws + z * plane + i * 4);
-    const float bb[4] = {bf2f((bf16_t)(braw.x & 0xffff)), bf2f((bf16_t)(braw.x >> 16)), bf2f((bf16_t)(braw.y & 0xffff)), bf2f((bf16_t)(braw.y >> 16))};
-    const float rr[4] = {bf2f((bf16_t)(rraw.x & 0xffff)), bf2f((bf16_t)(rraw.x >> 16)), bf2f((bf16_t)(rraw.y & 0xffff)), bf2f((bf16_t)(rraw.y >> 16))};
+    const float bb[4] = {bf_lo(braw.x), bf_hi(braw.x), bf_lo(braw.y), bf_hi(braw.y)};
+    const float rr[4] = {bf_lo(rraw.x), bf_hi(rraw.x), bf_lo(rraw.y), bf_hi(rraw.y)};
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float v = a[j] * alpha + (bias ? bb[j] : 0.f);
+      float v = epi_linear(a[j], alpha, bias ? bb[j] : 0.f);
       if (act != VLA_ACT_NONE) v = apply_act(rbf(v), act);
       if (R) v = rbf(v) + rr[j];
       o[j] = v;
     }
     if (vec) {
-      *reinterpret_cast<uint2*>(C + (long long)m * ldc + n) = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
+      *reinterpret_cast<uint2*>(C + (long long)m * ldc + n) = pack4(o);
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) C[(long long)m * ldc + n + j] = f2bf(o[j]);

@@ -39,8 +39,8 @@
 //     atomic tickets fetched a tile ahead measured 0.5 - 1 % SLOWER on the whole step (26.03-26.14 vs 25.82-25.86 ms, one
 //     workgroup per tile 25.90-26.02) and needed device-side state; it is gone.
 #include <type_traits>
+#include "gemm_epilogue.h"
 #include "gemm_params.h"
-#include "../../include/vla_native.h"
 
 namespace {
 
@@ -48,17 +48,6 @@ constexpr int BK = 64;
 constexpr int HT = 16384;            // bytes per half-tile (128 rows x 64 k x 2 B)
 constexpr int LDS_BYTES = 8 * HT;    // 128 KiB of operands: one workgroup per CU
 constexpr int STG = 8192;            // epilogue staging per wave: 64 rows x 128 B, 16-B chunk c of row r at c ^ ((r >> 1) & 7)
-
-// LDS-DMA issued from inline asm: 16 B per lane from (wave-uniform base + per-lane 32-bit byte offset) to LDS address `dst`
-// (+ lane * 16).  Hidden from hipcc on purpose: beside a builtin global_load_lds it drains vmcnt(0) before every ordinary
-// load, every ds_write that might alias the DMA target and every reuse of a loaded register - i.e. all through an epilogue
-// that runs under the next tile's K-tile 0.  Its completion is counted by hand (the s_waitcnt statements below); M0 is
-// saved and restored in the same statement (it is compiler-reserved).
-__device__ __forceinline__ void glds16s(const char* base, unsigned voff, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 
 // One quadrant x one K-tile, written out IN PLACE in each phase (a lambda here let the compiler sink MFMAs below the phase's
 // closing barrier - the machine scheduler's region no longer ended at the sched_barrier - and cost 0.9 ms on the step):
@@ -76,21 +65,6 @@ __device__ __forceinline__ void glds16s(const char* base, unsigned voff, unsigne
           _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                                                            \
             Q[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FB[ni][s], FA[mi][s], Q[ni][mi], 0, 0, 0);                            \
     }                                                                                                                                 \
-  } while (0)
-
-typedef int v8i_f8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ v8i_f8 cat8(bf16x8 lo, bf16x8 hi) {          // two 16-B fragment reads -> the 32-byte fp8 operand
-  typedef float f32x8 __attribute__((ext_vector_type(8)));
-  const f32x4 l = __builtin_bit_cast(f32x4, lo), h = __builtin_bit_cast(f32x4, hi);
-  return __builtin_bit_cast(v8i_f8, f32x8{l[0], l[1], l[2], l[3], h[0], h[1], h[2], h[3]});
-}
-
-#define VLA_BARRIER()                      \
-  do {                                     \
-    __builtin_amdgcn_sched_barrier(0);     \
-    __builtin_amdgcn_s_barrier();          \
-    asm volatile("" ::: "memory");         \
-    __builtin_amdgcn_sched_barrier(0);     \
   } while (0)
 
 // F8: OCP e4m3 operands with per-row fp32 scales (gemm.hip's fp8 form, same conventions): a K-tile stays 128 B per row = 128
@@ -153,7 +127,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int ra = min(m0 + wr * 128 + h * 64 + (wid & 3) * 16 + j * 8 + lrow, p.M - 1);
-        oa[h][j] = (unsigned)((gA > 0 ? (long long)(ra / gA) * p.sgA + (long long)(ra % gA) * p.lda : (long long)ra * p.lda) * EB + kc);
+        oa[h][j] = (unsigned)(grouped_row(ra, gA, p.sgA, p.lda) * EB + kc);
         const int rb = min(n0 + (wid >> 1) * 64 + h * 32 + (wid & 1) * 16 + j * 8 + lrow, p.N - 1);
         ob[h][j] = (unsigned)((long long)rb * p.ldb * EB + kc);
         if constexpr (EXT) {
@@ -363,8 +337,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
     for (int t4 = 0; t4 < 4; ++t4) {
       const int n = wn0 + t4 * 16 + lq * 4;
       const bool ok = ebvec != 0 && n + 3 < p.N;
-      bv[t4][0] = ok ? bf2f((bf16_t)(braw[t4].x & 0xffff)) : 0.f; bv[t4][1] = ok ? bf2f((bf16_t)(braw[t4].x >> 16)) : 0.f;
-      bv[t4][2] = ok ? bf2f((bf16_t)(braw[t4].y & 0xffff)) : 0.f; bv[t4][3] = ok ? bf2f((bf16_t)(braw[t4].y >> 16)) : 0.f;
+      bv[t4][0] = ok ? bf_lo(braw[t4].x) : 0.f; bv[t4][1] = ok ? bf_hi(braw[t4].x) : 0.f;
+      bv[t4][2] = ok ? bf_lo(braw[t4].y) : 0.f; bv[t4][3] = ok ? bf_hi(braw[t4].y) : 0.f;
       if (bias && !ok) {                   // unaligned bias / the ragged last columns: element loads
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -392,7 +366,6 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
     // conditional load reaches its registers through a copy that waits for it, and a load that some path never reads leaves the
     // compiler a pending register to protect with vmcnt(0) wherever it reuses it.  A half that takes the general path, or a
     // GEMM without residual, reads the head of B instead and ignores it.
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     u32x4 rv[2][8];
     int fres0 = 0, fres1 = 0;
     const char* rsrc = nullptr;
@@ -440,24 +413,18 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
 #pragma unroll
               for (int t4 = 0; t4 < 4; ++t4) {
                 const int hc = wn0 + t4 * 16 + lq * 4;
-                const long long go = (gR > 0 ? (long long)(m / gR) * p.sgR + (long long)(m % gR) * p.ldr : (long long)m * p.ldr) +
-                                     (hc >> 4) * 32 + (hc & 15);
+                const long long go = grouped_row(m, gR, p.sgR, p.ldr) + (hc >> 4) * 32 + (hc & 15);
                 const bool ok = hc + 3 < p.N;
                 const uint2 gv = ok ? *reinterpret_cast<const uint2*>(GU + go) : uint2{0, 0};
                 const uint2 uv = ok ? *reinterpret_cast<const uint2*>(GU + go + 16) : uint2{0, 0};
-                const float gg[4] = {bf2f((bf16_t)(gv.x & 0xffff)), bf2f((bf16_t)(gv.x >> 16)), bf2f((bf16_t)(gv.y & 0xffff)), bf2f((bf16_t)(gv.y >> 16))};
-                const float uu[4] = {bf2f((bf16_t)(uv.x & 0xffff)), bf2f((bf16_t)(uv.x >> 16)), bf2f((bf16_t)(uv.y & 0xffff)), bf2f((bf16_t)(uv.y >> 16))};
-                float dg[4], du[4];
+                float gg[4], uu[4], dg[4], du[4];
+                unpack4(gv, gg);
+                unpack4(uv, uu);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                  const float dd = rbf(A4(t4, mi)[j] * p.alpha);
-                  const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-gg[j]));
-                  du[j] = dd * gg[j] * sg;
-                  dg[j] = dd * uu[j] * (sg * (1.0f + gg[j] * (1.0f - sg)));
-                }
+                for (int j = 0; j < 4; ++j) swiglu_bwd(rbf(A4(t4, mi)[j] * p.alpha), gg[j], uu[j], dg[j], du[j]);
                 char* rowp = reg2 + (mq * 16 + lr) * ROWB + (t4 * 32 + lq * 4) * 2;
-                *reinterpret_cast<uint2*>(rowp) = uint2{pack2(dg[0], dg[1]), pack2(dg[2], dg[3])};
-                *reinterpret_cast<uint2*>(rowp + 32) = uint2{pack2(du[0], du[1]), pack2(du[2], du[3])};
+                *reinterpret_cast<uint2*>(rowp) = pack4(dg);
+                *reinterpret_cast<uint2*>(rowp + 32) = pack4(du);
               }
             }
 #pragma unroll
@@ -470,9 +437,6 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
           }
       }
     } else {
-      auto flo = [](unsigned v) { return __builtin_bit_cast(float, v << 16); };
-      auto fhi = [](unsigned v) { return __builtin_bit_cast(float, v & 0xffff0000u); };
-
       // ---- phase A: alpha / bias / activation on all 128 values of the lane, rounded and packed.  The fp32 accumulators end
       //      here: what the stores below carry is half the registers, and the residual segments fit beside it.
       uint2 pk[2][4][4];          // [mh][t4 = 2 nh + ni][mi]: columns t4*16 + lq*4 .. +3 of row mi*16 + lr
@@ -490,20 +454,21 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
               f32x4 ga = acc[mh][pr][0][mi], ua = acc[mh][pr][1][mi];
               if (!plain) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { ga[j] = ga[j] * p.alpha + bv[2 * pr][j]; ua[j] = ua[j] * p.alpha + bv[2 * pr + 1][j]; }
+                for (int j = 0; j < 4; ++j) { ga[j] = epi_linear(ga[j], p.alpha, bv[2 * pr][j]); ua[j] = epi_linear(ua[j], p.alpha, bv[2 * pr + 1][j]); }
               }
-              const uint2 gp = {pack2(ga[0], ga[1]), pack2(ga[2], ga[3])}, up = {pack2(ua[0], ua[1]), pack2(ua[2], ua[3])};
-              const float g[4] = {flo(gp.x), fhi(gp.x), flo(gp.y), fhi(gp.y)}, u[4] = {flo(up.x), fhi(up.x), flo(up.y), fhi(up.y)};
-              float h[4];
+              const uint2 gp = pack4(ga), up = pack4(ua);          // (the rounding of g and u is their pack)
+              float g[4], u[4], h[4];
+              unpack4(gp, g);
+              unpack4(up, u);
 #pragma unroll
-              for (int j = 0; j < 4; ++j) h[j] = rbf(g[j] * __builtin_amdgcn_rcpf(1.0f + __expf(-g[j]))) * u[j];
+              for (int j = 0; j < 4; ++j) h[j] = swiglu_h(g[j], u[j]);
               pk[mh][2 * pr][mi] = gp;
               pk[mh][2 * pr + 1][mi] = up;
-              hp[mh][pr][mi] = uint2{pack2(h[0], h[1]), pack2(h[2], h[3])};
+              hp[mh][pr][mi] = pack4(h);
             }
       } else {
         auto phase_a = [&](auto fn, auto post_t) {
-          constexpr bool POST = decltype(post_t)::value;     // bf16(bf16(alpha acc) + bias): torch CPU Linear on a strided input
+          constexpr bool POST = decltype(post_t)::value;     // epi_linear's post-round form
           const float alpha = p.alpha;
 #pragma unroll
           for (int mh = 0; mh < 2; ++mh)
@@ -515,14 +480,13 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
                 float x[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                  x[j] = fn(POST ? rbf(a[j] * alpha) + bv[t4][j] : a[j] * alpha + bv[t4][j]);
+                  x[j] = fn(epi_linear<POST>(a[j], alpha, bv[t4][j]));
                 }
                 pk[mh][t4][mi] = uint2{pack2(x[0], x[1]), pack2(x[2], x[3])};
               }
         };
         // HF rotate_half RoPE on the projected q / k columns (rope_mode 1, head dim 64 == this wave's 64 columns: d <-> d + 32 are
-        // the n tiles t4 and t4 + 2 of the same lane), on the bf16-rounded projection, every product rounded - the arithmetic of
-        // gemm.hip's fused epilogue, value for value
+        // the n tiles t4 and t4 + 2 of the same lane): rope_half, gemm_epilogue.h
         auto phase_a_rope = [&]() {
           const float alpha = p.alpha;
 #pragma unroll
@@ -539,9 +503,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
                 float ya[4], yb[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                  const float a = rbf(xa[j] * alpha + bv[ni][j]), b = rbf(xb[j] * alpha + bv[ni + 2][j]);
-                  ya[j] = rbf(a * c[j]) + rbf(-b * sn[j]);
-                  yb[j] = rbf(b * c[j]) + rbf(a * sn[j]);
+                  const float a = rbf(epi_linear(xa[j], alpha, bv[ni][j])), b = rbf(epi_linear(xb[j], alpha, bv[ni + 2][j]));
+                  ya[j] = rope_rot_a(a, b, c[j], sn[j]);
+                  yb[j] = rope_rot_b(a, b, c[j], sn[j]);
                 }
                 pk[mh][ni][mi] = uint2{pack2(ya[0], ya[1]), pack2(ya[2], ya[3])};
                 pk[mh][ni + 2][mi] = uint2{pack2(yb[0], yb[1]), pack2(yb[2], yb[3])};
@@ -549,10 +513,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
               __builtin_amdgcn_sched_barrier(0);      // (one row block's table segments at a time)
             }
         };
-        // interleaved RoPE of the action head (action_heads.py:125-146: pairs (2i, 2i+1), tables of cat([f, f]); rope_mode 2): the
-        // rotation partners are neighbours inside a lane's four columns - gemm.hip's fused epilogue value for value, on the
-        // bf16-rounded projection, every product rounded.  (The head's task-token K|V projection, 8192 x 1792: fused it used to leave
-        // this kernel for the 128-row one - 76 us in situ against 39 + the stand-alone pass's 10-20.)
+        // interleaved RoPE of the action head (rope_mode 2): the rotation partners are neighbours inside a lane's four columns -
+        // rope_interleaved, gemm_epilogue.h.  (The head's task-token K|V projection, 8192 x 1792: fused it used to leave this
+        // kernel for the 128-row one - 76 us in situ against 39 + the stand-alone pass's 10-20.)
         auto phase_a_rope2 = [&](auto post_t) {
           constexpr bool POST = decltype(post_t)::value;
           const float alpha = p.alpha;
@@ -570,10 +533,10 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
                 float x[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                  x[j] = rbf(POST ? rbf(a[j] * alpha) + bv[t4][j] : a[j] * alpha + bv[t4][j]);
+                  x[j] = rbf(epi_linear<POST>(a[j], alpha, bv[t4][j]));
                 }
-                const float y0 = rbf(x[0] * c[0]) + rbf(-x[1] * sn[0]), y1 = rbf(x[1] * c[1]) + rbf(x[0] * sn[1]);
-                const float y2 = rbf(x[2] * c[2]) + rbf(-x[3] * sn[2]), y3 = rbf(x[3] * c[3]) + rbf(x[2] * sn[3]);
+                const float y0 = rope_rot_a(x[0], x[1], c[0], sn[0]), y1 = rope_rot_b(x[0], x[1], c[1], sn[1]);
+                const float y2 = rope_rot_a(x[2], x[3], c[2], sn[2]), y3 = rope_rot_b(x[2], x[3], c[3], sn[3]);
                 pk[mh][t4][mi] = uint2{pack2(y0, y1), pack2(y2, y3)};
                 if (t4 & 1) __builtin_amdgcn_sched_barrier(0);      // (two n tiles' table segments at a time)
               }
@@ -583,11 +546,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
         else if (R2 && p.rope_mode == 2 && wn0 < p.rope_cols) {      // (its own instantiation: the table segments cost registers)
           if (p.bias_post) phase_a_rope2(std::true_type{});
           else phase_a_rope2(std::false_type{});
-        } else if (p.bias_post) phase_a([](float v) { return v; }, std::true_type{});       // (plain epilogue only: checked by the host)
-        else if (p.act == VLA_ACT_GELU) phase_a([](float v) { return gelu_erf(rbf(v)); }, std::false_type{});
-        else if (p.act == VLA_ACT_RELU) phase_a([](float v) { return fmaxf(v, 0.f); }, std::false_type{});
-        else if (p.act == VLA_ACT_GELU_TANH) phase_a([](float v) { return gelu_tanh(rbf(v)); }, std::false_type{});
-        else phase_a([](float v) { return v; }, std::false_type{});
+        } else if (p.bias_post) phase_a(ActNone{}, std::true_type{});       // (plain epilogue only: checked by the host)
+        else if (p.act == VLA_ACT_GELU) phase_a(ActGelu{}, std::false_type{});
+        else if (p.act == VLA_ACT_RELU) phase_a(ActRelu{}, std::false_type{});
+        else if (p.act == VLA_ACT_GELU_TANH) phase_a(ActGeluTanh{}, std::false_type{});
+        else phase_a(ActNone{}, std::false_type{});
       }
       // Phase A ends HERE, for the compiler too: every packed value is pinned, and the lane index that phase B computes its
       // addresses from is only defined afterwards (left alone, the residual loads are hoisted above the packing and the
@@ -684,7 +647,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
               const unsigned a[4] = {v.x, v.y, v.z, v.w};
               unsigned o[4];
 #pragma unroll
-              for (int k = 0; k < 4; ++k) o[k] = (mh == 0 ? fres0 : fres1) ? pack2(flo(a[k]) + flo(r[k]), fhi(a[k]) + fhi(r[k])) : a[k];
+              for (int k = 0; k < 4; ++k) o[k] = (mh == 0 ? fres0 : fres1) ? add_packed2(a[k], r[k]) : a[k];
               v = uint4{o[0], o[1], o[2], o[3]};
             }
             *reinterpret_cast<uint4*>(Cb + (long long)(wm0 + row) * p.ldc + wn0 + ch * 8) = v;
@@ -709,34 +672,15 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
               roff = (long long)m * p.ldr;
               crow = (long long)m * p.ldc;
             } else {
-              if (c_live_mod > 0 && (m % c_live_mod) < p.c_live_from) continue;
-              roff = res_mod > 0 ? (long long)(m % res_mod) * p.ldr
-                     : gR > 0 ? (long long)(m / gR) * p.sgR + (long long)(m % gR) * p.ldr : (long long)m * p.ldr;
-              crow = gC > 0 ? (long long)(m / gC) * p.sgC + (long long)(m % gC) * p.ldc : (long long)m * p.ldc;
+              if (!row_live(m, c_live_mod, p.c_live_from)) continue;
+              roff = residual_row(m, res_mod, gR, p.sgR, p.ldr);
+              crow = grouped_row(m, gC, p.sgC, p.ldc);
             }
             if (vec_ok && n + 8 <= p.N) {
-              if (Rb) {
-                const uint4 rv = *reinterpret_cast<const uint4*>(Rb + roff + n);
-                const unsigned a[4] = {v.x, v.y, v.z, v.w};
-                const unsigned b[4] = {rv.x, rv.y, rv.z, rv.w};
-                unsigned o[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                  o[k] = pack2(bf2f((bf16_t)(a[k] & 0xffff)) + bf2f((bf16_t)(b[k] & 0xffff)),
-                               bf2f((bf16_t)(a[k] >> 16)) + bf2f((bf16_t)(b[k] >> 16)));
-                v = uint4{o[0], o[1], o[2], o[3]};
-              }
+              if (Rb) v = add_packed8(v, *reinterpret_cast<const uint4*>(Rb + roff + n));
               *reinterpret_cast<uint4*>(Cb + crow + n) = v;
             } else {
-              const unsigned wv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-              for (int k = 0; k < 8; ++k) {
-                if (n + k < p.N) {
-                  float f = bf2f((bf16_t)((k & 1) ? (wv[k >> 1] >> 16) : (wv[k >> 1] & 0xffffu)));
-                  if (Rb) f += bf2f(Rb[roff + n + k]);
-                  Cb[crow + n + k] = f2bf(f);
-                }
-              }
+              store_tail8(Cb, crow, Rb, roff, v, n, p.N);
             }
           }
         };

@@ -17,9 +17,8 @@
 // Rounding: fp32 accumulation as four K-quarter partial sums added in order 0..3, then gemm.hip's epilogue at gemm.hip's rounding points
 // (alpha, bias, activation on the bf16-rounded value, rotate_half or interleaved RoPE, bf16, + residual, bf16): the arithmetic of vla_gemm_bf16_nt
 // with split_k = 4 (bit-identical to it when K % 256 == 0: test_gemm_skinny / test_gemm_small_rows).
-#include "common.h"
+#include "gemm_epilogue.h"
 #include "gemm_params.h"
-#include "../../include/vla_native.h"
 
 namespace {
 
@@ -91,19 +90,11 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmP p) {
       }
       const float r[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
       float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (p.bias) {
-        const uint4 b4 = *reinterpret_cast<const uint4*>(p.bias + n0 + cc);
-        const unsigned bw[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) bb[2 * k] = bf2f((bf16_t)(bw[k] & 0xffff)), bb[2 * k + 1] = bf2f((bf16_t)(bw[k] >> 16));
-      }
+      if (p.bias) unpack8(*reinterpret_cast<const uint4*>(p.bias + n0 + cc), bb);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        float x = p.bias_post ? rbf(r[k] * p.alpha) + bb[k] : r[k] * p.alpha + bb[k];
-        if (act == VLA_ACT_GELU) x = gelu_erf(rbf(x));
-        else if (act == VLA_ACT_RELU) x = fmaxf(x, 0.f);
-        else if (act == VLA_ACT_GELU_TANH) x = gelu_tanh(rbf(x));
-        v[k] = x;
+        const float x = p.bias_post ? epi_linear<true>(r[k], p.alpha, bb[k]) : epi_linear(r[k], p.alpha, bb[k]);
+        epi_with_act(act, [&](auto fn) { v[k] = fn(x); });
       }
     };
     float v[8];
@@ -120,8 +111,8 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmP p) {
       const float cc[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]}, ss[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const float own = rbf(v[k]), oth = rbf(q[k]);                  // first half: a c - b s;  second half: b c + a s  (a = first, b = second half)
-        v[k] = lo ? rbf(own * cc[k]) + rbf(-oth * ss[k]) : rbf(own * cc[k]) + rbf(oth * ss[k]);
+        const float own = rbf(v[k]), oth = rbf(q[k]);                  // this chunk holds the first (a) or the second (b) half of the pair
+        v[k] = lo ? rope_rot_a(own, oth, cc[k], ss[k]) : rope_rot_b(oth, own, cc[k], ss[k]);
       }
     }
     if (p.rope_mode == 2 && n < p.rope_cols) {                       // action_heads.py:125-146: pairs (2i, 2i+1), tables of cat([f, f])
@@ -134,8 +125,8 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmP p) {
 #pragma unroll
       for (int k = 0; k < 8; k += 2) {
         const float x0 = rbf(v[k]), x1 = rbf(v[k + 1]);
-        v[k] = rbf(x0 * cc[k]) + rbf(-x1 * ss[k]);
-        v[k + 1] = rbf(x1 * cc[k + 1]) + rbf(x0 * ss[k + 1]);
+        v[k] = rope_rot_a(x0, x1, cc[k], ss[k]);
+        v[k + 1] = rope_rot_b(x0, x1, cc[k + 1], ss[k + 1]);
       }
     }
     unsigned o[4] = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
@@ -143,8 +134,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmP p) {
       const uint4 r4 = *reinterpret_cast<const uint4*>(p.R + (long long)m * p.ldr + n);
       const unsigned rw[4] = {r4.x, r4.y, r4.z, r4.w};
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        o[k] = pack2(bf2f((bf16_t)(o[k] & 0xffff)) + bf2f((bf16_t)(rw[k] & 0xffff)), bf2f((bf16_t)(o[k] >> 16)) + bf2f((bf16_t)(rw[k] >> 16)));
+      for (int k = 0; k < 4; ++k) o[k] = add_packed2(o[k], rw[k]);
     }
     *reinterpret_cast<uint4*>(p.C + (long long)m * p.ldc + n) = uint4{o[0], o[1], o[2], o[3]};
   }

@@ -21,9 +21,8 @@
 //   * column groups on A (column c at (c / g) * stride + c % g): the gate or the up columns of an interleaved dGU;
 //   * split over the contraction (blockIdx.z slices, fp32 planes + a finalize pass) for few-tile long-M products.
 #include <algorithm>
-#include "common.h"
+#include "gemm_epilogue.h"
 #include "gemm_params.h"
-#include "../../include/vla_native.h"
 
 namespace {
 
@@ -44,13 +43,6 @@ struct TnP {
 
 __device__ __forceinline__ bf16x4 tr_read(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)p);
-}
-
-// XCD-aware bijective order over `nwg` workgroups (as gemm.hip): workgroups b and b + 8 share an XCD (round-robin dispatch); every
-// XCD gets a contiguous run of the tile list, so consecutive tiles (same A column panel) hit the same L2
-__device__ __forceinline__ int xcd_order(int bid, int nwg) {
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
 // One 128 x 128 output tile (tile index `swz` of problem p; bz = batch * split + contraction slice).
@@ -88,7 +80,7 @@ __device__ __forceinline__ void tn_tile(const TnP& p, const int swz, const int b
   }
   auto stage = [&](int buf, int t) {
     const int mt = m_begin + t * TBK;                                      // wave-uniform
-    const long long tb = grp > 0 ? (long long)(mt / grp) * sgrp + (long long)(mt % grp) * ld : (long long)mt * ld;
+    const long long tb = grouped_row(mt, grp, sgrp, ld);
     const int lim = m_end - 1 - mt;                                        // last valid row of this K-tile (>= 0)
     char* dst = smem + buf * STAGE_BYTES + (isA ? 0 : TILE_BYTES) + (wid & 3) * 4096;
 #pragma unroll
@@ -183,12 +175,8 @@ __device__ __forceinline__ void tn_tile(const TnP& p, const int swz, const int b
       float v[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = acc[ni][mi][j] * p.alpha;
-      if (Rb) {
-        const uint2 rv = *reinterpret_cast<const uint2*>(Rb + (long long)r * p.ldr + c);
-        v[0] = rbf(v[0]) + bf2f((bf16_t)(rv.x & 0xffff)); v[1] = rbf(v[1]) + bf2f((bf16_t)(rv.x >> 16));
-        v[2] = rbf(v[2]) + bf2f((bf16_t)(rv.y & 0xffff)); v[3] = rbf(v[3]) + bf2f((bf16_t)(rv.y >> 16));
-      }
-      *reinterpret_cast<uint2*>(Cb + (long long)r * p.ldc + c) = uint2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+      if (Rb) add_residual4(v, *reinterpret_cast<const uint2*>(Rb + (long long)r * p.ldr + c));
+      *reinterpret_cast<uint2*>(Cb + (long long)r * p.ldc + c) = pack4(v);
     }
 }
 
@@ -205,21 +193,7 @@ __device__ __forceinline__ void tn_tile(const TnP& p, const int swz, const int b
 constexpr int T2_HT = 16384;
 constexpr int T2_LDS = 8 * T2_HT;
 
-// LDS-DMA from inline asm (see gemm256.hip: a builtin global_load_lds makes hipcc drain vmcnt(0) around it; counted by hand below)
-__device__ __forceinline__ void glds16s(const char* base, unsigned voff, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
-
-#define TN_BARRIER()                       \
-  do {                                     \
-    __builtin_amdgcn_sched_barrier(0);     \
-    __builtin_amdgcn_s_barrier();          \
-    asm volatile("" ::: "memory");         \
-    __builtin_amdgcn_sched_barrier(0);     \
-  } while (0)
-
+// (LDS-DMA from inline asm, counted by hand below: glds16s, common.h)
 #define TN_MMA_QUADRANT(Q, FN, FM)                                                                             \
   do {                                                                                                         \
     _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                           \
@@ -258,19 +232,16 @@ __device__ __forceinline__ void tn256_tile(const TnP& p, const int swz, const in
     }
   }
   const unsigned wdst = (unsigned)(size_t)((__attribute__((address_space(3))) char*)smem) + wid * 2048;
-  auto row_base = [&](int mt, int grp, long long sgrp, int ld) -> long long {          // wave-uniform, elements
-    return grp > 0 ? (long long)(mt / grp) * sgrp + (long long)(mt % grp) * ld : (long long)mt * ld;
-  };
   auto stage_a = [&](int slot, int h, int t) {
     const int mt = t * TBK;
-    const char* base = Ab + row_base(mt, p.gA, p.sgA, p.lda) * 2;
+    const char* base = Ab + grouped_row(mt, p.gA, p.sgA, p.lda) * 2;
     const unsigned lim = (unsigned)(p.M - 1 - mt), ld2 = (unsigned)p.lda * 2u;          // contraction tail: clamped to the last valid row
     glds16s(base, min((unsigned)r0, lim) * ld2 + ca[h][0], wdst + slot * T2_HT);
     glds16s(base, min((unsigned)r0 + 4u, lim) * ld2 + ca[h][1], wdst + slot * T2_HT + 1024);
   };
   auto stage_b = [&](int slot, int h, int t) {
     const int mt = t * TBK;
-    const char* base = Bb + row_base(mt, p.gB, p.sgB, p.ldb) * 2;
+    const char* base = Bb + grouped_row(mt, p.gB, p.sgB, p.ldb) * 2;
     const unsigned lim = (unsigned)(p.M - 1 - mt), ld2 = (unsigned)p.ldb * 2u;
     glds16s(base, min((unsigned)r0, lim) * ld2 + cb[h][0], wdst + slot * T2_HT);
     glds16s(base, min((unsigned)r0 + 4u, lim) * ld2 + cb[h][1], wdst + slot * T2_HT + 1024);
@@ -324,8 +295,8 @@ __device__ __forceinline__ void tn256_tile(const TnP& p, const int swz, const in
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  TN_BARRIER();
-  if (wr == 1) TN_BARRIER();         // stagger: the wr = 1 waves run one segment behind
+  VLA_BARRIER();
+  if (wr == 1) VLA_BARRIER();         // stagger: the wr = 1 waves run one segment behind
 
   f32x4 acc[2][2][2][4];             // [mh][nh][ni][mi]
 #pragma unroll
@@ -357,12 +328,12 @@ __device__ __forceinline__ void tn256_tile(const TnP& p, const int swz, const in
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (valid < TBK) { mask_tail(fn0, valid); mask_tail(fn1, valid); }
-      TN_BARRIER();
+      VLA_BARRIER();
       __builtin_amdgcn_s_setprio(1);
       TN_MMA_QUADRANT(acc[0][0], fn0, fm);
       TN_MMA_QUADRANT(acc[0][1], fn1, fm);
       __builtin_amdgcn_s_setprio(0);
-      TN_BARRIER();
+      VLA_BARRIER();
     }
     // ================= phase Y: reads A1; issues B0, A0, B1 of K-tile t+2; retires B0, A0, B1 of K-tile t+1
     {
@@ -377,16 +348,16 @@ __device__ __forceinline__ void tn256_tile(const TnP& p, const int swz, const in
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      TN_BARRIER();
+      VLA_BARRIER();
       __builtin_amdgcn_s_setprio(1);
       TN_MMA_QUADRANT(acc[1][1], fn1, fm);
       TN_MMA_QUADRANT(acc[1][0], fn0, fm);
       __builtin_amdgcn_s_setprio(0);
-      TN_BARRIER();
+      VLA_BARRIER();
     }
     d ^= 1;
   }
-  if (wr == 0) TN_BARRIER();         // pairs with the last barrier of the wr = 1 waves
+  if (wr == 0) VLA_BARRIER();         // pairs with the last barrier of the wr = 1 waves
 
   // ---- epilogue: lane owns, per (mh, nh, ni, mi): row n1 = 16 mi + (lane & 15), columns n2 = 16 ni + 4 (lane >> 4) + {0..3}
   const int lq = lane >> 4, lr = lane & 15;
@@ -405,12 +376,8 @@ __device__ __forceinline__ void tn256_tile(const TnP& p, const int swz, const in
           float v[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = acc[mh][nh][ni][mi][j] * p.alpha;
-          if (Rb) {
-            const uint2 rv = *reinterpret_cast<const uint2*>(Rb + (long long)r * p.ldr + c);
-            v[0] = rbf(v[0]) + bf2f((bf16_t)(rv.x & 0xffff)); v[1] = rbf(v[1]) + bf2f((bf16_t)(rv.x >> 16));
-            v[2] = rbf(v[2]) + bf2f((bf16_t)(rv.y & 0xffff)); v[3] = rbf(v[3]) + bf2f((bf16_t)(rv.y >> 16));
-          }
-          *reinterpret_cast<uint2*>(Cb + (long long)r * p.ldc + c) = uint2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+          if (Rb) add_residual4(v, *reinterpret_cast<const uint2*>(Rb + (long long)r * p.ldr + c));
+          *reinterpret_cast<uint2*>(Cb + (long long)r * p.ldc + c) = pack4(v);
         }
 }
 
@@ -517,12 +484,8 @@ __global__ void tn_finalize_kernel(const float* __restrict__ ws, const bf16_t* _
     float v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = a[j] * alpha;
-    if (R) {
-      const uint2 rv = *reinterpret_cast<const uint2*>(R + b * sR + (long long)r * ldr + c);
-      v[0] = rbf(v[0]) + bf2f((bf16_t)(rv.x & 0xffff)); v[1] = rbf(v[1]) + bf2f((bf16_t)(rv.x >> 16));
-      v[2] = rbf(v[2]) + bf2f((bf16_t)(rv.y & 0xffff)); v[3] = rbf(v[3]) + bf2f((bf16_t)(rv.y >> 16));
-    }
-    *reinterpret_cast<uint2*>(C + b * sC + (long long)r * ldc + c) = uint2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+    if (R) add_residual4(v, *reinterpret_cast<const uint2*>(R + b * sR + (long long)r * ldr + c));
+    *reinterpret_cast<uint2*>(C + b * sC + (long long)r * ldc + c) = pack4(v);
   }
 }
 

@@ -24,14 +24,6 @@ __device__ __forceinline__ bf16_t* seg_row_w(bf16_t* s0, bf16_t* s1, bf16_t* s2,
   return const_cast<bf16_t*>(seg_row(s0, s1, s2, p, b, n, hoff));
 }
 
-__device__ __forceinline__ void unpack8h(const uint4& u, float (&f)[8]) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(w[k] << 16);
-    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-  }
-}
 
 // dynamic LDS layout (floats): sq[TQ][dh] | sdo[TQ][dh] | sS[TQ][N] | sX[TQ][N] | sY[TQ][N] | red[64]
 __global__ __launch_bounds__(256) void head_attn_fwd_kernel(HP p) {
@@ -52,7 +44,7 @@ __global__ __launch_bounds__(256) void head_attn_fwd_kernel(HP p) {
     for (int t = 0; t < TQ; ++t) acc[t] = 0.f;
     for (int c = 0; c < dh; c += 8) {
       float kv[8];
-      unpack8h(*reinterpret_cast<const uint4*>(kr + c), kv);
+      unpack8(*reinterpret_cast<const uint4*>(kr + c), kv);
 #pragma unroll
       for (int t = 0; t < TQ; ++t) {
         const float* qq = sq + t * dh + c;
@@ -134,8 +126,8 @@ __global__ __launch_bounds__(256) void head_attn_bwd_kernel(HP p) {
     for (int t = 0; t < TQ; ++t) { ad[t] = 0.f; ap[t] = 0.f; pn[t] = sP[t * N + n]; }
     for (int c = 0; c < dh; c += 8) {
       float kv[8], vv[8], dv[8];
-      unpack8h(*reinterpret_cast<const uint4*>(kr + c), kv);
-      unpack8h(*reinterpret_cast<const uint4*>(vr + c), vv);
+      unpack8(*reinterpret_cast<const uint4*>(kr + c), kv);
+      unpack8(*reinterpret_cast<const uint4*>(vr + c), vv);
 #pragma unroll
       for (int j = 0; j < 8; ++j) dv[j] = 0.f;
 #pragma unroll

@@ -17,18 +17,6 @@ __device__ __forceinline__ void load_row(const bf16_t* x, int cols, int lane, ui
     v[c] = (e < cols) ? *reinterpret_cast<const uint4*>(x + e) : uint4{0, 0, 0, 0};
   }
 }
-__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(w[k] << 16);
-    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  return uint4{pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7])};
-}
-
 
 // Row-wise e4m3 quantisation of a normalised row that is still in registers (packed bf16, the values the bf16 output holds):
 // the fused form of vla_quant_fp8_rows - same scale, same conversion, no second pass over the row.
@@ -399,7 +387,6 @@ extern "C" int vla_rmsnorm_bwd(void* stream, const void* dy, const void* x, cons
   VLA_CHECK_LAUNCH("rmsnorm_bwd");
   return VLA_OK;
 }
-
 
 // ---------------------------------------------------------------- RMSNorm weight gradient (full fine-tune, BASELINE config 4)
 // Qwen2RMSNorm: y = w * bf16(x * rstd)  ->  dw[c] += sum_rows dy[r, c] * bf16(x[r, c] * rstd[r])   (fp32 accumulator, += ).

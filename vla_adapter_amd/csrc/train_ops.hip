@@ -6,18 +6,6 @@
 
 namespace {
 
-__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(w[k] << 16);
-    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  return uint4{pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7])};
-}
-
 // dst[g][r][0:cols] = src[g][r][0:cols]  (bf16; 16-B lanes when VEC)
 template <bool VEC>
 __global__ void copy_rows3d_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int groups, int rows, int cols, long long s_sg,
