@@ -36,6 +36,8 @@ extern "C" {
  *   6  round 4: new entry points vla_gemm_latency_hint, vla_dropout_bf16, vla_dropout_bwd_add_bf16, vla_inc_i32 (no layout change).
  *   7  new entry points vla_augment_slab_floats, vla_augment_stats, vla_augment_apply (no layout change).
  *   8  vla_gemm_nt_plan and vla_gemm_tn_plan (kernel ids VLA_KERNEL_*) replace vla_gemm_uses_256; the latency hint is per thread.
+ *      Added since without a version change (no signature or layout moved): vla_token_ce_metrics, vla_token_metrics_finish,
+ *      vla_token_row_class.  A binder that calls them looks the symbols up first: a library built before them reports 8 too.
  * A binder checks vla_version() AND vla_desc_size() against its own struct definitions before the first call. */
 #define VLA_ABI_VERSION 8
 int vla_version(void);
@@ -369,6 +371,28 @@ int vla_token_ce(void* stream, const void* logits, long long ld_logits, const lo
  * forward, read on the device.  dlogits may alias logits. */
 int vla_token_ce_bwd(void* stream, const void* logits, long long ld_logits, const long long* shifted_labels, int rows, int V,
                      const float* loss_sum_and_count, float gscale, void* dlogits, long long ld_dlogits);
+
+/* vla_token_ce plus the metrics the reference's trainer commits after every micro-step (prismatic/training/strategies/
+ * base_strategy.py:316-356; training/train_utils.py:44-58; vla/action_tokenizer.py:76-95), in the same launch.  loss_sum_and_count
+ * receives exactly what vla_token_ce adds.  row_class u8 [rows]: 0 = not an action row, 1 = current action, 2 = next actions
+ * (vla_token_row_class).  For a row of class 1 or 2 the argmax over the V columns (torch.argmax's rule: lowest index among equal
+ * values, a NaN is the greatest value, the first NaN wins) is taken in the pass that finds the row maximum, predicted id and label
+ * are decoded as d = clip(tokenizer_len - id - 1, 0, n_bins - 2), and counters u64 [2][3] (zero them first) receive per class
+ * (rows, rows with predicted id == label, sum of |d_pred - d_label|) by integer atomics: bit-reproducible.  An action row whose label
+ * is outside [0, V) adds nothing to the loss and still counts for the metrics.  pred_ids (int32 [rows], may be NULL) receives the
+ * predicted id of every action row and -1 elsewhere. */
+int vla_token_ce_metrics(void* stream, const void* logits, long long ld_logits, const long long* shifted_labels,
+                         const unsigned char* row_class, int rows, int V, float* loss_sum_and_count, unsigned long long* counters,
+                         int* pred_ids, long long tokenizer_len, int n_bins);
+/* out4 f32 = (action_accuracy, l1_loss, next_actions_accuracy, next_actions_l1_loss) of the reference's metrics.commit from the
+ * counters above: per class correct / rows and sum * spacing / rows, spacing = (max_action - min_action) / (n_bins - 1), the
+ * distance of two neighbouring bin centres.  A class without rows gives NaN (the reference's 0 / 0). */
+int vla_token_metrics_finish(void* stream, const unsigned long long* counters, double spacing, float* out4);
+/* row_class u8 [B, L - shift] of labels int64 [B, L] read from column `shift` on: get_current_action_mask (1) /
+ * get_next_actions_mask (2) of training/train_utils.py:8-41 - c = cumsum(label != -100); an id > begin_idx is class 1 while
+ * c <= action_dim, class 2 behind it; everything else 0. */
+int vla_token_row_class(void* stream, const long long* labels, unsigned char* row_class, int B, int L, int shift, long long begin_idx,
+                        int action_dim);
 
 /* ---------------------------------------------------------------- host-glue replacements
  * The reference's training step strings its ops together with dozens of small ATen index / cast / copy kernels

@@ -932,30 +932,79 @@ extern "C" int vla_embed_grad(void* stream, const void* dx, const long long* ids
 // prismatic/models/vlms/prismatic.py:469-481): logits are bf16, upcast to fp32, shifted by one position, mean over the labels
 // != -100.  One workgroup per logits row: row_loss = logsumexp(logits[row]) - logits[row, label]; loss_sum += row_loss,
 // count += 1 (two f32 atomics per valid row); the caller divides.  labels = the SHIFTED targets, one per row (-100: ignore).
-__global__ __launch_bounds__(256) void token_ce_kernel(const bf16_t* __restrict__ logits, long long ldl, const long long* __restrict__ labels,
-                                                       int V, float* __restrict__ out2) {
-  const long long row = blockIdx.x;
-  const long long lab = labels[row];
-  if (lab < 0 || lab >= V) return;                 // IGNORE_INDEX (-100)
-  const bf16_t* x = logits + row * ldl;
-  __shared__ float red[8];
+//
+// The row arithmetic is stated once (token_ce_row) for this kernel and for token_ce_metrics_kernel below.  ARGMAX = true makes
+// the max pass also carry each thread's (value, lowest index) pair and leaves the row's argmax in `best`: torch.argmax's rule
+// on the CPU - the lowest index among equal values, a NaN greater than everything, the first NaN wins.
+
+// Does the pair (bv, bi) come before (av, ai) in that order?
+__device__ __forceinline__ bool argmax_before(float bv, int bi, float av, int ai) {
+  const bool an = av != av, bn = bv != bv;
+  return an ? (bn && bi < ai) : (bn || bv > av || (bv == av && bi < ai));
+}
+// A thread meets its columns in ascending order: a strictly greater value (or the first NaN) replaces the pair.
+__device__ __forceinline__ void argmax_take(float v, int i, float& bv, int& bi) {
+  if (v > bv || (v != v && bv == bv)) { bv = v; bi = i; }
+}
+
+// Row maximum (as every thread's return value; fmaxf: NaNs are skipped, as before) through red[0..3]; ARGMAX: the row's argmax in
+// `best` (every thread) through red[4..7] / redi[0..3].  One read of the row.
+template <bool ARGMAX>
+__device__ __forceinline__ float token_row_max(const bf16_t* __restrict__ x, int V, float* red, int* redi, int& best) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   float m = -3.0e38f;
+  float bv = -__builtin_inff();                    // (a thread without a column keeps (-inf, tid * 8 >= V): it loses every tie)
+  int bi = tid * 8;
   for (int c = tid * 8; c < V; c += 256 * 8) {
     if (c + 8 <= V) {
       const uint4 v = *reinterpret_cast<const uint4*>(x + c);
       const unsigned u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) m = fmaxf(m, fmaxf(bf_lo(u[k]), bf_hi(u[k])));
+      if constexpr (ARGMAX) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          argmax_take(bf_lo(u[k]), c + 2 * k, bv, bi);
+          argmax_take(bf_hi(u[k]), c + 2 * k + 1, bv, bi);
+        }
+      }
     } else {
       for (int k = c; k < V; ++k) m = fmaxf(m, bf2f(x[k]));
+      if constexpr (ARGMAX)
+        for (int k = c; k < V; ++k) argmax_take(bf2f(x[k]), k, bv, bi);
     }
   }
   m = wave_max(m);
-  if (lane == 0) red[w] = m;
+  if constexpr (ARGMAX) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {               // the order is total: every lane of the butterfly ends on the same pair
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (argmax_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+  }
+  if (lane == 0) {
+    red[w] = m;
+    if constexpr (ARGMAX) { red[4 + w] = bv; redi[w] = bi; }
+  }
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  if constexpr (ARGMAX) {
+    bv = red[4]; bi = redi[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+      if (argmax_before(red[4 + k], redi[k], bv, bi)) { bv = red[4 + k]; bi = redi[k]; }
+    best = bi;
+  }
   __syncthreads();
+  return m;
+}
+
+// Loss term of one valid row, logsumexp(float(x)) - x[lab]: meaningful in thread 0.  red: 8 floats of LDS (redi: 4 ints, ARGMAX only).
+template <bool ARGMAX>
+__device__ __forceinline__ float token_ce_row(const bf16_t* __restrict__ x, int V, long long lab, float* red, int* redi, int& best) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float m = token_row_max<ARGMAX>(x, V, red, redi, best);
   float s = 0.f;
   for (int c = tid * 8; c < V; c += 256 * 8) {
     if (c + 8 <= V) {
@@ -970,9 +1019,21 @@ __global__ __launch_bounds__(256) void token_ce_kernel(const bf16_t* __restrict_
   s = wave_sum(s);
   if (lane == 0) red[w] = s;
   __syncthreads();
-  if (tid == 0) {
-    const float lse = m + __logf(red[0] + red[1] + red[2] + red[3]);
-    atomicAdd(out2, lse - bf2f(x[lab]));
+  if (tid != 0) return 0.f;
+  const float lse = m + __logf(red[0] + red[1] + red[2] + red[3]);
+  return lse - bf2f(x[lab]);
+}
+
+__global__ __launch_bounds__(256) void token_ce_kernel(const bf16_t* __restrict__ logits, long long ldl, const long long* __restrict__ labels,
+                                                       int V, float* __restrict__ out2) {
+  const long long row = blockIdx.x;
+  const long long lab = labels[row];
+  if (lab < 0 || lab >= V) return;                 // IGNORE_INDEX (-100)
+  __shared__ float red[8];
+  int best;
+  const float term = token_ce_row<false>(logits + row * ldl, V, lab, red, nullptr, best);
+  if (threadIdx.x == 0) {
+    atomicAdd(out2, term);
     atomicAdd(out2 + 1, 1.0f);
   }
 }
@@ -984,6 +1045,109 @@ extern "C" int vla_token_ce(void* stream, const void* logits, long long ld_logit
   hipLaunchKernelGGL(token_ce_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, ld_logits, shifted_labels, V,
                      loss_sum_and_count);
   VLA_CHECK_LAUNCH("token_ce");
+  return VLA_OK;
+}
+
+
+// ---------------------------------------------------------------- token-CE training metrics (base_strategy.py:316-356)
+// The same loss, plus what the reference's trainer reads off `logits[:, num_patches:-1].argmax(dim=2)` after every micro-step:
+// token accuracy and the L1 distance of the decoded bin centres under the current-action (class 1) and next-actions (class 2)
+// masks (training/train_utils.py:44-58).  The argmax rides the max pass of an action row (token_ce_row<true>); rows of class 0
+// run token_ce_row<false>, exactly what token_ce_kernel runs.  Thread 0 decodes the predicted id and the label the way
+// ActionTokenizer.decode_token_ids_to_actions does (vla/action_tokenizer.py:76-95), d = clip(tokenizer_len - id - 1, 0,
+// n_bins - 2): the bin centres are equally spaced, so |centre[dp] - centre[dt]| = |dp - dt| * spacing and the sum stays an
+// integer.  counters u64 [2][3] = per class (rows, correct rows, sum |dp - dt|): integer atomics, the same bits run after run.
+// An action row whose label is no valid column (a label >= V: vocabularies smaller than the tokenizer) adds nothing to the loss,
+// like every ignored row, but is still an action row of the metrics: one max / argmax pass, no exp pass.
+__global__ __launch_bounds__(256) void token_ce_metrics_kernel(const bf16_t* __restrict__ logits, long long ldl,
+                                                               const long long* __restrict__ labels,
+                                                               const unsigned char* __restrict__ row_class, int V, float* __restrict__ out2,
+                                                               unsigned long long* __restrict__ counters, int* __restrict__ pred_ids,
+                                                               long long tokenizer_len, int n_bins) {
+  const long long row = blockIdx.x;
+  const long long lab = labels[row];
+  const int cls = row_class[row];
+  const bool valid = lab >= 0 && lab < V, action = cls == 1 || cls == 2;
+  if (!action && pred_ids && threadIdx.x == 0) pred_ids[row] = -1;
+  if (!valid && !action) return;
+  const bf16_t* x = logits + row * ldl;
+  __shared__ float red[8];
+  __shared__ int redi[4];
+  int best = 0;
+  float term = 0.f;
+  if (!valid) token_row_max<true>(x, V, red, redi, best);
+  else if (action) term = token_ce_row<true>(x, V, lab, red, redi, best);
+  else term = token_ce_row<false>(x, V, lab, red, redi, best);
+  if (threadIdx.x != 0) return;
+  if (valid) {
+    atomicAdd(out2, term);
+    atomicAdd(out2 + 1, 1.0f);
+  }
+  if (action) {
+    const long long top = n_bins - 2;
+    const long long dp = min(max(tokenizer_len - best - 1, 0ll), top), dt = min(max(tokenizer_len - lab - 1, 0ll), top);
+    unsigned long long* c = counters + (cls - 1) * 3;
+    atomicAdd(c, 1ull);
+    if (best == lab) atomicAdd(c + 1, 1ull);
+    atomicAdd(c + 2, (unsigned long long)(dp > dt ? dp - dt : dt - dp));
+    if (pred_ids) pred_ids[row] = best;
+  }
+}
+
+extern "C" int vla_token_ce_metrics(void* stream, const void* logits, long long ld_logits, const long long* shifted_labels,
+                                    const unsigned char* row_class, int rows, int V, float* loss_sum_and_count,
+                                    unsigned long long* counters, int* pred_ids, long long tokenizer_len, int n_bins) {
+  VLA_REQUIRE(logits && shifted_labels && row_class && loss_sum_and_count && counters && rows > 0 && V > 0 && ld_logits % 8 == 0 &&
+                  ld_logits >= V && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)counters & 7) == 0 && n_bins >= 2 && tokenizer_len > 0,
+              "token_ce_metrics: bad args (row stride % 8 and >= V, 16-B aligned logits, 8-B aligned counters, n_bins >= 2)");
+  hipLaunchKernelGGL(token_ce_metrics_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, ld_logits,
+                     shifted_labels, row_class, V, loss_sum_and_count, counters, pred_ids, tokenizer_len, n_bins);
+  VLA_CHECK_LAUNCH("token_ce_metrics");
+  return VLA_OK;
+}
+
+// The four numbers of the reference's metrics.commit (base_strategy.py:350-356) from the six counters: out4 = (action_accuracy,
+// l1_loss, next_actions_accuracy, next_actions_l1_loss) = per class (correct / rows, sum * spacing / rows); a class without rows
+// gives NaN, as the reference's 0 / 0 and its l1_loss of two empty tensors do.
+__global__ void token_metrics_finish_kernel(const unsigned long long* __restrict__ counters, double spacing, float* __restrict__ out4) {
+  const int k = threadIdx.x;                         // 0, 1: the class
+  if (k >= 2) return;
+  const double n = (double)counters[3 * k];
+  out4[2 * k] = (float)((double)counters[3 * k + 1] / n);
+  out4[2 * k + 1] = (float)((double)counters[3 * k + 2] * spacing / n);
+}
+
+extern "C" int vla_token_metrics_finish(void* stream, const unsigned long long* counters, double spacing, float* out4) {
+  VLA_REQUIRE(counters && out4 && ((uintptr_t)counters & 7) == 0, "token_metrics_finish: bad args");
+  hipLaunchKernelGGL(token_metrics_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counters, spacing, out4);
+  VLA_CHECK_LAUNCH("token_metrics_finish");
+  return VLA_OK;
+}
+
+// Row classes of the two masks (train_utils.py:8-41) on labels[:, shift:]: c = cumsum(label != -100) along the row; an id above
+// begin_idx (ACTION_TOKEN_BEGIN_IDX) is a current-action row (1) while c <= action_dim and a next-actions row (2) behind it;
+// every other position 0.  One wave per sequence, as action_mask_kernel.
+__global__ void token_row_class_kernel(const long long* __restrict__ labels, unsigned char* __restrict__ cls, int L, int shift,
+                                       long long begin_idx, int action_dim) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long long* row = labels + (long long)b * L + shift;
+  const int n = L - shift;
+  int base = 0;
+  for (int j0 = 0; j0 < n; j0 += 64) {
+    const int j = j0 + lane;
+    const bool nz = j < n && row[j] != -100;
+    const unsigned long long bal = __ballot(nz);
+    const int c = base + __popcll(bal & ((1ull << lane) - 1ull)) + (nz ? 1 : 0);
+    if (j < n) cls[(long long)b * n + j] = (nz && row[j] > begin_idx) ? (c <= action_dim ? 1 : 2) : 0;
+    base += __popcll(bal);
+  }
+}
+
+extern "C" int vla_token_row_class(void* stream, const long long* labels, unsigned char* row_class, int B, int L, int shift,
+                                   long long begin_idx, int action_dim) {
+  VLA_REQUIRE(labels && row_class && B > 0 && shift >= 0 && L > shift && action_dim > 0, "token_row_class: bad args");
+  hipLaunchKernelGGL(token_row_class_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, labels, row_class, L, shift, begin_idx, action_dim);
+  VLA_CHECK_LAUNCH("token_row_class");
   return VLA_OK;
 }
 

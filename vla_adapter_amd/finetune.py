@@ -573,11 +573,18 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
             flats = [eng.head.P.data] + ([trainer.P.data] if trainer is not None else [])
             ddp.assert_ranks_in_sync(flats, what=f"parameters after optimizer step {steps_done}")
         if boundary and (log_step % cfg.wandb_log_freq == 0 or last):          # the only host sync, every log_freq gradient steps
-            l = loss3.tolist()
+            ce = cfg.objective == "token_ce"
+            # token-CE: the four metrics of the reference's trainer (base_strategy.py:350-356; this rank's batch, as there) ride the
+            # loss's read-back - one copy, one sync
+            l = torch.cat([loss3, trainer.ce_metrics]).tolist() if ce else loss3.tolist()
+            l, tm = l[:3], l[3:]
             if not all(x == x for x in l):
                 raise FloatingPointError(f"non-finite loss at step {log_step}: {l} (a captured step replayed on a batch whose action "
                                          "block starts before the frozen live-row window poisons the loss: --conservative_rows true)")
             log.append(dict(step=log_step, loss_value=l[0], curr_action_l1_loss=l[1], next_actions_l1_loss=l[2], lr=lr))
+            if ce:      # (next_actions_l1_loss: the reference's name for the decoded next-actions L1 replaces the copy of the loss)
+                from .ops import TOKEN_METRIC_NAMES
+                log[-1].update(zip(TOKEN_METRIC_NAMES, tm))
             if rank == 0:
                 print(json.dumps(log[-1]), flush=True)
         if save:

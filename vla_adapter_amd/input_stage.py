@@ -132,6 +132,8 @@ class GPUInputStage:
         self.device, self.tokenizer_len, self.pad, self.max_len = device, tokenizer_len, pad_token_id, model_max_length
         self.lo, self.hi = float(min_action), float(max_action)
         self.bins = torch.from_numpy(np.linspace(min_action, max_action, n_bins)).to(device)       # f64, numpy's own edges
+        self.n_bins = n_bins
+        self.bin_centers = (self.bins[:-1] + self.bins[1:]) / 2.0                                    # f64 [n_bins - 1] (action_tokenizer.py:47)
         self.norm = [dict(dino=(IMAGENET_MEAN, IMAGENET_STD), siglip=(SIGLIP_MEAN, SIGLIP_STD))[b] for b in backbones]
         self.out_dtype = out_dtype
         self.image_size = image_size
@@ -166,6 +168,13 @@ class GPUInputStage:
     def tokenize_actions(self, actions: torch.Tensor) -> torch.Tensor:
         """[..., action_dim] f32 on the device -> int64 token ids (same shape)."""
         return ops.action_tokenize(actions.to(self.device, torch.float32).contiguous(), self.bins, self.tokenizer_len, self.lo, self.hi)
+
+    def decode_token_ids_to_actions(self, ids: torch.Tensor) -> torch.Tensor:
+        """ActionTokenizer.decode_token_ids_to_actions (action_tokenizer.py:76-95): int64 token ids (any shape) -> f64 bin centres
+        (same shape), centre[clip(tokenizer_len - id - 1, 0, n_bins - 2)].  The clip makes every id decodable; on ids that
+        tokenize_actions made it inverts the binning (the last bin edge shares the last interval)."""
+        d = (self.tokenizer_len - ids.to(self.bin_centers.device, torch.int64) - 1).clamp_(0, self.bin_centers.numel() - 1)
+        return self.bin_centers[d]
 
     def pixels(self, frames_u8, augment: Optional[ImageAugment] = None, center_crop: bool = False, return_aux: bool = False):
         """frames_u8: list over images per sample (primary first, then wrist ...) of uint8 [B, H, W, 3] tensors, or one uint8

@@ -123,6 +123,9 @@ _PROTOS = {
                            C.POINTER(C.c_float), C.c_ulonglong, _L, _L], _I),
     "vla_token_ce": ([_P, _P, _L, _P, _I, _I, _P], _I),
     "vla_token_ce_bwd": ([_P, _P, _L, _P, _I, _I, _P, _F, _P, _L], _I),
+    "vla_token_ce_metrics": ([_P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _L, _I], _I),
+    "vla_token_metrics_finish": ([_P, _P, _D, _P], _I),
+    "vla_token_row_class": ([_P, _P, _P, _I, _I, _I, _L, _I], _I),
     "vla_copy2d": ([_P, _P, _P, _L, _I, _L, _L, _I, _I, _I, _I, _L], _I),
     "vla_fill_zero": ([_P, _P, _L], _I),
     "vla_dropout_bf16": ([_P, _P, _P, _L, C.c_int, _L, _L, C.c_float, C.c_ulonglong, _P], _I),
@@ -155,7 +158,9 @@ def load():
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (args, res) in _PROTOS.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
+            raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")
         fn.argtypes, fn.restype = args, res
     lib.vla_last_error.argtypes, lib.vla_last_error.restype = [], C.c_char_p
     # the struct ABI: a library built from another header revision would read past (or short of) the descriptors passed to it

@@ -754,6 +754,56 @@ def token_ce(logits, tgt, out_f32):
     return out_f32
 
 
+TOKENIZER_LEN, N_BINS = 151643, 256          # GPUInputStage's defaults (Qwen2.5's tokenizer.vocab_size, ActionTokenizer's bins)
+TOKEN_METRIC_NAMES = ("action_accuracy", "l1_loss", "next_actions_accuracy", "next_actions_l1_loss")    # base_strategy.py:350-356
+
+
+def token_row_class(labels: torch.Tensor, shift: int = 1, tokenizer_len: int = TOKENIZER_LEN, n_bins: int = N_BINS,
+                    action_dim: Optional[int] = None, out: Optional[torch.Tensor] = None):
+    """-> uint8 [B, L - shift]: 1 where get_current_action_mask(labels[:, shift:]) holds, 2 where get_next_actions_mask does, else 0
+    (train_utils.py:8-41 with ACTION_TOKEN_BEGIN_IDX = tokenizer_len - (n_bins + 1), action_tokenizer.py:57)."""
+    from .constants import ACTION_DIM
+    assert labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 2
+    B, L = labels.shape
+    if out is None:
+        out = torch.empty(B, L - shift, device=labels.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == B * (L - shift)
+    N.check(_lib().vla_token_row_class(_st(), _p(labels), _p(out), B, L, shift, tokenizer_len - (n_bins + 1),
+                                       ACTION_DIM if action_dim is None else action_dim), "token_row_class")
+    return out
+
+
+def token_ce_metrics(logits, tgt, row_class, out_f32, counters_u64, pred_ids=None, tokenizer_len: int = TOKENIZER_LEN,
+                     n_bins: int = N_BINS):
+    """token_ce (out_f32 receives the same two sums) plus, for the rows of class 1 (current action) / 2 (next actions) of row_class
+    (uint8 [rows]), the argmax over the vocabulary and the decoded-bin statistics: counters_u64 (6 64-bit integers, zeroed by the
+    caller) += per class (rows, rows whose argmax is the target, sum of |bin(argmax) - bin(target)|).  pred_ids (int32 [rows],
+    optional): the argmax of every action row, -1 elsewhere.  logits [rows, V] bf16, any row stride that is a multiple of 8."""
+    _chk_bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows, V = logits.shape
+    assert tgt.dtype == torch.int64 and tgt.is_contiguous() and tgt.numel() == rows
+    assert row_class.dtype == torch.uint8 and row_class.is_contiguous() and row_class.numel() == rows
+    assert out_f32.dtype == torch.float32 and out_f32.numel() >= 2
+    assert counters_u64.dtype in (torch.int64, torch.uint64) and counters_u64.is_contiguous() and counters_u64.numel() == 6
+    assert pred_ids is None or (pred_ids.dtype == torch.int32 and pred_ids.is_contiguous() and pred_ids.numel() == rows)
+    N.check(_lib().vla_token_ce_metrics(_st(), _p(logits), logits.stride(0), _p(tgt), _p(row_class), rows, V, _p(out_f32),
+                                        _p(counters_u64), _p(pred_ids), tokenizer_len, n_bins), "token_ce_metrics")
+    return out_f32
+
+
+def token_metrics_finish(counters, n_bins: int = N_BINS, min_action: float = -1.0, max_action: float = 1.0, out=None) -> dict:
+    """The reference's four metric values from token_ce_metrics' counters, divided on the device (no sync): accuracy = correct /
+    rows, L1 = sum * spacing / rows with spacing = (max_action - min_action) / (n_bins - 1), the distance of neighbouring bin
+    centres.  -> {name: 0-dim f32 tensor} (views of one [4] buffer, `out` if given); a class without rows gives NaN."""
+    assert counters.dtype in (torch.int64, torch.uint64) and counters.is_contiguous() and counters.numel() == 6
+    if out is None:
+        out = torch.empty(4, device=counters.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 4
+    N.check(_lib().vla_token_metrics_finish(_st(), _p(counters), (max_action - min_action) / (n_bins - 1), _p(out)), "token_metrics_finish")
+    return {k: out[i] for i, k in enumerate(TOKEN_METRIC_NAMES)}
+
+
 def token_ce_bwd(logits, tgt, sums_f32, gscale: float, out):
     """d loss / d logits = gscale (softmax - onehot) / count (sums_f32 from token_ce); out may be logits itself (in place)."""
     V = logits.shape[-1]

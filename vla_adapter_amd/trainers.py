@@ -519,12 +519,21 @@ class BackboneTrainer(E.Linear):
                 e = lambda *sh, dt=BF16: torch.empty(*sh, device=self.dev, dtype=dt)
                 self.ce_h, self.ce_dh, self.ce_logits = e(B * Lm, D), e(B * Lm, D), e(B * Lm, V)
                 self.ce_out = torch.zeros(2, device=self.dev, dtype=torch.float32)
+                self.ce_cls = torch.empty(B, Lm, device=self.dev, dtype=torch.uint8)
+                self.ce_counters = torch.zeros(6, device=self.dev, dtype=torch.int64)       # (64-bit counters of vla_token_ce_metrics)
+                self.ce_metrics = torch.empty(4, device=self.dev, dtype=torch.float32)
                 self._ce_key = (B, S)
             ops.copy_rows3d(llm.HS[n][0, Np], self.ce_h, B, Lm, D, S * D, D, Lm * D, D)
             ops.gemm_nt(self.ce_h, llm.embed, out=self.ce_logits, split_k=0)
             tgt = self._ce_tgt = batch["labels"][:, 1:].contiguous().view(-1)
             ops.zero_(self.ce_out)
-            ops.token_ce(self.ce_logits, tgt, self.ce_out)
+            # the loss and, off the same vocabulary-wide pass, what the reference's trainer reads from the argmax of these logits
+            # (base_strategy.py:316-356): counters and the four divisions stay on the device, inside this segment
+            tlen, nb = self.ce_tokenizer
+            ops.token_row_class(batch["labels"].contiguous(), 1, tlen, nb, out=self.ce_cls)
+            ops.zero_(self.ce_counters)
+            ops.token_ce_metrics(self.ce_logits, tgt, self.ce_cls, self.ce_out, self.ce_counters, None, tlen, nb)
+            self.token_metrics = ops.token_metrics_finish(self.ce_counters, nb, out=self.ce_metrics)
             loss = self.ce_out[0:1] / self.ce_out[1:2]
             self._loss3 = torch.cat([loss, loss, loss])              # (same three-slot shape the L1 path logs)
             ops.token_ce_bwd(self.ce_logits, tgt, self.ce_out, gscale, out=self.ce_logits)
@@ -553,12 +562,17 @@ class BackboneTrainer(E.Linear):
             add("M", f_tail, [sg.signal for sg in segs if sg.stream == "G"], ("end", 0), self._ranges("embed") + self._ranges("tail"))
         return segs
 
-    def set_objective(self, objective: str):
+    def set_objective(self, objective: str, tokenizer_len: int = ops.TOKENIZER_LEN, n_bins: int = ops.N_BINS):
         """"l1" (default: action head + L1 regression, vla-scripts/finetune.py) or "token_ce" (the native VLM / VLA trainer's token
-        cross-entropy, base_strategy.py:257-417).  Before capture()."""
+        cross-entropy, base_strategy.py:257-417).  Before capture().  Under "token_ce" every step leaves ``token_metrics``: the
+        reference trainer's action_accuracy / l1_loss / next_actions_accuracy / next_actions_l1_loss (:316-356) of this rank's batch
+        as four device scalars; tokenizer_len / n_bins: the ActionTokenizer they decode with (action ids = the last n_bins ids
+        below tokenizer_len, action_tokenizer.py:57)."""
         assert objective in ("l1", "token_ce") and self._graphs is None
         self.objective = objective
         if objective == "token_ce":
+            self.ce_tokenizer = (int(tokenizer_len), int(n_bins))
+            self.token_metrics = None
             self.n_active = self.cfg.llm.n_layers                    # every layer and the final norm reach this loss
             V, D = self.llm.embed.shape
             self.lmT = torch.empty(D, V, device=self.dev, dtype=BF16)
