@@ -37,7 +37,8 @@ extern "C" {
  *   7  new entry points vla_augment_slab_floats, vla_augment_stats, vla_augment_apply (no layout change).
  *   8  vla_gemm_nt_plan and vla_gemm_tn_plan (kernel ids VLA_KERNEL_*) replace vla_gemm_uses_256; the latency hint is per thread.
  *      Added since without a version change (no signature or layout moved): vla_token_ce_metrics, vla_token_metrics_finish,
- *      vla_token_row_class.  A binder that calls them looks the symbols up first: a library built before them reports 8 too.
+ *      vla_token_row_class; vla_grad_sumsq_slots, vla_grad_sumsq, vla_grad_norm_finalise, vla_adamw_clipped_bf16 (--max_grad_norm).
+ *      A binder that calls them looks the symbols up first: a library built before them reports 8 too.
  * A binder checks vla_version() AND vla_desc_size() against its own struct definitions before the first call. */
 #define VLA_ABI_VERSION 8
 int vla_version(void);
@@ -474,6 +475,26 @@ int vla_l1_loss(void* stream, const void* pred, const void* target, float* loss3
  * foreach implementation does (finetune.py:910, 1079).  g may be f32 (g_f32=1: rounded to bf16 first). */
 int vla_adamw_bf16(void* stream, void* p, const void* g, void* m, void* v, long long n, double lr, double beta1,
                    double beta2, double eps, double wd, int step, int g_f32, float gscale);
+
+/* Global gradient-norm clipping, torch.nn.utils.clip_grad_norm_(parameters, max_norm) (prismatic/training/strategies/ddp.py:127-128),
+ * without a host sync: partial sums of squares per slice of a flat gradient buffer, one finalise, AdamW with the coefficient read
+ * from device memory.
+ * vla_grad_sumsq_slots: host arithmetic (no GPU needed): the number of fp32 partials vla_grad_sumsq writes for a slice of n elements -
+ *   a function of n alone (one per 16384 elements), so a slot layout fixed once holds on every device and stream schedule.
+ * vla_grad_sumsq: slots[0 .. vla_grad_sumsq_slots(n)) = fixed-order fp32 partial sums of x^2 over g[0 .. n), where x is the value
+ *   vla_adamw_bf16 consumes for the same (g_f32, gscale): bf16(g * gscale) for f32 gradients, bf16(bf16 g * gscale) for bf16 gradients
+ *   with gscale != 1, the bf16 gradient itself otherwise.  g: any element-aligned address (16-B loads on the aligned body).  No atomics:
+ *   the same input gives the same bits.  Nothing outside g[0 .. n) is read, no slot beyond the count is written.
+ * vla_grad_norm_finalise: one workgroup adds n_slots partials in a fixed order in fp64; out2[0] = total_norm = (float)sqrt(sum),
+ *   out2[1] = min(1, max_norm / (total_norm + 1e-6f)) in fp32 with torch's operation order (reciprocal, then the product; a NaN norm
+ *   gives a NaN coefficient as with error_if_nonfinite=False).  max_norm > 0; +inf clips nothing and still reports the norm.
+ * vla_adamw_clipped_bf16: vla_adamw_bf16 with every gradient scaled once more, gr = bf16(gr * *coef) behind the gscale rounding (the
+ *   bf16 grad.mul_(clip_coef) of clip_grad_norm_); coef: device pointer, normally out2 + 1.  *coef == 1 is bit-identical to vla_adamw_bf16. */
+long long vla_grad_sumsq_slots(long long n);
+int vla_grad_sumsq(void* stream, const void* g, long long n, int g_f32, float gscale, float* slots);
+int vla_grad_norm_finalise(void* stream, const float* slots, long long n_slots, float max_norm, float* out2);
+int vla_adamw_clipped_bf16(void* stream, void* p, const void* g, void* m, void* v, long long n, double lr, double beta1,
+                           double beta2, double eps, double wd, int step, int g_f32, float gscale, const float* coef);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 // HBM-bound glue kernels of the fine-tune hot path (gfx950): im2col, action masks, embedding splice, gathers,
 // RoPE (both conventions), SwiGLU backward, transposes, casts, L1 loss, AdamW.  All bf16 traffic is 16 B per lane.
 #include "gemm_epilogue.h"
+#include <type_traits>
 
 namespace {
 
@@ -346,23 +347,8 @@ __global__ __launch_bounds__(256) void l1_loss_kernel(const bf16_t* __restrict__
 }
 
 // ---------------------------------------------------------------- AdamW, bf16 state, torch op-by-op rounding
-__global__ void adamw_kernel(bf16_t* __restrict__ p, const void* __restrict__ g, bf16_t* __restrict__ m, bf16_t* __restrict__ v,
-                             long long n, float decay, float omb1, float beta2, float omb2, float bc2_sqrt, float eps,
-                             float neg_step, int g_f32, float gscale) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    float gr = g_f32 ? rbf(((const float*)g)[i] * gscale) : bf2f(((const bf16_t*)g)[i]);
-    if (!g_f32 && gscale != 1.f) gr = rbf(gr * gscale);
-    float pf = rbf(bf2f(p[i]) * decay);                          // param.mul_(1 - lr*wd)
-    const float m0 = bf2f(m[i]);
-    const float mf = rbf(__builtin_fmaf(omb1, gr - m0, m0));     // exp_avg.lerp_(grad, 1-beta1)
-    const float vf = rbf(__builtin_fmaf(omb2 * gr, gr, rbf(bf2f(v[i]) * beta2)));  // mul_(beta2).addcmul_(g,g,1-beta2)
-    const float den = rbf(rbf(rbf(sqrtf(vf)) / bc2_sqrt) + eps); // (sqrt / bias_correction2_sqrt).add_(eps)
-    pf = rbf(__builtin_fmaf(neg_step, mf / den, pf));            // addcdiv_(exp_avg, denom, -lr/bc1)
-    p[i] = f2bf(pf); m[i] = f2bf(mf); v[i] = f2bf(vf);
-  }
-}
-
-// 8 parameters per thread, 16-B accesses (the scalar kernel above stays for tails and unaligned slices): same arithmetic
+// One parameter: param.mul_(1 - lr*wd); exp_avg.lerp_(grad, 1-beta1); exp_avg_sq.mul_(beta2).addcmul_(g,g,1-beta2);
+// (sqrt / bias_correction2_sqrt).add_(eps); addcdiv_(exp_avg, denom, -lr/bc1) - a bf16 rounding after each.
 __device__ __forceinline__ void adamw_one(float& pf, float gr, float& mf, float& vf, float decay, float omb1, float beta2, float omb2,
                                           float bc2_sqrt, float eps, float neg_step) {
   pf = rbf(pf * decay);
@@ -371,29 +357,57 @@ __device__ __forceinline__ void adamw_one(float& pf, float gr, float& mf, float&
   const float den = rbf(rbf(rbf(sqrtf(vf)) / bc2_sqrt) + eps);
   pf = rbf(__builtin_fmaf(neg_step, mf / den, pf));
 }
+// The gradient value AdamW consumes - and the global norm squares: the averaged bf16 gradient torch would see (an f32 gradient
+// is scaled, then rounded; a bf16 one is rounded again only when a scale applies).
+template <bool F32>
+__device__ __forceinline__ float adamw_grad(float g, float gscale) {
+  if (F32) return rbf(g * gscale);
+  return gscale != 1.f ? rbf(g * gscale) : g;
+}
+// 8 consecutive gradients behind a 16-B aligned address (index i counts groups of 8) -> the values AdamW consumes
+__device__ __forceinline__ void adamw_grad8(const void* __restrict__ g, long long i, int g_f32, float gscale, float (&gr)[8]) {
+  if (g_f32) {
+    const float4 g0 = ((const float4*)g)[2 * i], g1 = ((const float4*)g)[2 * i + 1];
+    const float t[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) gr[k] = adamw_grad<true>(t[k], gscale);
+  } else {
+    unpack8(((const uint4*)g)[i], gr);
+    if (gscale != 1.f) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) gr[k] = rbf(gr[k] * gscale);
+    }
+  }
+}
+// CLIP: gr = rbf(gr * *coef) behind the gscale rounding - the bf16 grad.mul_(clip_coef) of torch's clip_grad_norm_; the
+// coefficient is read from device memory (vla_grad_norm_finalise wrote it), and 1.0 leaves every gradient as it is.
+template <bool CLIP>
+__global__ void adamw_kernel(bf16_t* __restrict__ p, const void* __restrict__ g, bf16_t* __restrict__ m, bf16_t* __restrict__ v,
+                             long long n, float decay, float omb1, float beta2, float omb2, float bc2_sqrt, float eps,
+                             float neg_step, int g_f32, float gscale, const float* __restrict__ coef) {
+  const float c = CLIP ? *coef : 1.f;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    float gr = g_f32 ? adamw_grad<true>(((const float*)g)[i], gscale) : adamw_grad<false>(bf2f(((const bf16_t*)g)[i]), gscale);
+    if (CLIP) gr = rbf(gr * c);
+    float pf = bf2f(p[i]), mf = bf2f(m[i]), vf = bf2f(v[i]);
+    adamw_one(pf, gr, mf, vf, decay, omb1, beta2, omb2, bc2_sqrt, eps, neg_step);
+    p[i] = f2bf(pf); m[i] = f2bf(mf); v[i] = f2bf(vf);
+  }
+}
+
+// 8 parameters per thread, 16-B accesses (the scalar kernel above stays for tails and unaligned slices): same arithmetic
+template <bool CLIP>
 __global__ void adamw_vec8_kernel(uint4* __restrict__ p, const void* __restrict__ g, uint4* __restrict__ m, uint4* __restrict__ v,
                                   long long n8, float decay, float omb1, float beta2, float omb2, float bc2_sqrt, float eps,
-                                  float neg_step, int g_f32, float gscale) {
+                                  float neg_step, int g_f32, float gscale, const float* __restrict__ coef) {
+  const float c = CLIP ? *coef : 1.f;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
     const uint4 pv = p[i], mv = m[i], vv = v[i];
     float gr[8];
-    if (g_f32) {
-      const float4 g0 = ((const float4*)g)[2 * i], g1 = ((const float4*)g)[2 * i + 1];
-      const float t[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+    adamw_grad8(g, i, g_f32, gscale, gr);
+    if (CLIP) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) gr[k] = rbf(t[k] * gscale);
-    } else {
-      const uint4 gv = ((const uint4*)g)[i];
-      const unsigned t[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        gr[2 * k] = bf_lo(t[k]);
-        gr[2 * k + 1] = bf_hi(t[k]);
-      }
-      if (gscale != 1.f) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) gr[k] = rbf(gr[k] * gscale);
-      }
+      for (int k = 0; k < 8; ++k) gr[k] = rbf(gr[k] * c);
     }
     const unsigned pw[4] = {pv.x, pv.y, pv.z, pv.w}, mw[4] = {mv.x, mv.y, mv.z, mv.w}, vw[4] = {vv.x, vv.y, vv.z, vv.w};
     unsigned po[4], mo[4], vo[4];
@@ -409,6 +423,77 @@ __global__ void adamw_vec8_kernel(uint4* __restrict__ p, const void* __restrict_
     p[i] = uint4{po[0], po[1], po[2], po[3]};
     m[i] = uint4{mo[0], mo[1], mo[2], mo[3]};
     v[i] = uint4{vo[0], vo[1], vo[2], vo[3]};
+  }
+}
+
+// ---------------------------------------------------------------- global gradient norm (torch.nn.utils.clip_grad_norm_)
+// Sum of squares of a slice of a flat gradient buffer, of the values AdamW consumes (adamw_grad).  Workgroup b owns elements
+// [b, b + 1) * GRAD_SSQ_CHUNK of the slice and writes ONE fp32 partial to slots[b]: the slot count depends on n alone, every
+// lane adds its values in a fixed order (16-B groups of the aligned body in ascending order, then at most one element of the
+// unaligned head and one of the tail), the 64 lanes of a wave and the four waves combine in a fixed order, and no atomic is
+// involved - the same gradients give the same bits on every stream schedule.  Nothing outside the slice is read.
+constexpr int GRAD_SSQ_ITERS = 8;
+constexpr long long GRAD_SSQ_CHUNK = 256LL * 8 * GRAD_SSQ_ITERS;
+template <bool F32>
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const void* __restrict__ g, long long n, float gscale, float* __restrict__ slots) {
+  typedef typename std::conditional<F32, float, bf16_t>::type T;
+  __shared__ float red[4];
+  const long long c0 = (long long)blockIdx.x * GRAD_SSQ_CHUNK;
+  const int cnt = (int)min(GRAD_SSQ_CHUNK, n - c0), tid = threadIdx.x;
+  const T* base = (const T*)g + c0;
+  const int head = min(cnt, (int)(((16 - ((uintptr_t)base & 15)) & 15) / sizeof(T)));   // elements in front of the first 16-B boundary
+  const int nv = (cnt - head) / 8, tail0 = head + nv * 8;
+  const T* body = base + head;
+  float acc = 0.f, gr[8];
+  if (nv == 256 * GRAD_SSQ_ITERS) {            // a whole aligned chunk: every load in flight before the first add (same order of adds)
+    float x[GRAD_SSQ_ITERS][8];
+#pragma unroll
+    for (int it = 0; it < GRAD_SSQ_ITERS; ++it) adamw_grad8(body, it * 256 + tid, F32, gscale, x[it]);
+#pragma unroll
+    for (int it = 0; it < GRAD_SSQ_ITERS; ++it)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc = __builtin_fmaf(x[it][k], x[it][k], acc);
+  } else {
+    for (int j = tid; j < nv; j += 256) {
+      adamw_grad8(body, j, F32, gscale, gr);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc = __builtin_fmaf(gr[k], gr[k], acc);
+    }
+  }
+  if (tid < head) {
+    const float x = adamw_grad<F32>(F32 ? ((const float*)base)[tid] : bf2f(((const bf16_t*)base)[tid]), gscale);
+    acc = __builtin_fmaf(x, x, acc);
+  }
+  if (tid < cnt - tail0) {
+    const float x = adamw_grad<F32>(F32 ? ((const float*)base)[tail0 + tid] : bf2f(((const bf16_t*)base)[tail0 + tid]), gscale);
+    acc = __builtin_fmaf(x, x, acc);
+  }
+  acc = wave_sum(acc);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) slots[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// One workgroup: the partials in a fixed order in fp64 -> out[0] = total_norm, out[1] = the clip coefficient, formed in fp32
+// the way clip_grad_norm_ forms it on an fp32 norm: max_norm / (total_norm + 1e-6) is Tensor.__rtruediv__, reciprocal() * max_norm,
+// then clamp(max=1.0), which lets a NaN through (error_if_nonfinite=False).
+__global__ __launch_bounds__(256) void grad_norm_finalise_kernel(const float* __restrict__ slots, long long n_slots, float max_norm,
+                                                                 float* __restrict__ out) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (long long i = tid; i < n_slots; i += 256) s += (double)slots[i];
+  red[tid] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const float total = (float)sqrt(red[0]);
+    const float c = (1.f / (total + 1e-6f)) * max_norm;
+    out[0] = total;
+    out[1] = c > 1.f ? 1.f : c;
   }
 }
 
@@ -602,8 +687,8 @@ extern "C" int vla_l1_loss(void* stream, const void* pred, const void* target, f
   return VLA_OK;
 }
 
-extern "C" int vla_adamw_bf16(void* stream, void* p, const void* g, void* m, void* v, long long n, double lr, double beta1,
-                              double beta2, double eps, double wd, int step, int g_f32, float gscale) {
+static int adamw_launch(void* stream, void* p, const void* g, void* m, void* v, long long n, double lr, double beta1, double beta2,
+                        double eps, double wd, int step, int g_f32, float gscale, const float* coef) {
   VLA_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adamw: bad args");
   // scalars are formed in double and narrowed once, exactly as torch narrows its Python-double hyper-parameters
   const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
@@ -614,13 +699,46 @@ extern "C" int vla_adamw_bf16(void* stream, void* p, const void* g, void* m, voi
   const bool aligned = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
   const long long n8 = aligned ? n / 8 : 0, done = n8 * 8;
   if (n8 > 0)
-    hipLaunchKernelGGL(adamw_vec8_kernel, GRID1D(n8, 256), dim3(256), 0, (hipStream_t)stream, (uint4*)p, g, (uint4*)m, (uint4*)v, n8,
-                       decay, omb1, (float)beta2, omb2, (float)sqrt(bc2), (float)eps, neg_step, g_f32, gs);
+    hipLaunchKernelGGL(coef ? adamw_vec8_kernel<true> : adamw_vec8_kernel<false>, GRID1D(n8, 256), dim3(256), 0, (hipStream_t)stream,
+                       (uint4*)p, g, (uint4*)m, (uint4*)v, n8, decay, omb1, (float)beta2, omb2, (float)sqrt(bc2), (float)eps, neg_step,
+                       g_f32, gs, coef);
   if (done < n)          // tail (< 8 elements) or an unaligned slice: scalar kernel
-    hipLaunchKernelGGL(adamw_kernel, GRID1D(n - done, 256), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p + done,
-                       g_f32 ? (const void*)((const float*)g + done) : (const void*)((const bf16_t*)g + done), (bf16_t*)m + done,
-                       (bf16_t*)v + done, n - done, decay, omb1, (float)beta2, omb2, (float)sqrt(bc2), (float)eps, neg_step, g_f32, gs);
+    hipLaunchKernelGGL(coef ? adamw_kernel<true> : adamw_kernel<false>, GRID1D(n - done, 256), dim3(256), 0, (hipStream_t)stream,
+                       (bf16_t*)p + done, g_f32 ? (const void*)((const float*)g + done) : (const void*)((const bf16_t*)g + done),
+                       (bf16_t*)m + done, (bf16_t*)v + done, n - done, decay, omb1, (float)beta2, omb2, (float)sqrt(bc2), (float)eps,
+                       neg_step, g_f32, gs, coef);
   VLA_CHECK_LAUNCH("adamw");
+  return VLA_OK;
+}
+
+extern "C" int vla_adamw_bf16(void* stream, void* p, const void* g, void* m, void* v, long long n, double lr, double beta1,
+                              double beta2, double eps, double wd, int step, int g_f32, float gscale) {
+  return adamw_launch(stream, p, g, m, v, n, lr, beta1, beta2, eps, wd, step, g_f32, gscale, nullptr);
+}
+
+extern "C" int vla_adamw_clipped_bf16(void* stream, void* p, const void* g, void* m, void* v, long long n, double lr, double beta1,
+                                      double beta2, double eps, double wd, int step, int g_f32, float gscale, const float* coef) {
+  VLA_REQUIRE(coef, "adamw_clipped: null coefficient");
+  return adamw_launch(stream, p, g, m, v, n, lr, beta1, beta2, eps, wd, step, g_f32, gscale, coef);
+}
+
+extern "C" long long vla_grad_sumsq_slots(long long n) { return n > 0 ? (n + GRAD_SSQ_CHUNK - 1) / GRAD_SSQ_CHUNK : 0; }
+
+extern "C" int vla_grad_sumsq(void* stream, const void* g, long long n, int g_f32, float gscale, float* slots) {
+  VLA_REQUIRE(g && slots && n > 0, "grad_sumsq: bad args");
+  VLA_REQUIRE(((uintptr_t)g & (g_f32 ? 3 : 1)) == 0 && ((uintptr_t)slots & 3) == 0, "grad_sumsq: misaligned pointer");
+  const long long nb = vla_grad_sumsq_slots(n);
+  VLA_REQUIRE(nb <= 0x7fffffffLL, "grad_sumsq: slice too long");
+  const float gs = gscale == 0.f ? 1.f : gscale;
+  hipLaunchKernelGGL(g_f32 ? grad_sumsq_kernel<true> : grad_sumsq_kernel<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, g, n, gs, slots);
+  VLA_CHECK_LAUNCH("grad_sumsq");
+  return VLA_OK;
+}
+
+extern "C" int vla_grad_norm_finalise(void* stream, const float* slots, long long n_slots, float max_norm, float* out2) {
+  VLA_REQUIRE(slots && out2 && n_slots > 0 && max_norm > 0.f, "grad_norm_finalise: bad args");
+  hipLaunchKernelGGL(grad_norm_finalise_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, slots, n_slots, max_norm, out2);
+  VLA_CHECK_LAUNCH("grad_norm_finalise");
   return VLA_OK;
 }
 

@@ -1045,6 +1045,7 @@ class VLAEngine:
         self._row0 = None          # frozen by capture(); None = derive from every batch (one host sync)
         self.reducer = None        # ddp.FlatGradReducer when world_size > 1
         self._accum = schedule.GradAccumulator(copy_flat, ops.add_)      # gradient accumulation (set_grad_accumulation)
+        self._clip: Optional[schedule.GradClip] = None      # global gradient-norm clipping (set_max_grad_norm)
         self.executed_steps = 0    # forward+backward passes enqueued so far (eager, pipelined or replayed): profile bookkeeping
         # LLM layers above the head's last block (Qwen2.5-1.5B: 28 layers, 24 blocks - action_heads.py:117-118 reads hidden_states[1..24])
         # never reach the loss or the predicted actions: the training step and predict() run the first n_act layers only, as the
@@ -1080,6 +1081,39 @@ class VLAEngine:
     @property
     def ga(self) -> int:
         return self._accum.ga
+
+    def set_max_grad_norm(self, max_norm: Optional[float]):
+        """torch.nn.utils.clip_grad_norm_(trainable parameters, max_norm) in front of every optimizer step (the reference's native
+        trainer: base_strategy.py:389, ddp.py:127-128; its L1 fine-tune script does not clip); None: off, inf: take the norm, clip
+        nothing.  The norm is that of head.P.grad - action head, proprio projector, action queries - as AdamW consumes it
+        (averaged over the ranks, bf16), and it stays on the device with the coefficient (``grad_norm``)."""
+        max_norm = schedule.check_max_grad_norm(max_norm)
+        self.flush()                                 # (a pending update belongs to the setting it ran under)
+        self._clip = None if max_norm is None else schedule.GradClip(max_norm, [self.head.P.grad])
+        if self._clip is not None:                   # slots and the two events of flush() reserved here: no step allocates
+            self._clip.begin(self._clip_ranges())
+            self._clip_events = (torch.cuda.Event(), torch.cuda.Event())
+
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return None if self._clip is None else self._clip.max_norm
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """Device scalar (f32): the global gradient norm of the last applied optimizer step, before clipping; None without
+        set_max_grad_norm().  Reading its value is the only host sync clipping can cause."""
+        return None if self._clip is None else self._clip.total_norm
+
+    @property
+    def clip_coef(self) -> Optional[torch.Tensor]:
+        """Device f32 [1]: min(1, max_grad_norm / (grad_norm + 1e-6)) of the last applied optimizer step."""
+        return None if self._clip is None else self._clip.coef
+
+    def _clip_ranges(self):
+        """The two ranges of head.P.grad that become final apart (head + proprio projector | action queries): one slot layout for
+        the eager and the captured update, so both give the same norm bit for bit."""
+        g, aq_off = self.head.P.grad, self.head.P.offsets["action_queries"][0]
+        return [(g, 0, aq_off), (g, aq_off, self.head.P.numel)]
 
     def forward(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None, for_training: bool = False):
         """VLM forward + action head (finetune.py:336-411) -> predicted actions [B, chunk, 7]."""
@@ -1310,7 +1344,14 @@ class VLAEngine:
         if self.reducer is not None:
             self.reducer.wait()
             gscale = self.reducer.grad_scale       # DDP averages: sum-all-reduce then 1/N, folded into AdamW
-        ops.adamw_(P.data, P.grad, P.m, P.v, self.step_count, lr, beta1, beta2, eps, wd, gscale=gscale)
+        if self._clip is not None:
+            self._clip.begin(self._clip_ranges())
+            for r in self._clip_ranges():
+                self._clip.sumsq(*r, gscale)
+            self._clip.finalise()
+            ops.adamw_clipped_(P.data, P.grad, P.m, P.v, self._clip.coef, self.step_count, lr, beta1, beta2, eps, wd, gscale=gscale)
+        else:
+            ops.adamw_(P.data, P.grad, P.m, P.v, self.step_count, lr, beta1, beta2, eps, wd, gscale=gscale)
         self.head.dirty = True
 
     def train_step(self, batch, lr: float, noise=None):
@@ -1540,11 +1581,32 @@ class VLAEngine:
             gscale = self.reducer.grad_scale
         if self.ga > 1:                                # accumulated gradient was assembled on the current stream
             self.side.wait_event(self._h_end)
+        clip = self._clip
+        if clip is not None:
+            # clipped: each stream takes the sum of squares of its own range where that range is final; the current stream adds the
+            # two (it waits for the head stream's pass: the one new edge), and each stream runs its AdamW behind the coefficient
+            r_head, r_aq = self._clip_ranges()
+            head_summed, finalised = self._clip_events
+            clip.begin([r_head, r_aq])
+            with torch.cuda.stream(self.side):
+                clip.sumsq(*r_head, gscale)
+                head_summed.record(self.side)
+            clip.sumsq(*r_aq, gscale)
+            cur.wait_event(head_summed)
+            clip.finalise()
+            finalised.record(cur)
+            self.side.wait_event(finalised)
+
+        def adam(sl):
+            if clip is None:
+                ops.adamw_(P.data[sl], P.grad[sl], P.m[sl], P.v[sl], self.step_count, lr, gscale=gscale)
+            else:
+                ops.adamw_clipped_(P.data[sl], P.grad[sl], P.m[sl], P.v[sl], clip.coef, self.step_count, lr, gscale=gscale)
         with torch.cuda.stream(self.side):
-            ops.adamw_(P.data[:aq_off], P.grad[:aq_off], P.m[:aq_off], P.v[:aq_off], self.step_count, lr, gscale=gscale)
+            adam(slice(None, aq_off))
             side_done = torch.cuda.Event()
             side_done.record()
-        ops.adamw_(P.data[aq_off:], P.grad[aq_off:], P.m[aq_off:], P.v[aq_off:], self.step_count, lr, gscale=gscale)
+        adam(slice(aq_off, None))
         if join:
             cur.wait_event(side_done)
         self.head.dirty = True

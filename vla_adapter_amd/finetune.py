@@ -97,6 +97,9 @@ class FinetuneConfig:
                                           # (every rank talks to every peer directly: all 7 xGMI links instead of a ring)
     sync_check_freq: int = 0              # > 0: every that many optimizer steps the ranks compare a checksum of their parameters (one 8-byte
                                           # all-reduce) and the run stops on a mismatch; 0 = off
+    max_grad_norm: Optional[float] = None   # clip the global gradient norm in front of every optimizer step (torch's clip_grad_norm_, on the
+                                          # device): the reference's native trainer uses 1.0 (prismatic/conf/vla.py:96), its L1 fine-tune script
+                                          # does not clip - default off; inf: log grad_norm, clip nothing
     backbone: Optional[str] = None        # model geometry: a name of engine.NAMED_CONFIGS ("config2", "dinosiglip-0_5b", "config5",
                                           # "tiny", "tiny_fused") - default: inferred from the --vlm_path state dict, else "config2"
     # fmt: on
@@ -112,7 +115,7 @@ def parse_args(argv=None) -> FinetuneConfig:
         elif t is type(Path(".")):
             ap.add_argument(f"--{f.name}", type=Path, default=default)
         else:
-            ap.add_argument(f"--{f.name}", type=(int if f.name in ("resume_step",) else t), default=default)
+            ap.add_argument(f"--{f.name}", type=(int if f.name in ("resume_step",) else float if f.name in ("max_grad_norm",) else t), default=default)
     ns = ap.parse_args(argv)
     cfg = FinetuneConfig(**vars(ns))
     import sys
@@ -157,6 +160,8 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         raise NotImplementedError("--lora_dropout > 0 together with --fp8_base_weights: the dropped inputs are bf16 (use one or the other)")
     if cfg.fp8_base_weights and not cfg.use_lora:
         raise NotImplementedError("--fp8_base_weights needs --use_lora True (frozen base weights); the adapter-only forward has engine.enable_fp8_frozen()")
+    if cfg.max_grad_norm is not None and not float(cfg.max_grad_norm) > 0.0:      # (NaN fails the comparison too)
+        raise ValueError(f"--max_grad_norm must be > 0 (inf: log the norm, clip nothing), got {cfg.max_grad_norm}")
     if cfg.ddp_algo not in ("allreduce", "rs_ag"):
         raise ValueError("--ddp_algo is allreduce or rs_ag")
     if cfg.objective not in ("l1", "token_ce"):
@@ -525,6 +530,9 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
     (trainer or eng).set_grad_accumulation(cfg.grad_accumulation_steps)
     if cfg.objective != "l1":
         trainer.set_objective(cfg.objective)
+    clip = cfg.max_grad_norm is not None
+    if clip:
+        (trainer or eng).set_max_grad_norm(cfg.max_grad_norm)
     stream = batch_stream(cfg, mcfg, dev, rank, batches, explicit)
     pad_id = min(S.PAD_ID, mcfg.llm.vocab - 1)
     cur = next(stream)
@@ -576,8 +584,12 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
             ce = cfg.objective == "token_ce"
             # token-CE: the four metrics of the reference's trainer (base_strategy.py:350-356; this rank's batch, as there) ride the
             # loss's read-back - one copy, one sync
-            l = torch.cat([loss3, trainer.ce_metrics]).tolist() if ce else loss3.tolist()
-            l, tm = l[:3], l[3:]
+            parts = [loss3] + ([trainer.ce_metrics] if ce else [])
+            if clip:    # the norm of this step's update rides the same read-back (the captured adapter step leaves its update pending: apply it)
+                eng.flush()
+                parts.append((trainer or eng).grad_norm.view(1))
+            l = (torch.cat(parts) if len(parts) > 1 else loss3).tolist()
+            l, tm, gn = l[:3], l[3:7] if ce else [], l[-1]
             if not all(x == x for x in l):
                 raise FloatingPointError(f"non-finite loss at step {log_step}: {l} (a captured step replayed on a batch whose action "
                                          "block starts before the frozen live-row window poisons the loss: --conservative_rows true)")
@@ -585,6 +597,8 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
             if ce:      # (next_actions_l1_loss: the reference's name for the decoded next-actions L1 replaces the copy of the loss)
                 from .ops import TOKEN_METRIC_NAMES
                 log[-1].update(zip(TOKEN_METRIC_NAMES, tm))
+            if clip:
+                log[-1]["grad_norm"] = gn
             if rank == 0:
                 print(json.dumps(log[-1]), flush=True)
         if save:

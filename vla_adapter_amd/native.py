@@ -140,6 +140,10 @@ _PROTOS = {
     "vla_head_attn_bwd": ([_P, C.POINTER(HeadAttnDesc)], _I),
     "vla_l1_loss": ([_P, _P, _P, _P, _P, _I, _I, _I, _F], _I),
     "vla_adamw_bf16": ([_P, _P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _I, _I, _F], _I),
+    "vla_adamw_clipped_bf16": ([_P, _P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _I, _I, _F, _P], _I),
+    "vla_grad_sumsq_slots": ([_L], _L),
+    "vla_grad_sumsq": ([_P, _P, _L, _I, _F, _P], _I),
+    "vla_grad_norm_finalise": ([_P, _P, _L, _F, _P], _I),
 }
 # symbols include/vla_native.h declares (checked by tests/test_abi.py without touching a GPU)
 ABI_SYMBOLS = sorted(list(_PROTOS) + ["vla_last_error"])

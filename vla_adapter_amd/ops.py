@@ -679,6 +679,39 @@ def adamw_(p, g, m, v, step: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, w
                                   int(g.dtype == torch.float32), gscale), "adamw")
 
 
+# ---- global gradient-norm clipping (torch.nn.utils.clip_grad_norm_) without a host sync -----------------------------------
+def grad_sumsq_slots(n: int) -> int:
+    """fp32 partials grad_sumsq_ writes for n elements: host arithmetic, a function of n alone (callable without a GPU)."""
+    return int(_lib().vla_grad_sumsq_slots(int(n)))
+
+
+def grad_sumsq_(g, slots, gscale: float = 1.0) -> int:
+    """slots[:grad_sumsq_slots(n)] <- fixed-order partial sums of squares of the gradients adamw_ would consume from ``g`` (a
+    contiguous bf16 / f32 slice at any element offset) under the same ``gscale``.  Returns the slot count."""
+    assert g.dtype in (BF16, torch.float32) and g.is_contiguous() and slots.dtype == torch.float32 and slots.is_contiguous()
+    k = grad_sumsq_slots(g.numel())
+    assert 0 < k <= slots.numel(), "grad_sumsq_: slot buffer too short"
+    N.check(_lib().vla_grad_sumsq(_st(), _p(g), g.numel(), int(g.dtype == torch.float32), gscale, _p(slots)), "grad_sumsq")
+    return k
+
+
+def grad_norm_finalise_(slots, max_norm: float, out):
+    """out[0] = total_norm, out[1] = min(1, max_norm / (total_norm + 1e-6)) from every partial in ``slots`` (f32, device)."""
+    assert slots.dtype == torch.float32 and slots.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= 2
+    N.check(_lib().vla_grad_norm_finalise(_st(), _p(slots), slots.numel(), float(max_norm), _p(out)), "grad_norm_finalise")
+    return out
+
+
+def adamw_clipped_(p, g, m, v, coef, step: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, gscale: float = 1.0):
+    """adamw_ with the gradients scaled by the device scalar ``coef`` (f32 [1], grad_norm_finalise_'s out[1:2]) after the gscale rounding."""
+    assert p.dtype == BF16 and m.dtype == BF16 and v.dtype == BF16 and g.dtype in (BF16, torch.float32)
+    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
+    assert p.numel() == g.numel() == m.numel() == v.numel()
+    assert coef.dtype == torch.float32 and coef.numel() == 1 and coef.device == p.device
+    N.check(_lib().vla_adamw_clipped_bf16(_st(), _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, wd, step,
+                                          int(g.dtype == torch.float32), gscale, _p(coef)), "adamw_clipped")
+
+
 # ---- host-glue replacements: no ATen kernel between the hand-written ones on the training step ---------------------------
 _DT = {BF16: 0, torch.float32: 1}
 

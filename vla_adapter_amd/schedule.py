@@ -118,6 +118,78 @@ class GradAccumulator:
         return True
 
 
+def check_max_grad_norm(max_norm) -> Optional[float]:
+    """None (no clipping) or a float > 0; +inf is allowed: it clips nothing and the norm is still taken."""
+    if max_norm is None:
+        return None
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:                           # (NaN fails the comparison too)
+        raise ValueError(f"max_grad_norm must be > 0 (inf: report the norm, clip nothing), got {max_norm}")
+    return max_norm
+
+
+class GradClip:
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) over ranges of flat gradient buffers, without a host sync
+    (prismatic/training/strategies/ddp.py:127-128; base_strategy.py:389).  Every range owns fp32 slots for the partial sums of
+    squares of its elements (ops.grad_sumsq_): the pass of a range can run as soon as that range is final, on any stream.
+    finalise() adds the slots in a fixed order and leaves ``out`` = (total_norm, clip coefficient) on the device, where
+    ops.adamw_clipped_ reads the coefficient.  The slot layout depends on the set of ranges alone - buffers in the order given,
+    ranges by first element, slots per range by its length - so the norm has the same bits whichever stream schedule ran the
+    passes, eager or captured, and on every data-parallel rank."""
+
+    def __init__(self, max_norm: float, bufs):
+        self.max_norm = check_max_grad_norm(max_norm)
+        assert self.max_norm is not None
+        self.bufs = list(bufs)
+        self._buf_index = {id(b): i for i, b in enumerate(self.bufs)}
+        self.out = torch.zeros(2, device=self.bufs[0].device, dtype=torch.float32)
+        self._layouts, self._seen, self._slot_of, self._slots = {}, {}, None, None
+
+    def _index(self, buf) -> int:
+        return self._buf_index[id(buf)]
+
+    def begin(self, ranges, check=None) -> list:
+        """Choose the slot layout of ``ranges`` = [(buffer, first element, end element)] for the passes that follow -> the ranges
+        as sorted (buffer index, first, end), empty ones dropped.  A list of ranges seen before costs one dictionary lookup; a new
+        one builds its layout and allocates its slots, so an owner hands its lists over once where it is set up (set_max_grad_norm,
+        capture) and no step allocates.  check(sorted ranges) runs once per new list (the owner's coverage assertion)."""
+        from . import ops
+        seen = tuple((id(buf), lo, hi) for buf, lo, hi in ranges)
+        hit = self._seen.get(seen)
+        if hit is None:
+            key = tuple(sorted((self._index(buf), lo, hi) for buf, lo, hi in ranges if hi > lo))
+            if check is not None:
+                check(list(key))
+            lay = self._layouts.get(key)
+            if lay is None:
+                assert all(a[0] != b[0] or a[2] <= b[1] for a, b in zip(key, key[1:])), "gradient ranges overlap"
+                slot_of, n = {}, 0
+                for r in key:
+                    slot_of[r], n = n, n + ops.grad_sumsq_slots(r[2] - r[1])
+                lay = self._layouts[key] = (slot_of, torch.zeros(max(n, 1), device=self.out.device, dtype=torch.float32))
+            hit = self._seen[seen] = (key, lay)
+        key, (self._slot_of, self._slots) = hit
+        return list(key)
+
+    def sumsq(self, buf, lo: int, hi: int, gscale: float = 1.0):
+        """The pass over buf[lo:hi] into that range's slots, on the current stream (gscale: as AdamW will be given it)."""
+        from . import ops
+        if hi > lo:
+            ops.grad_sumsq_(buf[lo:hi], self._slots[self._slot_of[(self._index(buf), lo, hi)]:], gscale)
+
+    def finalise(self):
+        from . import ops
+        ops.grad_norm_finalise_(self._slots, self.max_norm, self.out)
+
+    @property
+    def total_norm(self) -> torch.Tensor:
+        return self.out[0]
+
+    @property
+    def coef(self) -> torch.Tensor:
+        return self.out[1:2]
+
+
 def captured_validation(model, batch, noise, make, replay):
     """val_step_graphed of an engine / trainer: on the first call two eager model.val_forward() (every buffer allocated and
     kernel attribute set outside the capture), then make() -> (graphs, segs), timed into model.val_capture_seconds and kept;

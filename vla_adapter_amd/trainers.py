@@ -162,6 +162,7 @@ class BackboneTrainer(E.Linear):
         self.exchange_layers, self.exchange_blocks = 4, 7
         self.n_active = min(cfg.llm.n_layers, cfg.num_blocks)      # LLM layers that reach the loss (see _segments)
         self._accum = schedule.GradAccumulator(E.copy_flat, ops.add_)      # gradient accumulation (set_grad_accumulation)
+        self._clip: Optional[schedule.GradClip] = None      # global gradient-norm clipping (set_max_grad_norm)
         self.objective = "l1"
         self.overlap_update = not os.environ.get("VLA_NO_UPDATE_OVERLAP")      # AdamW range by range under the backward (_run)
         # Streams of the step schedule (_segments): the caller's stream carries the dX chain, `gstream` everything that only feeds a
@@ -590,18 +591,22 @@ class BackboneTrainer(E.Linear):
     def _stream(self, name: str, main):
         return {"H": self.hstream, "G": self.gstream, "V": self.vstream}.get(name) or main
 
-    def _run(self, segs, graphs=None, exchange: bool = True, update=None):
+    def _run(self, segs, graphs=None, exchange: bool = True, update=None, norm: bool = False):
         """Enqueue the segments (schedule.run, eagerly or as replays of their captured graphs); a segment's finished gradient ranges
         go to the exchange behind the event recorded after it.  The caller's stream joins the others at the end.
         update=(lr, betas, eps, wd): AdamW runs RANGE BY RANGE on the gradient stream as soon as a range is final (and exchanged) -
         the backward reads only the W^T copies of a weight, never the parameter itself, so the 15 GB of optimiser traffic of a full
         fine-tune hides under the rest of the backward instead of trailing it (torch's optimizer.step() after loss.backward(),
-        vla-scripts/finetune.py:1078-1082: same arithmetic, every use of a parameter in the NEXT forward sees the updated value)."""
+        vla-scripts/finetune.py:1078-1082: same arithmetic, every use of a parameter in the NEXT forward sees the updated value).
+        norm: a clipped step (set_max_grad_norm) - no range can be updated before the global norm is known, so the sum-of-squares
+        pass of each finished range takes the update's place there and _clipped_update() follows the last segment."""
         def after(k, seg, e):
             if seg.ranges and exchange:
                 self._exchange(seg.ranges, after_event=e)
             if seg.ranges and update is not None:
                 self._update_ranges(seg.ranges, e, update, k if graphs is not None else None)
+            if seg.ranges and norm:
+                self._sumsq_ranges(seg.ranges, e)
         schedule.run(segs, self._stream, graphs, fork=[st for st in (self.hstream, self.gstream, self.vstream) if st is not None],
                      join=True, call=self._call, after=after, timeline=self._timeline)   # (tools/trainer_timeline.py)
 
@@ -643,6 +648,21 @@ class BackboneTrainer(E.Linear):
                     fn()
             elif seg_index in self._rgraphs:
                 self._rgraphs[seg_index].replay()
+
+    def _sumsq_ranges(self, ranges, final_event):
+        """The global norm's share of the ranges a segment has finished: their sum-of-squares passes on the gradient stream, behind
+        the ranges' collectives, into the slots GradClip keeps for them - underneath the rest of the backward, where the update
+        of an unclipped step runs."""
+        red = self.eng.reducer
+        st = self.gstream or torch.cuda.current_stream()
+        with torch.cuda.stream(st):
+            st.wait_event(final_event)
+            gscale = 1.0
+            if red is not None:
+                st.wait_stream(red.stream)
+                gscale = red.grad_scale
+            for buf, lo, hi in ranges:
+                self._clip.sumsq(buf, lo, hi, gscale)
 
     # ---- derived operands, piecewise
     def _refresh_pieces(self):
@@ -771,6 +791,63 @@ class BackboneTrainer(E.Linear):
     def ga(self) -> int:
         return self._accum.ga
 
+    def set_max_grad_norm(self, max_norm: Optional[float]):
+        """torch.nn.utils.clip_grad_norm_(vlm.parameters(), max_norm) in front of every optimizer step, as the reference's native
+        trainer does it (base_strategy.py:389, ddp.py:127-128; every shipped configuration: 1.0); None: off.  inf clips nothing
+        and still takes the norm.  The norm covers exactly what AdamW updates (_adam_ranges() and the head's buffer), of the
+        averaged bf16 gradients, and stays on the device with the coefficient (``grad_norm``).  Before capture()."""
+        assert self._graphs is None, "set_max_grad_norm() before capture()"
+        max_norm = schedule.check_max_grad_norm(max_norm)
+        self._clip = None if max_norm is None else schedule.GradClip(max_norm, [self.P.grad, self.head.P.grad])
+        if self._clip is not None:                   # (optimizer_step()'s slots now; the schedule's own in capture() / the first eager step)
+            self._clip_begin(self._update_buffers())
+
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return None if self._clip is None else self._clip.max_norm
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """Device scalar (f32): the global gradient norm of the last optimizer step, before clipping; None without
+        set_max_grad_norm().  Reading its value is the only host sync clipping can cause."""
+        return None if self._clip is None else self._clip.total_norm
+
+    @property
+    def clip_coef(self) -> Optional[torch.Tensor]:
+        """Device f32 [1]: min(1, max_grad_norm / (grad_norm + 1e-6)) of the last optimizer step."""
+        return None if self._clip is None else self._clip.coef
+
+    def _update_buffers(self):
+        """[(flat gradient buffer, first, end)] of everything an optimizer step moves: _adam_ranges() and the head's buffer."""
+        return [(self.P.grad, lo, hi) for lo, hi in self._adam_ranges()] + [(self.head.P.grad, 0, self.head.P.numel)]
+
+    def _clip_begin(self, ranges):
+        """Select the norm's slot layout over ``ranges``.  A list of ranges GradClip has not seen yet is laid out (slots allocated)
+        and must cover exactly the elements the optimizer step updates; one it has seen costs a lookup."""
+        def merged(rs):
+            out = []
+            for r in sorted(rs):
+                if out and out[-1][0] == r[0] and out[-1][2] == r[1]:
+                    out[-1] = (r[0], out[-1][1], r[2])
+                else:
+                    out.append(r)
+            return out
+
+        def check(got):
+            want = [(self._clip._index(buf), lo, hi) for buf, lo, hi in self._update_buffers() if hi > lo]
+            assert merged(got) == merged(want), f"gradient ranges of the schedule {merged(got)} are not the optimizer's {merged(want)}"
+        self._clip.begin(ranges, check)
+
+    def _clipped_update(self, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01):
+        """End of a clipped step, on the current stream behind every range's pass: the finalise, then AdamW over what
+        optimizer_step() covers with the coefficient read on the device."""
+        gscale = self._exchange_and_scale()
+        self._clip.finalise()
+        for buf, lo, hi in self._update_buffers():
+            P = self.P if buf is self.P.grad else self.head.P
+            ops.adamw_clipped_(P.data[lo:hi], P.grad[lo:hi], P.m[lo:hi], P.v[lo:hi], self._clip.coef, self.step_count, lr, beta1, beta2,
+                               eps, wd, gscale=gscale)
+
     def train_step(self, batch, lr: float, noise=None):
         """One micro-step, launched eagerly on the three streams (with a reducer and no accumulation: every gradient range goes
         to the exchange as soon as it is final); the optimizer steps on every ``ga``-th call."""
@@ -778,7 +855,15 @@ class BackboneTrainer(E.Linear):
 
     def _step(self, segs, graphs, lr: float):
         """train_step (graphs None: eager, derived operands rebuilt in line) or train_step_graphed (their graphs replayed)."""
-        if self.ga == 1 and self.overlap_update:
+        if self.ga == 1 and self._clip is not None:  # clipped: exchange and norm range by range, the update behind the last segment
+            self.step_count += 1
+            self._clip_begin(self._seg_ranges if graphs is not None else [r for sg in segs for r in (sg.ranges or [])])
+            self._run(segs, graphs, norm=True)
+            self._clipped_update(lr)
+            self.head.dirty = True
+            if graphs is None:
+                self.refresh()
+        elif self.ga == 1 and self.overlap_update:
             self.step_count += 1
             self._run(segs, graphs, update=(lr, 0.9, 0.999, 1e-8, 0.01))
             self._after_update(refresh=graphs is None)
@@ -809,9 +894,12 @@ class BackboneTrainer(E.Linear):
         self.head.dirty = True                       # the head's own W^T / padded-operand refresh becomes part of its graphs
         self._segs = self._segments(batch, noise, 1.0 / self.ga)
         self._graphs, caps, pools = self._capture(self._segs)
+        self._seg_ranges = [r for sg in self._segs for r in (sg.ranges or [])]
+        if self.ga == 1 and self._clip is not None:  # the norm's slots of the captured schedule: reserved and checked here, once
+            self._clip_begin(self._seg_ranges)
         # derived operands: per finished range a small graph behind that range's AdamW (overlapped update only), the rest at the step's end
         self._rgraphs, covered, rpool = {}, set(), torch.cuda.graph_pool_handle()
-        if self.ga == 1 and self.overlap_update and self._refresh_pieces():
+        if self.ga == 1 and self.overlap_update and self._clip is None and self._refresh_pieces():
             for k, (st, fn, _, _, ranges) in enumerate(self._segs):
                 if not ranges:
                     continue
@@ -898,6 +986,16 @@ class BackboneTrainer(E.Linear):
 
     def optimizer_step(self, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, refresh: bool = True):
         self.step_count += 1
+        if self._clip is not None:                    # (gradient accumulation: the norm of the folded, exchanged sums)
+            gscale = self._exchange_and_scale()
+            self._clip_begin(self._update_buffers())
+            for buf, lo, hi in self._update_buffers():
+                self._clip.sumsq(buf, lo, hi, gscale)
+            self._clipped_update(lr, beta1, beta2, eps, wd)
+            self.head.dirty = True
+            if refresh:
+                self.refresh()
+            return
         gscale = self._exchange_and_scale()
         P, HP = self.P, self.head.P
         for lo, hi in self._adam_ranges():            # (parameters of dead LLM layers: see _segments)
