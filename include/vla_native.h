@@ -37,7 +37,8 @@ extern "C" {
  *   7  new entry points vla_augment_slab_floats, vla_augment_stats, vla_augment_apply (no layout change).
  *   8  vla_gemm_nt_plan and vla_gemm_tn_plan (kernel ids VLA_KERNEL_*) replace vla_gemm_uses_256; the latency hint is per thread.
  *      Added since without a version change (no signature or layout moved): vla_token_ce_metrics, vla_token_metrics_finish,
- *      vla_token_row_class; vla_grad_sumsq_slots, vla_grad_sumsq, vla_grad_norm_finalise, vla_adamw_clipped_bf16 (--max_grad_norm).
+ *      vla_token_row_class; vla_grad_sumsq_slots, vla_grad_sumsq, vla_grad_norm_finalise, vla_adamw_clipped_bf16 (--max_grad_norm);
+ *      vla_normalize_bounds, vla_collate_tokens (the on-device collator).
  *      A binder that calls them looks the symbols up first: a library built before them reports 8 too.
  * A binder checks vla_version() AND vla_desc_size() against its own struct definitions before the first call. */
 #define VLA_ABI_VERSION 8
@@ -304,6 +305,25 @@ int vla_augment_apply(void* stream, const void* frames, float* params, const flo
  * digitize(clip(actions[i], lo, hi), bins) with numpy semantics (bins: device f64 [nbins], increasing). */
 int vla_action_tokenize(void* stream, const float* actions, const double* bins, long long* ids, long long n, int nbins,
                         float lo, float hi, long long tokenizer_len);
+/* normalize_action_and_proprio, BOUNDS / BOUNDS_Q99 (prismatic/vla/datasets/rlds/utils/data_utils.py:67-90) on x f32 [n / D, D] -> y f32:
+ * y = mask[d] ? clip(2 * (x - low[d]) / (high[d] - low[d] + 1e-8) - 1, -1, 1) : x, then y = zero_mask[d] ? 0 : y, in f32 with TF's
+ * association.  low / high f32 [D]: the caller resolves min / max (BOUNDS) or q01 / q99 (BOUNDS_Q99); mask, zero_mask u8 [D] or NULL
+ * (all ones / all zeros); zero_mask = the stats' min == max under both types.  y may be x. */
+int vla_normalize_bounds(void* stream, const float* x, float* y, long long n, int D, const float* low, const float* high,
+                         const unsigned char* mask, const unsigned char* zero_mask);
+/* RLDSBatchTransform.__call__ (use_minivlm, prismatic/vla/datasets/datasets.py:76-89, 124) + PaddedCollatorForActionPrediction's right
+ * padding (prismatic/util/data_utils.py:114-134) for a whole batch in one launch.  prompt_flat int64 [n_flat]: the samples' prompt ids
+ * back to back, still carrying the three trailing ids the reference deletes; prompt_off int32 [B + 1] (clamped into [0, n_flat]);
+ * actions f32 [B, n_act] normalised; bins f64 [nbins] as for vla_action_tokenize.  Row b of ids int64 [B, L] = prompt minus its last three
+ * ids (kept whole when shorter than three) | num_tokens (<= 256) action ids | pad_id, cut at L.  The action block = the first
+ * min(n_act, num_tokens) binned ids; if n_act < num_tokens every further slot k holds flat[r % n_act] with r drawn from the counter-based
+ * generator keyed by (seed, rank, step, b, k) (random.choices in the reference, whose stream is not reproduced).  labels int64 [B, L] = ids,
+ * ignore_index below row_len - (num_tokens + 1) (row_len untruncated) and on padding; attention_mask u8 [B, L] = ids != pad_id.  Every
+ * element of the three outputs is written. */
+int vla_collate_tokens(void* stream, const long long* prompt_flat, const int* prompt_off, long long n_flat, const float* actions,
+                       const double* bins, long long* ids, long long* labels, unsigned char* attention_mask, int B, int n_act, int L,
+                       int nbins, float lo, float hi, long long tokenizer_len, long long pad_id, long long ignore_index, int num_tokens,
+                       unsigned long long seed, long long rank, long long step);
 
 /* ---------------------------------------------------------------- glue */
 /* timm PatchEmbed conv PxP/P as im2col: pixels [B, Ctot, H, W] (f32 if px_f32 else bf16), channels c0..c0+2 ->

@@ -4,6 +4,8 @@
     torchrun --standalone --nnodes 1 --nproc-per-node K vla-scripts/finetune.py --batch_size 32 --max_steps 100 ...
 
 Every ``FinetuneConfig`` field of the reference (finetune.py:66-128) is accepted as ``--flag value``.
+Batches: ``--batch_file`` (collated), ``--frame_batch_file`` (collated, raw uint8 frames) or ``--raw_batch_file`` with
+``--dataset_statistics_file`` (raw transitions, normalised and collated on the device); one of the three at most.
 """
 import os
 import sys

@@ -35,13 +35,8 @@ struct AugArgs {
   float mean[3 * AUG_MAX_BB], std[3 * AUG_MAX_BB];
 };
 
-// splitmix64 finaliser, the scheme of the LoRA dropout mask (elementwise.hip drop_hash)
-__device__ __forceinline__ unsigned long long aug_mix(unsigned long long seed, unsigned long long idx) {
-  unsigned long long z = seed + idx * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// the scheme of the LoRA dropout mask (common.h splitmix64_key)
+__device__ __forceinline__ unsigned long long aug_mix(unsigned long long seed, unsigned long long idx) { return splitmix64_key(seed, idx); }
 
 // tf.random.uniform's affine map of a unit variate: (hi - lo) * u + lo
 __device__ __forceinline__ float aug_uniform(float lo, float hi, float u) { return (hi - lo) * u + lo; }

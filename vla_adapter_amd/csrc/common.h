@@ -81,6 +81,29 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
   return uint4{pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7])};
 }
 
+// splitmix64 finaliser of (seed + idx * golden ratio): the ONE counter-based generator of the device-side draws (LoRA dropout mask,
+// image augmentation, the collator's filler tokens).  Keys chain: mix(mix(seed, a), b) ...
+__device__ __forceinline__ unsigned long long splitmix64_key(unsigned long long seed, unsigned long long idx) {
+  unsigned long long z = seed + idx * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// ActionTokenizer.__call__ (action_tokenizer.py:60-74, use_minivlm branch) of one value: clip to [lo, hi], np.digitize against the
+// caller's bin edges (count of edges <= x, compared in f64 like numpy; bins increasing), token id = tokenizer_len - bin index.
+__device__ __forceinline__ long long action_token_id(float v, const double* __restrict__ bins, int nbins, float lo, float hi,
+                                                     long long tokenizer_len) {
+  const double x = (double)fminf(fmaxf(v, lo), hi);
+  int a = 0, b = nbins;                       // first edge index with bins[idx] > x  (== np.digitize(x, bins))
+  while (a < b) {
+    const int mid = (a + b) >> 1;
+    if (bins[mid] <= x) a = mid + 1;
+    else b = mid;
+  }
+  return tokenizer_len - a;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

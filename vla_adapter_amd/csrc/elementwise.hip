@@ -521,20 +521,12 @@ __global__ void image_normalize_kernel(const unsigned char* __restrict__ img, vo
   }
 }
 
-// ActionTokenizer.__call__ (action_tokenizer.py:60-74, use_minivlm branch): clip to [lo, hi], np.digitize against the
-// caller's bin edges (count of edges <= x, compared in f64 like numpy), token id = tokenizer_len - bin index.
+// ActionTokenizer.__call__ over a flat array: one value per thread (the arithmetic: common.h action_token_id).
 __global__ void action_tokenize_kernel(const float* __restrict__ act, const double* __restrict__ bins, long long* __restrict__ ids,
                                        long long n, int nbins, float lo, float hi, long long tokenizer_len) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double x = (double)fminf(fmaxf(act[i], lo), hi);
-  int a = 0, b = nbins;                       // first edge index with bins[idx] > x  (== np.digitize(x, bins), bins increasing)
-  while (a < b) {
-    const int mid = (a + b) >> 1;
-    if (bins[mid] <= x) a = mid + 1;
-    else b = mid;
-  }
-  ids[i] = tokenizer_len - a;
+  ids[i] = action_token_id(act[i], bins, nbins, lo, hi, tokenizer_len);
 }
 
 extern "C" int vla_im2col_patch(void* stream, const void* pixels, void* cols, int B, int Ctot, int c0, int H, int W, int P,
@@ -880,12 +872,7 @@ extern "C" int vla_fill_zero(void* stream, void* ptr, long long nbytes) {
 // constant with `step` read from DEVICE memory (a captured step draws fresh masks on every replay: vla_inc_i32 bumps it).  Forward and
 // backward regenerate the same mask from (seed, step) - nothing is stored.  Kept values are scaled by 1 / (1 - p) in fp32 and rounded to
 // bf16 once, as torch's dropout kernel does.  (torch's own Philox stream is not reproduced: parity with a peft run is statistical.)
-__device__ __forceinline__ unsigned long long drop_hash(unsigned long long seed, unsigned long long idx) {
-  unsigned long long z = seed + idx * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+__device__ __forceinline__ unsigned long long drop_hash(unsigned long long seed, unsigned long long idx) { return splitmix64_key(seed, idx); }
 
 template <bool ADD>
 __global__ void dropout_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long long rows, int cols, long long ldx, long long ldy,

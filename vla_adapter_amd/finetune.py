@@ -5,8 +5,9 @@ absent here: parsed with argparse from the dataclass fields), the per-step metri
 warm-up / MultiStepLR schedule (:903-921, 1061-1065) and the checkpoint file names (:527-572).  What is NOT here, on
 purpose: HF-hub / network loaders (:752-754), the RLDS/TensorFlow input pipeline (out of scope) -
 batches come from an iterable / ``--batch_file`` (a .pt dict or a directory of them: the collator's contract), from
-``--frame_batch_file`` (the same with raw uint8 frames, augmented on the device under ``--image_aug``) or
-``synthetic.make_batch``; weights are random-init unless ``--vlm_path`` / ``--resum_vla_path`` point at local state-dict
+``--frame_batch_file`` (the same with raw uint8 frames, augmented on the device under ``--image_aug``), from
+``--raw_batch_file`` (raw transitions: frames, prompt ids, un-normalised actions / proprio, collated on the device with the
+statistics of ``--dataset_statistics_file``) or ``synthetic.make_batch``; weights are random-init unless ``--vlm_path`` / ``--resum_vla_path`` point at local state-dict
 files.  ``--use_val_set`` runs the reference's validation pass (finetune.py:605-685, 1101-1117) on held-out batches of the same
 form (``--val_batch_file`` / ``finetune(val_batches=...)``; ``ValidationPass``); the RLDS val split itself is not read.  Every
 reference flag is either honoured or refused with an error (``check_supported``); none is silently dropped.
@@ -85,6 +86,9 @@ class FinetuneConfig:
                                           # augmented), one pass per validation sweep
     frame_batch_file: Optional[str] = None  # same, with raw frames: frames_u8 uint8 [B, n_img, H, W, 3] instead of pixel_values (the
                                           # input stage normalises them on the device, augmented under --image_aug)
+    raw_batch_file: Optional[str] = None  # raw transitions (a .pt dict or a directory of them): frames_u8, prompt_flat int64 [n], prompt_off int32
+                                          # [B + 1], actions_raw [B, chunk, action_dim], proprio_raw [B, Pd], optional dataset_name - normalised with
+                                          # --dataset_statistics_file and collated on the device (GPUInputStage.collate), L = --max_seq_len
     use_graph: bool = True                # replay the captured hipGraphs
     max_seq_len: int = 0                  # static token length every batch is right-padded to (0: length of the first batch)
     conservative_rows: bool = False       # captured live-row window starts at the first text row instead of the first batch's action block
@@ -194,9 +198,12 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         raise ValueError("grad_accumulation_steps must be >= 1")
     if cfg.resume and cfg.resume_step is None:
         raise ValueError("--resume needs --resume_step (finetune.py:1056 computes log_step = resume_step + gradient_step_idx)")
-    if cfg.batch_file and cfg.frame_batch_file:
-        raise ValueError("--batch_file and --frame_batch_file are two batch sources: pass one")
-    frames = bool(cfg.frame_batch_file) or frame_batches
+    sources = [n for n in ("batch_file", "frame_batch_file", "raw_batch_file") if getattr(cfg, n)]
+    if len(sources) > 1:
+        raise ValueError(" and ".join("--" + n for n in sources) + f" are {len(sources)} batch sources: pass one")
+    if cfg.raw_batch_file and not cfg.dataset_statistics_file:
+        raise ValueError("--raw_batch_file carries un-normalised actions / proprio: pass the statistics with --dataset_statistics_file")
+    frames = bool(cfg.frame_batch_file or cfg.raw_batch_file) or frame_batches
     if "image_aug" in explicit and not frames:
         raise NotImplementedError(IMAGE_AUG_REFUSAL)
     bad = [n for n in explicit if n in OUT_OF_PATH_FLAGS and not (validating and n in VAL_FLAGS)]
@@ -409,9 +416,25 @@ def _pad_to(batch: dict, L: int, pad_id: int) -> dict:
     return out
 
 
+RAW_BATCH_KEYS = ("frames_u8", "prompt_flat", "prompt_off", "actions_raw", "proprio_raw")
+
+
+def raw_batch_stats(norm_stats: dict, dataset_name: Optional[str] = None) -> dict:
+    """The dataset_statistics.json entry a raw batch is normalised with: the one its ``dataset_name`` names, else the file's only one."""
+    if dataset_name is None and len(norm_stats) == 1:
+        dataset_name = next(iter(norm_stats))
+    if dataset_name not in norm_stats:
+        raise KeyError(f"dataset statistics hold no entry {dataset_name!r} (the batch's dataset_name; without one the file must hold a "
+                       f"single entry): its keys are {sorted(norm_stats)}")
+    st = norm_stats[dataset_name]
+    if "action" not in st or "proprio" not in st:
+        raise KeyError(f"dataset statistics entry {dataset_name!r} needs 'action' and 'proprio', got {sorted(st)}")
+    return st
+
+
 def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, explicit=()):
-    """Endless iterator over collated batches: an explicit iterable, ``--batch_file`` / ``--frame_batch_file`` (one .pt dict, or
-    a directory of them, cycled in sorted order; every rank starts at its own offset - the reference's ranks draw independent
+    """Endless iterator over collated batches: an explicit iterable, ``--batch_file`` / ``--frame_batch_file`` / ``--raw_batch_file``
+    (one .pt dict, or a directory of them, cycled in sorted order; every rank starts at its own offset - the reference's ranks draw independent
     shuffles, finetune.py:988-994), or seeded synthetic batches (a new one every micro-step).
 
     A batch carrying ``frames_u8`` (uint8 [B, n_img, H, W, 3]) instead of ``pixel_values`` goes through the GPU input stage here:
@@ -419,13 +442,40 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
     (datasets.py:204-218, drawn per image from --seed, the rank and this rank's micro-step counter), else a plain normalise.  The
     normalisation per backbone follows the model config (input_stage.backbone_norms: DINOv2-like ViTs ImageNet, others SigLIP).
     Frames not at the model's image size go through the Pillow-exact bicubic resize of the processor first; the reference's RLDS
-    stage resizes with TF's lanczos3 there, which is not reproduced."""
+    stage resizes with TF's lanczos3 there, which is not reproduced.
+
+    A raw batch (``actions_raw`` ...: RAW_BATCH_KEYS) is collated on the device by ``GPUInputStage.collate``: actions and proprio
+    normalised with the statistics of ``--dataset_statistics_file`` (the entry named by the batch's ``dataset_name``, or the file's
+    only one), token length --max_seq_len (0: the batch's own), filler tokens and augmentation keyed by the same (seed, rank, step)."""
     from . import synthetic as S
     from .input_stage import GPUInputStage, ImageAugment, backbone_norms
-    stage, step = None, 0
+    stage, step, norm_stats = None, 0, None
+
+    def collate_raw(b):
+        nonlocal stage, step, norm_stats
+        missing = [k for k in RAW_BATCH_KEYS if k not in b]
+        if missing:
+            raise ValueError(f"raw batch lacks {missing}: it carries {RAW_BATCH_KEYS} and optionally dataset_name")
+        if norm_stats is None:
+            if not cfg.dataset_statistics_file:
+                raise ValueError("raw batches carry un-normalised actions / proprio: pass the statistics with --dataset_statistics_file")
+            norm_stats = json.load(open(cfg.dataset_statistics_file))
+        st = raw_batch_stats(norm_stats, b.get("dataset_name"))
+        if stage is None:
+            stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img)
+        aug = ImageAugment(seed=cfg.seed, rank=rank, step=step) if cfg.image_aug else None
+        L = cfg.max_seq_len or None
+        if L is None and b["prompt_off"].is_cuda:
+            raise ValueError("raw batches with prompt offsets on the device need --max_seq_len (the natural length would be read back)")
+        out = stage.collate(b["frames_u8"], (b["prompt_flat"], b["prompt_off"]), b["actions_raw"], b["proprio_raw"], action_stats=st["action"],
+                            proprio_stats=st["proprio"], L=L, seed=cfg.seed, rank=rank, step=step, augment=aug)
+        step += 1
+        return out
 
     def collate(b):
         nonlocal stage, step
+        if "actions_raw" in b:
+            return collate_raw(b)
         b = {k: v.to(dev) for k, v in b.items()}
         if "frames_u8" not in b:
             if "image_aug" in explicit:
@@ -449,8 +499,8 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
                 yield collate(b)
             if n == 0:
                 raise ValueError("empty batch iterable")
-    elif cfg.batch_file or cfg.frame_batch_file:
-        src = cfg.batch_file or cfg.frame_batch_file
+    elif cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file:
+        src = cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file
         files = sorted(str(p) for p in Path(src).glob("*.pt")) if os.path.isdir(src) else [src]
         if not files:
             raise FileNotFoundError(f"no .pt batch files under {src}")
@@ -459,6 +509,8 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
             b = torch.load(files[i], weights_only=True)
             if cfg.frame_batch_file and "frames_u8" not in b:
                 raise ValueError(f"{files[i]}: --frame_batch_file batches carry frames_u8 (uint8 [B, n_img, H, W, 3])")
+            if cfg.raw_batch_file and "actions_raw" not in b:
+                raise ValueError(f"{files[i]}: --raw_batch_file batches carry {RAW_BATCH_KEYS}")
             yield collate(b)
             i = (i + 1) % len(files)
     else:

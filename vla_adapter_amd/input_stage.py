@@ -14,7 +14,10 @@ the model consumes, following the reference's CPU pipeline step by step:
 
 The heavy parts (pixels, binning) run as HIP kernels on the device; the variable-length id bookkeeping is a few hundred
 integers per batch and stays on the host, using Python's ``random`` exactly like the reference so that a seeded run draws
-the same 8 filler tokens.
+the same 8 filler tokens.  That is ``build()``.  ``collate()`` produces the same batch without the host: the reference's
+``normalize_action_and_proprio`` (rlds/utils/data_utils.py:52-90) and the whole id / label / padding assembly run as two more
+kernels (csrc/collate.hip), nothing is read back, and the filler tokens come from the device's counter-based generator
+(DESIGN.md section 12).
 """
 from __future__ import annotations
 
@@ -125,6 +128,20 @@ def pil_bicubic_coeffs(in_size: int, out_size: int):
     return bounds, coefs
 
 
+NORMALIZATION_KINDS = ("bounds", "bounds_q99")     # NormalizationType.BOUNDS / BOUNDS_Q99 (rlds/utils/data_utils.py:44-49)
+
+
+def collate_layout(prompt_lens: Sequence[int], max_len: int, num_tokens: int = NUM_TOKENS) -> Tuple[List[int], int]:
+    """Host side of ``GPUInputStage.collate``, from the prompt lengths alone: the offset table [B + 1] of the concatenated prompts
+    and the batch's token length L = min(longest row, max_len), a row being its prompt minus the three trailing ids (kept whole
+    when shorter than three, datasets.py:76-79) plus the ``num_tokens`` action ids."""
+    off = [0]
+    for n in prompt_lens:
+        off.append(off[-1] + int(n))
+    rows = [(n - 3 if n >= 3 else n) + num_tokens for n in map(int, prompt_lens)]
+    return off, min(max(rows), max_len)
+
+
 class GPUInputStage:
     def __init__(self, device="cuda", tokenizer_len: int = 151643, n_bins: int = 256, min_action: float = -1.0, max_action: float = 1.0,
                  pad_token_id: int = 151643, model_max_length: int = 2048, backbones: Sequence[str] = ("siglip",),
@@ -138,6 +155,7 @@ class GPUInputStage:
         self.out_dtype = out_dtype
         self.image_size = image_size
         self._taps = {}
+        self._stats = {}
 
     def resize(self, frames_u8: torch.Tensor, out_h: int = 224, out_w: int = 224) -> torch.Tensor:
         """uint8 [B, H, W, 3] -> uint8 [B, out_h, out_w, 3], bit-identical to PIL.Image.resize((out_w, out_h), BICUBIC): horizontal
@@ -253,4 +271,66 @@ class GPUInputStage:
                      actions=actions.to(self.device))
         if proprio is not None:
             batch["proprio"] = proprio.to(self.device, torch.float32).reshape(B, -1)
+        return batch
+
+    def normalize(self, x: torch.Tensor, stats: dict, kind: str = "bounds_q99") -> torch.Tensor:
+        """normalize_action_and_proprio (rlds/utils/data_utils.py:52-90) on the device: raw actions / proprio [..., D] -> f32 of the
+        same shape.  ``stats``: one entry of dataset_statistics.json (e.g. norm_stats[name]["action"]) - q01 / q99 for "bounds_q99",
+        min / max for "bounds", optional mask; dimensions whose min == max become 0 under both kinds (:87-89; skipped when the entry
+        has no min / max).  The statistics are uploaded once per (stats object, kind)."""
+        if kind not in NORMALIZATION_KINDS:
+            raise NotImplementedError(f"normalisation type {kind!r}: only {NORMALIZATION_KINDS} are built (NORMAL, mean / std, is used by "
+                                      "no shipped configuration)")
+        key = (id(stats), kind)
+        if key not in self._stats:
+            lo_k, hi_k = ("min", "max") if kind == "bounds" else ("q01", "q99")
+            if lo_k not in stats or hi_k not in stats:
+                raise KeyError(f"normalisation type {kind!r} needs {lo_k!r} and {hi_k!r} in the statistics, got {sorted(stats)}")
+            f32 = lambda v: torch.as_tensor(np.asarray(v, dtype=np.float32)).to(self.device)
+            u8 = lambda v: torch.as_tensor(np.asarray(v, dtype=bool).astype(np.uint8)).to(self.device)
+            zero = None
+            if "min" in stats and "max" in stats:
+                zero = u8(np.asarray(stats["min"], dtype=np.float32) == np.asarray(stats["max"], dtype=np.float32))
+            mask = u8(stats["mask"]) if "mask" in stats else None
+            self._stats[key] = (stats, f32(stats[lo_k]), f32(stats[hi_k]), mask, zero)      # (stats itself: its id stays taken)
+        _, low, high, mask, zero = self._stats[key]
+        x = x.to(self.device, torch.float32).contiguous()
+        if x.shape[-1] != low.numel():
+            raise ValueError(f"last dimension {x.shape[-1]} does not match the statistics' {low.numel()}")
+        return ops.normalize_bounds(x, low, high, mask, zero)
+
+    def collate(self, frames_u8, prompt_ids, actions: torch.Tensor, proprio: Optional[torch.Tensor] = None, *, action_stats: Optional[dict] = None,
+                proprio_stats: Optional[dict] = None, L: Optional[int] = None, seed: int = 0, rank: int = 0, step: int = 0,
+                augment: Optional[ImageAugment] = None, center_crop: bool = False) -> Dict[str, torch.Tensor]:
+        """build() without the host: the same batch dict from kernels only (vla_normalize_bounds, vla_collate_tokens, pixels()).
+        prompt_ids: list of id lists, or (prompt_flat int64 [n], prompt_off int32 [B + 1]) tensors - with tensors on the device nothing
+        is copied, read back or looped over.  action_stats / proprio_stats: raw values are normalised first (normalize(), "bounds_q99")
+        and batch["actions"] holds the normalised window.  L: static token length (rows are padded or cut to it); default
+        min(longest row, model_max_length), from the prompt lengths on the host - device-resident offsets therefore need L.  The
+        filler ids of the action block are drawn on the device from (seed, rank, step, sample, slot), not from Python's random."""
+        B = actions.shape[0]
+        if isinstance(prompt_ids, (tuple, list)) and len(prompt_ids) == 2 and all(isinstance(t, torch.Tensor) for t in prompt_ids):
+            flat, off = prompt_ids
+            if L is None:
+                if off.is_cuda:
+                    raise ValueError("collate: prompt offsets on the device need an explicit L (the default would read them back)")
+                L = collate_layout(off.diff().tolist(), self.max_len)[1]
+        else:
+            lens = [len(r) for r in prompt_ids]
+            off_l, L_nat = collate_layout(lens, self.max_len)
+            L = L_nat if L is None else L
+            flat = torch.tensor([t for r in prompt_ids for t in r], dtype=torch.int64)
+            off = torch.tensor(off_l, dtype=torch.int32)
+        if off.numel() != B + 1:
+            raise ValueError(f"collate: {off.numel()} prompt offsets for {B} samples (expected B + 1)")
+        flat, off = flat.to(self.device, torch.int64).contiguous(), off.to(self.device, torch.int32).contiguous()
+        act = self.normalize(actions, action_stats) if action_stats is not None else actions.to(self.device)
+        ids, labels, am = ops.collate_tokens(flat, off, act.to(torch.float32).reshape(B, -1).contiguous(), self.bins, int(L),
+                                             tokenizer_len=self.tokenizer_len, lo=self.lo, hi=self.hi, pad_id=self.pad, ignore_index=IGNORE_INDEX,
+                                             num_tokens=NUM_TOKENS, seed=seed, rank=rank, step=step)
+        batch = dict(pixel_values=self.pixels(frames_u8, augment=augment, center_crop=center_crop), input_ids=ids, labels=labels,
+                     attention_mask=am.view(torch.bool), actions=act)
+        if proprio is not None:
+            pr = self.normalize(proprio, proprio_stats) if proprio_stats is not None else proprio.to(self.device, torch.float32)
+            batch["proprio"] = pr.reshape(B, -1)
         return batch

@@ -144,6 +144,8 @@ _PROTOS = {
     "vla_grad_sumsq_slots": ([_L], _L),
     "vla_grad_sumsq": ([_P, _P, _L, _I, _F, _P], _I),
     "vla_grad_norm_finalise": ([_P, _P, _L, _F, _P], _I),
+    "vla_normalize_bounds": ([_P, _P, _P, _L, _I, _P, _P, _P, _P], _I),
+    "vla_collate_tokens": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _L, _L, _L, _I, C.c_ulonglong, _L, _L], _I),
 }
 # symbols include/vla_native.h declares (checked by tests/test_abi.py without touching a GPU)
 ABI_SYMBOLS = sorted(list(_PROTOS) + ["vla_last_error"])

@@ -902,3 +902,36 @@ def action_tokenize(actions_f32: torch.Tensor, bins_f64: torch.Tensor, tokenizer
     N.check(_lib().vla_action_tokenize(_st(), _p(actions_f32), _p(bins_f64), _p(ids), actions_f32.numel(), bins_f64.numel(), lo, hi,
                                        tokenizer_len), "action_tokenize")
     return ids
+
+
+def normalize_bounds(x_f32: torch.Tensor, low: torch.Tensor, high: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                     zero_mask: Optional[torch.Tensor] = None):
+    """normalize_action_and_proprio's BOUNDS / BOUNDS_Q99 branch (data_utils.py:67-90) on x f32 [..., D]: clip(2 (x - low) / (high - low +
+    1e-8) - 1, -1, 1) where mask (u8 [D], None = everywhere), then 0 where zero_mask (u8 [D], None = nowhere).  low / high f32 [D]."""
+    D = x_f32.shape[-1]
+    assert x_f32.dtype == torch.float32 and x_f32.is_contiguous() and x_f32.numel() > 0
+    for t, dt in ((low, torch.float32), (high, torch.float32), (mask, torch.uint8), (zero_mask, torch.uint8)):
+        assert t is None or (t.dtype == dt and t.is_contiguous() and t.numel() == D and t.device == x_f32.device), "per-dimension statistics: [D] on x's device"
+    out = torch.empty_like(x_f32)
+    N.check(_lib().vla_normalize_bounds(_st(), _p(x_f32), _p(out), x_f32.numel(), D, _p(low), _p(high), _p(mask), _p(zero_mask)), "normalize_bounds")
+    return out
+
+
+def collate_tokens(prompt_flat: torch.Tensor, prompt_off: torch.Tensor, actions_f32: torch.Tensor, bins_f64: torch.Tensor, L: int, *,
+                   tokenizer_len: int, lo: float = -1.0, hi: float = 1.0, pad_id: int, ignore_index: int = -100, num_tokens: int = 64,
+                   seed: int = 0, rank: int = 0, step: int = 0):
+    """vla_collate_tokens: prompt_flat int64 [n] + prompt_off int32 [B + 1] + normalised actions f32 [B, n_act] -> (input_ids int64 [B, L],
+    labels int64 [B, L], attention_mask u8 [B, L]), one launch, nothing read back."""
+    B, n_act = actions_f32.shape
+    dev = actions_f32.device
+    assert actions_f32.dtype == torch.float32 and actions_f32.is_contiguous() and bins_f64.dtype == torch.float64 and bins_f64.is_contiguous()
+    assert prompt_flat.dtype == torch.int64 and prompt_flat.is_contiguous() and prompt_flat.dim() == 1
+    assert prompt_off.dtype == torch.int32 and prompt_off.is_contiguous() and tuple(prompt_off.shape) == (B + 1,)
+    assert prompt_flat.device == dev and prompt_off.device == dev and bins_f64.device == dev
+    assert L > 0
+    ids, labels = torch.empty(B, L, device=dev, dtype=torch.int64), torch.empty(B, L, device=dev, dtype=torch.int64)
+    am = torch.empty(B, L, device=dev, dtype=torch.uint8)
+    N.check(_lib().vla_collate_tokens(_st(), _p(prompt_flat) if prompt_flat.numel() else None, _p(prompt_off), prompt_flat.numel(), _p(actions_f32),
+                                      _p(bins_f64), _p(ids), _p(labels), _p(am), B, n_act, L, bins_f64.numel(), lo, hi, tokenizer_len, pad_id,
+                                      ignore_index, num_tokens, int(seed) & (2 ** 64 - 1), int(rank), int(step)), "collate_tokens")
+    return ids, labels, am
