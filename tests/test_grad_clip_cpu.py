@@ -87,3 +87,73 @@ def test_argument_validation_without_gpu(lib):
     assert lib.vla_grad_norm_finalise(None, 4096, 4, float("nan"), 4096) == -1
     assert lib.vla_adamw_clipped_bf16(None, 4096, 4096, 4096, 4096, 8, 1e-3, 0.9, 0.999, 1e-8, 0.01, 1, 0, 1.0, None) == -1
     assert b"coefficient" in lib.vla_last_error()
+
+
+def test_shared_step_controls_on_cpu_tensors():
+    """schedule.StepControls - the accumulation and clipping members VLAEngine and BackboneTrainer share - driven by a bare owner
+    with CPU gradient buffers, as far as it goes without the native library: ga reset and fold boundary, the handling of
+    None / inf / <= 0 / NaN by set_max_grad_norm, the properties reading None while clipping is off, the "before capture()"
+    assertion, and the owner's _set_clip hook seeing every new clip object and every drop."""
+    import torch
+    from vla_adapter_amd import schedule
+
+    class Owner(schedule.StepControls):
+        def __init__(self):
+            self._graphs, self.seen = None, []
+            self.bufs = [torch.zeros(8), torch.zeros(4)]
+            self._init_step_controls(lambda dst, src: dst.copy_(src), lambda dst, src: dst.add_(src))
+
+        def _grad_buffers(self):
+            return self.bufs
+
+        def _set_clip(self, clip):
+            self.seen.append(clip)
+            self._clip = clip
+
+    o = Owner()
+    assert o.ga == 1 and o._accum.fold() and o.max_grad_norm is None and o.grad_norm is None and o.clip_coef is None
+    # accumulation: three micro-steps, the buffers hold the sums on the boundary; a reset starts a new window
+    o.set_grad_accumulation(3)
+    assert o.ga == 3
+    boundary = []
+    for k in (1.0, 2.0, 4.0, 8.0, 16.0, 32.0):
+        for b in o.bufs:
+            b.fill_(k)
+        boundary.append(o._accum.fold())
+        if boundary[-1]:
+            assert all(bool((b == (7.0 if k == 4.0 else 56.0)).all()) for b in o.bufs), (k, o.bufs)
+    assert boundary == [False, False, True, False, False, True]
+    o._accum.fold()                                  # (one micro-step into a window ...)
+    o.set_grad_accumulation(2)                       # (... that the reset drops)
+    assert o.ga == 2 and [o._accum.fold(), o._accum.fold()] == [False, True]
+    o.set_grad_accumulation(1)
+    assert o.ga == 1 and o._accum.fold() and not o._accum._pairs
+    with pytest.raises(AssertionError):
+        o.set_grad_accumulation(0)
+    # clipping: a clip object over the owner's buffers per valid setting, dropped by None, bad values refused and nothing changed
+    o.set_max_grad_norm(1.0)
+    clip = o._clip
+    assert isinstance(clip, schedule.GradClip) and o.seen == [clip] and clip.bufs[0] is o.bufs[0] and clip.bufs[1] is o.bufs[1]
+    assert o.max_grad_norm == 1.0 and o.grad_norm.shape == () and o.clip_coef.shape == (1,)
+    assert o.grad_norm.dtype == o.clip_coef.dtype == torch.float32 and o.clip_coef.data_ptr() == clip.out[1:].data_ptr()
+    for bad in (0, 0.0, -1.0, float("nan"), float("-inf")):
+        with pytest.raises(ValueError, match="max_grad_norm"):
+            o.set_max_grad_norm(bad)
+    assert o._clip is clip and o.seen == [clip], "a refused value leaves the setting alone and never reaches the owner"
+    o.set_max_grad_norm(float("inf"))
+    assert math.isinf(o.max_grad_norm) and o._clip is not clip and o.grad_norm is not None
+    o.set_max_grad_norm(None)
+    assert o.seen[-1] is None and len(o.seen) == 3
+    assert o.max_grad_norm is None and o.grad_norm is None and o.clip_coef is None
+    o._graphs = [object()]                           # captured: the accumulation factor is baked into the loss kernel
+    with pytest.raises(AssertionError, match=r"before capture\(\)"):
+        o.set_grad_accumulation(2)
+
+
+def test_engine_and_trainer_keep_no_copy_of_the_step_controls():
+    """The six members live in schedule.StepControls alone; VLAEngine and BackboneTrainer inherit them."""
+    from vla_adapter_amd import engine, schedule, trainers
+    for name in ("set_grad_accumulation", "ga", "set_max_grad_norm", "max_grad_norm", "grad_norm", "clip_coef"):
+        for cls in (engine.VLAEngine, trainers.BackboneTrainer, trainers.FullFinetune, trainers.LoRAFinetune):
+            assert issubclass(cls, schedule.StepControls) and name not in vars(cls), (cls.__name__, name)
+            assert getattr(cls, name) is getattr(schedule.StepControls, name)

@@ -339,3 +339,58 @@ def test_engine_schedule_equals_the_sequential_step(geom, B, sched, monkeypatch)
     _env(monkeypatch, ENGINE_SCHED[sched])
     for how in ("pipelined", "captured"):
         _assert_same(_EREF[key], _run_engine(cfg, batch, how), f"engine {geom}/B{B}/{sched} {how}")
+
+
+# ---- the adapter-only engine's one update -------------------------------------------------------------------------------------
+UPDATE_CASES = {"unclipped": (None, 1), "clip1": (1.0, 1), "clip_inf": (float("inf"), 1), "ga2": (None, 2)}
+
+
+@pytest.mark.parametrize("case", list(UPDATE_CASES))
+def test_engine_update_is_one_through_optimizer_step_and_flush(case, monkeypatch):
+    """VLAEngine._apply_update in its two placements, directly instead of through whole schedules: two engines from the same
+    weights run the same eager two-stream forward + backward (_fwd_bwd) on the same batch and noise; one applies every update
+    through optimizer_step() (both ranges on the current stream), the other leaves it pending the way train_step_graphed does
+    (fold, the event of the summed gradient, _pending_lr) and applies it through flush() (head range on the head stream).  After
+    each of three steps parameters, both AdamW moments and the step count are the same bits - and, clipped, the norm and the
+    coefficient: the sums of squares land in the same slots whichever stream took them, and AdamW is elementwise."""
+    from vla_adapter_amd import engine as E
+    _env(monkeypatch, {})
+    max_norm, ga = UPDATE_CASES[case]
+    cfg = _cfg("tiny")
+    batch = _batch(cfg, 2)
+    noise = (torch.randn(cfg.chunk, cfg.action_dim * cfg.llm.d, device=DEV, generator=torch.Generator(device=DEV).manual_seed(4)) * 0.02).to(BF)
+    engines = [E.VLAEngine(cfg, _trainer_weights(cfg), DEV) for _ in range(2)]
+    for e in engines:
+        e.set_grad_accumulation(ga)
+        e.set_max_grad_norm(max_norm)
+        e._ensure_streams()
+    direct, pending = engines
+    cur, start = torch.cuda.current_stream(), direct.head.P.data.clone()
+    assert torch.equal(start, pending.head.P.data)
+    for step in range(1, 4):
+        for _ in range(ga):
+            for e in engines:
+                e._fwd_bwd(batch, noise)
+                if not e._accum.fold():
+                    continue
+                if e is direct:
+                    e.optimizer_step(LR)
+                    continue
+                if ga > 1:                           # (train_step_graphed: the summed gradient is final on the current stream)
+                    e._h_end = torch.cuda.Event()
+                    e._h_end.record(cur)
+                e._pending_lr = LR
+                assert e.step_count == step - 1, "the update stays pending until flush()"
+                e.flush()
+        torch.cuda.synchronize()
+        assert direct.step_count == pending.step_count == step
+        for k in ("data", "m", "v"):
+            a, b = getattr(direct.head.P, k), getattr(pending.head.P, k)
+            assert torch.equal(a, b), f"{case} step {step}: P.{k} differs at {int((a != b).sum())} of {a.numel()} elements"
+        if max_norm is None:
+            assert direct.grad_norm is None and pending.clip_coef is None
+        else:
+            assert torch.isfinite(direct.grad_norm) and direct.grad_norm > 0
+            assert torch.equal(direct.grad_norm, pending.grad_norm) and torch.equal(direct.clip_coef, pending.clip_coef), \
+                f"{case} step {step}: norm {direct.grad_norm.item()!r} vs {pending.grad_norm.item()!r}"
+    assert not torch.equal(direct.head.P.data, start), "the steps moved the parameters"

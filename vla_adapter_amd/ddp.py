@@ -113,7 +113,12 @@ class FlatGradReducer:
         if self._pending:
             for s in (streams or (torch.cuda.current_stream(),)):
                 s.wait_stream(self.stream)
-            self._pending = False
+            self.joined()
+
+    def joined(self):
+        """The caller has joined every queued collective itself (its streams waited for the events reduce_async returned, or for
+        the exchange stream): wait() has nothing left to do."""
+        self._pending = False
 
     @property
     def grad_scale(self) -> float:

@@ -1024,7 +1024,7 @@ class Head:
 
 
 # ------------------------------------------------------------------------------------------------ whole model
-class VLAEngine:
+class VLAEngine(schedule.StepControls):
     """Adapter-only fine-tune step of VLA-Adapter (finetune.py:288-447 + 1039-1082) on one GPU."""
 
     def __init__(self, cfg: VLACfg, weights: Dict, device="cuda"):
@@ -1044,8 +1044,7 @@ class VLAEngine:
         self.full_llm_backward = bool(int(os.environ.get("VLA_FULL_LLM_BWD", "0")))
         self._row0 = None          # frozen by capture(); None = derive from every batch (one host sync)
         self.reducer = None        # ddp.FlatGradReducer when world_size > 1
-        self._accum = schedule.GradAccumulator(copy_flat, ops.add_)      # gradient accumulation (set_grad_accumulation)
-        self._clip: Optional[schedule.GradClip] = None      # global gradient-norm clipping (set_max_grad_norm)
+        self._init_step_controls(copy_flat, ops.add_)
         self.executed_steps = 0    # forward+backward passes enqueued so far (eager, pipelined or replayed): profile bookkeeping
         # LLM layers above the head's last block (Qwen2.5-1.5B: 28 layers, 24 blocks - action_heads.py:117-118 reads hidden_states[1..24])
         # never reach the loss or the predicted actions: the training step and predict() run the first n_act layers only, as the
@@ -1070,44 +1069,15 @@ class VLAEngine:
         self.llm.enable_fp8()
         self.fp8_frozen = True
 
-    def set_grad_accumulation(self, n: int):
-        """finetune.py:1039-1042, 1078-1082: loss / n on every micro-batch, gradients summed over n micro-batches (in bf16, as
-        autograd accumulates ``.grad``), one optimizer step per n.  The data-parallel exchange runs on the boundary
-        micro-step only (the reference's DDP all-reduces on every one; same result, n-1 exchanges saved).  Call before
-        capture(): the captured loss kernel carries the 1/n."""
-        assert n >= 1 and self._graphs is None, "set_grad_accumulation() before capture()"
-        self._accum.reset(n, [self.head.P.grad])
+    def _grad_buffers(self):
+        return [self.head.P.grad]                    # (schedule.StepControls)
 
-    @property
-    def ga(self) -> int:
-        return self._accum.ga
-
-    def set_max_grad_norm(self, max_norm: Optional[float]):
-        """torch.nn.utils.clip_grad_norm_(trainable parameters, max_norm) in front of every optimizer step (the reference's native
-        trainer: base_strategy.py:389, ddp.py:127-128; its L1 fine-tune script does not clip); None: off, inf: take the norm, clip
-        nothing.  The norm is that of head.P.grad - action head, proprio projector, action queries - as AdamW consumes it
-        (averaged over the ranks, bf16), and it stays on the device with the coefficient (``grad_norm``)."""
-        max_norm = schedule.check_max_grad_norm(max_norm)
+    def _set_clip(self, clip):
         self.flush()                                 # (a pending update belongs to the setting it ran under)
-        self._clip = None if max_norm is None else schedule.GradClip(max_norm, [self.head.P.grad])
-        if self._clip is not None:                   # slots and the two events of flush() reserved here: no step allocates
-            self._clip.begin(self._clip_ranges())
+        self._clip = clip
+        if clip is not None:                         # slots and the two events of _apply_update() reserved here: no step allocates
+            clip.begin(self._clip_ranges())
             self._clip_events = (torch.cuda.Event(), torch.cuda.Event())
-
-    @property
-    def max_grad_norm(self) -> Optional[float]:
-        return None if self._clip is None else self._clip.max_norm
-
-    @property
-    def grad_norm(self) -> Optional[torch.Tensor]:
-        """Device scalar (f32): the global gradient norm of the last applied optimizer step, before clipping; None without
-        set_max_grad_norm().  Reading its value is the only host sync clipping can cause."""
-        return None if self._clip is None else self._clip.total_norm
-
-    @property
-    def clip_coef(self) -> Optional[torch.Tensor]:
-        """Device f32 [1]: min(1, max_grad_norm / (grad_norm + 1e-6)) of the last applied optimizer step."""
-        return None if self._clip is None else self._clip.coef
 
     def _clip_ranges(self):
         """The two ranges of head.P.grad that become final apart (head + proprio projector | action queries): one slot layout for
@@ -1317,42 +1287,54 @@ class VLAEngine:
         ops.zero_(self._dHS)
         return self._dHS
 
+    def _prep_backward(self, actions, row0: Optional[int] = None):
+        """Everything the backward needs that depends only on the batch (the step schedule runs it at the start of the step, off
+        the forward->backward turn-around): live-row window, zeroed dHS, guard, scatter indices, bf16 targets.  row0: the window
+        capture() froze; None: derived from this batch (one host sync) - no action block can start before it, so no guard."""
+        frozen = row0 is not None
+        self._row0_used = row0 = row0 if frozen else self.live_row0()
+        self._dhs(row0)
+        self.head.prep_backward(self.pos1, self.Np, self.B, self.S, row0, self.pos0, self.cnt0)
+        self._guard = self.head.guard if frozen and row0 else None      # NaN when a sample's action block starts before the frozen window
+        self._actions_bf = self._to_bf16(actions)
+
+    def _turn_around(self, pred, gscale: float) -> torch.Tensor:
+        """Forward -> backward turn-around: L1 loss (finetune.py:418) with its gradient scaled by gscale, the frozen window's
+        guard folded into the reported loss, the head's backward begun -> loss3."""
+        loss3, dpred = ops.l1_loss(pred, self._actions_bf, True, gscale)
+        if self._guard is not None:
+            ops.add_scalar_f32_(loss3, self._guard)
+        self.head.bwd_begin(dpred, self._row0_used)
+        return loss3
+
+    def _query_grad(self):
+        """Tail of the backward: the LLM's input gradient at the action-query rows -> the ``action_queries`` gradient."""
+        dq = ops.action_query_grad(self.llm.bwd_result().contiguous(), self.pos0, self.Np, self._row0_used)
+        ops.cast_f32_bf16(dq, out=self.head.P.g("action_queries"))
+
     def loss_and_backward(self, pred, actions, gscale: float = 1.0, exchange: bool = True):
-        """L1 loss (finetune.py:418) + backward into the flat grad buffer.  gscale scales the gradient (loss / grad-accumulation
-        steps); exchange=False leaves the data-parallel exchange to the caller (non-boundary micro-steps)."""
+        """L1 loss + backward into the flat grad buffer: the pieces of the step schedule (_segments) one after the other on the
+        current stream.  gscale scales the gradient (loss / grad-accumulation steps); exchange=False leaves the data-parallel
+        exchange to the caller (non-boundary micro-steps)."""
         llm, head = self.llm, self.head
-        B, S, Np = self.B, self.S, self.Np
-        loss3, dpred = ops.l1_loss(pred, self._to_bf16(actions), True, gscale)
-        row0 = self.live_row0()
-        dHS = self._dhs(row0)
-        head.backward(dpred, dHS, row0)
+        exchange = exchange and self.reducer is not None
+        self._prep_backward(actions)
+        loss3 = self._turn_around(pred, gscale)
+        for i in range(head.nb - 1, -1, -1):
+            head.bwd_layer(i, self._dHS)
+        head.bwd_end()
         aq_off = head.P.offsets["action_queries"][0]
-        if self.reducer is not None and exchange:       # head/proprio grads are final: exchange them under the LLM backward
+        if exchange:                                    # head/proprio grads are final: exchange them under the LLM backward
             self.reducer.reduce_async(head.P.grad, 0, aq_off)
-        dX0 = llm.backward(dHS, B, S, row0, n_run=self.n_act)
-        dq = ops.action_query_grad(dX0.contiguous(), self.pos0, Np, row0)
-        ops.cast_f32_bf16(dq, out=head.P.g("action_queries"))
-        if self.reducer is not None and exchange:
+        llm.backward(self._dHS, self.B, self.S, self._row0_used, n_run=self.n_act)
+        self._query_grad()
+        if exchange:
             self.reducer.reduce_async(head.P.grad, aq_off, None)
         return loss3
 
     def optimizer_step(self, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01):
-        """torch.optim.AdamW semantics on the flat trainable buffer (finetune.py:910, 1078-1082)."""
-        self.step_count += 1
-        P = self.head.P
-        gscale = 1.0
-        if self.reducer is not None:
-            self.reducer.wait()
-            gscale = self.reducer.grad_scale       # DDP averages: sum-all-reduce then 1/N, folded into AdamW
-        if self._clip is not None:
-            self._clip.begin(self._clip_ranges())
-            for r in self._clip_ranges():
-                self._clip.sumsq(*r, gscale)
-            self._clip.finalise()
-            ops.adamw_clipped_(P.data, P.grad, P.m, P.v, self._clip.coef, self.step_count, lr, beta1, beta2, eps, wd, gscale=gscale)
-        else:
-            ops.adamw_(P.data, P.grad, P.m, P.v, self.step_count, lr, beta1, beta2, eps, wd, gscale=gscale)
-        self.head.dirty = True
+        """torch.optim.AdamW semantics on the flat trainable buffer (finetune.py:910, 1078-1082), on the current stream."""
+        self._apply_update(lr, beta1, beta2, eps, wd, two_stream=False, join=False)
 
     def train_step(self, batch, lr: float, noise=None):
         """One micro-batch; the optimizer steps on every ``ga``-th call (set_grad_accumulation)."""
@@ -1379,16 +1361,6 @@ class VLAEngine:
             self.vis_stream = torch.cuda.Stream()      # vision stage of the NEXT step (fills the backward's idle CUs)
             self._vstreams = [self.vis_stream] + [torch.cuda.Stream() for _ in range(max(0, len(self.vits) - 1))]   # one per backbone
 
-    def _prep_backward(self, batch):
-        """Everything the backward needs that depends only on the batch (runs at the start of the step, off the
-        forward->backward turn-around): live-row window, zeroed dHS, guard, scatter indices, bf16 targets."""
-        row0 = self._row0 if self._row0 is not None else self.live_row0()
-        self._row0_used = row0
-        self._dhs(row0)
-        self.head.prep_backward(self.pos1, self.Np, self.B, self.S, row0, self.pos0, self.cnt0)
-        self._guard = self.head.guard if row0 else None          # NaN when a sample's action block starts before the frozen window
-        self._actions_bf = self._to_bf16(batch["actions"])
-
     def _segments(self, batch, noise):
         """[Segment(stream 'M'|'H', fn, wait_key|None, signal_key|None)] for everything after the vision stage."""
         llm, head = self.llm, self.head
@@ -1400,16 +1372,12 @@ class VLAEngine:
         def llm_fwd(c, lo, hi):
             if c == 0:
                 mm = self._embed(batch)
-                self._prep_backward(batch)
+                self._prep_backward(batch["actions"], self._row0)
                 llm.fwd_begin(self.B, self.S, mm, self._row0_used)
             llm.fwd_layers(lo, hi)
 
         def turn_around():
-            pred = head.fwd_end()
-            self._loss3, dpred = ops.l1_loss(pred, self._actions_bf, True, 1.0 / self.ga)
-            if self._guard is not None:
-                ops.add_scalar_f32_(self._loss3, self._guard)
-            head.bwd_begin(dpred, self._row0_used)
+            self._loss3 = self._turn_around(head.fwd_end(), 1.0 / self.ga)
 
         def llm_bwd(k, lo, hi):
             if k == 0:
@@ -1417,8 +1385,7 @@ class VLAEngine:
             for i in range(hi - 1, lo - 1, -1):
                 llm.bwd_layer(i, self._dHS)
             if k == len(fch) - 1:
-                dq = ops.action_query_grad(llm.bwd_result().contiguous(), self.pos0, self.Np, self._row0_used)
-                ops.cast_f32_bf16(dq, out=head.P.g("action_queries"))
+                self._query_grad()
 
         # ONE whole-batch forward pipeline (round 1's two half-batch pipelines left the tree in round 4: DESIGN section 5b)
         return (schedule.pipeline_forward(head, fch, llm_fwd, lambda: (llm.HS, self.pos1, batch["proprio"], self.Np, noise), turn_around,
@@ -1554,17 +1521,23 @@ class VLAEngine:
         return self._loss3
 
     def flush(self, join: bool = True):
-        """Apply the pending parameter update of the last train_step_graphed (no-op if none).  The update is two AdamW
-        launches: the action queries (64 x D, the only trainable tensor the LLM stream reads, in _embed) on the current
-        stream, everything else (head + proprio projector, 99.97 % of the bytes) on the head stream, behind that stream's
-        last backward kernel and ahead of its first forward kernel of the next step - the 0.5 ms of optimiser traffic
-        runs beside the first LLM forward segment instead of in front of it.  ``join`` (default) makes the current stream
-        wait for the head-stream half too, so that callers may read any parameter afterwards (checkpoints, evaluation);
-        the captured step passes False: its head segments run on the head stream anyway."""
+        """Apply the pending parameter update of the last train_step_graphed (no-op if none), in the two-stream placement of
+        _apply_update().  ``join`` (default) makes the current stream wait for the head-stream half too, so that callers may
+        read any parameter afterwards (checkpoints, evaluation); the captured step passes False: its head segments run on the
+        head stream anyway."""
         if self._pending_lr is None:
             return
         lr, self._pending_lr = self._pending_lr, None
-        cur, P = torch.cuda.current_stream(), self.head.P
+        self._apply_update(lr, two_stream=True, join=join)
+
+    def _apply_update(self, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, *, two_stream: bool, join: bool):
+        """THE parameter update: reducer join, step count, clip passes, AdamW.  It is two AdamW launches: the action queries (64 x
+        D, the only trainable tensor the LLM stream reads, in _embed) on the current stream, everything else (head + proprio
+        projector, 99.97 % of the bytes) on the head stream ``hs`` - with ``two_stream`` the engine's (behind that stream's last
+        backward kernel and ahead of its first forward kernel of the next step: the 0.5 ms of optimiser traffic runs beside the
+        first LLM forward segment instead of in front of it), else the current one too.  join: the current stream waits for hs."""
+        cur, P, clip = torch.cuda.current_stream(), self.head.P, self._clip
+        hs = self.side if two_stream else cur
         aq_off = P.offsets["action_queries"][0]
         assert aq_off + rup(math.prod(P.offsets["action_queries"][1]), 8) == P.numel, "action_queries must close the flat buffer"
         self.step_count += 1
@@ -1573,36 +1546,36 @@ class VLAEngine:
             ev_aq, ev_head = self._reduced or (None, None)
             if ev_aq is not None and ev_head is not None:
                 cur.wait_event(ev_aq)                 # the LLM stream needs the action queries only ...
-                self.side.wait_event(ev_head)         # ... the 437 MB head exchange is joined by the head stream
-                self.reducer._pending = False
+                hs.wait_event(ev_head)                # ... the 437 MB head exchange is joined by the head stream
+                self.reducer.joined()
             else:
-                self.reducer.wait(cur, self.side)
+                self.reducer.wait(*((cur, hs) if two_stream else (cur,)))
             self._reduced = None
-            gscale = self.reducer.grad_scale
-        if self.ga > 1:                                # accumulated gradient was assembled on the current stream
-            self.side.wait_event(self._h_end)
-        clip = self._clip
+            gscale = self.reducer.grad_scale          # DDP averages: sum-all-reduce then 1/N, folded into AdamW
+        if two_stream and self.ga > 1:                # accumulated gradient was assembled on the current stream
+            hs.wait_event(self._h_end)
         if clip is not None:
             # clipped: each stream takes the sum of squares of its own range where that range is final; the current stream adds the
             # two (it waits for the head stream's pass: the one new edge), and each stream runs its AdamW behind the coefficient
             r_head, r_aq = self._clip_ranges()
             head_summed, finalised = self._clip_events
             clip.begin([r_head, r_aq])
-            with torch.cuda.stream(self.side):
+            with torch.cuda.stream(hs):
                 clip.sumsq(*r_head, gscale)
-                head_summed.record(self.side)
+                head_summed.record(hs)
             clip.sumsq(*r_aq, gscale)
             cur.wait_event(head_summed)
             clip.finalise()
             finalised.record(cur)
-            self.side.wait_event(finalised)
+            hs.wait_event(finalised)
 
         def adam(sl):
+            args = (self.step_count, lr, beta1, beta2, eps, wd)
             if clip is None:
-                ops.adamw_(P.data[sl], P.grad[sl], P.m[sl], P.v[sl], self.step_count, lr, gscale=gscale)
+                ops.adamw_(P.data[sl], P.grad[sl], P.m[sl], P.v[sl], *args, gscale=gscale)
             else:
-                ops.adamw_clipped_(P.data[sl], P.grad[sl], P.m[sl], P.v[sl], clip.coef, self.step_count, lr, gscale=gscale)
-        with torch.cuda.stream(self.side):
+                ops.adamw_clipped_(P.data[sl], P.grad[sl], P.m[sl], P.v[sl], clip.coef, *args, gscale=gscale)
+        with torch.cuda.stream(hs):
             adam(slice(None, aq_off))
             side_done = torch.cuda.Event()
             side_done.record()

@@ -10,7 +10,7 @@ The part every step shares - the LLM in layer chunks on "M" with the action head
 running ahead of the LLM's over the reversed chunks - is built here, once: turnaround_chunks() cuts the layers, pipeline_forward()
 and pipeline_backward() return the two halves.  engine.VLAEngine (adapter-only step, predict(), validation) and
 trainers.BackboneTrainer (LoRA / full fine-tune step) supply the calls that are theirs, put their own segments (vision, gradient
-hand-overs) around the halves, and run and capture the lists here; they share GradAccumulator and captured_validation() too.
+hand-overs) around the halves, and run and capture the lists here; they share StepControls (accumulation, clipping) and captured_validation() too.
 """
 from __future__ import annotations
 
@@ -188,6 +188,54 @@ class GradClip:
     @property
     def coef(self) -> torch.Tensor:
         return self.out[1:2]
+
+
+class StepControls:
+    """Gradient accumulation and gradient-norm clipping of whoever owns a step (engine.VLAEngine, trainers.BackboneTrainer): the
+    GradAccumulator, the GradClip and the public members around them.  The owner calls _init_step_controls(), keeps ``_graphs``
+    (None until its capture()) and supplies _grad_buffers() -> its flat gradient buffers and _set_clip(clip), which settles
+    what belongs to the old setting, stores ``self._clip = clip`` (a new GradClip, or None: off) and lays out its slots."""
+
+    def _init_step_controls(self, copy, add):
+        self._accum = GradAccumulator(copy, add)     # gradient accumulation (set_grad_accumulation)
+        self._clip: Optional[GradClip] = None        # global gradient-norm clipping (set_max_grad_norm)
+
+    def set_grad_accumulation(self, n: int):
+        """finetune.py:1039-1042, 1078-1082: loss / n on every micro-batch, gradients summed over n micro-batches (in bf16, as
+        autograd accumulates ``.grad``; over every flat gradient buffer of the owner), one optimizer step per n.  The
+        data-parallel exchange runs once, on the boundary micro-step's sums (the reference's DDP all-reduces on every
+        micro-step; same result, n-1 exchanges saved).  Call before capture(): the captured loss kernel carries the 1/n."""
+        assert n >= 1 and self._graphs is None, "set_grad_accumulation() before capture()"
+        self._accum.reset(n, self._grad_buffers())
+
+    @property
+    def ga(self) -> int:
+        return self._accum.ga
+
+    def set_max_grad_norm(self, max_norm: Optional[float]):
+        """torch.nn.utils.clip_grad_norm_(trainable parameters, max_norm) in front of every optimizer step, as the reference's
+        native trainer does it (base_strategy.py:389, ddp.py:127-128; every shipped configuration: 1.0; its L1 fine-tune script
+        does not clip); None: off, inf: take the norm, clip nothing.  The norm covers exactly what AdamW updates - the engine:
+        head.P.grad (action head, proprio projector, action queries); a trainer: _adam_ranges() and the head's buffer - as AdamW
+        consumes it (averaged over the ranks, bf16), and it stays on the device with the coefficient (``grad_norm``).  A
+        trainer takes it before capture() only."""
+        max_norm = check_max_grad_norm(max_norm)
+        self._set_clip(None if max_norm is None else GradClip(max_norm, self._grad_buffers()))
+
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return None if self._clip is None else self._clip.max_norm
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """Device scalar (f32): the global gradient norm of the last applied optimizer step, before clipping; None without
+        set_max_grad_norm().  Reading its value is the only host sync clipping can cause."""
+        return None if self._clip is None else self._clip.total_norm
+
+    @property
+    def clip_coef(self) -> Optional[torch.Tensor]:
+        """Device f32 [1]: min(1, max_grad_norm / (grad_norm + 1e-6)) of the last applied optimizer step."""
+        return None if self._clip is None else self._clip.coef
 
 
 def captured_validation(model, batch, noise, make, replay):

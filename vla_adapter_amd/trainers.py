@@ -133,7 +133,7 @@ class _Slot:
             setattr(self.holder, self.key, t)
 
 
-class BackboneTrainer(E.Linear):
+class BackboneTrainer(E.Linear, schedule.StepControls):
     """Training forward / backward through ViT(s) -> projector -> Qwen2 stack -> action head, shared by both modes.  The layers are
     the engine's own (ViT.forward / block, LLM.fwd_layer / bwd_layer), run with the trainer as their Linear."""
 
@@ -161,8 +161,7 @@ class BackboneTrainer(E.Linear):
         # of bf16 gradients at the 0.5B geometry: large messages for the point-to-point xGMI links) / `exchange_blocks` ViT blocks
         self.exchange_layers, self.exchange_blocks = 4, 7
         self.n_active = min(cfg.llm.n_layers, cfg.num_blocks)      # LLM layers that reach the loss (see _segments)
-        self._accum = schedule.GradAccumulator(E.copy_flat, ops.add_)      # gradient accumulation (set_grad_accumulation)
-        self._clip: Optional[schedule.GradClip] = None      # global gradient-norm clipping (set_max_grad_norm)
+        self._init_step_controls(E.copy_flat, ops.add_)
         self.objective = "l1"
         self.overlap_update = not os.environ.get("VLA_NO_UPDATE_OVERLAP")      # AdamW range by range under the backward (_run)
         # Streams of the step schedule (_segments): the caller's stream carries the dX chain, `gstream` everything that only feeds a
@@ -782,40 +781,14 @@ class BackboneTrainer(E.Linear):
                     red.reduce_async(buf, lo, hi, after_event=after_event)
 
     # ---- update / capture ----------------------------------------------------------------------------------------------
-    def set_grad_accumulation(self, n: int):
-        """As VLAEngine.set_grad_accumulation, over both flat gradient buffers; the data-parallel exchange runs once, on the sums (_step)."""
-        assert n >= 1 and self._graphs is None, "set_grad_accumulation() before capture()"
-        self._accum.reset(n, [self.P.grad, self.head.P.grad])
+    def _grad_buffers(self):
+        return [self.P.grad, self.head.P.grad]       # (schedule.StepControls: accumulated and clipped together)
 
-    @property
-    def ga(self) -> int:
-        return self._accum.ga
-
-    def set_max_grad_norm(self, max_norm: Optional[float]):
-        """torch.nn.utils.clip_grad_norm_(vlm.parameters(), max_norm) in front of every optimizer step, as the reference's native
-        trainer does it (base_strategy.py:389, ddp.py:127-128; every shipped configuration: 1.0); None: off.  inf clips nothing
-        and still takes the norm.  The norm covers exactly what AdamW updates (_adam_ranges() and the head's buffer), of the
-        averaged bf16 gradients, and stays on the device with the coefficient (``grad_norm``).  Before capture()."""
+    def _set_clip(self, clip):
         assert self._graphs is None, "set_max_grad_norm() before capture()"
-        max_norm = schedule.check_max_grad_norm(max_norm)
-        self._clip = None if max_norm is None else schedule.GradClip(max_norm, [self.P.grad, self.head.P.grad])
-        if self._clip is not None:                   # (optimizer_step()'s slots now; the schedule's own in capture() / the first eager step)
+        self._clip = clip
+        if clip is not None:                         # (optimizer_step()'s slots now; the schedule's own in capture() / the first eager step)
             self._clip_begin(self._update_buffers())
-
-    @property
-    def max_grad_norm(self) -> Optional[float]:
-        return None if self._clip is None else self._clip.max_norm
-
-    @property
-    def grad_norm(self) -> Optional[torch.Tensor]:
-        """Device scalar (f32): the global gradient norm of the last optimizer step, before clipping; None without
-        set_max_grad_norm().  Reading its value is the only host sync clipping can cause."""
-        return None if self._clip is None else self._clip.total_norm
-
-    @property
-    def clip_coef(self) -> Optional[torch.Tensor]:
-        """Device f32 [1]: min(1, max_grad_norm / (grad_norm + 1e-6)) of the last optimizer step."""
-        return None if self._clip is None else self._clip.coef
 
     def _update_buffers(self):
         """[(flat gradient buffer, first, end)] of everything an optimizer step moves: _adam_ranges() and the head's buffer."""
@@ -968,7 +941,7 @@ class BackboneTrainer(E.Linear):
 
     def _after_update(self, refresh: bool):
         if self.eng.reducer is not None:
-            self.eng.reducer._pending = False        # every collective was joined range by range (_update_ranges)
+            self.eng.reducer.joined()                # every collective was joined range by range (_update_ranges)
         self.head.dirty = True
         if refresh:
             self._refresh_rest()                     # (eager: the ranges' pieces ran behind their AdamW; captured: the caller replays _g_r)
@@ -986,21 +959,17 @@ class BackboneTrainer(E.Linear):
 
     def optimizer_step(self, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, refresh: bool = True):
         self.step_count += 1
+        gscale = self._exchange_and_scale()
+        P, HP = self.P, self.head.P
         if self._clip is not None:                    # (gradient accumulation: the norm of the folded, exchanged sums)
-            gscale = self._exchange_and_scale()
             self._clip_begin(self._update_buffers())
             for buf, lo, hi in self._update_buffers():
                 self._clip.sumsq(buf, lo, hi, gscale)
             self._clipped_update(lr, beta1, beta2, eps, wd)
-            self.head.dirty = True
-            if refresh:
-                self.refresh()
-            return
-        gscale = self._exchange_and_scale()
-        P, HP = self.P, self.head.P
-        for lo, hi in self._adam_ranges():            # (parameters of dead LLM layers: see _segments)
-            ops.adamw_(P.data[lo:hi], P.grad[lo:hi], P.m[lo:hi], P.v[lo:hi], self.step_count, lr, beta1, beta2, eps, wd, gscale=gscale)
-        ops.adamw_(HP.data, HP.grad, HP.m, HP.v, self.step_count, lr, beta1, beta2, eps, wd, gscale=gscale)
+        else:
+            for lo, hi in self._adam_ranges():        # (parameters of dead LLM layers: see _segments)
+                ops.adamw_(P.data[lo:hi], P.grad[lo:hi], P.m[lo:hi], P.v[lo:hi], self.step_count, lr, beta1, beta2, eps, wd, gscale=gscale)
+            ops.adamw_(HP.data, HP.grad, HP.m, HP.v, self.step_count, lr, beta1, beta2, eps, wd, gscale=gscale)
         self.head.dirty = True
         if refresh:
             self.refresh()
