@@ -12,6 +12,13 @@
  *  - bf16 tensors are raw uint16 storage; "f32" = float.  Leading dimensions / strides are in ELEMENTS.
  *  - Return 0 on success, negative on error (VLA_ERR_*); vla_last_error() gives a message.  No exceptions cross
  *    the ABI.  Shapes are validated on the host BEFORE launch (a faulting kernel can take the node down).
+ *  - Memory contract (tests/test_memory_contract_gpu.py): an operand is the elements its shape and strides declare - `width` elements
+ *    of every row, the rows of every batch / row group.  Nothing else is written: not the elements between the width and the row
+ *    stride, not a row before the first or behind the last, not the rows between two groups.  What lies there never reaches a result
+ *    either (a kernel may load it where a tile overhangs; it is masked before use, so a NaN next to an operand stays there).  Inputs
+ *    are never written.  Operands are handed over as windows of larger buffers: results do not depend on an operand's strides or on
+ *    its alignment beyond what the entry point states, except where an entry says that an unaligned operand takes another
+ *    summation order.
  *  - Rounding points follow the reference under bf16 autocast (one bf16 rounding after every Linear(+bias),
  *    activation, residual add, norm); accumulation / softmax / statistics are fp32.
  */
@@ -185,6 +192,9 @@ int vla_layernorm_fwd_q8(void* stream, const void* x, const void* w, const void*
  * timm ViT qkv/proj/mlp (modeling_prismatic.py:120-144), PrismaticProjector (:261-273), Qwen2 q/k/v/o/gate/up/down
  * (:644-655), ProprioProjector (projectors.py:19-24), MLPResNet / MLPResNetBlock(_Pro) Linears
  * (action_heads.py:111-121, 337-410).  K % 64 == 0; lda, ldb % 8 == 0; M/N edges are handled.
+ * Alignment: A, B (A2, B2, the RoPE tables, a split-K workspace) 16 B.  C 16 B when ldc % 8 == 0, any element address otherwise (element
+ * stores then); R 16 B when ldc and ldr are both multiples of 8, any element address otherwise (SwiGLU backward: 8 B, ldr % 4 == 0);
+ * bias and the fp8 scale vectors any element address; C2 8 B with ldc2 % 4 == 0.  Rows of C that c_live_mod excludes keep their bytes.
  * VLA_ACT_SWIGLU: B rows interleaved in groups of 16 (rows 32t..32t+15 = gate[16t..], 32t+16.. = up[16t..]);
  * C (optional) receives the interleaved pre-activations, C2 the product.
  * VLA_ACT_SWIGLU_BWD: the product A.B^T is dH [M, N]; R = the forward's interleaved pre-activations GU [M, 2N];
@@ -201,7 +211,9 @@ int vla_transpose_bf16(void* stream, const void* in, void* out, int rows, int co
  * x,y bf16 [rows, cols]; w,b bf16 [cols]; stats (optional) f32 [rows,2] = (mean, rstd) for the backward. */
 int vla_layernorm_fwd(void* stream, const void* x, const void* w, const void* b, void* y, float* stats, int rows,
                       int cols, int ldx, int ldy, float eps);
-/* dx (bf16, may be NULL) and dw/db (f32 [cols], accumulated with +=, may be NULL) of the above. */
+/* dx (bf16, may be NULL) and dw/db (f32 [cols], accumulated with +=, may be NULL) of the above.  With dx: dy, x, w, dx 16-B aligned.
+ * The dw / db sums run in a fixed order when dy and x are 16-B aligned; at any other element address one thread per column adds the rows
+ * in order (another fp32 summation order, same bounds). */
 int vla_layernorm_bwd(void* stream, const void* dy, const void* x, const void* w, const float* stats, void* dx,
                       float* dw, float* db, int rows, int cols, int ldx, int lddy, int lddx);
 /* Qwen2RMSNorm: y = bf16(w * bf16(x * rsqrt(mean(x^2)+eps))) (transformers Qwen2RMSNorm.forward; call site
@@ -209,12 +221,14 @@ int vla_layernorm_bwd(void* stream, const void* dy, const void* x, const void* w
 int vla_rmsnorm_fwd(void* stream, const void* x, const void* w, void* y, float* rstd, int rows, int cols, float eps);
 /* dx = rmsnorm backward (+ optional residual-stream gradient add: dx += dres).  No dw (frozen LLM).
  * dy/dres/dx are compact [rows, cols]; x_group > 0: row r of x / rstd is row (r / x_group) * x_group_rows + x_row0 +
- * r % x_group of the forward's tensors (the live-row window [x_row0, x_row0 + x_group) of every sequence). */
+ * r % x_group of the forward's tensors (the live-row window [x_row0, x_row0 + x_group) of every sequence): the rows of x / rstd outside
+ * the window are not read.  dy, x, w, dres, dx 16-B aligned. */
 int vla_rmsnorm_bwd(void* stream, const void* dy, const void* x, const void* w, const float* rstd, const void* dres,
                     void* dx, int rows, int cols, int x_group, int x_group_rows, int x_row0);
 
 /* Qwen2RMSNorm weight gradient: dw[c] += sum_r dy[r, c] * bf16(x[r, c] * rstd[r]) (f32 accumulator).  Needed once the LLM
- * trains (full fine-tune, vla-scripts/finetune.py:846-849; LoRA leaves the norms frozen). */
+ * trains (full fine-tune, vla-scripts/finetune.py:846-849; LoRA leaves the norms frozen).  dy / x compact [rows, cols]; 16-B aligned
+ * with cols % 8 == 0 they are summed in a fixed order, at any other element address by one thread per column, rows in order. */
 int vla_rmsnorm_dw(void* stream, const void* dy, const void* x, const float* rstd, float* dw, int rows, int cols);
 
 /* ---------------------------------------------------------------- attention (MFMA, flash-style) */
@@ -236,14 +250,17 @@ typedef struct vla_attn_desc {
   /* optional window (all 0 = plain): query i sits at sequence position q_off + i (causal masking and RoPE use that
    * position; q/o/dout/dq point at the first live query row); lse is f32 [B, Hq, lse_hs] (0 -> Sq) indexed by i;
    * backward: dK/dV are produced for keys >= dkv_k0 only, stored at row key - dkv_k0 of dk/dv.  With q_off = dkv_k0 = r0
-   * the backward costs only what the rows >= r0 of a causal sequence need (live-row backward of a frozen LLM). */
+   * the backward costs only what the rows >= r0 of a causal sequence need (live-row backward of a frozen LLM).  The rows of q / o /
+   * dout in front of the first live row are not read. */
   int q_off, dkv_k0, lse_hs;
 } vla_attn_desc;
 
 /* softmax(scale * Q K^T + mask) V, GQA (Hq % Hkv == 0), causal and/or key-padding mask, dh in {64,72,112,128}.
  * Replaces F.scaled_dot_product_attention in timm Attention and flash-attn / eager attention in Qwen2Attention. */
 int vla_attn_fwd(void* stream, const vla_attn_desc* desc /* host */);
-/* dQ, dK, dV of the above (recompute from q,k,v,o,lse).  Replaces flash-attn backward / autograd of eager attention. */
+/* dQ, dK, dV of the above (recompute from q,k,v,o,lse).  Replaces flash-attn backward / autograd of eager attention.
+ * Alignment: q, k, v, dout 16 B with strides % 8 == 0; o 8 B with strides % 4 == 0 in the forward, 16 B / % 8 in the backward;
+ * dq, dk, dv 8 B with strides % 4 == 0; lse, delta, kmask, the RoPE tables any element address. */
 int vla_attn_bwd(void* stream, const vla_attn_desc* desc /* host */);
 
 /* ---------------------------------------------------------------- rotary embeddings */
@@ -261,6 +278,7 @@ int vla_rope_interleaved(void* stream, void* x, const float* cos_t, const float*
 /* ToTensor + Normalize of PrismaticImageProcessor.apply_transform (processing_prismatic.py:128-145) for images already at
  * the model's input size: img u8 [B, H, W, 3] -> out[b, c0 + c, y, x] = ((img / 255) - mean[c]) / std[c]  (f32 math in
  * torchvision's order; stored bf16, or f32 if out_f32) inside a channel-stacked [B, Ctot, H, W] tensor.  mean3 / std3: host. */
+/* The channels of `out` outside [c0, c0 + 3) are not touched. */
 int vla_image_normalize_u8(void* stream, const void* img, void* out, int B, int H, int W, int Ctot, int c0,
                            const float* mean3 /* host */, const float* std3 /* host */, int out_f32);
 /* Training-time image augmentation of the reference's RLDS pipeline (prismatic/vla/datasets/datasets.py:204-218 ->
@@ -336,18 +354,22 @@ int vla_im2col_patch(void* stream, const void* pixels, void* cols, int B, int Ct
 int vla_action_mask(void* stream, const long long* labels, int* qidx, int* pos, int* count, int B, int L, int shift);
 /* Embedding gather + action-query splice + multimodal layout (modeling_prismatic.py:601, 418-454, 486-510):
  * out[b, 0] = tok 0, out[b, 1..Np] untouched (projector GEMM writes there), out[b, Np+j] = tok j (j>=1);
- * tok j = action_queries[qidx[b,j]] if qidx>=0 else table[ids[b,j]].  mm_mask u8 [B, S]. */
+ * tok j = action_queries[qidx[b,j]] if qidx>=0 else table[ids[b,j]].  mm_mask u8 [B, S]: every element is written (1 on the patch rows).
+ * table, action_queries, out 16-B aligned (D % 8 == 0: rows move in 16-B chunks). */
 int vla_embed_splice(void* stream, const long long* ids, const unsigned char* attn_mask, const int* qidx,
                      const void* table, const void* action_queries, void* out, unsigned char* mm_mask, int B, int L,
                      int Np, int D, int vocab);
 /* d action_queries[k] = sum_b dX[b, Np + pos[b,k]] (f32 [64, D]); backward of the splice. pos from shift=0 mask.
- * dx holds the rows >= row0 of every sequence: bf16 [B, S, D] with S = (sequence length - row0). */
+ * dx holds the rows >= row0 of every sequence: bf16 [B, S, D] with S = (sequence length - row0).  All 64 rows of dq are written
+ * (zeros for a k no sample has). */
 int vla_action_query_grad(void* stream, const void* dx, const int* pos, float* dq, int B, int S, int Np, int D, int row0);
-/* out[i, :] = in[idx[i], :] (idx == -2 -> row i is left untouched, any other idx < 0 -> zeros); bf16 rows of D elements. */
+/* out[i, :] = in[idx[i], :] (idx == -2 -> row i is left untouched, any other idx < 0 -> zeros); bf16 rows of D elements.
+ * D, ldi, ldo % 8 == 0, in / out 16-B aligned (here and in vla_scatter_add_rows: rows move in 16-B chunks). */
 int vla_gather_rows(void* stream, const void* in, const int* idx, void* out, int n, int D, int ldi, int ldo);
 /* out[idx[i], :] += in[i, :] (idx unique, idx<0 skipped). */
 int vla_scatter_add_rows(void* stream, const void* in, const int* idx, void* out, int n, int D, int ldi, int ldo);
-/* y = bf16(a + b) elementwise over n bf16 (n % 8 == 0) */
+/* y = bf16(a + b) elementwise over n bf16 (n % 8 == 0).  This and the five activation entry points below take compact, 16-B aligned
+ * tensors (16 B per lane). */
 int vla_add_bf16(void* stream, const void* a, const void* b, void* y, long long n);
 /* GELU(erf) forward y=gelu(x) / backward dx = dy*gelu'(x), bf16, n elements */
 int vla_gelu_fwd(void* stream, const void* x, void* y, long long n);
@@ -359,7 +381,8 @@ int vla_swiglu_bwd(void* stream, const void* dh, const void* gu, void* dgu, int 
 /* h[M, I] = bf16(bf16(silu(gate)) * up) from the interleaved pre-activations gu[M, 2I] (same layout as VLA_ACT_SWIGLU): the
  * stand-alone form of the fused epilogue, used when LoRA deltas are added to the pre-activations first (finetune.py:832-844). */
 int vla_swiglu_fwd(void* stream, const void* gu, void* h, int M, int I);
-/* column sums of bf16 matrices [batch][rows, cols] into f32 out[batch][cols] (+=): bias gradients. */
+/* column sums of bf16 matrices [batch][rows, cols] into f32 out[batch][cols] (+=): bias gradients.  x 16-B aligned with cols, ldx,
+ * s_x % 8 == 0: a fixed summation order; any other element address / width: one thread per column, rows in order. */
 int vla_colsum_bf16(void* stream, const void* x, float* out, int rows, int cols, int ldx, int batch, long long s_x,
                     long long s_out);
 /* f32 -> bf16 / bf16 -> f32 casts */
@@ -462,7 +485,7 @@ typedef struct vla_head_attn_desc {
   const void* k_adp;  const void* v_adp;      /* [B, Ka, H*dh] */
   const void* k_task; const void* v_task;     /* [B, Kt, H*dh] */
   const void* gate;   /* bf16 scalar gating_factor (device) */
-  void* out;          /* [B, T, H*dh] */
+  void* out;          /* [B, T, H*dh]; every bf16 tensor of this descriptor, gradients included: 16-B aligned, sample b at row b * T (Ka, Kt) */
   float* probs;       /* f32 [B, H, T, T+Ka+Kt] saved softmax (workspace for backward) */
   int B, T, Ka, Kt, H, dh;
   int ld_q, ld_self, ld_adp, ld_task, ld_out; /* row strides */
@@ -504,7 +527,9 @@ int vla_adamw_bf16(void* stream, void* p, const void* g, void* m, void* v, long 
  * vla_grad_sumsq: slots[0 .. vla_grad_sumsq_slots(n)) = fixed-order fp32 partial sums of x^2 over g[0 .. n), where x is the value
  *   vla_adamw_bf16 consumes for the same (g_f32, gscale): bf16(g * gscale) for f32 gradients, bf16(bf16 g * gscale) for bf16 gradients
  *   with gscale != 1, the bf16 gradient itself otherwise.  g: any element-aligned address (16-B loads on the aligned body).  No atomics:
- *   the same input gives the same bits.  Nothing outside g[0 .. n) is read, no slot beyond the count is written.
+ *   the same input at the same address gives the same bits.  Where a slot's elements fall against the 16-B boundaries decides which of
+ *   them are its head, its 8-wide body and its tail, and so the order of the fp32 adds: the same values at another address modulo 16 B
+ *   may give other bits (within 1e-5 of the fp64 sum either way).  Nothing outside g[0 .. n) is read, no slot beyond the count is written.
  * vla_grad_norm_finalise: one workgroup adds n_slots partials in a fixed order in fp64; out2[0] = total_norm = (float)sqrt(sum),
  *   out2[1] = min(1, max_norm / (total_norm + 1e-6f)) in fp32 with torch's operation order (reciprocal, then the product; a NaN norm
  *   gives a NaN coefficient as with error_if_nonfinite=False).  max_norm > 0; +inf clips nothing and still reports the norm.

@@ -552,6 +552,7 @@ extern "C" int vla_embed_splice(void* stream, const long long* ids, const unsign
                                 int L, int Np, int D, int vocab) {
   VLA_REQUIRE(ids && qidx && table && action_queries && out && B > 0 && L > 0 && Np >= 0 && D % 8 == 0 && vocab > 0,
               "embed_splice: bad args");
+  VLA_REQUIRE(((((uintptr_t)table) | ((uintptr_t)action_queries) | ((uintptr_t)out)) & 15) == 0, "embed_splice: 16-B aligned table / action_queries / out");
   const long long rows = (long long)B * (L + Np);
   hipLaunchKernelGGL(embed_splice_kernel, dim3(nblk(rows, 4)), dim3(256), 0, (hipStream_t)stream, ids, attn_mask, qidx,
                      (const bf16_t*)table, (const bf16_t*)action_queries, (bf16_t*)out, mm_mask, B, L, Np, D, vocab);
@@ -569,6 +570,7 @@ extern "C" int vla_action_query_grad(void* stream, const void* dx, const int* po
 
 extern "C" int vla_gather_rows(void* stream, const void* in, const int* idx, void* out, int n, int D, int ldi, int ldo) {
   VLA_REQUIRE(in && idx && out && n > 0 && D % 8 == 0 && ldi % 8 == 0 && ldo % 8 == 0, "gather_rows: bad args");
+  VLA_REQUIRE(((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0, "gather_rows: 16-B aligned in / out");
   hipLaunchKernelGGL(gather_rows_kernel, dim3(nblk(n, 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, idx, (bf16_t*)out, n, D, ldi, ldo);
   VLA_CHECK_LAUNCH("gather_rows");
   return VLA_OK;
@@ -576,6 +578,7 @@ extern "C" int vla_gather_rows(void* stream, const void* in, const int* idx, voi
 
 extern "C" int vla_scatter_add_rows(void* stream, const void* in, const int* idx, void* out, int n, int D, int ldi, int ldo) {
   VLA_REQUIRE(in && idx && out && n > 0 && D % 8 == 0 && ldi % 8 == 0 && ldo % 8 == 0, "scatter_add_rows: bad args");
+  VLA_REQUIRE(((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0, "scatter_add_rows: 16-B aligned in / out");
   hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(nblk(n, 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, idx, (bf16_t*)out, n, D, ldi, ldo);
   VLA_CHECK_LAUNCH("scatter_add_rows");
   return VLA_OK;
@@ -584,6 +587,7 @@ extern "C" int vla_scatter_add_rows(void* stream, const void* in, const int* idx
 #define EW_ENTRY(NAME, OP, NEEDB)                                                                                  \
   extern "C" int NAME(void* stream, const void* a, const void* b, void* y, long long n) {                           \
     VLA_REQUIRE(a && y && (!(NEEDB) || b) && n > 0 && n % 8 == 0, #NAME ": null / n%8");                              \
+    VLA_REQUIRE(((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)y)) & 15) == 0, #NAME ": 16-B aligned tensors");     \
     hipLaunchKernelGGL(ew_kernel<OP>, GRID1D(n / 8, 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a,     \
                        (const bf16_t*)b, (bf16_t*)y, n / 8);                                                       \
     VLA_CHECK_LAUNCH(#NAME);                                                                                       \
@@ -594,6 +598,7 @@ EW_ENTRY(vla_gelu_bwd, EW_GELU_B, 1)
 EW_ENTRY(vla_relu_bwd, EW_RELU_B, 1)
 extern "C" int vla_gelu_fwd(void* stream, const void* x, void* y, long long n) {
   VLA_REQUIRE(x && y && n > 0 && n % 8 == 0, "gelu_fwd: null / n%8");
+  VLA_REQUIRE(((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0, "gelu_fwd: 16-B aligned tensors");
   hipLaunchKernelGGL(ew_kernel<EW_GELU_F>, GRID1D(n / 8, 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                      (const bf16_t*)nullptr, (bf16_t*)y, n / 8);
   VLA_CHECK_LAUNCH("gelu_fwd");
@@ -602,6 +607,7 @@ extern "C" int vla_gelu_fwd(void* stream, const void* x, void* y, long long n) {
 
 extern "C" int vla_swiglu_bwd(void* stream, const void* dh, const void* gu, void* dgu, int M, int I) {
   VLA_REQUIRE(dh && gu && dgu && M > 0 && I > 0 && I % 16 == 0, "swiglu_bwd: I%16");
+  VLA_REQUIRE(((((uintptr_t)dh) | ((uintptr_t)gu) | ((uintptr_t)dgu)) & 15) == 0, "swiglu_bwd: 16-B aligned tensors");
   const long long nch = (long long)M * (I / 8);
   hipLaunchKernelGGL(swiglu_bwd_kernel, GRID1D(nch, 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dh, (const bf16_t*)gu, (bf16_t*)dgu, nch, I);
   VLA_CHECK_LAUNCH("swiglu_bwd");
@@ -1358,6 +1364,7 @@ __global__ void swiglu_fwd_kernel(const bf16_t* __restrict__ gu, bf16_t* __restr
 
 extern "C" int vla_swiglu_fwd(void* stream, const void* gu, void* h, int M, int I) {
   VLA_REQUIRE(gu && h && M > 0 && I > 0 && I % 16 == 0, "swiglu_fwd: I%16");
+  VLA_REQUIRE(((((uintptr_t)gu) | ((uintptr_t)h)) & 15) == 0, "swiglu_fwd: 16-B aligned tensors");
   const long long nch = (long long)M * I / 8;
   hipLaunchKernelGGL(swiglu_fwd_kernel, GRID1D(nch, 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)gu, (bf16_t*)h, nch, I);
   VLA_CHECK_LAUNCH("swiglu_fwd");

@@ -217,6 +217,14 @@ int fill(HP& p, const vla_head_attn_desc* d, bool bwd) {
               "head_attn: row strides must be multiples of 8");
   VLA_REQUIRE(d->ld_q >= d->H * d->dh && d->ld_self >= d->H * d->dh && d->ld_adp >= d->H * d->dh && d->ld_task >= d->H * d->dh,
               "head_attn: row stride < H*dh");
+  // every bf16 tensor is read / written in 16-B (outputs: 8-B) fragments at multiples of 8 elements from its base
+  VLA_REQUIRE((((uintptr_t)d->q | (uintptr_t)d->k_self | (uintptr_t)d->v_self | (uintptr_t)d->k_adp | (uintptr_t)d->v_adp | (uintptr_t)d->k_task |
+                (uintptr_t)d->v_task | (uintptr_t)d->out) & 15) == 0,
+              "head_attn: tensors must be 16-B aligned");
+  if (bwd)
+    VLA_REQUIRE((((uintptr_t)d->dout | (uintptr_t)d->dq | (uintptr_t)d->dk_self | (uintptr_t)d->dv_self | (uintptr_t)d->dk_adp | (uintptr_t)d->dv_adp |
+                  (uintptr_t)d->dk_task | (uintptr_t)d->dv_task) & 15) == 0,
+                "head_attn_bwd: gradient tensors must be 16-B aligned");
   p.q = (const bf16_t*)d->q; p.ks = (const bf16_t*)d->k_self; p.vs = (const bf16_t*)d->v_self;
   p.ka = (const bf16_t*)d->k_adp; p.va = (const bf16_t*)d->v_adp; p.kt = (const bf16_t*)d->k_task; p.vt = (const bf16_t*)d->v_task;
   p.gate = (const bf16_t*)d->gate; p.out = (bf16_t*)d->out; p.probs = d->probs;

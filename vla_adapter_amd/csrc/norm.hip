@@ -323,6 +323,7 @@ extern "C" int vla_layernorm_bwd(void* stream, const void* dy, const void* x, co
   VLA_REQUIRE(cols % 8 == 0 && ldx % 8 == 0 && lddy % 8 == 0 && cols <= 12288, "layernorm_bwd: cols%8, ld%8");
   if (dx) {
     VLA_REQUIRE(lddx % 8 == 0, "layernorm_bwd: lddx%8");
+    VLA_REQUIRE((((uintptr_t)dy | (uintptr_t)x | (uintptr_t)w | (uintptr_t)dx) & 15) == 0, "layernorm_bwd: 16-B alignment (dx form)");
     const int n = nch_for(cols);
     dim3 grid((rows + 3) / 4);
 #define CALL(N) hipLaunchKernelGGL(layernorm_bwd_dx_kernel<N>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, \
@@ -377,6 +378,7 @@ extern "C" int vla_rmsnorm_bwd(void* stream, const void* dy, const void* x, cons
   VLA_REQUIRE(dy && x && w && rstd && dx && rows > 0 && cols > 0, "rmsnorm_bwd: null/empty");
   VLA_REQUIRE(x_group >= 0 && (x_group == 0 || (x_row0 >= 0 && x_row0 + x_group <= x_group_rows)), "rmsnorm_bwd: bad row window");
   VLA_REQUIRE(cols % 8 == 0 && cols <= 12288, "rmsnorm_bwd: cols%8==0");
+  VLA_REQUIRE((((uintptr_t)dy | (uintptr_t)x | (uintptr_t)w | (uintptr_t)dres | (uintptr_t)dx) & 15) == 0, "rmsnorm_bwd: 16-B alignment");
   const int n = nch_for(cols);
   dim3 grid((rows + 3) / 4);
 #define CALL(N) hipLaunchKernelGGL(rmsnorm_bwd_kernel<N>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, \

@@ -38,13 +38,15 @@ def _chk_bf16(*ts):
 def gemm_nt(a: torch.Tensor, b: torch.Tensor, *, bias=None, residual=None, res_mod: int = 0, act: int = ACT_NONE,
             out: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None, alpha: float = 1.0,
             want_pre: bool = True, a_group=None, c_group=None, r_group=None, rope=None, c_live=None,
-            split_k: Optional[int] = None, bias_post_round: bool = False, fp8=None, ext=None, query_256: bool = False) -> torch.Tensor:
+            split_k: Optional[int] = None, bias_post_round: bool = False, fp8=None, ext=None, query_256: bool = False,
+            query_plan: bool = False):
     """C = epilogue(A @ B^T).  a: [M,K] or [batch,M,K] (row stride = a.stride(-2)); b: [N,K] or [batch,N,K].
     SwiGLU: returns (pre [.., N] or None, h [.., N/2]).  split_k: None = automatic, 0/1 = off, k = forced.
     fp8=(a_scale [M] f32, b_scale [N] f32): a and b are uint8 tensors of OCP e4m3 codes (quant_fp8_rows).
     ext=(a2 [M, K2], b2 [N, K2]) bf16: K extension, C = epilogue(A @ B^T + A2 @ B2^T) in one fp32 accumulator (LoRA branch); with fp8
     the base pair is e4m3 and dequantised before the extension adds to it.  query_256=True: no launch, returns whether this call
-    would run on the 256-row kernel."""
+    would run on the 256-row kernel; query_plan=True: no launch, returns (kernel id, K slices) of this call (gemm_plan) - one query
+    path, query_256 is its kernel id compared with KERNEL_NT_256.  Otherwise returns the output tensor (SwiGLU: the pair)."""
     if fp8 is not None:
         assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.dim() == 2 and split_k in (None, 0, 1)
         _chk_bf16(bias, residual, out, out2)
@@ -120,8 +122,9 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, *, bias=None, residual=None, res_m
         split_k = _nt_plan(d)[1]
     if split_k and split_k > 1:
         d.split_k, d.ws = split_k, _splitk_ws(split_k * M * Nn, a.device).data_ptr()
-    if query_256:
-        return _nt_plan(d)[0] == N.KERNEL_NT_256
+    if query_plan or query_256:
+        plan = _nt_plan(d)
+        return plan if query_plan else plan[0] == N.KERNEL_NT_256
     N.check(_lib().vla_gemm_bf16_nt(_st(), C.byref(d)), "gemm_bf16_nt")
     if act == ACT_SWIGLU:
         return out, out2
@@ -134,6 +137,12 @@ def _nt_plan(d) -> Tuple[int, int]:
     kernel = _lib().vla_gemm_nt_plan(C.byref(d), -1, 0, C.byref(split))
     N.check(min(kernel, 0), "gemm_nt_plan")
     return kernel, split.value
+
+
+def gemm_plan(a: torch.Tensor, b: torch.Tensor, **kw) -> Tuple[int, int]:
+    """(kernel id N.KERNEL_NT_*, K slices) gemm_nt(a, b, **kw) would run with, under the calling thread's latency hint and the test
+    overrides in force: the library's own routing (vla_gemm_nt_plan) on the descriptor gemm_nt builds.  Nothing is launched."""
+    return gemm_nt(a, b, query_plan=True, **kw)
 
 
 class latency_hint:
@@ -163,11 +172,12 @@ def _splitk_ws(numel: int, device) -> torch.Tensor:
 
 
 def gemm_swiglu_bwd(d: torch.Tensor, w_downT: torch.Tensor, gu: torch.Tensor, out: Optional[torch.Tensor] = None,
-                    gu_group=None, ext=None, fp8=None) -> torch.Tensor:
+                    gu_group=None, ext=None, fp8=None, query_plan: bool = False):
     """dGU[M, 2I] = swiglu'(GU) * (d[M, D] @ w_downT[I, D]^T): the dH GEMM with the SwiGLU backward in its epilogue.
     gu_group=(rows per group, element stride between groups): ``gu`` is then the first row-group window of a larger
     tensor (row m of the product reads gu row (m // g) * stride + (m % g) * ld).
-    fp8=(d_scale [M], w_scale [I]) (with ext only): d and w_downT are uint8 e4m3 codes (quant_fp8_rows)."""
+    fp8=(d_scale [M], w_scale [I]) (with ext only): d and w_downT are uint8 e4m3 codes (quant_fp8_rows).
+    query_plan=True: no launch, returns (kernel id, K slices) of this call."""
     if fp8 is not None:
         assert ext is not None and d.dtype == torch.uint8 and w_downT.dtype == torch.uint8
         _chk_bf16(gu, out)
@@ -195,6 +205,8 @@ def gemm_swiglu_bwd(d: torch.Tensor, w_downT: torch.Tensor, gu: torch.Tensor, ou
         sa, sb = fp8
         assert sa.dtype == torch.float32 and sb.dtype == torch.float32 and sa.numel() == M and sb.numel() == I and sa.is_contiguous() and sb.is_contiguous()
         desc.fp8, desc.a_scale, desc.b_scale = 1, sa.data_ptr(), sb.data_ptr()
+    if query_plan:
+        return _nt_plan(desc)
     N.check(_lib().vla_gemm_bf16_nt(_st(), C.byref(desc)), "gemm_bf16_nt(swiglu_bwd)")
     return out
 
@@ -441,17 +453,20 @@ def attn_fwd(q, k, v, Hq: int, Hkv: int, dh: int, causal: bool, kmask=None, scal
 
 
 def attn_bwd(dout, q, k, v, o, lse, Hq: int, Hkv: int, dh: int, causal: bool, kmask=None,
-             scale: Optional[float] = None, dq=None, dk=None, dv=None, rope=None, row0: int = 0):
+             scale: Optional[float] = None, dq=None, dk=None, dv=None, rope=None, row0: int = 0, delta=None):
     """row0 > 0 (causal only, multiple of 32): live-row backward.  q/o/dout/dq are the [B, Sk - row0, ...] windows
     (views) of the rows >= row0, k/v the full [B, Sk, ...] tensors, lse the forward's full [B, Hq, Sk]; dk/dv are
-    produced for the keys >= row0 only ([B, Sk - row0, ...]).  Exactly the gradients the rows >= row0 receive."""
+    produced for the keys >= row0 only ([B, Sk - row0, ...]).  Exactly the gradients the rows >= row0 receive.
+    delta: the f32 [B, Hq, Sq] scratch of the backward (default: a new tensor)."""
     _chk_bf16(dout, q, k, v, o)
     B, Sq, Sk = q.shape[0], q.shape[1], k.shape[1]
     assert Sq + row0 == Sk or row0 == 0
     dq = torch.empty(B, Sq, Hq * dh, device=q.device, dtype=BF16) if dq is None else dq
     dk = torch.empty(B, Sk - row0, Hkv * dh, device=q.device, dtype=BF16) if dk is None else dk
     dv = torch.empty(B, Sk - row0, Hkv * dh, device=q.device, dtype=BF16) if dv is None else dv
-    delta = torch.empty(B, Hq, Sq, device=q.device, dtype=torch.float32)
+    if delta is None:
+        delta = torch.empty(B, Hq, Sq, device=q.device, dtype=torch.float32)
+    assert delta.dtype == torch.float32 and delta.is_contiguous() and delta.numel() >= B * Hq * Sq
     d = _attn_desc(q, k, v, o, lse, kmask, causal, scale if scale is not None else dh ** -0.5, Hq, Hkv, dh)
     if row0:
         assert causal and row0 % 32 == 0 and lse.shape == (B, Hq, Sk) and lse.is_contiguous()
