@@ -20,6 +20,7 @@ Layout decisions (MI355X-first, 288 GB HBM):
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from dataclasses import dataclass, field
@@ -381,7 +382,25 @@ class ViT:
 
 
 # ------------------------------------------------------------------------------------------------ frozen LLM
-class LLM:
+class _BufferSets:
+    """Mixin of the classes whose ``_alloc`` rebinds one set of activation buffers per shape (LLM, Head).  A captured graph holds the
+    addresses of the set it was captured on, so whoever keeps graphs of several shapes alive (VLAEngine.predict: one per (B, L))
+    takes ``buffer_set()`` after the capture and ``bind_buffer_set()`` before each replay: the tensors stay allocated and the
+    attributes the host reads afterwards (llm.HS, ...) are those of the replayed shape.  ``_track_alloc`` runs inside ``_alloc``: the
+    attributes an allocation rebinds are found by identity, their names accumulated over all allocations."""
+
+    def _track_alloc(self, before: dict):
+        names = getattr(self, "_buf_names", set())
+        self._buf_names = names | {k for k, v in self.__dict__.items() if k != "_buf_names" and (k not in before or before[k] is not v)}
+
+    def buffer_set(self) -> dict:
+        return {k: self.__dict__[k] for k in self._buf_names}
+
+    def bind_buffer_set(self, bufs: dict):
+        self.__dict__.update(bufs)
+
+
+class LLM(_BufferSets):
     """Qwen2 decoder stack (transformers Qwen2ForCausalLM; reference call site modeling_prismatic.py:644-655),
     forward with hidden-state taps and explicit dX backward (weights frozen: adapter-only fine-tune).  The trainers run the
     same layer bodies with themselves as the Linear and per-layer slots for what their gradient work reads (keep_per_layer)."""
@@ -421,6 +440,7 @@ class LLM:
     def _alloc(self, B: int, S: int):
         if self._buf_key == (B, S):
             return
+        before = dict(self.__dict__)
         c, dev = self.cfg, self.device
         n, M, D = c.n_layers, B * S, c.d
         W = (c.heads + 2 * c.kv_heads) * c.dh
@@ -442,6 +462,7 @@ class LLM:
                 self.G_n1, self.G_n2 = e(n, M, D), e(n, M, D)
         self.cos, self.sin = ops.rope_half_tables(S, c.dh, c.theta, dev)
         self._buf_key = (B, S)
+        self._track_alloc(before)
 
     def out_slot(self, i: int) -> int:
         """HS slot holding the output of layer i (0-based)."""
@@ -626,7 +647,7 @@ class FlatParams:
         return self.view(name, self.grad)
 
 
-class Head:
+class Head(_BufferSets):
     """L1RegressionActionHead + ProprioProjector + action_queries: the trainable set of the adapter-only fine-tune
     (action_heads.py:21-121; projectors.py:6-24; modeling_prismatic.py:375-376).  cfg.pro selects the block:
     MLPResNetBlock_Pro (:287-410, the reference default) - separate k/v projections per segment, RoPE on q/k - or the
@@ -757,6 +778,7 @@ class Head:
     def _alloc(self, B: int, Kt: int):
         if self._key == (B, Kt):
             return
+        before = dict(self.__dict__)
         D, nb, T, dev = self.D, self.nb, self.cfg.chunk, self.device
         Ka = NUM_TOKENS + 1
         e = lambda *s, dt=BF16: torch.empty(*s, device=dev, dtype=dt)
@@ -801,6 +823,8 @@ class Head:
         self.dpad = z(R, 64)
         self.rope_tab = ops.rope_inter_tables(max(T, Ka, Kt), D // self.H, dev)
         self._key = (B, Kt)
+        self._prep_key = None    # (the scatter indices of a backward were those of the buffers just replaced)
+        self._track_alloc(before)
 
     # ---- forward (action_heads.py:43-81, 111-121, 337-410) -------------------------------------------------
     def forward(self, HS: torch.Tensor, pos1: torch.Tensor, proprio: torch.Tensor, Np: int,
@@ -1090,32 +1114,49 @@ class VLAEngine(schedule.StepControls):
         self.forward_vlm(batch, for_training)
         return self.head.forward(self.llm.HS, self.pos1, batch["proprio"], self.Np, noise)
 
-    # ---- batch-1 inference (modeling_prismatic.py:892-972): forward only, captured per input shape ------------------
-    def predict(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
-        """Forward pass in phase "Inference" (no input perturbation) -> normalised actions [B, chunk, action_dim] bf16.
+    # ---- inference (modeling_prismatic.py:892-972; batched: OpenVLAForActionPrediction.predict_actions): forward only, captured per input shape
+    def predict(self, batch: Dict[str, torch.Tensor], latency_hint: Optional[bool] = None) -> torch.Tensor:
+        """Forward pass in phase "Inference" (no input perturbation) -> normalised actions [B, chunk, action_dim] bf16, for any B.
         At batch 1 every kernel is a handful of workgroups and the ~1000 launches form dependent chains, so the forward is
         cut into single-stream segments like the training step: one stream per vision backbone (they are independent),
         the LLM on the caller's stream with the action head trailing it on the head stream; each segment is a linear
-        hipGraph captured on first use of an input shape and replayed on static input buffers afterwards."""
-        key = (tuple(batch["input_ids"].shape), tuple(batch["pixel_values"].shape), batch["pixel_values"].dtype)
+        hipGraph captured on first use of an input shape and replayed on static input buffers afterwards.
+
+        B > 1 (a serving batch: right-padded rows, every sample's 64 action rows found from its labels by the mask / splice /
+        head-index kernels, attention masking the padding): one cache entry - graphs, static inputs and the LLM's and the head's
+        activation buffers - per (B, L, pixel shape).  The activation buffers are one set per shape and a graph holds the addresses
+        of the set it was captured on, so every entry keeps its set and rebinds it before a replay: calls of different shapes may
+        alternate, and llm.HS read after a call is that call's.  The cache therefore grows by one such set per shape served
+        (DESIGN, "Serving a batch"); callers bound the number of shapes by rounding L (input_stage.serve_layout).
+
+        latency_hint: capture under ops.latency_hint() - kernel variants for sub-chip launches on an idle chip (deep-ring GEMMs,
+        short-M skinny tiles, uneven split-K, key-split attention), baked into the graphs.  Default (None): at B == 1 only, where it
+        was measured; the setting is part of the cache key.  The warm-up always runs under the same
+        setting as the capture, so that every kernel the graphs use has been launched, its LDS attribute set and its split-K
+        workspace allocated before the capture."""
+        hint = batch["input_ids"].shape[0] == 1 if latency_hint is None else bool(latency_hint)
+        key = (tuple(batch["input_ids"].shape), tuple(batch["pixel_values"].shape), batch["pixel_values"].dtype, hint)
         cache = self._predict_graphs
         if os.environ.get("VLA_PREDICT_EAGER"):
             return self.forward(batch, None)
         self._ensure_streams()
         if key not in cache:
             static = {k: v.clone() for k, v in batch.items()}
-            # sub-chip launches on an idle chip (ops.latency_hint: deep-ring GEMMs, short-M skinny tiles, uneven split-K, key-split
-            # attention - baked into the graphs).  The warm-up runs under the hint too, so that every kernel the graphs use has been
-            # launched, its LDS attribute set and its split-K workspace allocated before the capture.
-            with ops.latency_hint():
+            with (ops.latency_hint() if hint else contextlib.nullcontext()):
                 for _ in range(2):
                     self.forward(static, None)
                 torch.cuda.synchronize()
                 segs = self._predict_segments(static)
                 graphs = schedule.capture(segs, {}, self._cap_stream)
             torch.cuda.synchronize()
-            cache[key] = (graphs, static, segs)
-        graphs, static, segs = cache[key]
+            bound = dict(llm=self.llm.buffer_set(), head=self.head.buffer_set(),
+                         eng={k: getattr(self, k) for k in ("B", "S", "Np", "feats", "patches", "qidx0", "pos0", "cnt0", "pos1", "cnt1", "_pred_out")},
+                         hint=hint)
+            cache[key] = (graphs, static, segs, bound)
+        graphs, static, segs, bound = cache[key]
+        self.llm.bind_buffer_set(bound["llm"])
+        self.head.bind_buffer_set(bound["head"])
+        self.__dict__.update(bound["eng"])
         for k, v in batch.items():
             static[k].copy_(v)
         self.head.refresh_forward_operands()     # parameters may have changed since the capture (no-op when fresh)

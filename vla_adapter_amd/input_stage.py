@@ -142,9 +142,51 @@ def collate_layout(prompt_lens: Sequence[int], max_len: int, num_tokens: int = N
     return off, min(max(rows), max_len)
 
 
+def serve_layout(prompt_lens: Sequence[int], len_multiple: int = 32, num_tokens: int = NUM_TOKENS) -> Tuple[List[int], int]:
+    """Host side of ``GPUInputStage.serve_tokens``, from the prompt lengths alone: the offset table [B + 1] of the concatenated prompts
+    and the batch's token length L = the longest row - its whole prompt, the ``num_tokens`` placeholders and the stop id
+    (prepare_inference_inputs) - rounded up to ``len_multiple``.  32 is the granularity live_row0 already uses: a stream of calls
+    whose longest prompts differ lands on few captured shapes."""
+    if len_multiple < 1:
+        raise ValueError("serve_layout: len_multiple must be at least 1")
+    off = [0]
+    for n in prompt_lens:
+        off.append(off[-1] + int(n))
+    longest = max(int(n) for n in prompt_lens) + num_tokens + 1
+    return off, -(-longest // len_multiple) * len_multiple
+
+
+def serve_prompt_lens(prompt_ids) -> Optional[List[int]]:
+    """The prompt lengths where the host knows them - id lists, or (flat, offsets) tensors with the offsets on the host - else None."""
+    if isinstance(prompt_ids, (tuple, list)) and len(prompt_ids) == 2 and all(isinstance(t, torch.Tensor) for t in prompt_ids):
+        return None if prompt_ids[1].is_cuda else prompt_ids[1].diff().tolist()
+    return [len(r) for r in prompt_ids]
+
+
+def serve_check(prompt_ids, L: Optional[int] = None, len_multiple: int = 32) -> Tuple[Optional[List[int]], Optional[int]]:
+    """Host-side validation of a serving batch's prompts -> (offsets or None, L).  Known lengths: ValueError on an empty prompt or
+    one that does not fit L (default serve_layout's).  Offsets on the device: L is required (nothing is read back)."""
+    lens = serve_prompt_lens(prompt_ids)
+    if lens is None:
+        if L is None:
+            raise ValueError("serve_tokens: prompt offsets on the device need an explicit L (the default would read them back)")
+        return None, int(L)
+    if len(lens) < 1 or min(lens) < 1:
+        raise ValueError("serve_tokens: every sample needs a prompt of at least one id")
+    off, L_nat = serve_layout(lens, len_multiple)
+    L = L_nat if L is None else int(L)
+    if max(lens) + NUM_TOKENS + 1 > L:
+        raise ValueError(f"serve_tokens: a prompt of {max(lens)} ids needs L >= {max(lens) + NUM_TOKENS + 1}, got L = {L}")
+    return off, L
+
+
+PAD_TOKEN_ID = 151643                               # Qwen2.5's <|endoftext|>, the processor's pad id
+SERVE_STATS_KINDS = {"bounds": ("min", "max"), "bounds_q99": ("q01", "q99")}     # openvla_utils.py:682-687, modeling_prismatic.py:787-796
+
+
 class GPUInputStage:
     def __init__(self, device="cuda", tokenizer_len: int = 151643, n_bins: int = 256, min_action: float = -1.0, max_action: float = 1.0,
-                 pad_token_id: int = 151643, model_max_length: int = 2048, backbones: Sequence[str] = ("siglip",),
+                 pad_token_id: int = PAD_TOKEN_ID, model_max_length: int = 2048, backbones: Sequence[str] = ("siglip",),
                  out_dtype=torch.bfloat16, image_size: int = 224):
         self.device, self.tokenizer_len, self.pad, self.max_len = device, tokenizer_len, pad_token_id, model_max_length
         self.lo, self.hi = float(min_action), float(max_action)
@@ -298,6 +340,61 @@ class GPUInputStage:
         if x.shape[-1] != low.numel():
             raise ValueError(f"last dimension {x.shape[-1]} does not match the statistics' {low.numel()}")
         return ops.normalize_bounds(x, low, high, mask, zero)
+
+    def serve_tokens(self, prompt_ids, L: Optional[int] = None, len_multiple: int = 32) -> Dict[str, torch.Tensor]:
+        """The batch of prepare_inference_inputs for B prompts of different lengths, right-padded to L, in one launch (vla_serve_tokens):
+        dict(input_ids, labels int64 [B, L], attention_mask bool [B, L], hid_row int32 [B], row_ok u8 [B]).  prompt_ids: list of id lists, or
+        (prompt_flat int64 [n], prompt_off int32 [B + 1]) tensors.  L: static token length; default serve_layout's, from the prompt
+        lengths on the host - offsets already on the device therefore need L (nothing is read back, exactly as collate() has it), and a
+        row that is empty or does not fit is then reported by row_ok alone.  Host-side lengths are checked here: ValueError."""
+        off_l, L = serve_check(prompt_ids, L, len_multiple)
+        if isinstance(prompt_ids, (tuple, list)) and len(prompt_ids) == 2 and all(isinstance(t, torch.Tensor) for t in prompt_ids):
+            flat, off = prompt_ids
+        else:
+            flat = torch.tensor([t for r in prompt_ids for t in r], dtype=torch.int64)
+            off = torch.tensor(off_l, dtype=torch.int32)
+        flat, off = flat.to(self.device, torch.int64).contiguous(), off.to(self.device, torch.int32).contiguous()
+        from .constants import ACTION_TOKEN_BEGIN_IDX, STOP_INDEX
+        ids, labels, am, hid_row, row_ok = ops.serve_tokens(flat, off, int(L), pad_id=self.pad, num_tokens=NUM_TOKENS, fill_id=1,
+                                                            stop_id=STOP_INDEX, action_label=ACTION_TOKEN_BEGIN_IDX + 1, ignore_index=IGNORE_INDEX)
+        return dict(input_ids=ids, labels=labels, attention_mask=am.view(torch.bool), hid_row=hid_row, row_ok=row_ok)
+
+    def _serve_stats(self, stats: dict, kind: str):
+        """(low f64 [D], high f64 [D], mask u8 [D] or None) on the device, uploaded once per (stats object, kind)."""
+        if kind not in SERVE_STATS_KINDS:
+            raise ValueError(f"Unsupported action/proprio normalization type {kind!r}: known {sorted(SERVE_STATS_KINDS)}")
+        key = (id(stats), kind, "serve")
+        if key not in self._stats:
+            lo_k, hi_k = SERVE_STATS_KINDS[kind]
+            if lo_k not in stats or hi_k not in stats:
+                raise KeyError(f"normalisation type {kind!r} needs {lo_k!r} and {hi_k!r} in the statistics, got {sorted(stats)}")
+            f64 = lambda v: torch.as_tensor(np.asarray(v, dtype=np.float64)).to(self.device)
+            mask = torch.as_tensor(np.asarray(stats["mask"], dtype=bool).astype(np.uint8)).to(self.device) if "mask" in stats else None
+            self._stats[key] = (stats, f64(stats[lo_k]), f64(stats[hi_k]), mask)               # (stats itself: its id stays taken)
+        return self._stats[key][1:]
+
+    def normalize_proprio(self, x, stats: dict, kind: str = "bounds_q99") -> torch.Tensor:
+        """The evaluator's normalize_proprio (experiments/robot/openvla_utils.py:671-701) on the device: raw proprio [..., D], f32 or f64
+        (tensor or ndarray) -> f32, clip(mask ? 2 (x - low) / (high - low + 1e-8) - 1 : x, -1, 1) in f64, rounded once.  Unlike
+        normalize() - the training pipeline's - it clips the unmasked dimensions too and zeroes none.  stats: norm_stats[key]["proprio"]."""
+        low, high, mask = self._serve_stats(stats, kind)
+        x = torch.as_tensor(x)
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float64)
+        x = x.to(self.device).contiguous()
+        if x.shape[-1] != low.numel():
+            raise ValueError(f"last dimension {x.shape[-1]} does not match the statistics' {low.numel()}")
+        return ops.normalize_proprio_serve(x, low, high, mask)
+
+    def unnormalize_actions(self, pred: torch.Tensor, stats: dict, kind: str = "bounds_q99", row_ok: Optional[torch.Tensor] = None,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """_unnormalize_actions (modeling_prismatic.py:784-805) on the device: the head's bf16 predictions [B, chunk, action_dim] -> f64 of
+        the same shape, bit-identical to the host function on pred.float(); rows with row_ok == 0 become NaN.  stats:
+        norm_stats[key]["action"]."""
+        low, high, mask = self._serve_stats(stats, kind)
+        if pred.shape[-1] != low.numel():
+            raise ValueError(f"last dimension {pred.shape[-1]} does not match the statistics' {low.numel()}")
+        return ops.unnormalize_actions(pred, low, high, mask, row_ok, out)
 
     def collate(self, frames_u8, prompt_ids, actions: torch.Tensor, proprio: Optional[torch.Tensor] = None, *, action_stats: Optional[dict] = None,
                 proprio_stats: Optional[dict] = None, L: Optional[int] = None, seed: int = 0, rank: int = 0, step: int = 0,

@@ -55,6 +55,7 @@ class OpenVLAForActionPrediction:
         self.llm_dim = cfg.llm.d
         self.norm_stats = norm_stats or {}
         self.training = True
+        self.serve_latency_hint = None   # predict_actions: None = the engine's default per batch size; True / False force it (tools/bench_serving.py)
 
     @property
     def action_queries(self) -> torch.Tensor:       # nn.Embedding(64, D).weight in the reference (:375-376)
@@ -126,6 +127,18 @@ class OpenVLAForActionPrediction:
         labels[:, -1] = K.STOP_INDEX
         return ids, am, labels
 
+    def _load_head(self, action_head, proprio_projector):
+        """The mirrors' parameters into the engine, once per (objects, versions); ``True``: the engine's own stay."""
+        eng = self.engine
+        if action_head is not True:
+            sd = action_head.state_dict()
+            psd = proprio_projector.state_dict() if (proprio_projector is not None and proprio_projector is not True) else {
+                k: v for k, v in eng.head.proprio_views().items()}
+            key = (id(action_head), id(proprio_projector), getattr(action_head, "_version", 0), getattr(proprio_projector, "_version", 0))
+            if getattr(self, "_loaded_head", None) != key:
+                eng.head.load_state_dicts(sd, psd)
+                self._loaded_head = key
+
     def predict_action(self, input_ids=None, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
                        noisy_action_projector=None, use_film: bool = False, **kwargs):
         """Same call as the reference (``pixel_values`` / ``attention_mask`` in kwargs, batch 1): returns
@@ -140,14 +153,7 @@ class OpenVLAForActionPrediction:
             raise NotImplementedError("discrete-token action prediction needs the lm_head (SURVEY 8f-4); pass the L1 regression head")
         assert input_ids.shape[0] == 1, "Generation with batch size > 1 is not currently supported!"     # :700-703
         eng, dev = self.engine, self.device
-        if action_head is not True:
-            sd = action_head.state_dict()
-            psd = proprio_projector.state_dict() if (proprio_projector is not None and proprio_projector is not True) else {
-                k: v for k, v in eng.head.proprio_views().items()}
-            key = (id(action_head), id(proprio_projector), getattr(action_head, "_version", 0), getattr(proprio_projector, "_version", 0))
-            if getattr(self, "_loaded_head", None) != key:
-                eng.head.load_state_dicts(sd, psd)
-                self._loaded_head = key
+        self._load_head(action_head, proprio_projector)
         ids, am, labels = self.prepare_inference_inputs(input_ids.to(dev), kwargs["attention_mask"].to(dev))
         use_proprio = proprio_projector is not None and proprio is not None
         assert use_proprio, "the regression head dereferences proprio and its projector (action_heads.py:53-54)"
@@ -161,6 +167,68 @@ class OpenVLAForActionPrediction:
         from . import constants as K
         hid = eng.llm.HS[n][:, s0:s0 + K.NUM_TOKENS].reshape(1, 1, K.NUM_TOKENS, -1)
         return self._unnormalize_actions(normalized, unnorm_key), hid
+
+    # ---- batched serving: B observations with prompts of different lengths in one device pass ------------------------------------
+    def input_stage(self):
+        """The GPUInputStage this model serves through (created on first use): pad id = the tokenizer's, or the last id of a
+        vocabulary too small to hold it (the plumbing-size configurations); Normalize per backbone from the vision config."""
+        if getattr(self, "_stage", None) is None:
+            from . import input_stage as IS
+            pad = IS.PAD_TOKEN_ID
+            vocab = self.cfg.llm.vocab
+            self._stage = IS.GPUInputStage(self.device, pad_token_id=pad if pad < vocab else vocab - 1, backbones=IS.backbone_norms(self.cfg),
+                                           image_size=self.cfg.vit[0].img)
+        return self._stage
+
+    def predict_actions(self, prompt_ids, *, pixel_values=None, frames_u8=None, center_crop: bool = False, proprio=None,
+                        proprio_normalized: bool = False, unnorm_key=None, action_head=True, proprio_projector=True, L=None,
+                        return_tensors: bool = False, use_film: bool = False, noisy_action_projector=None):
+        """predict_action for a batch: B observations, prompts of different lengths, one forward.  Returns (un-normalised actions
+        float64 ndarray [B, chunk, action_dim], action hidden states [B, 1, 64, D] of the last layer) - row b is what
+        predict_action returns for sample b alone (same layout per row; the bf16 sums of the head run in a batch-dependent order, so
+        the values agree to bf16 accuracy, and bit for bit at B == 1 with L = P + 65).
+
+        prompt_ids: list of id lists (the processor's output per sample, untrimmed), or (prompt_flat int64 [n], prompt_off int32
+        [B + 1]) tensors; rows are right-padded to L (default: the longest row, P + 65, rounded up to a multiple of 32 -
+        input_stage.serve_layout - so that a stream of calls replays few captured shapes).  Host-side prompts with an empty row or
+        one that does not fit L raise ValueError; with offsets already on the device nothing is read back, L must be given, and such a
+        row comes back as NaN actions (row_ok, include/vla_serve.h).
+        Exactly one of pixel_values ([B, C, H, W], already processed) / frames_u8 (raw uint8 frames as GPUInputStage.pixels takes
+        them; center_crop: the evaluator's crop first).  Frames are resized by the Pillow-bicubic path of the input stage
+        ("resize-naive", the processor's own); the evaluator's TF lanczos3 resize after a JPEG round trip
+        (experiments/robot/openvla_utils.py: resize_image_for_policy) is NOT reproduced.
+        proprio [B, Pd]: raw, normalised on the device with norm_stats[key]["proprio"] (the evaluator's normalize_proprio), or
+        already normalised (proprio_normalized=True).  action_head / proprio_projector: as in predict_action.
+        return_tensors: device tensors (actions f64 [B, chunk, action_dim]) and no host synchronisation on a replayed shape."""
+        from . import constants as K
+        if use_film or noisy_action_projector is not None:
+            raise NotImplementedError("FiLM / diffusion heads are outside the accelerated path")
+        if action_head is None:
+            raise NotImplementedError("discrete-token action prediction needs the lm_head (SURVEY 8f-4); pass the L1 regression head")
+        if (pixel_values is None) == (frames_u8 is None):
+            raise ValueError("predict_actions: pass exactly one of pixel_values / frames_u8")
+        if proprio is None or proprio_projector is None:
+            raise ValueError("predict_actions: the regression head dereferences proprio and its projector (action_heads.py:53-54)")
+        from . import input_stage as IS
+        IS.serve_check(prompt_ids, L)                                                # ValueError on a bad host-side prompt, before any work
+        eng, dev, stage = self.engine, self.device, self.input_stage()
+        tok = stage.serve_tokens(prompt_ids, L)
+        self._load_head(action_head, proprio_projector)
+        key = self._check_unnorm_key(self.norm_stats, unnorm_key)
+        kind = K.ACTION_PROPRIO_NORMALIZATION_TYPE
+        B = tok["input_ids"].shape[0]
+        px = stage.pixels(frames_u8, center_crop=center_crop) if frames_u8 is not None else pixel_values.to(dev).contiguous()
+        if proprio_normalized:
+            import numpy as np
+            pr = torch.as_tensor(np.asarray(proprio) if not isinstance(proprio, torch.Tensor) else proprio).to(dev, torch.float32)
+        else:
+            pr = stage.normalize_proprio(proprio, self.norm_stats[key]["proprio"], kind)
+        batch = dict(input_ids=tok["input_ids"], labels=tok["labels"], attention_mask=tok["attention_mask"], pixel_values=px,
+                     proprio=pr.reshape(B, -1))
+        pred = eng.predict(batch, latency_hint=self.serve_latency_hint)              # [B, chunk, action_dim] bf16
+        actions = stage.unnormalize_actions(pred, self.get_action_stats(key), kind, row_ok=tok["row_ok"])
+        hid = ops.serve_gather_hidden(eng.llm.HS[self.cfg.llm.n_layers], tok["hid_row"], self.cfg.n_patches, K.NUM_TOKENS)
+        return (actions, hid) if return_tensors else (actions.cpu().numpy(), hid)
 
 
 @dataclass

@@ -150,6 +150,17 @@ _PROTOS = {
 # symbols include/vla_native.h declares (checked by tests/test_abi.py without touching a GPU)
 ABI_SYMBOLS = sorted(list(_PROTOS) + ["vla_last_error"])
 
+
+# the serving entry points (include/vla_serve.h, csrc/serve.hip): a table of their own, bound beside _PROTOS - the training ABI above
+# (its header, its version) does not move for them (tests/test_serve_cpu.py checks header, table and library against each other)
+SERVE_PROTOS = {
+    "vla_serve_tokens": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L], _I),
+    "vla_normalize_proprio_serve": ([_P, _P, _I, _P, _L, _I, _P, _P, _P], _I),
+    "vla_unnormalize_actions": ([_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P], _I),
+    "vla_serve_gather_hidden": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I], _I),
+}
+SERVE_SYMBOLS = sorted(SERVE_PROTOS)
+
 _lib = None
 
 
@@ -163,7 +174,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in _PROTOS.items():
+    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()):
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

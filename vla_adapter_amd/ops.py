@@ -950,3 +950,70 @@ def collate_tokens(prompt_flat: torch.Tensor, prompt_off: torch.Tensor, actions_
                                       _p(bins_f64), _p(ids), _p(labels), _p(am), B, n_act, L, bins_f64.numel(), lo, hi, tokenizer_len, pad_id,
                                       ignore_index, num_tokens, int(seed) & (2 ** 64 - 1), int(rank), int(step)), "collate_tokens")
     return ids, labels, am
+
+
+# ---- serving a batch (include/vla_serve.h, csrc/serve.hip) --------------------------------------------------------------------------
+def serve_tokens(prompt_flat: torch.Tensor, prompt_off: torch.Tensor, L: int, *, pad_id: int, num_tokens: int = 64, fill_id: int = 1,
+                 stop_id: int = 2, action_label: int = 151387, ignore_index: int = -100):
+    """vla_serve_tokens: prompt_flat int64 [n] + prompt_off int32 [B + 1] -> (input_ids int64 [B, L], labels int64 [B, L], attention_mask
+    u8 [B, L], hid_row int32 [B], row_ok u8 [B]): the batch of prepare_inference_inputs, right-padded, one launch, nothing read back."""
+    B, dev = prompt_off.numel() - 1, prompt_off.device
+    assert prompt_flat.dtype == torch.int64 and prompt_flat.is_contiguous() and prompt_flat.dim() == 1
+    assert prompt_off.dtype == torch.int32 and prompt_off.is_contiguous() and prompt_off.dim() == 1 and B >= 1
+    assert prompt_flat.device == dev and prompt_off.is_cuda
+    if L < num_tokens + 2:
+        raise ValueError(f"serve_tokens: L = {L} cannot hold one prompt id, {num_tokens} placeholders and the stop id")
+    ids, labels = torch.empty(B, L, device=dev, dtype=torch.int64), torch.empty(B, L, device=dev, dtype=torch.int64)
+    am = torch.empty(B, L, device=dev, dtype=torch.uint8)
+    hid_row, row_ok = torch.empty(B, device=dev, dtype=torch.int32), torch.empty(B, device=dev, dtype=torch.uint8)
+    N.check(_lib().vla_serve_tokens(_st(), _p(prompt_flat) if prompt_flat.numel() else None, _p(prompt_off), prompt_flat.numel(), _p(ids),
+                                    _p(labels), _p(am), _p(hid_row), _p(row_ok), B, int(L), num_tokens, fill_id, stop_id, action_label, pad_id,
+                                    ignore_index), "serve_tokens")
+    return ids, labels, am, hid_row, row_ok
+
+
+def _chk_stats64(D, dev, low, high, mask):
+    for t, dt in ((low, torch.float64), (high, torch.float64), (mask, torch.uint8)):
+        assert t is None or (t.dtype == dt and t.is_contiguous() and t.numel() == D and t.device == dev), "per-dimension statistics: [D] on the operand's device"
+
+
+def normalize_proprio_serve(x: torch.Tensor, low: torch.Tensor, high: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vla_normalize_proprio_serve: the evaluator's normalize_proprio on x f32 / f64 [..., D] -> f32; low / high f64 [D], mask u8 [D] or None."""
+    D = x.shape[-1]
+    assert x.is_cuda and x.dtype in (torch.float32, torch.float64) and x.is_contiguous() and x.numel() > 0
+    _chk_stats64(D, x.device, low, high, mask)
+    out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    N.check(_lib().vla_normalize_proprio_serve(_st(), _p(x), int(x.dtype == torch.float64), _p(out), x.numel(), D, _p(low), _p(high), _p(mask)),
+            "normalize_proprio_serve")
+    return out
+
+
+def unnormalize_actions(pred: torch.Tensor, low: torch.Tensor, high: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                        row_ok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vla_unnormalize_actions: pred bf16 [B, chunk, Da] (or [B, chunk * Da]; rows may be strided) -> f64 of the same shape, the bits of
+    OpenVLAForActionPrediction._unnormalize_actions; rows whose row_ok (u8 [B]) is 0 become NaN."""
+    _chk_bf16(pred)
+    B, Da = pred.shape[0], low.numel()
+    p2 = pred.reshape(B, -1) if pred.dim() != 2 else pred
+    assert p2.stride(1) == 1 and p2.shape[1] % Da == 0
+    _chk_stats64(Da, pred.device, low, high, mask)
+    assert row_ok is None or (row_ok.dtype == torch.uint8 and row_ok.is_contiguous() and row_ok.numel() == B and row_ok.device == pred.device)
+    if out is None:
+        out = torch.empty(pred.shape, device=pred.device, dtype=torch.float64)
+    o2 = out.view(B, -1) if out.dim() != 2 else out
+    assert out.dtype == torch.float64 and o2.stride(1) == 1 and o2.shape == p2.shape
+    N.check(_lib().vla_unnormalize_actions(_st(), _p(p2), _p(o2), B, p2.shape[1], Da, p2.stride(0), o2.stride(0), _p(low), _p(high), _p(mask),
+                                           _p(row_ok)), "unnormalize_actions")
+    return out
+
+
+def serve_gather_hidden(hs: torch.Tensor, hid_row: torch.Tensor, Np: int, T: int = 64, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vla_serve_gather_hidden: hs bf16 [B, S, D] (one hidden state) + hid_row int32 [B] -> [B, 1, T, D]: rows [Np + hid_row[b], +T) of sample b."""
+    _chk_bf16(hs)
+    B, S, D = hs.shape
+    assert hs.stride(2) == 1 and hid_row.dtype == torch.int32 and hid_row.is_contiguous() and hid_row.numel() == B and hid_row.device == hs.device
+    if out is None:
+        out = torch.empty(B, 1, T, D, device=hs.device, dtype=BF16)
+    assert out.is_contiguous() and out.numel() == B * T * D and out.dtype == BF16
+    N.check(_lib().vla_serve_gather_hidden(_st(), _p(hs), _p(hid_row), _p(out), B, S, Np, T, D, hs.stride(0), hs.stride(1)), "serve_gather_hidden")
+    return out
