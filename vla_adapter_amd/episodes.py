@@ -1,0 +1,295 @@
+"""Device-resident demonstration episodes: the part of the reference's batch producer that decides WHICH transitions form a batch.
+
+The reference's RLDS stage cuts every episode into windows of one observation plus ``NUM_ACTIONS_CHUNK - 1`` future actions
+(``chunk_act_obs``, prismatic/vla/datasets/rlds/traj_transforms.py:14-57, configured in prismatic/vla/datasets/datasets.py:183-189),
+shuffles all windows of the dataset, and computes the q01 / q99 statistics both training and ``predict_action`` need
+(``get_dataset_statistics``, rlds/utils/data_utils.py:176-262).  ``EpisodeStore`` loads the episodes once, keeps them on the device
+and draws each step's batch with two kernels (csrc/episodes.hip, include/vla_episodes.h): ``vla_episode_sample`` picks the windows -
+shuffled, every window exactly once per epoch across all ranks and steps - and ``vla_episode_gather`` copies them into the raw-batch
+dict ``GPUInputStage.collate`` consumes.  No host work per step: nothing is read back, synchronised or, after the first call,
+allocated.
+
+An episode file is a ``.pt`` dict, or a directory of them (the shards are concatenated in sorted order):
+
+  frames_u8     uint8   [T, n_img, H, W, 3]   all episodes back to back
+  actions_raw   float32 [T, A]
+  proprio_raw   float32 [T, Pd]
+  episode_off   int64   [E + 1]               row offsets of the episodes
+  prompt_flat   int64   [n]                   one tokenised prompt per episode (the instruction is constant within an episode)
+  prompt_off    int32   [E + 1]
+  dataset_name  str, optional
+  action_mask   bool    [A], optional         the reference's action_normalization_mask
+
+The sampling rule is stated here in plain Python - ``sample_position``, ``permute_index``, ``locate`` - and is the specification the
+kernel is tested against, bit for bit.
+"""
+from __future__ import annotations
+
+import os
+from pathlib import Path
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .constants import NUM_ACTIONS_CHUNK
+from .finetune import RAW_BATCH_KEYS                # what sample() returns: the raw batch finetune.batch_stream collates
+
+EPISODE_KEYS = ("frames_u8", "actions_raw", "proprio_raw", "episode_off", "prompt_flat", "prompt_off")
+EPISODE_STREAM = 0xE9150DE5A391E        # csrc/episodes.hip: keeps the shuffle apart from the augmentation's and the collator's draws
+MAX_BATCH = 1024                        # vla_episode_sample is one workgroup
+_M64 = (1 << 64) - 1
+
+
+# ---------------------------------------------------------------------------------------------------------------- the sampling rule
+def splitmix64_key(seed: int, idx: int) -> int:
+    """csrc/common.h: splitmix64 finaliser of (seed + idx * golden ratio), in 64-bit wrap-around arithmetic."""
+    z = (seed + idx * 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def sample_position(B: int, rank: int, world: int, step: int, b: int) -> int:
+    """Where sample b of the batch of (rank, step) stands in the endless sequence of draws: the ranks' batches of one step are
+    consecutive, so positions [k N, (k + 1) N) - epoch k - are shared out over all ranks and steps without gap or overlap."""
+    return (step * world + rank) * B + b
+
+
+def epoch_key(seed: int, epoch: int) -> int:
+    return splitmix64_key((seed & _M64) ^ EPISODE_STREAM, epoch)
+
+
+def _feistel4(x: int, key: int, half: int) -> int:
+    """Four rounds (L, R) -> (R, L ^ F(R)) over two halves of ``half`` bits: a bijection on [0, 4^half) whatever F is, since every
+    round is undone by (L, R) -> (R ^ F(L), L)."""
+    mask = (1 << half) - 1
+    l, r = x >> half, x & mask
+    for rnd in range(4):
+        l, r = r, l ^ (splitmix64_key(splitmix64_key(key, rnd), r) & mask)
+    return (l << half) | r
+
+
+def permute_index(i: int, N: int, key: int) -> int:
+    """A keyed bijection on [0, N): a balanced Feistel network over 2 * ceil(bits(N - 1) / 2) bits, results >= N walked on along
+    their cycle (cycle-walking).  It needs no table of N entries, so every sample of every rank computes its own index.
+
+    Termination: i lies inside [0, N); the walk follows the cycle through i of a permutation of the domain [0, 4^half), so it comes
+    back to i - an element of [0, N) - after at most 4^half steps, and stops at the first element below N it meets.  The domain is
+    smaller than 4 N (N > 2^(bits - 1) and 2 * half <= bits + 1), so a walk takes fewer than four passes on average."""
+    if not 0 <= i < N:
+        raise ValueError(f"permute_index: i = {i} outside [0, {N})")
+    if N == 1:
+        return 0
+    half = max(((N - 1).bit_length() + 1) // 2, 1)
+    y = _feistel4(i, key, half)
+    while y >= N:
+        y = _feistel4(y, key, half)
+    return y
+
+
+def locate(j: int, valid_off) -> Tuple[int, int]:
+    """Window j of the dataset -> (episode, step inside it): the episode with valid_off[e] <= j < valid_off[e + 1], by the kernel's
+    binary search (the largest e below E with valid_off[e] <= j: episodes without a window are stepped over)."""
+    lo, hi = 0, len(valid_off) - 2
+    while lo < hi:
+        mid = lo + (hi - lo + 1) // 2
+        if int(valid_off[mid]) <= j:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo, j - int(valid_off[lo])
+
+
+def sample_windows(valid_off, B: int, seed: int, rank: int, world: int, step: int) -> List[Tuple[int, int]]:
+    """The (episode, step inside it) of every sample of the batch of (rank, step): what vla_episode_sample computes."""
+    N = int(valid_off[-1])
+    out = []
+    for b in range(B):
+        pos = sample_position(B, rank, world, step, b)
+        out.append(locate(permute_index(pos % N, N, epoch_key(seed, pos // N)), valid_off))
+    return out
+
+
+def window_rows(row: int, episode_end: int, chunk: int) -> List[int]:
+    """The action rows of the window that starts at global row ``row`` of an episode ending at ``episode_end`` (exclusive):
+    chunk_act_obs' minimum(index, goal_timestep) - it cannot bind for a start the sampler chose."""
+    return [min(row + k, episode_end - 1) for k in range(chunk)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- statistics
+def dataset_statistics(actions: np.ndarray, proprio: np.ndarray, num_trajectories: int, action_mask=None) -> dict:
+    """get_dataset_statistics (rlds/utils/data_utils.py:231-256) on the float32 arrays, written as the reference writes it."""
+    def part(x):
+        return {"mean": x.mean(0).tolist(), "std": x.std(0).tolist(), "max": x.max(0).tolist(), "min": x.min(0).tolist(),
+                "q01": np.quantile(x, 0.01, axis=0).tolist(), "q99": np.quantile(x, 0.99, axis=0).tolist()}
+    meta = {"action": part(actions), "proprio": part(proprio), "num_transitions": int(actions.shape[0]),
+            "num_trajectories": int(num_trajectories)}
+    if action_mask is not None:
+        meta["action"]["mask"] = [bool(m) for m in np.asarray(action_mask).tolist()]
+    return meta
+
+
+# ---------------------------------------------------------------------------------------------------------------- the store
+def _check_shard(d: dict, where: str) -> None:
+    """ValueError naming the key for every table that does not fit the others."""
+    if not isinstance(d, dict):
+        raise ValueError(f"{where}: an episode file is a dict of {EPISODE_KEYS}")
+    for k in EPISODE_KEYS:
+        if k not in d or not isinstance(d[k], torch.Tensor):
+            raise ValueError(f"{where}: {k} is missing (an episode file carries {EPISODE_KEYS})")
+    fr, act, pr, eo, pf, po = (d[k] for k in EPISODE_KEYS)
+    if fr.dtype != torch.uint8 or fr.dim() != 5 or fr.shape[-1] != 3 or fr.shape[0] < 1:
+        raise ValueError(f"{where}: frames_u8 must be uint8 [T, n_img, H, W, 3] with T >= 1, got {fr.dtype} {tuple(fr.shape)}")
+    T = fr.shape[0]
+    if act.dtype != torch.float32 or act.dim() != 2 or act.shape[0] != T or act.shape[1] < 1:
+        raise ValueError(f"{where}: actions_raw must be float32 [T = {T}, A], got {act.dtype} {tuple(act.shape)}")
+    if pr.dtype != torch.float32 or pr.dim() != 2 or pr.shape[0] != T or pr.shape[1] < 1:
+        raise ValueError(f"{where}: proprio_raw must be float32 [T = {T}, Pd], got {pr.dtype} {tuple(pr.shape)}")
+    if eo.dtype != torch.int64 or eo.dim() != 1 or eo.numel() < 2:
+        raise ValueError(f"{where}: episode_off must be int64 [E + 1] with E >= 1, got {eo.dtype} {tuple(eo.shape)}")
+    E = eo.numel() - 1
+    if int(eo[0]) != 0 or int(eo[-1]) != T or bool((eo.diff() < 0).any()):
+        raise ValueError(f"{where}: episode_off must rise from 0 to T = {T} without a step back, got {eo.tolist()[:8]} ... {int(eo[-1])}")
+    if pf.dtype != torch.int64 or pf.dim() != 1:
+        raise ValueError(f"{where}: prompt_flat must be int64 [n], got {pf.dtype} {tuple(pf.shape)}")
+    if po.dtype != torch.int32 or po.dim() != 1 or po.numel() != E + 1:
+        raise ValueError(f"{where}: prompt_off must be int32 [E + 1 = {E + 1}] (one prompt per episode), got {po.dtype} {tuple(po.shape)}")
+    if int(po[0]) != 0 or int(po[-1]) != pf.numel() or bool((po.diff() < 0).any()):
+        raise ValueError(f"{where}: prompt_off must rise from 0 to len(prompt_flat) = {pf.numel()} without a step back")
+    if "action_mask" in d:
+        m = torch.as_tensor(d["action_mask"])
+        if m.dtype != torch.bool or tuple(m.shape) != (act.shape[1],):
+            raise ValueError(f"{where}: action_mask must be bool [A = {act.shape[1]}], got {m.dtype} {tuple(m.shape)}")
+    if "dataset_name" in d and not isinstance(d["dataset_name"], str):
+        raise ValueError(f"{where}: dataset_name must be a str")
+
+
+def valid_offsets(episode_off: torch.Tensor, chunk: int) -> torch.Tensor:
+    """int64 [E + 1]: prefix sum of max(len_e - (chunk - 1), 0), the windows each episode yields (traj_transforms.py:27:
+    effective_traj_len = traj_len - future_action_window_size; an episode shorter than the chunk yields none)."""
+    n = (episode_off.diff() - (chunk - 1)).clamp_(min=0)
+    return torch.cat([torch.zeros(1, dtype=torch.int64), n.cumsum(0)])
+
+
+class EpisodeStore:
+    """Episodes on the device; ``sample()`` draws one raw batch.  Build with ``EpisodeStore.load`` or ``EpisodeStore.from_dict``."""
+
+    def __init__(self, tables: dict, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, _where: str = "episode store"):
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        _check_shard(tables, _where)
+        self.device, self.chunk = device, int(chunk)
+        self.dataset_name = tables.get("dataset_name") or dataset_name or "episodes"
+        self.action_mask = torch.as_tensor(tables["action_mask"]).tolist() if "action_mask" in tables else None
+        act, pr, eo, po = tables["actions_raw"], tables["proprio_raw"], tables["episode_off"], tables["prompt_off"]
+        valid = valid_offsets(eo.cpu(), self.chunk)
+        self.N = int(valid[-1])
+        if self.N < 1:
+            raise ValueError(f"{_where}: no valid window - every one of the {eo.numel() - 1} episodes is shorter than the action chunk of "
+                             f"{self.chunk} steps (episode_off)")
+        self.T, self.E = int(act.shape[0]), int(eo.numel() - 1)
+        self.A, self.Pd = int(act.shape[1]), int(pr.shape[1])
+        self.frame_shape = tuple(tables["frames_u8"].shape[1:])
+        self.row_bytes = int(np.prod(self.frame_shape))
+        self.Pmax = int(po.diff().max())
+        self._stats = {self.dataset_name: dataset_statistics(act.cpu().numpy(), pr.cpu().numpy(), self.E, self.action_mask)}
+        self.valid_off_host = valid
+        dv = lambda t: t.to(device).contiguous()
+        self.frames_u8, self.actions_raw, self.proprio_raw = dv(tables["frames_u8"]), dv(act), dv(pr)
+        self.episode_off, self.valid_off = dv(eo), dv(valid)
+        self.prompt_flat, self.prompt_off = dv(tables["prompt_flat"]), dv(po)
+        self._out: Dict[int, dict] = {}
+
+    # ---- construction --------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_dict(cls, tables: dict, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None) -> "EpisodeStore":
+        return cls(tables, device, chunk, dataset_name)
+
+    @classmethod
+    def load(cls, path, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None) -> "EpisodeStore":
+        """``path``: a .pt episode file or a directory of them (concatenated in sorted order).  Validates the tables (ValueError that
+        names the key), moves everything to the device and builds valid_off; ``dataset_name``: used when the file names none."""
+        path = str(path)
+        files = sorted(str(p) for p in Path(path).glob("*.pt")) if os.path.isdir(path) else [path]
+        if not files:
+            raise FileNotFoundError(f"no .pt episode files under {path}")
+        shards = []
+        for f in files:
+            d = torch.load(f, weights_only=True, mmap=True)
+            _check_shard(d, f)
+            shards.append(d)
+        return cls(concat_shards(shards, files, device), device, chunk, dataset_name, _where=path)
+
+    # ---- the two products ----------------------------------------------------------------------------------------------------
+    def statistics(self) -> dict:
+        """The reference's get_dataset_statistics dict, keyed by the dataset's name: what --dataset_statistics_file would hold."""
+        return self._stats
+
+    def _buffers(self, B: int) -> dict:
+        if B not in self._out:
+            dev, e = self.device, torch.empty
+            self._out[B] = dict(ep=e(B, dtype=torch.int32, device=dev), row=e(B, dtype=torch.int64, device=dev),
+                                frames_u8=e((B,) + self.frame_shape, dtype=torch.uint8, device=dev),
+                                actions_raw=e(B, self.chunk, self.A, dtype=torch.float32, device=dev),
+                                proprio_raw=e(B, self.Pd, dtype=torch.float32, device=dev),
+                                prompt_flat=e(B * self.Pmax, dtype=torch.int64, device=dev),
+                                prompt_off=e(B + 1, dtype=torch.int32, device=dev))
+        return self._out[B]
+
+    def sample_indices(self, B: int, seed: int, rank: int, world: int, step: int):
+        """vla_episode_sample into the store's buffers of batch size B -> (ep int32 [B], row int64 [B], prompt_off int32 [B + 1])."""
+        from . import ops
+        if not 1 <= B <= MAX_BATCH:
+            raise ValueError(f"sample: the batch size must lie in [1, {MAX_BATCH}] (one workgroup draws the batch), got {B}")
+        if not (world >= 1 and 0 <= rank < world and step >= 0):
+            raise ValueError(f"sample: need 0 <= rank < world and step >= 0, got rank {rank}, world {world}, step {step}")
+        o = self._buffers(B)
+        ops.episode_sample(self.valid_off, self.episode_off, self.prompt_off, seed, rank, world, step, self.Pmax, o["ep"], o["row"], o["prompt_off"])
+        return o["ep"], o["row"], o["prompt_off"]
+
+    def sample(self, B: int, seed: int, rank: int = 0, world: int = 1, step: int = 0) -> dict:
+        """The raw batch of (rank, step): RAW_BATCH_KEYS on the device plus dataset_name, from the two kernels.  Every rank passes the
+        same seed.  The tensors are the store's own buffers of this batch size: the next call with the same B overwrites them (in
+        stream order), so consume - collate - a batch before drawing the next, or clone it."""
+        from . import ops
+        ep, row, off = self.sample_indices(B, seed, rank, world, step)
+        o = self._buffers(B)
+        ops.episode_gather(self.frames_u8, self.actions_raw, self.proprio_raw, self.episode_off, self.prompt_flat, self.prompt_off, ep, row, off,
+                           o["frames_u8"], o["actions_raw"], o["proprio_raw"], o["prompt_flat"], self.Pmax)
+        out = {k: o[k] for k in RAW_BATCH_KEYS}
+        out["dataset_name"] = self.dataset_name
+        return out
+
+
+def concat_shards(shards: List[dict], names: Optional[List[str]] = None, device="cpu") -> dict:
+    """The shards' tables back to back: rows concatenated, both offset tables shifted; dataset_name / action_mask must agree.  The
+    frames are assembled on ``device`` shard by shard (the host never holds a second copy of them)."""
+    names = names or [f"shard {i}" for i in range(len(shards))]
+    first = shards[0]
+    for d, n in zip(shards[1:], names[1:]):
+        for k in ("frames_u8", "actions_raw", "proprio_raw"):
+            if d[k].shape[1:] != first[k].shape[1:]:
+                raise ValueError(f"{n}: {k} has rows of shape {tuple(d[k].shape[1:])}, {names[0]} of {tuple(first[k].shape[1:])}")
+        if d.get("dataset_name") != first.get("dataset_name"):
+            raise ValueError(f"{n}: dataset_name {d.get('dataset_name')!r} differs from {names[0]}'s {first.get('dataset_name')!r}")
+        if ("action_mask" in d) != ("action_mask" in first) or ("action_mask" in d and not torch.equal(torch.as_tensor(d["action_mask"]), torch.as_tensor(first["action_mask"]))):
+            raise ValueError(f"{n}: action_mask differs from {names[0]}'s")
+    if len(shards) == 1:
+        return first
+    out = {k: torch.cat([d[k] for d in shards]) for k in ("actions_raw", "proprio_raw", "prompt_flat")}
+    out["frames_u8"] = torch.empty((out["actions_raw"].shape[0],) + tuple(first["frames_u8"].shape[1:]), dtype=torch.uint8, device=device)
+    eo, po, t0, p0 = [first["episode_off"][:1]], [first["prompt_off"][:1].to(torch.int64)], 0, 0
+    for d in shards:
+        out["frames_u8"][t0:t0 + d["frames_u8"].shape[0]].copy_(d["frames_u8"])
+        eo.append(d["episode_off"][1:] + t0)
+        po.append(d["prompt_off"][1:].to(torch.int64) + p0)
+        t0 += d["frames_u8"].shape[0]
+        p0 += d["prompt_flat"].numel()
+    if p0 > 2 ** 31 - 1:
+        raise ValueError(f"prompt_off: {p0} prompt ids in all do not fit its int32 offsets")
+    out["episode_off"], out["prompt_off"] = torch.cat(eo), torch.cat(po).to(torch.int32)
+    for k in ("dataset_name", "action_mask"):
+        if k in first:
+            out[k] = first[k]
+    return out

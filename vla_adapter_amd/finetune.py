@@ -7,7 +7,8 @@ purpose: HF-hub / network loaders (:752-754), the RLDS/TensorFlow input pipeline
 batches come from an iterable / ``--batch_file`` (a .pt dict or a directory of them: the collator's contract), from
 ``--frame_batch_file`` (the same with raw uint8 frames, augmented on the device under ``--image_aug``), from
 ``--raw_batch_file`` (raw transitions: frames, prompt ids, un-normalised actions / proprio, collated on the device with the
-statistics of ``--dataset_statistics_file``) or ``synthetic.make_batch``; weights are random-init unless ``--vlm_path`` / ``--resum_vla_path`` point at local state-dict
+statistics of ``--dataset_statistics_file``), from ``--episode_file`` (demonstration episodes kept on the device: shuffled windows drawn and
+chunked by two kernels, statistics computed at load - episodes.EpisodeStore) or ``synthetic.make_batch``; weights are random-init unless ``--vlm_path`` / ``--resum_vla_path`` point at local state-dict
 files.  ``--use_val_set`` runs the reference's validation pass (finetune.py:605-685, 1101-1117) on held-out batches of the same
 form (``--val_batch_file`` / ``finetune(val_batches=...)``; ``ValidationPass``); the RLDS val split itself is not read.  Every
 reference flag is either honoured or refused with an error (``check_supported``); none is silently dropped.
@@ -89,6 +90,10 @@ class FinetuneConfig:
     raw_batch_file: Optional[str] = None  # raw transitions (a .pt dict or a directory of them): frames_u8, prompt_flat int64 [n], prompt_off int32
                                           # [B + 1], actions_raw [B, chunk, action_dim], proprio_raw [B, Pd], optional dataset_name - normalised with
                                           # --dataset_statistics_file and collated on the device (GPUInputStage.collate), L = --max_seq_len
+    episode_file: Optional[str] = None    # demonstration episodes (a .pt dict or a directory of them: episodes.py), loaded once and kept on the
+                                          # device; every micro-step's raw batch is drawn there - shuffled, each window once per epoch across the
+                                          # ranks, actions chunked as the reference's RLDS stage does - and collated like a --raw_batch_file batch
+                                          # (needs --max_seq_len; without --dataset_statistics_file the store's own statistics are used and saved)
     use_graph: bool = True                # replay the captured hipGraphs
     max_seq_len: int = 0                  # static token length every batch is right-padded to (0: length of the first batch)
     conservative_rows: bool = False       # captured live-row window starts at the first text row instead of the first batch's action block
@@ -180,6 +185,9 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         raise NotImplementedError("native path = L1-regression action head; --use_film / --use_diffusion are not built")
     validating = False
     if cfg.use_val_set:
+        if cfg.episode_file and not (cfg.val_batch_file or val_batches):
+            raise NotImplementedError("--use_val_set with --episode_file: no validation split is cut from the episodes (ValidationPass takes "
+                                      "collated batches); pass held-out batches with --val_batch_file")
         if not (cfg.val_batch_file or val_batches):
             raise NotImplementedError("--use_val_set needs held-out batches: pass --val_batch_file (a .pt dict or a directory of them) or "
                                       "finetune(val_batches=...); the RLDS val split is not read (out of scope, SURVEY section 2 #16)")
@@ -198,12 +206,17 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         raise ValueError("grad_accumulation_steps must be >= 1")
     if cfg.resume and cfg.resume_step is None:
         raise ValueError("--resume needs --resume_step (finetune.py:1056 computes log_step = resume_step + gradient_step_idx)")
-    sources = [n for n in ("batch_file", "frame_batch_file", "raw_batch_file") if getattr(cfg, n)]
+    sources = [n for n in ("batch_file", "frame_batch_file", "raw_batch_file", "episode_file") if getattr(cfg, n)]
     if len(sources) > 1:
         raise ValueError(" and ".join("--" + n for n in sources) + f" are {len(sources)} batch sources: pass one")
     if cfg.raw_batch_file and not cfg.dataset_statistics_file:
         raise ValueError("--raw_batch_file carries un-normalised actions / proprio: pass the statistics with --dataset_statistics_file")
-    frames = bool(cfg.frame_batch_file or cfg.raw_batch_file) or frame_batches
+    if cfg.episode_file and not cfg.max_seq_len:
+        raise ValueError("raw batches with prompt offsets on the device need --max_seq_len (the natural length would be read back): "
+                         "--episode_file draws its prompt offsets on the device")
+    if cfg.episode_file and not 1 <= cfg.batch_size <= 1024:
+        raise ValueError("--episode_file draws a batch in one workgroup: --batch_size must lie in [1, 1024]")
+    frames = bool(cfg.frame_batch_file or cfg.raw_batch_file or cfg.episode_file) or frame_batches
     if "image_aug" in explicit and not frames:
         raise NotImplementedError(IMAGE_AUG_REFUSAL)
     bad = [n for n in explicit if n in OUT_OF_PATH_FLAGS and not (validating and n in VAL_FLAGS)]
@@ -432,10 +445,15 @@ def raw_batch_stats(norm_stats: dict, dataset_name: Optional[str] = None) -> dic
     return st
 
 
-def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, explicit=()):
+def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, explicit=(), world: int = 1, info: Optional[dict] = None):
     """Endless iterator over collated batches: an explicit iterable, ``--batch_file`` / ``--frame_batch_file`` / ``--raw_batch_file``
     (one .pt dict, or a directory of them, cycled in sorted order; every rank starts at its own offset - the reference's ranks draw independent
-    shuffles, finetune.py:988-994), or seeded synthetic batches (a new one every micro-step).
+    shuffles, finetune.py:988-994), ``--episode_file``, or seeded synthetic batches (a new one every micro-step).
+
+    ``--episode_file``: the episodes are loaded once into an ``episodes.EpisodeStore`` on the device; micro-step s of this rank collates
+    ``store.sample(batch_size, seed, rank, world, s)`` - a raw batch as below, keyed by the same (seed, rank, step).  Without
+    --dataset_statistics_file it is normalised with ``store.statistics()``, which is then also left in ``info["dataset_statistics"]``
+    (the caller's dict) for the checkpoints.
 
     A batch carrying ``frames_u8`` (uint8 [B, n_img, H, W, 3]) instead of ``pixel_values`` goes through the GPU input stage here:
     with --image_aug (default True, as in the reference) the training augmentation of the reference's RLDS pipeline
@@ -499,6 +517,20 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
                 yield collate(b)
             if n == 0:
                 raise ValueError("empty batch iterable")
+    elif cfg.episode_file:
+        from .episodes import EpisodeStore
+        store = EpisodeStore.load(cfg.episode_file, dev, chunk=mcfg.chunk, dataset_name=cfg.dataset_name)
+        if (store.A, store.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
+            raise ValueError(f"{cfg.episode_file}: actions_raw / proprio_raw have {store.A} / {store.Pd} columns, the model takes "
+                             f"{mcfg.action_dim} / {mcfg.proprio_dim}")
+        if store.frame_shape[0] != mcfg.n_img:
+            raise ValueError(f"{cfg.episode_file}: frames_u8 carries {store.frame_shape[0]} images per step, --num_images_in_input is {mcfg.n_img}")
+        if not cfg.dataset_statistics_file:
+            norm_stats = store.statistics()
+            if info is not None:
+                info["dataset_statistics"] = norm_stats
+        while True:
+            yield collate_raw(store.sample(cfg.batch_size, cfg.seed, rank, world, step))
     elif cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file:
         src = cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file
         files = sorted(str(p) for p in Path(src).glob("*.pt")) if os.path.isdir(src) else [src]
@@ -585,7 +617,8 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
     clip = cfg.max_grad_norm is not None
     if clip:
         (trainer or eng).set_max_grad_norm(cfg.max_grad_norm)
-    stream = batch_stream(cfg, mcfg, dev, rank, batches, explicit)
+    info = {}
+    stream = batch_stream(cfg, mcfg, dev, rank, batches, explicit, world=world, info=info)
     pad_id = min(S.PAD_ID, mcfg.llm.vocab - 1)
     cur = next(stream)
     L = cfg.max_seq_len or cur["input_ids"].shape[1]
@@ -594,7 +627,7 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
     gen = torch.Generator(device=dev).manual_seed(cfg.seed * 7919 + rank)
     noise = torch.zeros(mcfg.chunk, mcfg.action_dim * mcfg.llm.d, device=dev, dtype=torch.bfloat16)
     run_dir = Path(cfg.run_root_dir) / (cfg.run_id_override or f"native+{cfg.dataset_name}+b{cfg.batch_size * world}+lr-{cfg.learning_rate}")
-    stats = json.load(open(cfg.dataset_statistics_file)) if cfg.dataset_statistics_file else None
+    stats = json.load(open(cfg.dataset_statistics_file)) if cfg.dataset_statistics_file else info.get("dataset_statistics")
     static = None
     if use_graph:
         static = {k: v.clone() for k, v in cur.items()}

@@ -161,6 +161,14 @@ SERVE_PROTOS = {
 }
 SERVE_SYMBOLS = sorted(SERVE_PROTOS)
 
+# the episode sampler (include/vla_episodes.h, csrc/episodes.hip): a third table, bound by name in the same way
+# (tests/test_episodes_cpu.py checks header, table and library against each other)
+EPISODE_PROTOS = {
+    "vla_episode_sample": ([_P, _P, _P, _P, _I, C.c_ulonglong, _L, _L, _L, _I, _I, _P, _P, _P], _I),
+    "vla_episode_gather": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _I, _I, _L, _I], _I),
+}
+EPISODE_SYMBOLS = sorted(EPISODE_PROTOS)
+
 _lib = None
 
 
@@ -174,7 +182,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()):
+    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()):
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

@@ -1017,3 +1017,37 @@ def serve_gather_hidden(hs: torch.Tensor, hid_row: torch.Tensor, Np: int, T: int
     assert out.is_contiguous() and out.numel() == B * T * D and out.dtype == BF16
     N.check(_lib().vla_serve_gather_hidden(_st(), _p(hs), _p(hid_row), _p(out), B, S, Np, T, D, hs.stride(0), hs.stride(1)), "serve_gather_hidden")
     return out
+
+
+# ---- device-resident episodes (include/vla_episodes.h, csrc/episodes.hip) -----------------------------------------------------------
+def episode_sample(valid_off: torch.Tensor, episode_off: torch.Tensor, prompt_off: torch.Tensor, seed: int, rank: int, world: int, step: int,
+                   Pmax: int, ep: torch.Tensor, row: torch.Tensor, out_off: torch.Tensor) -> None:
+    """vla_episode_sample: the windows of the batch of (rank, step) -> ep int32 [B], row int64 [B], out_off int32 [B + 1] (all given)."""
+    E, B, dev = valid_off.numel() - 1, ep.numel(), valid_off.device
+    for t, dt, n in ((valid_off, torch.int64, E + 1), (episode_off, torch.int64, E + 1), (prompt_off, torch.int32, E + 1), (ep, torch.int32, B),
+                     (row, torch.int64, B), (out_off, torch.int32, B + 1)):
+        assert t.is_cuda and t.device == dev and t.dtype == dt and t.dim() == 1 and t.numel() == n and t.is_contiguous(), "episode_sample: bad operand"
+    N.check(_lib().vla_episode_sample(_st(), _p(valid_off), _p(episode_off), _p(prompt_off), E, int(seed) & (2 ** 64 - 1), int(rank), int(world),
+                                      int(step), B, int(Pmax), _p(ep), _p(row), _p(out_off)), "episode_sample")
+
+
+def episode_gather(frames: torch.Tensor, actions: torch.Tensor, proprio: torch.Tensor, episode_off: torch.Tensor, prompt_flat: torch.Tensor,
+                   prompt_off: torch.Tensor, ep: torch.Tensor, row: torch.Tensor, out_off: torch.Tensor, out_frames: torch.Tensor,
+                   out_actions: torch.Tensor, out_proprio: torch.Tensor, out_prompt: torch.Tensor, Pmax: int) -> None:
+    """vla_episode_gather: the store's tensors + the sampler's index vectors -> the raw batch (all outputs given): out_frames u8
+    [B, *frame], out_actions f32 [B, chunk, A], out_proprio f32 [B, Pd], out_prompt int64 [B * Pmax]."""
+    B, E, T, dev = ep.numel(), episode_off.numel() - 1, frames.shape[0], frames.device
+    chunk, A, Pd = out_actions.shape[1], actions.shape[1], proprio.shape[1]
+    row_bytes = frames[0].numel()
+    for t in (frames, actions, proprio, episode_off, prompt_flat, prompt_off, ep, row, out_off, out_frames, out_actions, out_proprio, out_prompt):
+        assert t.is_cuda and t.device == dev and t.is_contiguous(), "episode_gather: operands are contiguous tensors on one device"
+    assert frames.dtype == torch.uint8 and out_frames.dtype == torch.uint8 and tuple(out_frames.shape) == (B,) + tuple(frames.shape[1:])
+    assert actions.dtype == torch.float32 and tuple(actions.shape) == (T, A) and out_actions.dtype == torch.float32 and tuple(out_actions.shape) == (B, chunk, A)
+    assert proprio.dtype == torch.float32 and tuple(proprio.shape) == (T, Pd) and out_proprio.dtype == torch.float32 and tuple(out_proprio.shape) == (B, Pd)
+    assert episode_off.dtype == torch.int64 and prompt_off.dtype == torch.int32 and prompt_off.numel() == E + 1 and prompt_flat.dtype == torch.int64
+    assert ep.dtype == torch.int32 and row.dtype == torch.int64 and row.numel() == B and out_off.dtype == torch.int32 and out_off.numel() == B + 1
+    assert out_prompt.dtype == torch.int64 and out_prompt.numel() == B * Pmax
+    N.check(_lib().vla_episode_gather(_st(), _p(frames), _p(actions), _p(proprio), _p(episode_off), _p(prompt_flat) if prompt_flat.numel() else None,
+                                      _p(prompt_off), _p(ep), _p(row), _p(out_off), _p(out_frames), _p(out_actions), _p(out_proprio),
+                                      _p(out_prompt) if out_prompt.numel() else None, B, E, T, row_bytes, chunk, A, Pd, prompt_flat.numel(), int(Pmax)),
+            "episode_gather")
