@@ -8,11 +8,10 @@
 // written by exactly one thread (plain stores, no atomics).  The sampling rule is restated in Python (vla_adapter_amd/episodes.py:
 // sample_position, permute_index, locate), which is what the kernel is tested against, bit for bit.
 #include "common.h"
+#include "permute.h"                            // feistel4 / permute_index: shared with mixture.hip
 #include "../../include/vla_episodes.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int SAMPLE_MAX_B = 1024;
 constexpr int GATHER_THREADS = 256;
@@ -21,35 +20,6 @@ constexpr int GATHER_MAX_BLOCKS = 2048;            // memory-bound grid: 256 CUs
 constexpr u64 EPISODE_STREAM = 0xE9150DE5A391Eull;   // keeps the shuffle apart from the augmentation's and the collator's draws under equal seed words
 
 __device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// One pass of the 4-round balanced Feistel network over two halves of `half` bits (1 <= half <= 32): a bijection on [0, 4^half)
-// whatever the round function is, since each round (L, R) -> (R, L ^ F(R)) is undone by (L, R) -> (R ^ F(L), L).
-__device__ __forceinline__ u64 feistel4(u64 x, u64 key, int half) {
-  const u64 mask = (1ull << half) - 1ull;
-  u64 l = x >> half, r = x & mask;
-#pragma unroll
-  for (int round = 0; round < 4; ++round) {
-    const u64 f = splitmix64_key(splitmix64_key(key, (u64)round), r) & mask;
-    const u64 t = l ^ f;
-    l = r;
-    r = t;
-  }
-  return (l << half) | r;
-}
-
-// permute_index of episodes.py: i in [0, n) -> the keyed bijection's image in [0, n).  Results >= n are walked on along their cycle.
-// Termination: i lies inside [0, n), the walk follows the cycle of a permutation of [0, 4^half) through i, so it comes back to i - an
-// element of [0, n) - after at most 4^half steps and stops at the first element below n it meets; 4^half < 4 n.
-__device__ __forceinline__ u64 permute_index(u64 i, u64 n, u64 key) {
-  if (n <= 1ull) return 0ull;
-  const int bits = 64 - __clzll((long long)(n - 1ull));
-  const int half = (bits + 1) / 2;                 // >= 1 because n >= 2
-  u64 y = i;
-  do {
-    y = feistel4(y, key, half);
-  } while (y >= n);
-  return y;
-}
 
 // One workgroup; thread b < B draws sample b, then all threads scan the prompt lengths (Hillis-Steele in LDS).
 __global__ void __launch_bounds__(SAMPLE_MAX_B)

@@ -210,16 +210,7 @@ class EpisodeStore:
     def load(cls, path, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None) -> "EpisodeStore":
         """``path``: a .pt episode file or a directory of them (concatenated in sorted order).  Validates the tables (ValueError that
         names the key), moves everything to the device and builds valid_off; ``dataset_name``: used when the file names none."""
-        path = str(path)
-        files = sorted(str(p) for p in Path(path).glob("*.pt")) if os.path.isdir(path) else [path]
-        if not files:
-            raise FileNotFoundError(f"no .pt episode files under {path}")
-        shards = []
-        for f in files:
-            d = torch.load(f, weights_only=True, mmap=True)
-            _check_shard(d, f)
-            shards.append(d)
-        return cls(concat_shards(shards, files, device), device, chunk, dataset_name, _where=path)
+        return cls(load_tables(path, device), device, chunk, dataset_name, _where=str(path))
 
     # ---- the two products ----------------------------------------------------------------------------------------------------
     def statistics(self) -> dict:
@@ -260,6 +251,20 @@ class EpisodeStore:
         out = {k: o[k] for k in RAW_BATCH_KEYS}
         out["dataset_name"] = self.dataset_name
         return out
+
+
+def load_tables(path, device="cpu") -> dict:
+    """The tables of a .pt episode file or of a directory of them (validated shard by shard, concatenated in sorted order)."""
+    path = str(path)
+    files = sorted(str(p) for p in Path(path).glob("*.pt")) if os.path.isdir(path) else [path]
+    if not files:
+        raise FileNotFoundError(f"no .pt episode files under {path}")
+    shards = []
+    for f in files:
+        d = torch.load(f, weights_only=True, mmap=True)
+        _check_shard(d, f)
+        shards.append(d)
+    return concat_shards(shards, files, device)
 
 
 def concat_shards(shards: List[dict], names: Optional[List[str]] = None, device="cpu") -> dict:

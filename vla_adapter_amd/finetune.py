@@ -8,7 +8,8 @@ batches come from an iterable / ``--batch_file`` (a .pt dict or a directory of t
 ``--frame_batch_file`` (the same with raw uint8 frames, augmented on the device under ``--image_aug``), from
 ``--raw_batch_file`` (raw transitions: frames, prompt ids, un-normalised actions / proprio, collated on the device with the
 statistics of ``--dataset_statistics_file``), from ``--episode_file`` (demonstration episodes kept on the device: shuffled windows drawn and
-chunked by two kernels, statistics computed at load - episodes.EpisodeStore) or ``synthetic.make_batch``; weights are random-init unless ``--vlm_path`` / ``--resum_vla_path`` point at local state-dict
+chunked by two kernels, statistics computed at load - episodes.EpisodeStore), from ``--episode_mix`` (a weighted mixture of such
+datasets, every sample normalised with its own dataset's statistics - mixture.EpisodeMix) or ``synthetic.make_batch``; weights are random-init unless ``--vlm_path`` / ``--resum_vla_path`` point at local state-dict
 files.  ``--use_val_set`` runs the reference's validation pass (finetune.py:605-685, 1101-1117) on held-out batches of the same
 form (``--val_batch_file`` / ``finetune(val_batches=...)``; ``ValidationPass``); the RLDS val split itself is not read.  Every
 reference flag is either honoured or refused with an error (``check_supported``); none is silently dropped.
@@ -94,6 +95,12 @@ class FinetuneConfig:
                                           # device; every micro-step's raw batch is drawn there - shuffled, each window once per epoch across the
                                           # ranks, actions chunked as the reference's RLDS stage does - and collated like a --raw_batch_file batch
                                           # (needs --max_seq_len; without --dataset_statistics_file the store's own statistics are used and saved)
+    episode_mix: Optional[str] = None     # a weighted mixture of episode datasets, "pathA=1.0,pathB=0.5" (a weight defaults to 1.0; each path as
+                                          # --episode_file takes it): all kept on the device, every sample drawn from dataset d with probability
+                                          # p_d and normalised with that dataset's own statistics, every dataset running through its own epochs
+                                          # (mixture.EpisodeMix; needs --max_seq_len; without --dataset_statistics_file the mix's statistics are
+                                          # used and saved, one entry per dataset)
+    episode_mix_balance: bool = True      # the reference's balance_weights: p_d = w_d T_d / sum(w T) over the transition counts, else w_d / sum(w)
     use_graph: bool = True                # replay the captured hipGraphs
     max_seq_len: int = 0                  # static token length every batch is right-padded to (0: length of the first batch)
     conservative_rows: bool = False       # captured live-row window starts at the first text row instead of the first batch's action block
@@ -188,6 +195,9 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         if cfg.episode_file and not (cfg.val_batch_file or val_batches):
             raise NotImplementedError("--use_val_set with --episode_file: no validation split is cut from the episodes (ValidationPass takes "
                                       "collated batches); pass held-out batches with --val_batch_file")
+        if cfg.episode_mix and not (cfg.val_batch_file or val_batches):
+            raise NotImplementedError("--use_val_set with --episode_mix: no validation split is cut from the episodes (ValidationPass takes "
+                                      "collated batches); pass held-out batches with --val_batch_file")
         if not (cfg.val_batch_file or val_batches):
             raise NotImplementedError("--use_val_set needs held-out batches: pass --val_batch_file (a .pt dict or a directory of them) or "
                                       "finetune(val_batches=...); the RLDS val split is not read (out of scope, SURVEY section 2 #16)")
@@ -206,7 +216,7 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         raise ValueError("grad_accumulation_steps must be >= 1")
     if cfg.resume and cfg.resume_step is None:
         raise ValueError("--resume needs --resume_step (finetune.py:1056 computes log_step = resume_step + gradient_step_idx)")
-    sources = [n for n in ("batch_file", "frame_batch_file", "raw_batch_file", "episode_file") if getattr(cfg, n)]
+    sources = [n for n in ("batch_file", "frame_batch_file", "raw_batch_file", "episode_file", "episode_mix") if getattr(cfg, n)]
     if len(sources) > 1:
         raise ValueError(" and ".join("--" + n for n in sources) + f" are {len(sources)} batch sources: pass one")
     if cfg.raw_batch_file and not cfg.dataset_statistics_file:
@@ -216,7 +226,15 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
                          "--episode_file draws its prompt offsets on the device")
     if cfg.episode_file and not 1 <= cfg.batch_size <= 1024:
         raise ValueError("--episode_file draws a batch in one workgroup: --batch_size must lie in [1, 1024]")
-    frames = bool(cfg.frame_batch_file or cfg.raw_batch_file or cfg.episode_file) or frame_batches
+    if cfg.episode_mix and not cfg.max_seq_len:
+        raise ValueError("raw batches with prompt offsets on the device need --max_seq_len (the natural length would be read back): "
+                         "--episode_mix draws its prompt offsets on the device")
+    if cfg.episode_mix and not 1 <= cfg.batch_size <= 1024:
+        raise ValueError("--episode_mix draws a batch in one workgroup: --batch_size must lie in [1, 1024]")
+    if cfg.episode_mix:
+        from .mixture import parse_mix
+        parse_mix(cfg.episode_mix)                # ValueError for a weight that is no number or an entry without a path
+    frames = bool(cfg.frame_batch_file or cfg.raw_batch_file or cfg.episode_file or cfg.episode_mix) or frame_batches
     if "image_aug" in explicit and not frames:
         raise NotImplementedError(IMAGE_AUG_REFUSAL)
     bad = [n for n in explicit if n in OUT_OF_PATH_FLAGS and not (validating and n in VAL_FLAGS)]
@@ -445,15 +463,31 @@ def raw_batch_stats(norm_stats: dict, dataset_name: Optional[str] = None) -> dic
     return st
 
 
+def mixture_stats(norm_stats: dict, dataset_names) -> tuple:
+    """(action entries, proprio entries) in the order of a mixed raw batch's ``dataset_names``: what its ``dataset_index`` indexes.
+    KeyError naming the dataset the statistics hold no entry for."""
+    for n in dataset_names:
+        if n not in norm_stats:
+            raise KeyError(f"dataset statistics hold no entry {n!r} (one of the batch's dataset_names {tuple(dataset_names)}): their keys "
+                           f"are {sorted(norm_stats)}")
+    sts = [raw_batch_stats(norm_stats, n) for n in dataset_names]
+    return tuple(st["action"] for st in sts), tuple(st["proprio"] for st in sts)
+
+
 def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, explicit=(), world: int = 1, info: Optional[dict] = None):
     """Endless iterator over collated batches: an explicit iterable, ``--batch_file`` / ``--frame_batch_file`` / ``--raw_batch_file``
     (one .pt dict, or a directory of them, cycled in sorted order; every rank starts at its own offset - the reference's ranks draw independent
-    shuffles, finetune.py:988-994), ``--episode_file``, or seeded synthetic batches (a new one every micro-step).
+    shuffles, finetune.py:988-994), ``--episode_file``, ``--episode_mix``, or seeded synthetic batches (a new one every micro-step).
 
     ``--episode_file``: the episodes are loaded once into an ``episodes.EpisodeStore`` on the device; micro-step s of this rank collates
     ``store.sample(batch_size, seed, rank, world, s)`` - a raw batch as below, keyed by the same (seed, rank, step).  Without
     --dataset_statistics_file it is normalised with ``store.statistics()``, which is then also left in ``info["dataset_statistics"]``
     (the caller's dict) for the checkpoints.
+
+    ``--episode_mix``: the same over a weighted mixture of datasets (``mixture.EpisodeMix``): the raw batch then carries
+    ``dataset_index`` (int32 [B]) and ``dataset_names``, and every sample is normalised with its own dataset's entry - of the mix's
+    statistics, or of --dataset_statistics_file, which must then hold every name (KeyError naming the missing one).  Such a batch
+    is collated the same way when it comes from ``--raw_batch_file`` or ``batches``.  ``info["mixture"]`` holds ``mixture_info()``.
 
     A batch carrying ``frames_u8`` (uint8 [B, n_img, H, W, 3]) instead of ``pixel_values`` goes through the GPU input stage here:
     with --image_aug (default True, as in the reference) the training augmentation of the reference's RLDS pipeline
@@ -467,26 +501,37 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
     only one), token length --max_seq_len (0: the batch's own), filler tokens and augmentation keyed by the same (seed, rank, step)."""
     from . import synthetic as S
     from .input_stage import GPUInputStage, ImageAugment, backbone_norms
-    stage, step, norm_stats = None, 0, None
+    stage, step, norm_stats, mix_stats = None, 0, None, {}
 
     def collate_raw(b):
         nonlocal stage, step, norm_stats
         missing = [k for k in RAW_BATCH_KEYS if k not in b]
         if missing:
             raise ValueError(f"raw batch lacks {missing}: it carries {RAW_BATCH_KEYS} and optionally dataset_name")
+        mixed = "dataset_index" in b or "dataset_names" in b
+        if mixed and not ("dataset_index" in b and "dataset_names" in b):
+            raise ValueError("a raw batch of a dataset mixture carries both dataset_index (int32 [B]) and dataset_names")
         if norm_stats is None:
             if not cfg.dataset_statistics_file:
                 raise ValueError("raw batches carry un-normalised actions / proprio: pass the statistics with --dataset_statistics_file")
             norm_stats = json.load(open(cfg.dataset_statistics_file))
-        st = raw_batch_stats(norm_stats, b.get("dataset_name"))
+        if mixed:               # every sample with its own dataset's statistics; the entry lists are built once per tuple of names
+            names = tuple(b["dataset_names"])
+            if names not in mix_stats:
+                mix_stats[names] = mixture_stats(norm_stats, names)
+            act_st, pr_st = mix_stats[names]
+            index = b["dataset_index"].to(dev, torch.int32)
+        else:
+            st = raw_batch_stats(norm_stats, b.get("dataset_name"))
+            act_st, pr_st, index = st["action"], st["proprio"], None
         if stage is None:
             stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img)
         aug = ImageAugment(seed=cfg.seed, rank=rank, step=step) if cfg.image_aug else None
         L = cfg.max_seq_len or None
         if L is None and b["prompt_off"].is_cuda:
             raise ValueError("raw batches with prompt offsets on the device need --max_seq_len (the natural length would be read back)")
-        out = stage.collate(b["frames_u8"], (b["prompt_flat"], b["prompt_off"]), b["actions_raw"], b["proprio_raw"], action_stats=st["action"],
-                            proprio_stats=st["proprio"], L=L, seed=cfg.seed, rank=rank, step=step, augment=aug)
+        out = stage.collate(b["frames_u8"], (b["prompt_flat"], b["prompt_off"]), b["actions_raw"], b["proprio_raw"], action_stats=act_st,
+                            proprio_stats=pr_st, L=L, seed=cfg.seed, rank=rank, step=step, augment=aug, stats_index=index)
         step += 1
         return out
 
@@ -531,6 +576,26 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
                 info["dataset_statistics"] = norm_stats
         while True:
             yield collate_raw(store.sample(cfg.batch_size, cfg.seed, rank, world, step))
+    elif cfg.episode_mix:
+        from .mixture import EpisodeMix, parse_mix
+        mix = EpisodeMix.load(parse_mix(cfg.episode_mix), dev, chunk=mcfg.chunk, balance_weights=cfg.episode_mix_balance)
+        if (mix.A, mix.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
+            raise ValueError(f"--episode_mix: actions_raw / proprio_raw have {mix.A} / {mix.Pd} columns, the model takes "
+                             f"{mcfg.action_dim} / {mcfg.proprio_dim}")
+        if mix.frame_shape[0] != mcfg.n_img:
+            raise ValueError(f"--episode_mix: frames_u8 carries {mix.frame_shape[0]} images per step, --num_images_in_input is {mcfg.n_img}")
+        if cfg.dataset_statistics_file:
+            mixture_stats(json.load(open(cfg.dataset_statistics_file)), mix.names)        # a missing entry is refused before the first step
+        else:
+            norm_stats = mix.statistics()
+            if info is not None:
+                info["dataset_statistics"] = norm_stats
+        if info is not None:
+            info["mixture"] = mix.mixture_info()
+        if rank == 0:
+            print(json.dumps(dict(mixture=mix.mixture_info())), flush=True)
+        while True:
+            yield collate_raw(mix.sample(cfg.batch_size, cfg.seed, rank, world, step))
     elif cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file:
         src = cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file
         files = sorted(str(p) for p in Path(src).glob("*.pt")) if os.path.isdir(src) else [src]
@@ -705,4 +770,7 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
         save_training_checkpoint(cfg, run_dir, final_step, eng, stats, trainer)
     model = dict(vit=[dict(v.as_oracle(), img=v.img) for v in mcfg.vit], llm=dict(mcfg.llm.as_oracle(), d=mcfg.llm.d, inter=mcfg.llm.inter, vocab=mcfg.llm.vocab),
                  n_img=mcfg.n_img, num_blocks=mcfg.num_blocks, pro=mcfg.pro)
-    return dict(log=log, val_log=val_log, seconds=time.time() - t0, steps=steps_done, world=world, final_step=final_step, run_dir=str(run_dir), mode=mode, model=model)
+    out = dict(log=log, val_log=val_log, seconds=time.time() - t0, steps=steps_done, world=world, final_step=final_step, run_dir=str(run_dir), mode=mode, model=model)
+    if "mixture" in info:                        # --episode_mix: names, probabilities, quotas, period, the reference's dataset_len
+        out["mixture"] = info["mixture"]
+    return out

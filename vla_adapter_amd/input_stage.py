@@ -341,6 +341,43 @@ class GPUInputStage:
             raise ValueError(f"last dimension {x.shape[-1]} does not match the statistics' {low.numel()}")
         return ops.normalize_bounds(x, low, high, mask, zero)
 
+    def normalize_rows(self, x: torch.Tensor, stats_list, sel: torch.Tensor, kind: str = "bounds_q99") -> torch.Tensor:
+        """normalize() with one statistics entry per row: x [R, ..., D], sel int32 [R] on the device names the entry of ``stats_list``
+        (a list / tuple of entries as normalize() takes them) row r is normalised with - a mixture of datasets, every sample with its
+        own dataset's statistics (rlds/dataset.py:544-550).  A row is bit-identical to normalize() on that row with that entry.  The
+        stacked tables are uploaded once per (list object, kind); an entry without ``mask`` gets all ones, ``zero`` is min == max
+        where an entry has both."""
+        if kind not in NORMALIZATION_KINDS:
+            raise NotImplementedError(f"normalisation type {kind!r}: only {NORMALIZATION_KINDS} are built (NORMAL, mean / std, is used by "
+                                      "no shipped configuration)")
+        if not isinstance(stats_list, (list, tuple)) or not stats_list:
+            raise ValueError("normalize_rows: stats_list is a non-empty list / tuple of statistics entries")
+        key = (id(stats_list), kind, "rows")
+        if key not in self._stats:
+            lo_k, hi_k = ("min", "max") if kind == "bounds" else ("q01", "q99")
+            for n, st in enumerate(stats_list):
+                if lo_k not in st or hi_k not in st:
+                    raise KeyError(f"normalisation type {kind!r} needs {lo_k!r} and {hi_k!r} in the statistics, entry {n} has {sorted(st)}")
+            f32 = lambda k: np.stack([np.asarray(st[k], dtype=np.float32) for st in stats_list])
+            low, high = f32(lo_k), f32(hi_k)
+            if low.ndim != 2 or low.shape != high.shape:
+                raise ValueError(f"normalize_rows: the entries' {lo_k!r} / {hi_k!r} must share one length")
+            D = low.shape[1]
+            mask = np.stack([np.asarray(st["mask"], dtype=bool) if "mask" in st else np.ones(D, dtype=bool) for st in stats_list])
+            zero = np.stack([np.asarray(st["min"], dtype=np.float32) == np.asarray(st["max"], dtype=np.float32)
+                             if "min" in st and "max" in st else np.zeros(D, dtype=bool) for st in stats_list])
+            if mask.shape != low.shape or zero.shape != low.shape:
+                raise ValueError("normalize_rows: the entries' mask / min / max must have the length of the bounds")
+            up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a.astype(dt))).to(self.device)
+            self._stats[key] = (stats_list, up(low, np.float32), up(high, np.float32), up(mask, np.uint8), up(zero, np.uint8))   # (the list itself: its id stays taken)
+        _, low, high, mask, zero = self._stats[key]
+        x = x.to(self.device, torch.float32).contiguous()
+        if x.shape[-1] != low.shape[1]:
+            raise ValueError(f"last dimension {x.shape[-1]} does not match the statistics' {low.shape[1]}")
+        if sel.dtype != torch.int32 or tuple(sel.shape) != (x.shape[0],):
+            raise ValueError(f"normalize_rows: sel must be int32 [{x.shape[0]}], got {sel.dtype} {tuple(sel.shape)}")
+        return ops.normalize_bounds_rows(x, sel.to(self.device).contiguous(), low, high, mask, zero)
+
     def serve_tokens(self, prompt_ids, L: Optional[int] = None, len_multiple: int = 32) -> Dict[str, torch.Tensor]:
         """The batch of prepare_inference_inputs for B prompts of different lengths, right-padded to L, in one launch (vla_serve_tokens):
         dict(input_ids, labels int64 [B, L], attention_mask bool [B, L], hid_row int32 [B], row_ok u8 [B]).  prompt_ids: list of id lists, or
@@ -398,14 +435,24 @@ class GPUInputStage:
 
     def collate(self, frames_u8, prompt_ids, actions: torch.Tensor, proprio: Optional[torch.Tensor] = None, *, action_stats: Optional[dict] = None,
                 proprio_stats: Optional[dict] = None, L: Optional[int] = None, seed: int = 0, rank: int = 0, step: int = 0,
-                augment: Optional[ImageAugment] = None, center_crop: bool = False) -> Dict[str, torch.Tensor]:
+                augment: Optional[ImageAugment] = None, center_crop: bool = False, stats_index: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """build() without the host: the same batch dict from kernels only (vla_normalize_bounds, vla_collate_tokens, pixels()).
         prompt_ids: list of id lists, or (prompt_flat int64 [n], prompt_off int32 [B + 1]) tensors - with tensors on the device nothing
         is copied, read back or looped over.  action_stats / proprio_stats: raw values are normalised first (normalize(), "bounds_q99")
         and batch["actions"] holds the normalised window.  L: static token length (rows are padded or cut to it); default
         min(longest row, model_max_length), from the prompt lengths on the host - device-resident offsets therefore need L.  The
-        filler ids of the action block are drawn on the device from (seed, rank, step, sample, slot), not from Python's random."""
+        filler ids of the action block are drawn on the device from (seed, rank, step, sample, slot), not from Python's random.
+        A list / tuple of entries as action_stats / proprio_stats with stats_index (int32 [B] on the device): sample b is normalised
+        with entry stats_index[b] (normalize_rows(): a batch of a dataset mixture); a single dict keeps the one-set kernel."""
         B = actions.shape[0]
+        per_row = [isinstance(s, (list, tuple)) for s in (action_stats, proprio_stats) if s is not None]
+        if any(per_row) and stats_index is None:
+            raise ValueError("collate: a list of statistics entries needs stats_index= (which entry each sample takes)")
+        if stats_index is not None and not (per_row and all(per_row)):
+            raise ValueError("collate: stats_index= goes with lists of statistics entries as action_stats / proprio_stats")
+
+        def norm(x, st):
+            return self.normalize_rows(x, st, stats_index) if isinstance(st, (list, tuple)) else self.normalize(x, st)
         if isinstance(prompt_ids, (tuple, list)) and len(prompt_ids) == 2 and all(isinstance(t, torch.Tensor) for t in prompt_ids):
             flat, off = prompt_ids
             if L is None:
@@ -421,13 +468,13 @@ class GPUInputStage:
         if off.numel() != B + 1:
             raise ValueError(f"collate: {off.numel()} prompt offsets for {B} samples (expected B + 1)")
         flat, off = flat.to(self.device, torch.int64).contiguous(), off.to(self.device, torch.int32).contiguous()
-        act = self.normalize(actions, action_stats) if action_stats is not None else actions.to(self.device)
+        act = norm(actions, action_stats) if action_stats is not None else actions.to(self.device)
         ids, labels, am = ops.collate_tokens(flat, off, act.to(torch.float32).reshape(B, -1).contiguous(), self.bins, int(L),
                                              tokenizer_len=self.tokenizer_len, lo=self.lo, hi=self.hi, pad_id=self.pad, ignore_index=IGNORE_INDEX,
                                              num_tokens=NUM_TOKENS, seed=seed, rank=rank, step=step)
         batch = dict(pixel_values=self.pixels(frames_u8, augment=augment, center_crop=center_crop), input_ids=ids, labels=labels,
                      attention_mask=am.view(torch.bool), actions=act)
         if proprio is not None:
-            pr = self.normalize(proprio, proprio_stats) if proprio_stats is not None else proprio.to(self.device, torch.float32)
+            pr = norm(proprio, proprio_stats) if proprio_stats is not None else proprio.to(self.device, torch.float32)
             batch["proprio"] = pr.reshape(B, -1)
         return batch

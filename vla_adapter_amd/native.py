@@ -169,6 +169,14 @@ EPISODE_PROTOS = {
 }
 EPISODE_SYMBOLS = sorted(EPISODE_PROTOS)
 
+# the dataset mixture (include/vla_mixture.h, csrc/mixture.hip): a fourth table, bound by name in the same way
+# (tests/test_mixture_cpu.py checks header, table and library against each other)
+MIXTURE_PROTOS = {
+    "vla_mixture_sample": ([_P, _P, _P, _P, _P, _P, _I, _I, C.c_ulonglong, _L, _L, _L, _I, _I, _P, _P, _P, _P], _I),
+    "vla_normalize_bounds_rows": ([_P, _P, _P, _L, _I, _I, _P, _I, _P, _P, _P, _P], _I),
+}
+MIXTURE_SYMBOLS = sorted(MIXTURE_PROTOS)
+
 _lib = None
 
 
@@ -182,7 +190,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()):
+    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()):
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

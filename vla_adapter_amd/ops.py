@@ -1051,3 +1051,37 @@ def episode_gather(frames: torch.Tensor, actions: torch.Tensor, proprio: torch.T
                                       _p(prompt_off), _p(ep), _p(row), _p(out_off), _p(out_frames), _p(out_actions), _p(out_proprio),
                                       _p(out_prompt) if out_prompt.numel() else None, B, E, T, row_bytes, chunk, A, Pd, prompt_flat.numel(), int(Pmax)),
             "episode_gather")
+
+
+# ---- a weighted mixture of device-resident datasets (include/vla_mixture.h, csrc/mixture.hip) ----------------------------------------
+def mixture_sample(valid_off: torch.Tensor, episode_off: torch.Tensor, prompt_off: torch.Tensor, dataset_off: torch.Tensor,
+                   quota_off: torch.Tensor, seed: int, rank: int, world: int, step: int, Pmax: int, ds: torch.Tensor, ep: torch.Tensor,
+                   row: torch.Tensor, out_off: torch.Tensor) -> None:
+    """vla_mixture_sample: the windows of the batch of (rank, step) -> ds int32 [B], ep int32 [B], row int64 [B], out_off int32 [B + 1]
+    (all given)."""
+    E, D, B, dev = valid_off.numel() - 1, dataset_off.numel() - 1, ep.numel(), valid_off.device
+    for t, dt, n in ((valid_off, torch.int64, E + 1), (episode_off, torch.int64, E + 1), (prompt_off, torch.int32, E + 1),
+                     (dataset_off, torch.int32, D + 1), (quota_off, torch.int64, D + 1), (ds, torch.int32, B), (ep, torch.int32, B),
+                     (row, torch.int64, B), (out_off, torch.int32, B + 1)):
+        assert t.is_cuda and t.device == dev and t.dtype == dt and t.dim() == 1 and t.numel() == n and t.is_contiguous(), "mixture_sample: bad operand"
+    N.check(_lib().vla_mixture_sample(_st(), _p(valid_off), _p(episode_off), _p(prompt_off), _p(dataset_off), _p(quota_off), E, D,
+                                      int(seed) & (2 ** 64 - 1), int(rank), int(world), int(step), B, int(Pmax), _p(ds), _p(ep), _p(row),
+                                      _p(out_off)), "mixture_sample")
+
+
+def normalize_bounds_rows(x_f32: torch.Tensor, sel: torch.Tensor, low: torch.Tensor, high: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                          zero_mask: Optional[torch.Tensor] = None):
+    """vla_normalize_bounds_rows: normalize_bounds on x f32 [R, ..., D] with the statistics set sel[r] (int32 [R], clamped into the
+    tables) for row r; low / high f32 [n_sets, D], mask / zero_mask u8 [n_sets, D] or None.  A row equals normalize_bounds on that row."""
+    R, D = x_f32.shape[0], x_f32.shape[-1]
+    assert x_f32.dim() >= 2 and x_f32.dtype == torch.float32 and x_f32.is_contiguous() and x_f32.numel() > 0
+    assert low.dim() == 2 and low.shape[1] == D, "per-set statistics: [n_sets, D]"
+    n_sets, dev = low.shape[0], x_f32.device
+    assert sel.dtype == torch.int32 and sel.is_contiguous() and tuple(sel.shape) == (R,) and sel.device == dev, "sel: int32 [R] on x's device"
+    for t, dt in ((low, torch.float32), (high, torch.float32), (mask, torch.uint8), (zero_mask, torch.uint8)):
+        assert t is None or (t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (n_sets, D) and t.device == dev), \
+            "per-set statistics: [n_sets, D] on x's device"
+    out = torch.empty_like(x_f32)
+    N.check(_lib().vla_normalize_bounds_rows(_st(), _p(x_f32), _p(out), R, x_f32.numel() // R, D, _p(sel), n_sets, _p(low), _p(high), _p(mask),
+                                             _p(zero_mask)), "normalize_bounds_rows")
+    return out
