@@ -1077,6 +1077,7 @@ class VLAEngine(schedule.StepControls):
         self.fp8_frozen = False
         self.side = None           # head stream: the streams are created on first use (_ensure_streams)
         self._vis_bufs = {}        # (feats, patches) per (batch, patches): captured graphs keep their addresses
+        self._val_pred = None
         self._predict_graphs, self._val_graphs = {}, None      # predict(): (graphs, static batch, segments) per input shape; val_step_graphed()
         self._timeline = None      # a list collects (kind, index, start, end) events of every segment run (tools/*_timeline.py)
         # captured step (capture()): its graphs, the vision graph, events of the vision stage in flight / of its pixel copy, pending update, exchange events
@@ -1182,6 +1183,7 @@ class VLAEngine(schedule.StepControls):
         def at_end():
             self._pred_out = head.fwd_end()
             if loss_of is not None:
+                self._val_pred = self._pred_out
                 self._val_loss3 = ops.l1_loss(self._pred_out, self._to_bf16(loss_of), want_grad=False)[0]
 
         return segs + schedule.pipeline_forward(head, ch, llm_fwd, lambda: (llm.HS, self.pos1, batch["proprio"], self.Np, noise), at_end,
@@ -1646,8 +1648,14 @@ class VLAEngine(schedule.StepControls):
 
     def val_forward(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Eager validation of one batch: forward() + the L1 loss without gradient -> f32 [3] (loss, current, next actions)."""
-        pred = self.forward(batch, noise)
+        pred = self._val_pred = self.forward(batch, noise)
         return ops.l1_loss(pred, self._to_bf16(batch["actions"]), want_grad=False)[0]
+
+    @property
+    def val_pred(self) -> torch.Tensor:
+        """The prediction of the last validation forward (val_forward / val_step_graphed): bf16 [B, chunk, action_dim] on the device,
+        final in stream order when that call returns - what a per-sample reduction of the sweep reads (heldout.HeldOutSweep)."""
+        return self._val_pred.view(self.B, self.cfg.chunk, self.cfg.action_dim)
 
     def val_step_graphed(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Captured validation of the static ``batch`` / ``noise`` buffers (copy each batch INTO them first): the forward-only

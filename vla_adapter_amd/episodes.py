@@ -22,9 +22,13 @@ An episode file is a ``.pt`` dict, or a directory of them (the shards are concat
 
 The sampling rule is stated here in plain Python - ``sample_position``, ``permute_index``, ``locate`` - and is the specification the
 kernel is tested against, bit for bit.
+
+``holdout=f`` sets every dataset's last episodes aside for validation without copying or reordering anything - ``holdout_count``,
+``split_offsets``: two complementary window tables - and ``heldout.HeldOutSweep`` walks them.
 """
 from __future__ import annotations
 
+import math
 import os
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
@@ -172,10 +176,54 @@ def valid_offsets(episode_off: torch.Tensor, chunk: int) -> torch.Tensor:
     return torch.cat([torch.zeros(1, dtype=torch.int64), n.cumsum(0)])
 
 
-class EpisodeStore:
-    """Episodes on the device; ``sample()`` draws one raw batch.  Build with ``EpisodeStore.load`` or ``EpisodeStore.from_dict``."""
+# ---------------------------------------------------------------------------------------------------------------- the held-out split
+def holdout_count(E: int, f: float) -> int:
+    """How many of a dataset's E episodes - its LAST ones - a hold-out fraction f sets aside: min(E - 1, max(1, floor(f E + 0.5)))."""
+    return min(E - 1, max(1, int(math.floor(f * E + 0.5))))
 
-    def __init__(self, tables: dict, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, _where: str = "episode store"):
+
+def check_holdout(f, E: int, name: str) -> int:
+    """H for dataset ``name``; ValueError naming it for a fraction outside (0, 1) or a dataset of fewer than 2 episodes."""
+    if isinstance(f, bool) or not isinstance(f, (int, float)) or not 0.0 < float(f) < 1.0:         # (NaN fails the comparison too)
+        raise ValueError(f"{name}: holdout must be a fraction inside (0, 1), got {f!r}")
+    if E < 2:
+        raise ValueError(f"{name}: holdout needs at least 2 episodes (one to train on, one to hold out), the dataset has {E}")
+    return holdout_count(E, float(f))
+
+
+def split_offsets(episode_off: torch.Tensor, chunk: int, held: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(training valid_off, val_off), both int64 [E + 1]: the prefix sums of the windows each episode yields (valid_offsets) in which
+    the held-out episodes (held bool [E]) / the training episodes contribute 0.  Nothing is copied or reordered: the samplers step over
+    an episode without windows, so the training samplers never draw a held-out episode and the sweep never a training one."""
+    n = (episode_off.diff() - (chunk - 1)).clamp_(min=0)
+    zero = torch.zeros(1, dtype=torch.int64)
+    return (torch.cat([zero, torch.where(held, 0, n).cumsum(0)]), torch.cat([zero, torch.where(held, n, 0).cumsum(0)]))
+
+
+def check_split(train_off, val_off, e_lo: int, e_hi: int, H: int, chunk: int, name: str) -> dict:
+    """The split of dataset ``name`` (episodes [e_lo, e_hi), the last H held out) as info["heldout"] records it; ValueError naming the
+    dataset when either side is left without a window."""
+    n_train, n_val = int(train_off[e_hi]) - int(train_off[e_lo]), int(val_off[e_hi]) - int(val_off[e_lo])
+    if n_train < 1:
+        raise ValueError(f"{name}: holdout leaves no training window - every one of the {e_hi - e_lo - H} training episodes is shorter than "
+                         f"the action chunk of {chunk} steps")
+    if n_val < 1:
+        raise ValueError(f"{name}: holdout leaves no held-out window - every one of the {H} held-out episodes (the last ones) is shorter "
+                         f"than the action chunk of {chunk} steps")
+    return dict(episodes=[e_hi - H, e_hi], num_episodes=H, train_windows=n_train, heldout_windows=n_val)
+
+
+class EpisodeStore:
+    """Episodes on the device; ``sample()`` draws one raw batch.  Build with ``EpisodeStore.load`` or ``EpisodeStore.from_dict``.
+
+    ``holdout=f`` (0 < f < 1) sets the last ``holdout_count(E, f)`` episodes aside for validation (heldout.HeldOutSweep): the training
+    table ``valid_off`` then counts no window of theirs - ``sample()`` never draws them, ``N`` is the number of training windows - and
+    ``val_off`` / ``Nv`` are the complementary table and count.  ``statistics()`` stays over ALL episodes, as the reference takes them
+    over split="all" (rlds/dataset.py:209-211): the split changes no dataset_statistics.json.  ``holdout=None``: every table and every
+    batch is what it is without the argument."""
+
+    def __init__(self, tables: dict, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, _where: str = "episode store",
+                 *, holdout: Optional[float] = None):
         if chunk < 1:
             raise ValueError("chunk must be >= 1")
         _check_shard(tables, _where)
@@ -184,10 +232,17 @@ class EpisodeStore:
         self.action_mask = torch.as_tensor(tables["action_mask"]).tolist() if "action_mask" in tables else None
         act, pr, eo, po = tables["actions_raw"], tables["proprio_raw"], tables["episode_off"], tables["prompt_off"]
         valid = valid_offsets(eo.cpu(), self.chunk)
-        self.N = int(valid[-1])
-        if self.N < 1:
+        if int(valid[-1]) < 1:
             raise ValueError(f"{_where}: no valid window - every one of the {eo.numel() - 1} episodes is shorter than the action chunk of "
                              f"{self.chunk} steps (episode_off)")
+        self.holdout, self.heldout, val = holdout, None, None
+        if holdout is not None:
+            E = int(eo.numel() - 1)
+            H = check_holdout(holdout, E, self.dataset_name)
+            valid, val = split_offsets(eo.cpu(), self.chunk, torch.arange(E) >= E - H)
+            self.heldout = {self.dataset_name: check_split(valid, val, 0, E, H, self.chunk, self.dataset_name)}
+        self.N = int(valid[-1])
+        self.Nv = int(val[-1]) if val is not None else 0
         self.T, self.E = int(act.shape[0]), int(eo.numel() - 1)
         self.A, self.Pd = int(act.shape[1]), int(pr.shape[1])
         self.frame_shape = tuple(tables["frames_u8"].shape[1:])
@@ -198,19 +253,23 @@ class EpisodeStore:
         dv = lambda t: t.to(device).contiguous()
         self.frames_u8, self.actions_raw, self.proprio_raw = dv(tables["frames_u8"]), dv(act), dv(pr)
         self.episode_off, self.valid_off = dv(eo), dv(valid)
+        self.val_off_host, self.val_off = val, (dv(val) if val is not None else None)
         self.prompt_flat, self.prompt_off = dv(tables["prompt_flat"]), dv(po)
         self._out: Dict[int, dict] = {}
 
     # ---- construction --------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_dict(cls, tables: dict, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None) -> "EpisodeStore":
-        return cls(tables, device, chunk, dataset_name)
+    def from_dict(cls, tables: dict, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, *,
+                  holdout: Optional[float] = None) -> "EpisodeStore":
+        return cls(tables, device, chunk, dataset_name, holdout=holdout)
 
     @classmethod
-    def load(cls, path, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None) -> "EpisodeStore":
+    def load(cls, path, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, *,
+             holdout: Optional[float] = None) -> "EpisodeStore":
         """``path``: a .pt episode file or a directory of them (concatenated in sorted order).  Validates the tables (ValueError that
-        names the key), moves everything to the device and builds valid_off; ``dataset_name``: used when the file names none."""
-        return cls(load_tables(path, device), device, chunk, dataset_name, _where=str(path))
+        names the key), moves everything to the device and builds valid_off; ``dataset_name``: used when the file names none;
+        ``holdout``: the fraction of episodes - the last ones - set aside for validation (see the class)."""
+        return cls(load_tables(path, device), device, chunk, dataset_name, _where=str(path), holdout=holdout)
 
     # ---- the two products ----------------------------------------------------------------------------------------------------
     def statistics(self) -> dict:

@@ -11,8 +11,9 @@ statistics of ``--dataset_statistics_file``), from ``--episode_file`` (demonstra
 chunked by two kernels, statistics computed at load - episodes.EpisodeStore), from ``--episode_mix`` (a weighted mixture of such
 datasets, every sample normalised with its own dataset's statistics - mixture.EpisodeMix) or ``synthetic.make_batch``; weights are random-init unless ``--vlm_path`` / ``--resum_vla_path`` point at local state-dict
 files.  ``--use_val_set`` runs the reference's validation pass (finetune.py:605-685, 1101-1117) on held-out batches of the same
-form (``--val_batch_file`` / ``finetune(val_batches=...)``; ``ValidationPass``); the RLDS val split itself is not read.  Every
-reference flag is either honoured or refused with an error (``check_supported``); none is silently dropped.
+form (``--val_batch_file`` / ``finetune(val_batches=...)``; ``ValidationPass``), or - with an episode source and
+``--val_episode_fraction`` - on the episodes that fraction holds out of every dataset, swept on the device (``heldout.HeldOutSweep``); the
+RLDS val split itself is not read.  Every reference flag is either honoured or refused with an error (``check_supported``); none is silently dropped.
 """
 from __future__ import annotations
 
@@ -101,6 +102,10 @@ class FinetuneConfig:
                                           # (mixture.EpisodeMix; needs --max_seq_len; without --dataset_statistics_file the mix's statistics are
                                           # used and saved, one entry per dataset)
     episode_mix_balance: bool = True      # the reference's balance_weights: p_d = w_d T_d / sum(w T) over the transition counts, else w_d / sum(w)
+    val_episode_fraction: Optional[float] = None   # --use_val_set with --episode_file / --episode_mix: hold out this fraction of every dataset's
+                                          # episodes (its last ones; never trained on) and sweep their windows on the device every --val_freq steps
+                                          # (heldout.HeldOutSweep); the statistics stay over all episodes, as the reference's split="all"
+    val_window_stride: int = 1            # the held-out sweep visits every k-th window (consecutive windows of an episode share 7 of 8 actions)
     use_graph: bool = True                # replay the captured hipGraphs
     max_seq_len: int = 0                  # static token length every batch is right-padded to (0: length of the first batch)
     conservative_rows: bool = False       # captured live-row window starts at the first text row instead of the first batch's action block
@@ -131,7 +136,7 @@ def parse_args(argv=None) -> FinetuneConfig:
         elif t is type(Path(".")):
             ap.add_argument(f"--{f.name}", type=Path, default=default)
         else:
-            ap.add_argument(f"--{f.name}", type=(int if f.name in ("resume_step",) else float if f.name in ("max_grad_norm",) else t), default=default)
+            ap.add_argument(f"--{f.name}", type=(int if f.name in ("resume_step",) else float if f.name in ("max_grad_norm", "val_episode_fraction") else t), default=default)
     ns = ap.parse_args(argv)
     cfg = FinetuneConfig(**vars(ns))
     import sys
@@ -144,7 +149,7 @@ def parse_args(argv=None) -> FinetuneConfig:
 # W&B, HF hub): the native entry point consumes pre-collated batches, so their DEFAULT values are inert - but a value the
 # user passes explicitly cannot be honoured and is refused instead of ignored.  (--image_aug is honoured where batches carry
 # raw frames, --frame_batch_file: check_supported / batch_stream; --val_freq / --val_time_limit under --use_val_set with a
-# validation source: ValidationPass.)
+# validation source: ValidationPass, or heldout.HeldOutSweep under --val_episode_fraction.)
 OUT_OF_PATH_FLAGS = ("data_root_dir", "shuffle_buffer_size", "wandb_entity", "wandb_project", "run_id_note",
                      "config_file_path", "phase1_path", "num_diffusion_steps", "diffusion_sample_freq", "val_freq", "val_time_limit",
                      "use_minivlm")
@@ -191,14 +196,28 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
     if cfg.use_film or cfg.use_diffusion or not cfg.use_l1_regression:
         raise NotImplementedError("native path = L1-regression action head; --use_film / --use_diffusion are not built")
     validating = False
+    heldout = cfg.val_episode_fraction is not None
+    if heldout:
+        if not cfg.use_val_set:
+            raise ValueError("--val_episode_fraction without --use_val_set True would hold episodes out and never validate on them: pass both")
+        if cfg.val_batch_file or val_batches:
+            raise ValueError("--val_episode_fraction and --val_batch_file / val_batches are two validation sources: pass one")
+        if not (cfg.episode_file or cfg.episode_mix):
+            raise ValueError("--val_episode_fraction holds episodes out of --episode_file / --episode_mix: no other batch source has episodes")
+        if not 0.0 < float(cfg.val_episode_fraction) < 1.0:            # (NaN fails the comparison too)
+            raise ValueError(f"--val_episode_fraction must lie inside (0, 1), got {cfg.val_episode_fraction}")
+        if cfg.val_window_stride < 1:
+            raise ValueError("--val_window_stride must be >= 1")
     if cfg.use_val_set:
-        if cfg.episode_file and not (cfg.val_batch_file or val_batches):
+        if cfg.episode_file and not (cfg.val_batch_file or val_batches or heldout):
             raise NotImplementedError("--use_val_set with --episode_file: no validation split is cut from the episodes (ValidationPass takes "
-                                      "collated batches); pass held-out batches with --val_batch_file")
-        if cfg.episode_mix and not (cfg.val_batch_file or val_batches):
+                                      "collated batches); pass held-out batches with --val_batch_file.  Or hold a fraction of the "
+                                      "episodes out with --val_episode_fraction.")
+        if cfg.episode_mix and not (cfg.val_batch_file or val_batches or heldout):
             raise NotImplementedError("--use_val_set with --episode_mix: no validation split is cut from the episodes (ValidationPass takes "
-                                      "collated batches); pass held-out batches with --val_batch_file")
-        if not (cfg.val_batch_file or val_batches):
+                                      "collated batches); pass held-out batches with --val_batch_file.  Or hold a fraction of the "
+                                      "episodes out with --val_episode_fraction.")
+        if not (cfg.val_batch_file or val_batches or heldout):
             raise NotImplementedError("--use_val_set needs held-out batches: pass --val_batch_file (a .pt dict or a directory of them) or "
                                       "finetune(val_batches=...); the RLDS val split is not read (out of scope, SURVEY section 2 #16)")
         if cfg.objective != "l1":
@@ -484,6 +503,10 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
     --dataset_statistics_file it is normalised with ``store.statistics()``, which is then also left in ``info["dataset_statistics"]``
     (the caller's dict) for the checkpoints.
 
+    ``--val_episode_fraction f``: store and mix are built with ``holdout=f`` - every dataset's last episodes are never drawn here (the
+    training table counts no window of theirs) and wait for ``heldout.HeldOutSweep``; the statistics stay over all episodes.
+    ``info["store"]`` hands the store / mix to the caller.
+
     ``--episode_mix``: the same over a weighted mixture of datasets (``mixture.EpisodeMix``): the raw batch then carries
     ``dataset_index`` (int32 [B]) and ``dataset_names``, and every sample is normalised with its own dataset's entry - of the mix's
     statistics, or of --dataset_statistics_file, which must then hold every name (KeyError naming the missing one).  Such a batch
@@ -564,7 +587,7 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
                 raise ValueError("empty batch iterable")
     elif cfg.episode_file:
         from .episodes import EpisodeStore
-        store = EpisodeStore.load(cfg.episode_file, dev, chunk=mcfg.chunk, dataset_name=cfg.dataset_name)
+        store = EpisodeStore.load(cfg.episode_file, dev, chunk=mcfg.chunk, dataset_name=cfg.dataset_name, holdout=cfg.val_episode_fraction)
         if (store.A, store.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
             raise ValueError(f"{cfg.episode_file}: actions_raw / proprio_raw have {store.A} / {store.Pd} columns, the model takes "
                              f"{mcfg.action_dim} / {mcfg.proprio_dim}")
@@ -574,11 +597,14 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
             norm_stats = store.statistics()
             if info is not None:
                 info["dataset_statistics"] = norm_stats
+        if info is not None:
+            info["store"] = store                 # (the held-out sweep walks the same device-resident tables)
         while True:
             yield collate_raw(store.sample(cfg.batch_size, cfg.seed, rank, world, step))
     elif cfg.episode_mix:
         from .mixture import EpisodeMix, parse_mix
-        mix = EpisodeMix.load(parse_mix(cfg.episode_mix), dev, chunk=mcfg.chunk, balance_weights=cfg.episode_mix_balance)
+        mix = EpisodeMix.load(parse_mix(cfg.episode_mix), dev, chunk=mcfg.chunk, balance_weights=cfg.episode_mix_balance,
+                              holdout=cfg.val_episode_fraction)
         if (mix.A, mix.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
             raise ValueError(f"--episode_mix: actions_raw / proprio_raw have {mix.A} / {mix.Pd} columns, the model takes "
                              f"{mcfg.action_dim} / {mcfg.proprio_dim}")
@@ -592,6 +618,7 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
                 info["dataset_statistics"] = norm_stats
         if info is not None:
             info["mixture"] = mix.mixture_info()
+            info["store"] = mix
         if rank == 0:
             print(json.dumps(dict(mixture=mix.mixture_info())), flush=True)
         while True:
@@ -701,7 +728,14 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
         else:
             eng.capture(static, noise if training else None, conservative_rows=cfg.conservative_rows)
     validator = None
-    if cfg.use_val_set:
+    if cfg.use_val_set and cfg.val_episode_fraction is not None:
+        from .heldout import HeldOutSweep
+        validator = HeldOutSweep(cfg, mcfg, dev, rank, world, trainer or eng, info["store"], stats, static if static is not None else cur, L,
+                                 use_graph)
+        info["heldout"] = validator.info()
+        if rank == 0:
+            print(json.dumps(dict(heldout=info["heldout"])), flush=True)
+    elif cfg.use_val_set:
         validator = ValidationPass(cfg, mcfg, dev, rank, trainer or eng, static if static is not None else cur, L, pad_id, use_graph,
                                    val_batches)
     log, val_log, t0, saved_at, steps_done = [], [], time.time(), None, 0
@@ -773,4 +807,6 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
     out = dict(log=log, val_log=val_log, seconds=time.time() - t0, steps=steps_done, world=world, final_step=final_step, run_dir=str(run_dir), mode=mode, model=model)
     if "mixture" in info:                        # --episode_mix: names, probabilities, quotas, period, the reference's dataset_len
         out["mixture"] = info["mixture"]
+    if "heldout" in info:                        # --val_episode_fraction: per dataset the held-out episode range and the window counts
+        out["heldout"] = info["heldout"]
     return out

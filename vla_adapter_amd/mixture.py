@@ -16,14 +16,14 @@ from __future__ import annotations
 
 import math
 from pathlib import Path
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .constants import NUM_ACTIONS_CHUNK
-from .episodes import (MAX_BATCH, _M64, _check_shard, concat_shards, dataset_statistics, epoch_key, load_tables, locate, permute_index,
-                       sample_position, splitmix64_key, valid_offsets)
+from .episodes import (MAX_BATCH, _M64, _check_shard, check_holdout, check_split, concat_shards, dataset_statistics, epoch_key, load_tables, locate, permute_index,
+                       sample_position, split_offsets, splitmix64_key, valid_offsets)
 from .finetune import RAW_BATCH_KEYS
 
 MIX_STREAM = 0x313D0DA7A5E75            # csrc/mixture.hip: keeps the period shuffle apart from the window shuffle (EPISODE_STREAM), the
@@ -114,7 +114,7 @@ class EpisodeMix:
     ``EpisodeMix.load`` or ``EpisodeMix.from_dicts``."""
 
     def __init__(self, tables: List[dict], weights: Sequence[float], names: Sequence[str], device, chunk: int = NUM_ACTIONS_CHUNK,
-                 period: int = DEFAULT_PERIOD, balance_weights: bool = True):
+                 period: int = DEFAULT_PERIOD, balance_weights: bool = True, *, holdout: Optional[float] = None):
         if chunk < 1:
             raise ValueError("chunk must be >= 1")
         if not tables:
@@ -152,6 +152,21 @@ class EpisodeMix:
         act, pr, eo, po = all_["actions_raw"], all_["proprio_raw"], all_["episode_off"], all_["prompt_off"]
         valid = valid_offsets(eo.cpu(), self.chunk)
         self.T, self.E = int(act.shape[0]), int(eo.numel() - 1)
+        # holdout=f: every dataset sets its own last H_d episodes aside (episodes.EpisodeStore).  transitions, p, the quotas and the
+        # statistics stay over ALL episodes - the reference balances and normalises over split="all" (rlds/dataset.py:209-211) -;
+        # windows becomes the training windows N_d, which the sampler reads from valid_off on the device
+        self.holdout, self.heldout, val = holdout, None, None
+        if holdout is not None:
+            held = torch.zeros(self.E, dtype=torch.bool)
+            counts = [check_holdout(holdout, ds_off[d + 1] - ds_off[d], n) for d, n in enumerate(names)]
+            for d, H in enumerate(counts):
+                held[ds_off[d + 1] - H:ds_off[d + 1]] = True
+            valid, val = split_offsets(eo.cpu(), self.chunk, held)
+            self.heldout = {n: check_split(valid, val, ds_off[d], ds_off[d + 1], counts[d], self.chunk, n) for d, n in enumerate(names)}
+            self.windows = [self.heldout[n]["train_windows"] for n in names]
+        self.N = int(valid[-1])
+        self.Nv = int(val[-1]) if val is not None else 0
+        self.val_off_host = val
         self.A, self.Pd = int(act.shape[1]), int(pr.shape[1])
         self.frame_shape = tuple(all_["frames_u8"].shape[1:])
         self.row_bytes = int(np.prod(self.frame_shape))
@@ -162,20 +177,24 @@ class EpisodeMix:
         dv = lambda t: t.to(device).contiguous()
         self.frames_u8, self.actions_raw, self.proprio_raw = dv(all_["frames_u8"]), dv(act), dv(pr)
         self.episode_off, self.valid_off = dv(eo), dv(valid)
+        self.val_off = dv(val) if val is not None else None
         self.prompt_flat, self.prompt_off = dv(all_["prompt_flat"]), dv(po)
         self.dataset_off, self.quota_off = dv(self.dataset_off_host), dv(self.quota_off_host)
         self._out: Dict[int, dict] = {}
 
     # ---- construction --------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_dicts(cls, entries, device, chunk: int = NUM_ACTIONS_CHUNK, period: int = DEFAULT_PERIOD, balance_weights: bool = True) -> "EpisodeMix":
+    def from_dicts(cls, entries, device, chunk: int = NUM_ACTIONS_CHUNK, period: int = DEFAULT_PERIOD, balance_weights: bool = True, *,
+                   holdout: Optional[float] = None) -> "EpisodeMix":
         """``entries``: [(tables dict, weight)]; a dict without dataset_name is called dataset_<index>."""
-        return cls.load(entries, device, chunk, period, balance_weights)
+        return cls.load(entries, device, chunk, period, balance_weights, holdout=holdout)
 
     @classmethod
-    def load(cls, entries, device, chunk: int = NUM_ACTIONS_CHUNK, period: int = DEFAULT_PERIOD, balance_weights: bool = True) -> "EpisodeMix":
+    def load(cls, entries, device, chunk: int = NUM_ACTIONS_CHUNK, period: int = DEFAULT_PERIOD, balance_weights: bool = True, *,
+             holdout: Optional[float] = None) -> "EpisodeMix":
         """``entries``: [(path or tables dict, weight)]; a path is anything ``EpisodeStore.load`` takes.  A dataset is called by its
-        file's dataset_name, else by the path's stem."""
+        file's dataset_name, else by the path's stem.  ``holdout``: the fraction of every dataset's episodes - its last ones - set aside
+        for validation (episodes.EpisodeStore); None: every table and batch is what it is without the argument."""
         tables, weights, names = [], [], []
         for i, entry in enumerate(entries):
             src, w = entry if isinstance(entry, (tuple, list)) else (entry, 1.0)
@@ -189,7 +208,7 @@ class EpisodeMix:
             tables.append(d)
             weights.append(w)
             names.append(name if isinstance(name, str) and name else fallback)
-        return cls(tables, weights, names, device, chunk, period, balance_weights)
+        return cls(tables, weights, names, device, chunk, period, balance_weights, holdout=holdout)
 
     # ---- what the mix is -----------------------------------------------------------------------------------------------------
     def statistics(self) -> dict:

@@ -177,6 +177,14 @@ MIXTURE_PROTOS = {
 }
 MIXTURE_SYMBOLS = sorted(MIXTURE_PROTOS)
 
+# validation on held-out episodes (include/vla_heldout.h, csrc/heldout.hip): a fifth table, bound by name in the same way
+# (tests/test_heldout_cpu.py checks header, table and library against each other)
+HELDOUT_PROTOS = {
+    "vla_heldout_sweep": ([_P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P], _I),
+    "vla_heldout_l1_accumulate": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
+}
+HELDOUT_SYMBOLS = sorted(HELDOUT_PROTOS)
+
 _lib = None
 
 
@@ -190,7 +198,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()):
+    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()) + list(HELDOUT_PROTOS.items()):
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

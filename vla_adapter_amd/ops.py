@@ -1085,3 +1085,35 @@ def normalize_bounds_rows(x_f32: torch.Tensor, sel: torch.Tensor, low: torch.Ten
     N.check(_lib().vla_normalize_bounds_rows(_st(), _p(x_f32), _p(out), R, x_f32.numel() // R, D, _p(sel), n_sets, _p(low), _p(high), _p(mask),
                                              _p(zero_mask)), "normalize_bounds_rows")
     return out
+
+
+# ---- validation on held-out episodes (include/vla_heldout.h, csrc/heldout.hip) -------------------------------------------------------
+def heldout_sweep(val_off: torch.Tensor, episode_off: torch.Tensor, prompt_off: torch.Tensor, dataset_off: Optional[torch.Tensor], rank: int,
+                  world: int, batch_j: int, stride: int, Pmax: int, ds: torch.Tensor, ep: torch.Tensor, row: torch.Tensor, out_off: torch.Tensor,
+                  valid: torch.Tensor) -> None:
+    """vla_heldout_sweep: the held-out windows of validation batch batch_j of this rank, in order -> ds int32 [B], ep int32 [B], row int64
+    [B], out_off int32 [B + 1], valid u8 [B] (all given).  dataset_off int32 [D + 1], or None for a single dataset."""
+    E, B, dev = val_off.numel() - 1, ep.numel(), val_off.device
+    D = 1 if dataset_off is None else dataset_off.numel() - 1
+    for t, dt, n in ((val_off, torch.int64, E + 1), (episode_off, torch.int64, E + 1), (prompt_off, torch.int32, E + 1),
+                     (dataset_off, torch.int32, D + 1), (ds, torch.int32, B), (ep, torch.int32, B), (row, torch.int64, B),
+                     (out_off, torch.int32, B + 1), (valid, torch.uint8, B)):
+        assert t is None or (t.is_cuda and t.device == dev and t.dtype == dt and t.dim() == 1 and t.numel() == n and t.is_contiguous()), \
+            "heldout_sweep: bad operand"
+    N.check(_lib().vla_heldout_sweep(_st(), _p(val_off), _p(episode_off), _p(prompt_off), _p(dataset_off), E, D, int(rank), int(world),
+                                     int(batch_j), int(stride), B, int(Pmax), _p(ds), _p(ep), _p(row), _p(out_off), _p(valid)), "heldout_sweep")
+
+
+def heldout_l1_accumulate(pred: torch.Tensor, target: torch.Tensor, ds: Optional[torch.Tensor], valid: torch.Tensor, acc: torch.Tensor,
+                          cnt: torch.Tensor) -> None:
+    """vla_heldout_l1_accumulate: acc f64 [D, C, A] += per-dataset sums over the valid rows of |pred - target| (bf16 [B, C, A]), cnt int64
+    [D] += their number; ds int32 [B] or None (all rows dataset 0), valid u8 [B]."""
+    _chk_bf16(pred, target)
+    B, Cc, A = pred.shape
+    D, dev = acc.shape[0], pred.device
+    assert pred.is_contiguous() and target.is_contiguous() and tuple(target.shape) == (B, Cc, A) and target.device == dev
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and tuple(acc.shape) == (D, Cc, A) and acc.device == dev
+    assert cnt.dtype == torch.int64 and cnt.is_contiguous() and tuple(cnt.shape) == (D,) and cnt.device == dev
+    assert valid.dtype == torch.uint8 and valid.is_contiguous() and tuple(valid.shape) == (B,) and valid.device == dev
+    assert ds is None or (ds.dtype == torch.int32 and ds.is_contiguous() and tuple(ds.shape) == (B,) and ds.device == dev)
+    N.check(_lib().vla_heldout_l1_accumulate(_st(), _p(pred), _p(target), _p(ds), _p(valid), B, Cc, A, D, _p(acc), _p(cnt)), "heldout_l1_accumulate")

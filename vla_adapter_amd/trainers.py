@@ -176,6 +176,7 @@ class BackboneTrainer(E.Linear, schedule.StepControls):
         self.group_tn = not os.environ.get("VLA_NO_GROUPED_TN")          # (A/B knob)
         self._deferred = []
         self._refreshed, self._rgraphs = set(), {}      # derived operands rebuilt behind a range's AdamW in this step; their graphs (captured step)
+        self._val_pred = None
         self._evaluating, self._val_graphs = False, None     # validation forward (val_forward / val_step_graphed)
         self._graphs = None      # the captured step (capture())
         self._timeline = None    # a list collects (kind, index, start, end) events of every segment run (tools/trainer_timeline.py)
@@ -921,8 +922,16 @@ class BackboneTrainer(E.Linear, schedule.StepControls):
         segs = self._segments(batch, noise)[:self._n_forward]
 
         def h_loss():
+            self._val_pred = self._pred
             self._val_loss3 = ops.l1_loss(self._pred, self.eng._to_bf16(batch["actions"]), want_grad=False)[0]
         return segs + [Segment("H", h_loss)]
+
+    @property
+    def val_pred(self) -> torch.Tensor:
+        """The prediction of the last validation forward (val_forward / val_step_graphed): bf16 [B, chunk, action_dim] on the device,
+        final in stream order when that call returns (heldout.HeldOutSweep reads it)."""
+        cfg = self.eng.cfg
+        return self._val_pred.view(-1, cfg.chunk, cfg.action_dim)
 
     def val_forward(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Eager validation of one batch on the current stream -> f32 [3] (loss, current action, next actions)."""
