@@ -30,7 +30,8 @@ extern "C" {
  *   row     int64 [B]      = episode_off[e] + t, the global row of the window's first step, kept inside episode e
  *   out_off int32 [B + 1]  = exclusive scan of the chosen episodes' prompt lengths, each clamped into [0, Pmax]  (out_off[B] <= B * Pmax)
  * One epoch therefore visits every window exactly once across all ranks and steps; every rank passes the same seed.  N is read from
- * valid_off[E] on the device; with N < 1 (a bad table) every sample is window 0 of episode 0.  0 <= rank < world, step >= 0. */
+ * valid_off[E] on the device; with N < 1 (a bad table) every sample is window 0 of episode 0.  0 <= rank < world, step >= 0, and the position
+ * of the batch's last sample, (step world + rank) B + B - 1, below 2^63 (refused otherwise: the kernel forms it in 64 bits). */
 int vla_episode_sample(void* stream, const long long* valid_off, const long long* episode_off, const int* prompt_off, int E,
                        unsigned long long seed, long long rank, long long world, long long step, int B, int Pmax, int* ep,
                        long long* row, int* out_off);

@@ -36,7 +36,8 @@ extern "C" {
  * [k q_d, (k + 1) q_d): each dataset runs through its own endless epochs, every window once per N_d ordinals, whatever B and world
  * are.  Q and N_d are read from the tables on the device.  A bad table does not make the kernel read outside: both searches end
  * inside their table (dataset_off is clamped into [0, E]); N_d < 1 yields window 0 of the dataset's first episode; Q < 1 yields
- * dataset 0 with c = position.  0 <= rank < world, step >= 0. */
+ * dataset 0 with c = position.  0 <= rank < world, step >= 0, and the position of the batch's last sample,
+ * (step world + rank) B + B - 1, below 2^63 (refused otherwise: the kernel forms it in 64 bits). */
 int vla_mixture_sample(void* stream, const long long* valid_off, const long long* episode_off, const int* prompt_off,
                        const int* dataset_off, const long long* quota_off, int E, int D, unsigned long long seed, long long rank,
                        long long world, long long step, int B, int Pmax, int* ds, int* ep, long long* row, int* out_off);

@@ -84,6 +84,36 @@ def test_training_abi_is_unchanged():
     assert sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", stripped))) == native.ABI_SYMBOLS, "vla_native.h declares the training table only"
 
 
+def largest_step(B, rank, world):
+    """The largest step whose batch ends at a position below 2^63, in Python integers."""
+    step = (2 ** 63 - 1 - (B - 1) - rank * B) // (world * B)
+    assert EP.sample_position(B, rank, world, step, B - 1) <= 2 ** 63 - 1 < EP.sample_position(B, rank, world, step + 1, B - 1)
+    return step
+
+
+@pytest.mark.parametrize("B, rank, world", [(4, 0, 1), (4, 2, 3), (2, 1, 2), (1024, 7, 8), (1000, 5, 2 ** 20)])
+def test_sample_refuses_a_stream_position_beyond_63_bits(lib, B, rank, world):
+    """The largest step whose last sample stands below 2^63 passes the position check - the call is then stopped by the NEXT check, B *
+    Pmax, which this test violates on purpose so that nothing is launched - and the step behind it is refused by name.  The Python
+    rule refuses the same arguments."""
+    P, step = 8, largest_step(B, rank, world)
+    call = lambda s: lib.vla_episode_sample(None, P, P, P, 5, 0, rank, world, s, B, 2 ** 31 - 1, P, P, P)
+    assert call(step) == -1 and b"B * Pmax" in lib.vla_last_error(), "accepted by the position check"
+    assert call(step + 1) == -1 and b"stream position overflows 63 bits" in lib.vla_last_error()
+    assert call(2 ** 63 - 1) == -1 and b"stream position overflows 63 bits" in lib.vla_last_error()
+    EP.check_position(B, rank, world, step)
+    with pytest.raises(ValueError, match="stream position overflows 63 bits"):
+        EP.check_position(B, rank, world, step + 1)
+    assert lib.vla_episode_sample(None, P, P, P, 5, 0, 2 ** 62, 2 ** 62 + 1, 0, B, 2 ** 31 - 1, P, P, P) == -1
+    assert b"stream position overflows 63 bits" in lib.vla_last_error(), "a rank term that overflows on its own"
+
+
+def test_the_store_refuses_the_overflowing_step_before_the_device():
+    st = EP.EpisodeStore.from_dict(make_tables(), "cpu", chunk=CHUNK)
+    with pytest.raises(ValueError, match="stream position overflows 63 bits"):
+        st.sample_indices(4, 0, 2, 3, largest_step(4, 2, 3) + 1)
+
+
 def test_every_episode_symbol_has_a_memory_contract_case_or_an_exemption():
     from tests import test_episodes_memory_contract_gpu as M
     from vla_adapter_amd import native

@@ -121,6 +121,21 @@ def test_host_checks_refuse_bad_arguments(lib):
     assert lib.vla_normalize_bounds_rows(None, P, P, 5, 56, 7, P, 0, P, P, None, None) == -1
 
 
+@pytest.mark.parametrize("B, rank, world", [(4, 0, 1), (4, 2, 3), (2, 1, 2), (1024, 7, 8), (1000, 5, 2 ** 20)])
+def test_sample_refuses_a_stream_position_beyond_63_bits(lib, mix, B, rank, world):
+    """As tests/test_episodes_cpu.py has it for vla_episode_sample: the largest step is accepted by the position check (and stopped by
+    the next one, B * Pmax, violated on purpose: nothing is launched), the step behind it is refused by name."""
+    from tests.test_episodes_cpu import largest_step
+    P, step = 8, largest_step(B, rank, world)
+    call = lambda s: lib.vla_mixture_sample(None, P, P, P, P, P, 8, 3, 0, rank, world, s, B, 2 ** 31 - 1, P, P, P, P)
+    assert call(step) == -1 and b"B * Pmax" in lib.vla_last_error(), "accepted by the position check"
+    assert call(step + 1) == -1 and b"stream position overflows 63 bits" in lib.vla_last_error()
+    assert call(2 ** 63 - 1) == -1 and b"stream position overflows 63 bits" in lib.vla_last_error()
+    _, m = mix
+    with pytest.raises(ValueError, match="stream position overflows 63 bits"):
+        m.sample_indices(B, 0, rank, world, step + 1)
+
+
 def test_every_mixture_symbol_has_a_memory_contract_case_or_an_exemption():
     from tests import test_mixture_memory_contract_gpu as M
     from vla_adapter_amd import native

@@ -116,8 +116,11 @@ extern "C" int vla_mixture_sample(void* stream, const long long* valid_off, cons
   VLA_REQUIRE(valid_off && episode_off && prompt_off && dataset_off && quota_off && ds && ep && row && out_off, "mixture_sample: null pointer");
   VLA_REQUIRE(E >= 1 && D >= 1 && D <= E, "mixture_sample: E >= 1, 1 <= D <= E (every dataset holds an episode)");
   VLA_REQUIRE(B >= 1 && B <= SAMPLE_MAX_B && Pmax >= 0, "mixture_sample: 1 <= B <= 1024 (one workgroup), Pmax >= 0");
-  VLA_REQUIRE((long long)B * Pmax <= 0x7fffffffll, "mixture_sample: B * Pmax must fit int32 offsets");
   VLA_REQUIRE(world >= 1 && rank >= 0 && rank < world && step >= 0, "mixture_sample: 0 <= rank < world, step >= 0");
+  // (step * world + rank) * B + (B - 1), the position of the batch's last sample, stays below 2^63: the kernel forms it in u64
+  const long long most = (0x7fffffffffffffffll - (B - 1)) / B;
+  VLA_REQUIRE(rank <= most && step <= (most - rank) / world, "mixture_sample: the stream position overflows 63 bits");
+  VLA_REQUIRE((long long)B * Pmax <= 0x7fffffffll, "mixture_sample: B * Pmax must fit int32 offsets");
   const int threads = (B + 63) / 64 * 64;
   hipLaunchKernelGGL(mixture_sample_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, valid_off, episode_off, prompt_off, dataset_off,
                      quota_off, E, D, (u64)seed, (u64)rank, (u64)world, (u64)step, B, Pmax, ds, ep, row, out_off);

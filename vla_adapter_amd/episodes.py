@@ -60,6 +60,15 @@ def sample_position(B: int, rank: int, world: int, step: int, b: int) -> int:
     return (step * world + rank) * B + b
 
 
+def check_position(B: int, rank: int, world: int, step: int) -> None:
+    """ValueError when the position of the batch's last sample does not fit 63 bits: the kernels form it in 64-bit wrap-around
+    arithmetic, this rule in Python integers, and the two part ways there (the entry points refuse the same arguments)."""
+    last = sample_position(B, rank, world, step, B - 1)
+    if last > 2 ** 63 - 1:
+        raise ValueError(f"sample: the stream position overflows 63 bits (rank {rank}, world {world}, step {step}, batch size {B}: the "
+                         f"last sample stands at {last})")
+
+
 def epoch_key(seed: int, epoch: int) -> int:
     return splitmix64_key((seed & _M64) ^ EPISODE_STREAM, epoch)
 
@@ -294,6 +303,7 @@ class EpisodeStore:
             raise ValueError(f"sample: the batch size must lie in [1, {MAX_BATCH}] (one workgroup draws the batch), got {B}")
         if not (world >= 1 and 0 <= rank < world and step >= 0):
             raise ValueError(f"sample: need 0 <= rank < world and step >= 0, got rank {rank}, world {world}, step {step}")
+        check_position(B, rank, world, step)
         o = self._buffers(B)
         ops.episode_sample(self.valid_off, self.episode_off, self.prompt_off, seed, rank, world, step, self.Pmax, o["ep"], o["row"], o["prompt_off"])
         return o["ep"], o["row"], o["prompt_off"]

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .constants import NUM_ACTIONS_CHUNK
-from .episodes import (MAX_BATCH, _M64, _check_shard, check_holdout, check_split, concat_shards, dataset_statistics, epoch_key, load_tables, locate, permute_index,
+from .episodes import (MAX_BATCH, _M64, _check_shard, check_holdout, check_position, check_split, concat_shards, dataset_statistics, epoch_key, load_tables, locate, permute_index,
                        sample_position, split_offsets, splitmix64_key, valid_offsets)
 from .finetune import RAW_BATCH_KEYS
 
@@ -244,6 +244,7 @@ class EpisodeMix:
             raise ValueError(f"sample: the batch size must lie in [1, {MAX_BATCH}] (one workgroup draws the batch), got {B}")
         if not (world >= 1 and 0 <= rank < world and step >= 0):
             raise ValueError(f"sample: need 0 <= rank < world and step >= 0, got rank {rank}, world {world}, step {step}")
+        check_position(B, rank, world, step)
         o = self._buffers(B)
         ops.mixture_sample(self.valid_off, self.episode_off, self.prompt_off, self.dataset_off, self.quota_off, seed, rank, world, step, self.Pmax,
                            o["dataset_index"], o["ep"], o["row"], o["prompt_off"])
