@@ -1174,12 +1174,13 @@ __global__ __launch_bounds__(256) void token_ce_metrics_kernel(const bf16_t* __r
                                                                const long long* __restrict__ labels,
                                                                const unsigned char* __restrict__ row_class, int V, float* __restrict__ out2,
                                                                unsigned long long* __restrict__ counters, int* __restrict__ pred_ids,
-                                                               long long tokenizer_len, int n_bins) {
+                                                               long long tokenizer_len, int n_bins, float* __restrict__ terms) {
   const long long row = blockIdx.x;
   const long long lab = labels[row];
   const int cls = row_class[row];
   const bool valid = lab >= 0 && lab < V, action = cls == 1 || cls == 2;
   if (!action && pred_ids && threadIdx.x == 0) pred_ids[row] = -1;
+  if (terms && !valid && threadIdx.x == 0) terms[row] = 0.f;     // (ordered form: every row's slot is written, token_ce_ordered_sum_kernel adds the valid ones)
   if (!valid && !action) return;
   const bf16_t* x = logits + row * ldl;
   __shared__ float red[8];
@@ -1191,8 +1192,12 @@ __global__ __launch_bounds__(256) void token_ce_metrics_kernel(const bf16_t* __r
   else term = token_ce_row<false>(x, V, lab, red, redi, best);
   if (threadIdx.x != 0) return;
   if (valid) {
-    atomicAdd(out2, term);
-    atomicAdd(out2 + 1, 1.0f);
+    if (terms) {
+      terms[row] = term;
+    } else {
+      atomicAdd(out2, term);
+      atomicAdd(out2 + 1, 1.0f);
+    }
   }
   if (action) {
     const long long top = n_bins - 2;
@@ -1212,8 +1217,54 @@ extern "C" int vla_token_ce_metrics(void* stream, const void* logits, long long 
                   ld_logits >= V && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)counters & 7) == 0 && n_bins >= 2 && tokenizer_len > 0,
               "token_ce_metrics: bad args (row stride % 8 and >= V, 16-B aligned logits, 8-B aligned counters, n_bins >= 2)");
   hipLaunchKernelGGL(token_ce_metrics_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, ld_logits,
-                     shifted_labels, row_class, V, loss_sum_and_count, counters, pred_ids, tokenizer_len, n_bins);
+                     shifted_labels, row_class, V, loss_sum_and_count, counters, pred_ids, tokenizer_len, n_bins, (float*)nullptr);
   VLA_CHECK_LAUNCH("token_ce_metrics");
+  return VLA_OK;
+}
+
+// The loss sum of vla_token_ce_metrics in a FIXED order (declared in include/vla_digest.h): the f32 atomicAdd per row above makes the
+// reported sum depend on the order in which the workgroups finish - the last bit of the logged loss differs between two runs of the
+// same step.  Here every row leaves its term in terms[row]; one workgroup then adds them: thread t the valid rows t, t + 256, ... in
+// ascending order, the 64 lanes of a wave by the xor butterfly 32, 16, .. 1 (wave_sum), the four waves in index order.  The count is
+// an integer.  out2[0] += sum, out2[1] += count, as the atomic form leaves them.
+__global__ __launch_bounds__(256) void token_ce_ordered_sum_kernel(const float* __restrict__ terms, const long long* __restrict__ labels,
+                                                                   int rows, int V, float* __restrict__ out2) {
+  __shared__ float red[4];
+  __shared__ int redn[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  float s = 0.f;
+  int n = 0;
+  for (int r = tid; r < rows; r += 256) {
+    const long long lab = labels[r];
+    if (lab >= 0 && lab < V) {
+      s += terms[r];
+      ++n;
+    }
+  }
+  s = wave_sum(s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if (lane == 0) { red[w] = s; redn[w] = n; }
+  __syncthreads();
+  if (tid == 0) {
+    out2[0] += ((red[0] + red[1]) + red[2]) + red[3];
+    out2[1] += (float)(redn[0] + redn[1] + redn[2] + redn[3]);
+  }
+}
+
+extern "C" int vla_token_ce_metrics_ordered(void* stream, const void* logits, long long ld_logits, const long long* shifted_labels,
+                                            const unsigned char* row_class, int rows, int V, float* loss_sum_and_count,
+                                            unsigned long long* counters, int* pred_ids, long long tokenizer_len, int n_bins, float* terms) {
+  VLA_REQUIRE(logits && shifted_labels && row_class && loss_sum_and_count && counters && terms && rows > 0 && V > 0 && ld_logits % 8 == 0 &&
+                  ld_logits >= V && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)counters & 7) == 0 && ((uintptr_t)terms & 3) == 0 &&
+                  n_bins >= 2 && tokenizer_len > 0,
+              "token_ce_metrics_ordered: bad args (row stride % 8 and >= V, 16-B aligned logits, 8-B aligned counters, terms f32 [rows], n_bins >= 2)");
+  hipLaunchKernelGGL(token_ce_metrics_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, ld_logits,
+                     shifted_labels, row_class, V, loss_sum_and_count, counters, pred_ids, tokenizer_len, n_bins, terms);
+  VLA_CHECK_LAUNCH("token_ce_metrics_ordered");
+  hipLaunchKernelGGL(token_ce_ordered_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)terms, shifted_labels, rows, V,
+                     loss_sum_and_count);
+  VLA_CHECK_LAUNCH("token_ce_metrics_ordered (sum)");
   return VLA_OK;
 }
 

@@ -1097,6 +1097,14 @@ class VLAEngine(schedule.StepControls):
     def _grad_buffers(self):
         return [self.head.P.grad]                    # (schedule.StepControls)
 
+    def _state_buffers(self):
+        return [("head", self.head.P)]               # (schedule.StepControls: optimizer_state / load_optimizer_state / state digests)
+
+    @property
+    def frozen_row0(self) -> Optional[int]:
+        """The live-row window capture() froze (None: eager, derived from every batch)."""
+        return self._row0
+
     def _set_clip(self, clip):
         self.flush()                                 # (a pending update belongs to the setting it ran under)
         self._clip = clip
@@ -1458,11 +1466,12 @@ class VLAEngine(schedule.StepControls):
     # value); the all-reduce is hidden under the next step's ViT instead of under a backward tail that the live-row
     # LLM backward has made too short to hide it.  `flush()` applies the last pending update.
     def capture(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None, warmup: int = 2,
-                conservative_rows: bool = False):
+                conservative_rows: bool = False, row0: Optional[int] = None):
         """``batch``/``noise`` become the static input buffers: copy new data INTO them before each replay.
         The live-row window of the LLM backward is frozen here: from the capture batch's first action-query row, or - with
         ``conservative_rows`` - from the first text row (valid for ANY later batch of the same shape: the action block
-        cannot start before tok0 + patches + one prompt token)."""
+        cannot start before tok0 + patches + one prompt token).  ``row0``: the window an earlier run froze (a resumed run captures
+        with the window of the run it continues, not with the one its own first batch would give)."""
         self._ensure_streams()
         self._static_batch, self._static_noise = batch, noise
         self._row0 = None
@@ -1470,6 +1479,9 @@ class VLAEngine(schedule.StepControls):
         self._row0 = self.live_row0()
         if conservative_rows and not self.full_llm_backward:
             self._row0 = min(self._row0, (self.cfg.n_patches + 1) // 32 * 32)
+        if row0 is not None:
+            assert 0 <= int(row0) < self.S and int(row0) % 32 == 0, f"row0 {row0}: a multiple of 32 inside the sequence"
+            self._row0 = int(row0)
         for _ in range(warmup):                      # allocate every buffer / set kernel attributes outside capture
             self.head.dirty = True
             self._fwd_bwd(batch, noise)

@@ -123,6 +123,14 @@ class FinetuneConfig:
                                           # does not clip - default off; inf: log grad_norm, clip nothing
     backbone: Optional[str] = None        # model geometry: a name of engine.NAMED_CONFIGS ("config2", "dinosiglip-0_5b", "config5",
                                           # "tiny", "tiny_fused") - default: inferred from the --vlm_path state dict, else "config2"
+    save_train_state: bool = False        # next to every checkpoint also write train_state--{suffix} (train_state.py): optimizer moments and step
+                                          # count, the position in the schedule and in the batch stream, generator / dropout / live-row state, the
+                                          # digests of the flat buffers and a fingerprint of the flags that define the trajectory
+    resume_train_state: bool = False      # with --resume: go on bit for bit where the checkpoint's run stood - the weights through the usual path,
+                                          # verified against the recorded digests, everything else from the state file; plain --resume (the
+                                          # reference's: weights only, everything else from zero) is unchanged
+    log_state_digest: bool = False        # every logged step also carries state_digest: the 64-bit digests (ops.state_digest) of data, m and v of
+                                          # every flat buffer as hex strings, read in the log line's own read-back
     # fmt: on
 
 
@@ -233,6 +241,9 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
                         "proprio projector, action_heads.py:53-55); pass --use_proprio True as every reference launch script does")
     if cfg.grad_accumulation_steps < 1:
         raise ValueError("grad_accumulation_steps must be >= 1")
+    if cfg.resume_train_state and not cfg.resume:
+        raise ValueError("--resume_train_state without --resume: the state continues the run of a checkpoint - pass --resume True, "
+                         "--resume_step and --resum_vla_path")
     if cfg.resume and cfg.resume_step is None:
         raise ValueError("--resume needs --resume_step (finetune.py:1056 computes log_step = resume_step + gradient_step_idx)")
     sources = [n for n in ("batch_file", "frame_batch_file", "raw_batch_file", "episode_file", "episode_mix") if getattr(cfg, n)]
@@ -274,17 +285,21 @@ def lr_at(gradient_step_idx: int, cfg: FinetuneConfig) -> float:
     return cfg.learning_rate * (0.1 if gradient_step_idx >= cfg.num_steps_before_decay else 1.0)
 
 
-def loop_plan(cfg: FinetuneConfig):
+def loop_plan(cfg: FinetuneConfig, start=None):
     """The reference loop's bookkeeping (finetune.py:1018-1122) as a generator of
     (batch_idx, gradient_step_idx, log_step, optimizer_step?, save?, last?) - one item per micro-batch.  The reference breaks
     behind the FIRST micro-batch whose log_step == max_steps (:1119-1121): with grad_accumulation_steps == 1 that batch's
     optimizer step has run (max_steps + 1 gradient steps from a fresh start); with ga > 1 it is the first micro-batch of gradient
     step max_steps - its forward / backward run, its gradients are never applied (boundary False).  A checkpoint is due when
     gradient_step_idx > 0 and log_step % save_freq == 0 (the reference re-saves on every micro-batch of such a step; here once,
-    behind the optimizer step that completes it)."""
+    behind the optimizer step that completes it).
+    ``start`` = (first micro-step, log-step base) of --resume_train_state (train_state.resumed_position): the plan is the tail of the
+    plan of the run it continues - batch_idx, gradient_step_idx (so lr_at) and log_step all go on where that run's next item stood."""
     ga = cfg.grad_accumulation_steps
     base = cfg.resume_step if cfg.resume else 0
     batch_idx = 0
+    if start is not None:
+        batch_idx, base = int(start[0]), int(start[1])
     while True:
         g = batch_idx // ga
         log_step = base + g
@@ -407,13 +422,16 @@ class ValidationPass:
 
 
 def save_training_checkpoint(cfg: FinetuneConfig, run_dir: Path, step: int, eng, dataset_statistics: Optional[dict] = None,
-                             trainer=None) -> Path:
+                             trainer=None, train_state=None) -> Path:
     """File names / key layout of finetune.py:527-572 (rank 0).  Where the VLM goes follows the reference: ``use_fz`` ->
     ``vla.module.save_pretrained(checkpoint_dir)`` (the whole VLM incl. the trained action queries at the top level, :551-552);
     otherwise ``save_pretrained(adapter_dir)`` - peft's adapter under ``lora_adapter/`` with LoRA, and, a quirk kept, the whole
     VLM under ``lora_adapter/`` for the full fine-tune (:553-554); the LoRA-merged VLM at the top level (:579-601).
     ``action_queries--{suffix}`` is a native addition (peft's adapter file does not hold them; the reference patches them into the
-    merged model, :586-587), read back by checkpoints.load_run_dir."""
+    merged model, :586-587), read back by checkpoints.load_run_dir.
+    ``train_state`` (--save_train_state): a callable -> the state dict, written as ``train_state--{suffix}`` beside the other files
+    (train_state.py); False: this checkpoint cannot be resumed exactly - a state file an earlier save left under the same name is
+    removed, it would describe other weights; None: nothing is written or removed."""
     suffix = "latest_checkpoint.pt" if cfg.save_latest_checkpoint_only else f"{step}_checkpoint.pt"
     d = run_dir if cfg.save_latest_checkpoint_only else Path(str(run_dir) + f"--{step}_chkpt")
     os.makedirs(d, exist_ok=True)
@@ -449,6 +467,14 @@ def save_training_checkpoint(cfg: FinetuneConfig, run_dir: Path, step: int, eng,
         save_file({k: v.contiguous().cpu() for k, v in CK.engine_vlm_state_dict(eng).items()}, str(d / "model.safetensors"))
     if dataset_statistics is not None:          # save_dataset_statistics (finetune.py:531): q01/q99 etc. used to un-normalise actions
         json.dump(dataset_statistics, open(d / "dataset_statistics.json", "w"), indent=2)
+    if train_state is not None:
+        from . import train_state as TS
+        if train_state is False:
+            stale = d / TS.file_name(step, cfg.save_latest_checkpoint_only)
+            if stale.exists():
+                os.remove(stale)
+        else:
+            TS.save(train_state(), d, step, cfg.save_latest_checkpoint_only)
     return d
 
 
@@ -493,7 +519,8 @@ def mixture_stats(norm_stats: dict, dataset_names) -> tuple:
     return tuple(st["action"] for st in sts), tuple(st["proprio"] for st in sts)
 
 
-def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, explicit=(), world: int = 1, info: Optional[dict] = None):
+def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, explicit=(), world: int = 1, info: Optional[dict] = None,
+                 start: int = 0):
     """Endless iterator over collated batches: an explicit iterable, ``--batch_file`` / ``--frame_batch_file`` / ``--raw_batch_file``
     (one .pt dict, or a directory of them, cycled in sorted order; every rank starts at its own offset - the reference's ranks draw independent
     shuffles, finetune.py:988-994), ``--episode_file``, ``--episode_mix``, or seeded synthetic batches (a new one every micro-step).
@@ -521,10 +548,17 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
 
     A raw batch (``actions_raw`` ...: RAW_BATCH_KEYS) is collated on the device by ``GPUInputStage.collate``: actions and proprio
     normalised with the statistics of ``--dataset_statistics_file`` (the entry named by the batch's ``dataset_name``, or the file's
-    only one), token length --max_seq_len (0: the batch's own), filler tokens and augmentation keyed by the same (seed, rank, step)."""
+    only one), token length --max_seq_len (0: the batch's own), filler tokens and augmentation keyed by the same (seed, rank, step).
+
+    ``start`` (--resume_train_state): the micro-step the first batch belongs to.  Every source is a function of that position - the
+    samplers', the augmentation's and the collator's step, the file sources' cyclic index, the synthetic source's counter - so the
+    stream yields what the stream of a run from 0 yields from its ``start``-th batch on; an explicit iterable is advanced by
+    cycling through it without collating."""
     from . import synthetic as S
     from .input_stage import GPUInputStage, ImageAugment, backbone_norms
-    stage, step, norm_stats, mix_stats = None, 0, None, {}
+    start = int(start)
+    assert start >= 0
+    stage, step, norm_stats, mix_stats = None, start, None, {}
 
     def collate_raw(b):
         nonlocal stage, step, norm_stats
@@ -578,10 +612,14 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
         return b
 
     if batches is not None:
+        skip = start
         while True:
             n = 0
             for b in batches:
                 n += 1
+                if skip > 0:
+                    skip -= 1
+                    continue
                 yield collate(b)
             if n == 0:
                 raise ValueError("empty batch iterable")
@@ -628,7 +666,7 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
         files = sorted(str(p) for p in Path(src).glob("*.pt")) if os.path.isdir(src) else [src]
         if not files:
             raise FileNotFoundError(f"no .pt batch files under {src}")
-        i = rank % len(files)
+        i = (rank + start) % len(files)
         while True:
             b = torch.load(files[i], weights_only=True)
             if cfg.frame_batch_file and "frames_u8" not in b:
@@ -638,16 +676,18 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
             yield collate(b)
             i = (i + 1) % len(files)
     else:
-        i = 0
+        i = start
         while True:
             yield S.make_batch(mcfg, cfg.batch_size, dev, seed=1_000_003 * cfg.seed + 7919 * rank + i, P=32, ragged=True)
             i += 1
 
 
-def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -> dict:
+def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None, on_finish=None) -> dict:
     """``batches``: optional iterable of collated batch dicts (util/data_utils.py:165-172 contract); ``explicit``: names of
     the flags given on the command line (parse_args records them); ``val_batches``: optional held-out batches of the same form
-    for --use_val_set (iterated once per validation sweep; instead of --val_batch_file)."""
+    for --use_val_set (iterated once per validation sweep; instead of --val_batch_file); ``on_finish(engine, trainer or None)``:
+    called once behind the last step and the final save, with every update applied and the device idle (a caller that wants
+    to look at the trained model itself, not at its checkpoint files)."""
     from . import ddp, engine as E, synthetic as S
     explicit = explicit or getattr(cfg, "_explicit", ())
     check_supported(cfg, explicit, frame_batches=batches is not None, val_batches=val_batches is not None)
@@ -673,9 +713,17 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
     if vlm_sd is not None:                                        # local VLM state dict (HF-style or native Prismatic keys)
         W.update(CK.split_reference_state_dict(vlm_sd, mcfg))
     lora_sd = None
+    from . import train_state as TS
+    # the flags that define the trajectory (--save_train_state writes them, --resume_train_state compares them), and the state to go on from
+    fp = TS.fingerprint(cfg, mode, world, mcfg.n_img, batches is not None) if (cfg.save_train_state or cfg.resume_train_state) else None
+    ts, start = None, None
     if cfg.resume:                    # head / proprio (finetune.py:275-278) + the action queries + whatever else this mode trained
         if not (cfg.resum_vla_path and os.path.isdir(cfg.resum_vla_path)):
             raise FileNotFoundError(f"--resume: --resum_vla_path {cfg.resum_vla_path!r} is not a checkpoint directory")
+        if cfg.resume_train_state:    # every rank reads the file rank 0 wrote; refused before a weight is loaded: no file, another step, other flags
+            ts = TS.load(cfg.resum_vla_path, cfg.resume_step)
+            TS.check(ts, fp=fp, mode=mode, resume_step=cfg.resume_step)
+            start = TS.resumed_position(ts)
         W["head"], W["proprio"], aq = CK.load_run_dir(cfg.resum_vla_path, cfg.resume_step, with_action_queries=True)
         if aq is not None:
             W["action_queries"] = aq
@@ -709,8 +757,12 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
     clip = cfg.max_grad_norm is not None
     if clip:
         (trainer or eng).set_max_grad_norm(cfg.max_grad_norm)
+    owner = trainer or eng
+    if ts is not None:                # the loaded weights are the ones the state was written beside (digests), then m, v and the step count
+        owner.verify_data_digests(ts)
+        owner.load_optimizer_state(ts)
     info = {}
-    stream = batch_stream(cfg, mcfg, dev, rank, batches, explicit, world=world, info=info)
+    stream = batch_stream(cfg, mcfg, dev, rank, batches, explicit, world=world, info=info, start=start[0] if start else 0)
     pad_id = min(S.PAD_ID, mcfg.llm.vocab - 1)
     cur = next(stream)
     L = cfg.max_seq_len or cur["input_ids"].shape[1]
@@ -726,7 +778,11 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
         if trainer is not None:       # LoRA / full fine-tune: forward + backward as one captured graph (trainers.BackboneTrainer.capture)
             trainer.capture(static, noise if training else None)
         else:
-            eng.capture(static, noise if training else None, conservative_rows=cfg.conservative_rows)
+            eng.capture(static, noise if training else None, conservative_rows=cfg.conservative_rows,
+                        row0=ts["row0"] if ts is not None and ts["row0"] >= 0 else None)     # (the window of the run this one continues)
+    if ts is not None:                # behind capture and its warm-up, which move the dropout counter: the counters, the head-noise generator
+        owner.load_device_counters(ts)
+        TS.restore_generator(gen, ts, writer=rank == 0)
     validator = None
     if cfg.use_val_set and cfg.val_episode_fraction is not None:
         from .heldout import HeldOutSweep
@@ -738,8 +794,13 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
     elif cfg.use_val_set:
         validator = ValidationPass(cfg, mcfg, dev, rank, trainer or eng, static if static is not None else cur, L, pad_id, use_graph,
                                    val_batches)
-    log, val_log, t0, saved_at, steps_done = [], [], time.time(), None, 0
-    for item in loop_plan(cfg):
+    log, val_log, t0, saved_at, steps_done, first = [], [], time.time(), None, 0, True
+
+    def state_after(batch_idx, g, log_step):
+        """--save_train_state: the state behind the optimizer step that closes micro-step batch_idx (every update applied)."""
+        return lambda: TS.collect(owner, mode=mode, fp=fp, next_grad_step=g + 1, next_micro_step=batch_idx + 1, log_step=log_step,
+                                  generator=gen, row0=eng.frozen_row0)
+    for item in loop_plan(cfg, start):
         batch_idx, g, log_step, boundary, save, last = item
         nxt = _pad_to(next(stream), L, pad_id)                    # one batch of look-ahead: its vision stage runs inside this step
         if training:   # fresh N(0, 0.02^2) perturbation every call (action_heads.py:14-17, 69-72)
@@ -753,13 +814,14 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
             loss3 = trainer.train_step(cur, lr, noise if training else None)
         elif use_graph:
             for k in static:
-                if k != "pixel_values" or batch_idx == 0:
+                if k != "pixel_values" or first:
                     static[k].copy_(cur[k])
             eng.stage_next_pixels(nxt["pixel_values"])
             loss3 = eng.train_step_graphed(lr)
         else:
             loss3 = eng.train_step(cur, lr, noise if training else None)
         steps_done += int(boundary)
+        first = False
         if boundary and world > 1 and cfg.sync_check_freq > 0 and steps_done % cfg.sync_check_freq == 0:
             eng.flush()                      # (the captured adapter step leaves its update pending: compare what the ranks really hold)
             flats = [eng.head.P.data] + ([trainer.P.data] if trainer is not None else [])
@@ -772,7 +834,13 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
             if clip:    # the norm of this step's update rides the same read-back (the captured adapter step leaves its update pending: apply it)
                 eng.flush()
                 parts.append((trainer or eng).grad_norm.view(1))
+            if cfg.log_state_digest:        # the digests ride it too, as 16-bit limbs (exact in f32); they are of the state behind this step's update
+                eng.flush()
+                parts.append(TS.limbs_f32(owner.state_digests_device()))
             l = (torch.cat(parts) if len(parts) > 1 else loss3).tolist()
+            if cfg.log_state_digest:
+                nd = parts[-1].numel()
+                l, digests = l[:-nd], owner.state_digest_dict(TS.from_limbs(l[-nd:]))
             l, tm, gn = l[:3], l[3:7] if ce else [], l[-1]
             if not all(x == x for x in l):
                 raise FloatingPointError(f"non-finite loss at step {log_step}: {l} (a captured step replayed on a batch whose action "
@@ -783,12 +851,15 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
                 log[-1].update(zip(TOKEN_METRIC_NAMES, tm))
             if clip:
                 log[-1]["grad_norm"] = gn
+            if cfg.log_state_digest:
+                log[-1]["state_digest"] = digests
             if rank == 0:
                 print(json.dumps(log[-1]), flush=True)
         if save:
             eng.flush()                      # the graphed step leaves its parameter update pending (engine.capture)
             if rank == 0:
-                save_training_checkpoint(cfg, run_dir, log_step, eng, stats, trainer)
+                save_training_checkpoint(cfg, run_dir, log_step, eng, stats, trainer,
+                                         train_state=state_after(batch_idx, g, log_step) if cfg.save_train_state else None)
             saved_at = log_step
             if world > 1:
                 torch.distributed.barrier()  # finetune.py:544, 575
@@ -801,7 +872,12 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None) -
     eng.flush()
     torch.cuda.synchronize()
     if saved_at != final_step and rank == 0:     # never discard a run: the reference only saves on save_freq multiples
-        save_training_checkpoint(cfg, run_dir, final_step, eng, stats, trainer)
+        # a state only where it can be resumed exactly: with grad accumulation the run ends INSIDE a gradient step (loop_plan: the last
+        # micro-batch's gradients are never applied, the accumulators hold a partial sum) - the weights are saved, no state is
+        final_state = None if not cfg.save_train_state else (state_after(batch_idx, g, final_step) if boundary else False)
+        save_training_checkpoint(cfg, run_dir, final_step, eng, stats, trainer, train_state=final_state)
+    if on_finish is not None:
+        on_finish(eng, trainer)
     model = dict(vit=[dict(v.as_oracle(), img=v.img) for v in mcfg.vit], llm=dict(mcfg.llm.as_oracle(), d=mcfg.llm.d, inter=mcfg.llm.inter, vocab=mcfg.llm.vocab),
                  n_img=mcfg.n_img, num_blocks=mcfg.num_blocks, pro=mcfg.pro)
     out = dict(log=log, val_log=val_log, seconds=time.time() - t0, steps=steps_done, world=world, final_step=final_step, run_dir=str(run_dir), mode=mode, model=model)

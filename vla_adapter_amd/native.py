@@ -185,6 +185,15 @@ HELDOUT_PROTOS = {
 }
 HELDOUT_SYMBOLS = sorted(HELDOUT_PROTOS)
 
+# the state digest (include/vla_digest.h, csrc/digest.hip): a sixth table, bound by name in the same way
+# (tests/test_digest_cpu.py checks header, table and library against each other)
+DIGEST_PROTOS = {
+    "vla_state_digest_slots": ([], _I),
+    "vla_state_digest": ([_P, _P, _L, C.c_ulonglong, _P, _L, _P], _I),
+    "vla_token_ce_metrics_ordered": ([_P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _L, _I, _P], _I),
+}
+DIGEST_SYMBOLS = sorted(DIGEST_PROTOS)
+
 _lib = None
 
 
@@ -198,7 +207,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()) + list(HELDOUT_PROTOS.items()):
+    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()) + list(HELDOUT_PROTOS.items()) + list(DIGEST_PROTOS.items()):
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

@@ -822,11 +822,13 @@ def token_row_class(labels: torch.Tensor, shift: int = 1, tokenizer_len: int = T
 
 
 def token_ce_metrics(logits, tgt, row_class, out_f32, counters_u64, pred_ids=None, tokenizer_len: int = TOKENIZER_LEN,
-                     n_bins: int = N_BINS):
+                     n_bins: int = N_BINS, terms: Optional[torch.Tensor] = None):
     """token_ce (out_f32 receives the same two sums) plus, for the rows of class 1 (current action) / 2 (next actions) of row_class
     (uint8 [rows]), the argmax over the vocabulary and the decoded-bin statistics: counters_u64 (6 64-bit integers, zeroed by the
     caller) += per class (rows, rows whose argmax is the target, sum of |bin(argmax) - bin(target)|).  pred_ids (int32 [rows],
-    optional): the argmax of every action row, -1 elsewhere.  logits [rows, V] bf16, any row stride that is a multiple of 8."""
+    optional): the argmax of every action row, -1 elsewhere.  logits [rows, V] bf16, any row stride that is a multiple of 8.
+    terms (f32 [rows] scratch): vla_token_ce_metrics_ordered - every row's loss term goes there and one workgroup adds them in a fixed
+    order, so the sum has the same bits in every run (the atomic form's last bit depends on the order the workgroups finish in)."""
     _chk_bf16(logits)
     assert logits.dim() == 2 and logits.stride(1) == 1
     rows, V = logits.shape
@@ -835,6 +837,11 @@ def token_ce_metrics(logits, tgt, row_class, out_f32, counters_u64, pred_ids=Non
     assert out_f32.dtype == torch.float32 and out_f32.numel() >= 2
     assert counters_u64.dtype in (torch.int64, torch.uint64) and counters_u64.is_contiguous() and counters_u64.numel() == 6
     assert pred_ids is None or (pred_ids.dtype == torch.int32 and pred_ids.is_contiguous() and pred_ids.numel() == rows)
+    if terms is not None:
+        assert terms.dtype == torch.float32 and terms.is_contiguous() and terms.numel() == rows and terms.device == logits.device
+        N.check(_lib().vla_token_ce_metrics_ordered(_st(), _p(logits), logits.stride(0), _p(tgt), _p(row_class), rows, V, _p(out_f32),
+                                                    _p(counters_u64), _p(pred_ids), tokenizer_len, n_bins, _p(terms)), "token_ce_metrics_ordered")
+        return out_f32
     N.check(_lib().vla_token_ce_metrics(_st(), _p(logits), logits.stride(0), _p(tgt), _p(row_class), rows, V, _p(out_f32),
                                         _p(counters_u64), _p(pred_ids), tokenizer_len, n_bins), "token_ce_metrics")
     return out_f32
@@ -1117,3 +1124,33 @@ def heldout_l1_accumulate(pred: torch.Tensor, target: torch.Tensor, ds: Optional
     assert valid.dtype == torch.uint8 and valid.is_contiguous() and tuple(valid.shape) == (B,) and valid.device == dev
     assert ds is None or (ds.dtype == torch.int32 and ds.is_contiguous() and tuple(ds.shape) == (B,) and ds.device == dev)
     N.check(_lib().vla_heldout_l1_accumulate(_st(), _p(pred), _p(target), _p(ds), _p(valid), B, Cc, A, D, _p(acc), _p(cnt)), "heldout_l1_accumulate")
+
+
+# ---- state digest (include/vla_digest.h, csrc/digest.hip) ---------------------------------------------------------------------------
+_DIGEST_SCRATCH = {}
+
+
+def state_digest(t: torch.Tensor, salt: int = 0, out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vla_state_digest: the position-weighted 64-bit digest of the contiguous tensor ``t`` of 16-bit elements (bf16,
+    fp16, int16) -> int64 [1] on t's device holding the u64's bits (``out``: given, 8-byte aligned).  Launched on the current stream;
+    nothing synchronises - digest_value() reads it.  ``scratch``: int64 [>= 1] for the workgroups' partial sums; by default one buffer
+    per device, so that calls sharing it must be ordered on one stream."""
+    assert t.is_cuda and t.element_size() == 2 and t.is_contiguous(), f"state_digest: a contiguous CUDA tensor of 16-bit elements, got {t.dtype} {t.device}"
+    n = t.numel()
+    if n == 0:
+        raise ValueError("state_digest: an empty view has no digest")
+    if out is None:
+        out = torch.empty(1, device=t.device, dtype=torch.int64)
+    assert out.dtype == torch.int64 and out.numel() == 1 and out.device == t.device, "state_digest: out is int64 [1] on t's device"
+    if scratch is None:
+        scratch = _DIGEST_SCRATCH.get(t.device)
+        if scratch is None:
+            scratch = _DIGEST_SCRATCH[t.device] = torch.empty(_lib().vla_state_digest_slots(), device=t.device, dtype=torch.int64)
+    assert scratch.dtype == torch.int64 and scratch.is_contiguous() and scratch.device == t.device and scratch.numel() >= 1
+    N.check(_lib().vla_state_digest(_st(), _p(t), n, int(salt) & (2 ** 64 - 1), _p(scratch), scratch.numel(), _p(out)), "state_digest")
+    return out
+
+
+def digest_value(d) -> int:
+    """The unsigned 64-bit value of a digest (an int64 [1] tensor of state_digest, or its .item()): a host sync for a tensor."""
+    return int(d.item() if isinstance(d, torch.Tensor) else d) & (2 ** 64 - 1)

@@ -237,6 +237,84 @@ class StepControls:
         """Device f32 [1]: min(1, max_grad_norm / (grad_norm + 1e-6)) of the last applied optimizer step."""
         return None if self._clip is None else self._clip.coef
 
+    # ---- optimizer state (train_state.py: --save_train_state / --resume_train_state / --log_state_digest) ------------------------------
+    # The owner supplies _state_buffers() -> [(name, FlatParams)] of everything its optimizer step moves, keeps ``step_count``, and
+    # may keep device counters of its own (_device_counters / _load_device_counters: LoRA dropout's mask counter).
+    def _device_counters(self) -> dict:
+        return {}
+
+    def _load_device_counters(self, counters: dict) -> None:
+        pass
+
+    def state_digests_device(self) -> torch.Tensor:
+        """ops.state_digest of data, m and v of every flat buffer -> int64 [3 * buffers] on the device, launched on the current stream
+        (the caller has applied a pending update: flush()); nothing synchronises."""
+        from . import train_state as TS
+        return TS.digests_device(self._state_buffers())
+
+    def state_digest_dict(self, values) -> dict:
+        """{buffer: {data, m, v: hex}} from the values of state_digests_device()."""
+        from . import train_state as TS
+        return TS.digest_dict(self._state_buffers(), values)
+
+    def optimizer_state(self) -> dict:
+        """What the optimizer carries from one gradient step to the next, on the host: per flat buffer m and v, the hash of its
+        offsets table and the digests of data, m and v (the weights themselves stay in the checkpoint files); the AdamW step count;
+        the owner's device counters.  Between two gradient steps only: every update applied (flush()), no micro-step folded."""
+        from . import train_state as TS
+        assert self._accum._micro == 0, "optimizer_state() inside a gradient step: the accumulators hold a partial sum"
+        bufs = self._state_buffers()
+        dg = TS.read_digests(bufs)
+        return dict(step_counts={type(self).__name__: int(self.step_count)}, counters=self._device_counters(),
+                    buffers={name: dict(m=P.m.detach().cpu().clone(), v=P.v.detach().cpu().clone(), numel=int(P.numel), offsets=TS.offsets_hash(P),
+                                        digest=dg[name]) for name, P in bufs})
+
+    def verify_data_digests(self, state: dict) -> None:
+        """The loaded weights against the digests recorded when they were written: ValueError naming the buffers that differ (the
+        checkpoint round trip lost bits, or the files are another checkpoint's)."""
+        from . import train_state as TS
+        bufs = self._state_buffers()
+        self._check_tables(state, bufs)
+        got = TS.read_digests(bufs)
+        bad = [f"{name}.data: recorded {state['buffers'][name]['digest']['data']}, loaded {got[name]['data']}"
+               for name, _ in bufs if got[name]["data"] != state["buffers"][name]["digest"]["data"]]
+        if bad:
+            raise ValueError("--resume_train_state: the loaded weights are not the ones the state was written beside - " + "; ".join(bad))
+
+    def _check_tables(self, state: dict, bufs) -> None:
+        from . import train_state as TS
+        if sorted(state["buffers"]) != sorted(name for name, _ in bufs):
+            raise ValueError(f"--resume_train_state: offsets-table mismatch - the state holds the buffers {sorted(state['buffers'])}, this "
+                             f"run trains {sorted(name for name, _ in bufs)}")
+        for name, P in bufs:
+            rec = state["buffers"][name]
+            if rec["offsets"] != TS.offsets_hash(P) or int(rec["numel"]) != P.numel:
+                raise ValueError(f"--resume_train_state: offsets-table mismatch in buffer {name!r} (names, shapes or order of the trainable "
+                                 f"tensors differ: {int(rec['numel'])} elements recorded, {P.numel} here)")
+
+    def load_optimizer_state(self, state: dict) -> None:
+        """The inverse of optimizer_state(): m, v and the step count, each moment buffer verified against its recorded digest
+        (the device counters follow capture() and its warm-up: load_device_counters)."""
+        from . import train_state as TS
+        bufs = self._state_buffers()
+        self._check_tables(state, bufs)
+        counts = state["step_counts"]
+        if list(counts) != [type(self).__name__]:
+            raise ValueError(f"--resume_train_state: the state holds the step counts of {list(counts)}, this run's optimizer is {type(self).__name__}")
+        for name, P in bufs:
+            rec = state["buffers"][name]
+            P.m.copy_(rec["m"].to(P.m.device))
+            P.v.copy_(rec["v"].to(P.v.device))
+        self.step_count = int(counts[type(self).__name__])
+        got = TS.read_digests(bufs)
+        bad = [f"{name}.{part}" for name, _ in bufs for part in ("m", "v") if got[name][part] != state["buffers"][name]["digest"][part]]
+        if bad:
+            raise ValueError(f"--resume_train_state: the optimizer moments do not reproduce their recorded digests: {bad}")
+
+    def load_device_counters(self, state: dict) -> None:
+        """Device counters of the owner (behind capture() and its warm-up, which move them)."""
+        self._load_device_counters(state.get("counters", {}))
+
 
 def captured_validation(model, batch, noise, make, replay):
     """val_step_graphed of an engine / trainer: on the first call two eager model.val_forward() (every buffer allocated and

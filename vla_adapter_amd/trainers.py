@@ -523,6 +523,7 @@ class BackboneTrainer(E.Linear, schedule.StepControls):
                 self.ce_cls = torch.empty(B, Lm, device=self.dev, dtype=torch.uint8)
                 self.ce_counters = torch.zeros(6, device=self.dev, dtype=torch.int64)       # (64-bit counters of vla_token_ce_metrics)
                 self.ce_metrics = torch.empty(4, device=self.dev, dtype=torch.float32)
+                self.ce_terms = torch.empty(B * Lm, device=self.dev, dtype=torch.float32)    # per-row loss terms: summed in a fixed order
                 self._ce_key = (B, S)
             ops.copy_rows3d(llm.HS[n][0, Np], self.ce_h, B, Lm, D, S * D, D, Lm * D, D)
             ops.gemm_nt(self.ce_h, llm.embed, out=self.ce_logits, split_k=0)
@@ -533,7 +534,7 @@ class BackboneTrainer(E.Linear, schedule.StepControls):
             tlen, nb = self.ce_tokenizer
             ops.token_row_class(batch["labels"].contiguous(), 1, tlen, nb, out=self.ce_cls)
             ops.zero_(self.ce_counters)
-            ops.token_ce_metrics(self.ce_logits, tgt, self.ce_cls, self.ce_out, self.ce_counters, None, tlen, nb)
+            ops.token_ce_metrics(self.ce_logits, tgt, self.ce_cls, self.ce_out, self.ce_counters, None, tlen, nb, terms=self.ce_terms)
             self.token_metrics = ops.token_metrics_finish(self.ce_counters, nb, out=self.ce_metrics)
             loss = self.ce_out[0:1] / self.ce_out[1:2]
             self._loss3 = torch.cat([loss, loss, loss])              # (same three-slot shape the L1 path logs)
@@ -784,6 +785,9 @@ class BackboneTrainer(E.Linear, schedule.StepControls):
     # ---- update / capture ----------------------------------------------------------------------------------------------
     def _grad_buffers(self):
         return [self.P.grad, self.head.P.grad]       # (schedule.StepControls: accumulated and clipped together)
+
+    def _state_buffers(self):
+        return [("head", self.head.P), ("backbone", self.P)]     # (schedule.StepControls: optimizer state and state digests)
 
     def _set_clip(self, clip):
         assert self._graphs is None, "set_max_grad_norm() before capture()"
@@ -1308,6 +1312,14 @@ class LoRAFinetune(BackboneTrainer):
     def _begin_forward(self):
         if self.dropout > 0:
             ops.inc_i32_(self._drop_step)
+
+    def _device_counters(self) -> dict:
+        return {"drop_step": int(self._drop_step.item())}        # (schedule.StepControls.optimizer_state: the masks' step counter)
+
+    def _load_device_counters(self, counters: dict) -> None:
+        if "drop_step" not in counters:
+            raise ValueError("--resume_train_state: the state holds no drop_step (it was not written by a LoRA run)")
+        self._drop_step.fill_(int(counters["drop_step"]))
 
     @contextlib.contextmanager
     def _eval_mode(self):
