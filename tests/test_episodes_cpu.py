@@ -129,6 +129,23 @@ def test_every_episode_symbol_has_a_memory_contract_case_or_an_exemption():
             assert callable(getattr(M, t, None)), f"{name}: case {t} does not exist"
 
 
+def test_the_window_tail_and_the_tables_are_stated_once():
+    """csrc/windows.h alone defines clampll, last_not_above, EPISODE_STREAM and the scan of the prompt lengths; the three picker files
+    include it, call emit_windows and restate none of them.  The package states the raw-batch buffers and MAX_BATCH once."""
+    csrc, pkg = os.path.join(ROOT, "vla_adapter_amd", "csrc"), os.path.join(ROOT, "vla_adapter_amd")
+    stated = ("long long clampll(", "int last_not_above(", "EPISODE_STREAM =", "scan[b] += v;")
+    head = open(os.path.join(csrc, "windows.h")).read()
+    assert all(head.count(s) == 1 for s in stated) and head.count("__forceinline__ void emit_windows(") == 1
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".hip"):
+            txt = open(os.path.join(csrc, f)).read()
+            assert not any(s in txt for s in stated), f
+            assert txt.count("emit_windows(") == ('#include "windows.h"' in txt) == (f in ("episodes.hip", "mixture.hip", "heldout.hip")), f
+    assert "windows.h" in open(os.path.join(csrc, "Makefile")).read()
+    py = "".join(open(os.path.join(pkg, f)).read() for f in sorted(os.listdir(pkg)) if f.endswith(".py"))
+    assert py.count("def _buffers") == 1 and len(re.findall(r"^MAX_BATCH = ", py, re.M)) == 1
+
+
 # ---------------------------------------------------------------------------------------------------------------- the sampling rule
 def test_splitmix64_key_restates_the_header():
     """The constants of csrc/common.h's splitmix64_key, and two values of the public splitmix64 sequence (seed 0: the first outputs of

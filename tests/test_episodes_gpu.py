@@ -42,19 +42,22 @@ def assert_batch_equal(got, want):
         assert torch.equal(got[k].cpu().view(torch.uint8), want[k].contiguous().view(torch.uint8)), k      # bit for bit
 
 
+@pytest.mark.parametrize("B", [6, 1, 64, 65])
 @pytest.mark.parametrize("world", [1, 2])
-def test_sampler_equals_the_python_rule(store, world):
-    """B = 6, steps 0 .. 5: 36 (72) positions over N = 16 windows cross epoch boundaries inside a batch."""
+def test_sampler_equals_the_python_rule(store, world, B):
+    """B = 6, steps 0 .. 5: 36 (72) positions over N = 16 windows cross epoch boundaries inside a batch.  B = 1, 64 and 65: one thread
+    of one wave, a full wave, and one thread into the second wave - the scan of the prompt lengths at a wave boundary (B = 1 runs the
+    16 steps that epoch 0 takes)."""
     d, st = store
     assert st.N == N_WINDOWS
     valid, eo, lens = st.valid_off_host.tolist(), d["episode_off"].tolist(), d["prompt_off"].diff().tolist()
     got, want = [], []
-    for step in range(6):
+    for step in range(max(6, -(-N_WINDOWS // (B * world)))):
         for rank in range(world):
-            ep, row, off = st.sample_indices(6, 21, rank, world, step)
+            ep, row, off = st.sample_indices(B, 21, rank, world, step)
             got.append((ep.tolist(), row.tolist(), off.tolist()))
-            w = EP.sample_windows(valid, 6, 21, rank, world, step)
-            want.append(([e for e, _ in w], [eo[e] + t for e, t in w], [sum(lens[e] for e, _ in w[:b]) for b in range(7)]))
+            w = EP.sample_windows(valid, B, 21, rank, world, step)
+            want.append(([e for e, _ in w], [eo[e] + t for e, t in w], [sum(lens[e] for e, _ in w[:b]) for b in range(B + 1)]))
     assert got == want
     firsts = [r for _, rows, _ in got for r in rows][:N_WINDOWS]
     assert len(set(firsts)) == N_WINDOWS, "epoch 0 visits every window once"

@@ -45,11 +45,13 @@ def sources():
 
 @pytest.mark.parametrize("stride", [1, 3])
 @pytest.mark.parametrize("world", [1, 2])
-@pytest.mark.parametrize("B", [6, 70])
+@pytest.mark.parametrize("B", [6, 70, 1, 64, 65])
 def test_sweep_kernel_equals_the_python_rule(sources, B, world, stride):
     """Batches j = 0 .. 3 of every rank.  The issue's store (8 held-out windows, dataset_off NULL) and the two-dataset mix (10, the
     last episode without a window) give a full batch at B = 6, j = 0, partly valid ones and wholly invalid ones; the long store (246)
-    fills a whole batch of 70 - a scan across two waves - even at stride 3, before its partly valid and its empty ones."""
+    fills a whole batch of 70 - a scan across two waves - even at stride 3, before its partly valid and its empty ones.  B = 1, 64 and
+    65: one thread of one wave, a full wave, and one thread into the second wave (batches of one are whole or empty, never part:
+    j = 0 .. 11 runs past the 8 and the 10 windows)."""
     from vla_adapter_amd import ops
     assert sources["long"].Nv == 246 and sources["store"].Nv == 8 and sources["mix"].Nv == 10
     kinds = set()
@@ -61,7 +63,7 @@ def test_sweep_kernel_equals_the_python_rule(sources, B, world, stride):
         ds, ep, valid = e(B, dtype=torch.int32, device=DEV), e(B, dtype=torch.int32, device=DEV), e(B, dtype=torch.uint8, device=DEV)
         row, off = e(B, dtype=torch.int64, device=DEV), e(B + 1, dtype=torch.int32, device=DEV)
         for rank in range(world):
-            for j in range(4):
+            for j in range(4 if B > 1 else 12):
                 for t in (ds, ep, valid, row, off):
                     t.fill_(99)
                 ops.heldout_sweep(s.val_off, s.episode_off, s.prompt_off, s.dataset_off if mixed else None, rank, world, j, stride, s.Pmax,
@@ -73,9 +75,49 @@ def test_sweep_kernel_equals_the_python_rule(sources, B, world, stride):
                 assert got == want, (name, rank, j)
                 n = sum(want[0])
                 kinds.add((name, "full" if n == B else "empty" if n == 0 else "part"))
-    assert ("long", "full") in kinds and {k for _, k in kinds} == {"full", "part", "empty"} and ("mix", "part") in kinds
+    if B == 1:
+        assert ("long", "full") in kinds and {k for _, k in kinds} == {"full", "empty"}
+    else:
+        assert ("long", "full") in kinds and {k for _, k in kinds} == {"full", "part", "empty"} and ("mix", "part") in kinds
     if B == 6 and stride == 1 and world == 1:
         assert ("store", "full") in kinds and ("mix", "full") in kinds
+
+
+def test_sweep_and_mixture_sampler_agree_on_the_same_window(sources):
+    """Two kernels through one tail (csrc/windows.h): over the mix's TRAINING table, window w of vla_heldout_sweep and the draw of
+    vla_mixture_sample at a position whose rule (MX.sample_window, on the CPU) lands on the same (episode, step) write the same ep, row
+    and prompt_off, bit for bit - for every one of the 20 training windows, each pair two launches of one workgroup of B = 1.  One sweep
+    batch over all 20 windows then repeats every pair's row and prompt length inside a scan over 20 threads."""
+    from vla_adapter_amd import ops
+    m = sources["mix"]
+    valid, ds_off, q_off = m.valid_off_host.tolist(), m.dataset_off_host.tolist(), m.quota_off_host.tolist()
+    N = m.N
+    assert N == 20 and m.windows == [16, 4]
+    position = {}                                                        # (e, t) -> the first position that draws it
+    for pos in range(64 * 16):
+        _, _, e, t = MX.sample_window(pos, valid, ds_off, q_off, 21)
+        position.setdefault((e, t), pos)
+        if len(position) == N:
+            break
+    assert len(position) == N, "64 periods draw every training window"
+    e_ = torch.empty
+    new = lambda n: dict(ds=e_(n, dtype=torch.int32, device=DEV), ep=e_(n, dtype=torch.int32, device=DEV), row=e_(n, dtype=torch.int64, device=DEV),
+                         off=e_(n + 1, dtype=torch.int32, device=DEV), valid=e_(n, dtype=torch.uint8, device=DEV))
+    a, b, pairs = new(1), new(1), []
+    for w in range(N):
+        for o in (a, b):
+            for t in o.values():
+                t.fill_(99)
+        ops.heldout_sweep(m.valid_off, m.episode_off, m.prompt_off, m.dataset_off, 0, 1, w, 1, m.Pmax, a["ds"], a["ep"], a["row"], a["off"], a["valid"])
+        pos = position[EP.locate(w, valid)]
+        ops.mixture_sample(m.valid_off, m.episode_off, m.prompt_off, m.dataset_off, m.quota_off, 21, 0, 1, pos, m.Pmax, b["ds"], b["ep"], b["row"], b["off"])
+        got = {k: a[k].tolist() for k in ("ds", "ep", "row", "off")}
+        assert got == {k: b[k].tolist() for k in ("ds", "ep", "row", "off")} and a["valid"].tolist() == [1], (w, pos)
+        assert (got["ep"][0], got["row"][0] - int(m.episode_off[got["ep"][0]])) == EP.locate(w, valid) and got["off"][0] == 0
+        pairs.append((got["ep"][0], got["row"][0], got["off"][1]))
+    c = new(N)
+    ops.heldout_sweep(m.valid_off, m.episode_off, m.prompt_off, m.dataset_off, 0, 1, 0, 1, m.Pmax, c["ds"], c["ep"], c["row"], c["off"], c["valid"])
+    assert list(zip(c["ep"].tolist(), c["row"].tolist(), c["off"].diff().tolist())) == pairs and c["off"][0].item() == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2: the accumulation

@@ -164,11 +164,14 @@ def test_the_feistel_network_is_stated_once():
 
 def test_the_streams_differ():
     """MIX_STREAM is none of the other stream constants (the augmentation keys its draws with the bare seed: 0), and the kernel file
-    restates the Python constants."""
+    restates the Python constants: its own, and EPISODE_STREAM in the csrc/windows.h it includes (the one place all three pickers take
+    it from)."""
     csrc = os.path.join(ROOT, "vla_adapter_amd", "csrc")
     collate = int(re.search(r"COLLATE_STREAM = (0x[0-9A-Fa-f]+)ull", open(os.path.join(csrc, "collate.hip")).read()).group(1), 16)
     assert len({MX.MIX_STREAM, EP.EPISODE_STREAM, collate, 0}) == 4
     txt = open(os.path.join(csrc, "mixture.hip")).read()
+    assert '#include "windows.h"' in txt
+    txt += open(os.path.join(csrc, "windows.h")).read()
     assert f"MIX_STREAM = 0x{MX.MIX_STREAM:X}ull" in txt and f"EPISODE_STREAM = 0x{EP.EPISODE_STREAM:X}ull" in txt
 
 

@@ -31,15 +31,17 @@ def host(m):
 
 
 @pytest.mark.parametrize("world", [1, 2])
-@pytest.mark.parametrize("B", [6, 70])
+@pytest.mark.parametrize("B", [6, 70, 1, 64, 65])
 def test_sampler_equals_the_python_rule(mix, B, world):
     """Steps 0 .. 7: at B = 6 the batches straddle the periods of 16; B = 70 spans two waves and more than four periods in one batch;
-    dataset 1 (6 windows, 4 draws per period) crosses several of its own epochs."""
+    dataset 1 (6 windows, 4 draws per period) crosses several of its own epochs.  B = 1, 64 and 65: one thread of one wave, a full
+    wave, and one thread into the second wave - the scan of the prompt lengths at a wave boundary (B = 1 runs the 16 steps of a whole
+    period)."""
     _, m, all_ = mix
     assert m.quota == QUOTA
     eo, lens = all_["episode_off"].tolist(), all_["prompt_off"].diff().tolist()
     got, want = [], []
-    for step in range(8):
+    for step in range(max(8, -(-PERIOD // (B * world)))):
         for rank in range(world):
             ds, ep, row, off = m.sample_indices(B, 21, rank, world, step)
             got.append((ds.tolist(), ep.tolist(), row.tolist(), off.tolist()))

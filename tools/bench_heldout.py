@@ -17,30 +17,15 @@ One JSON line."""
 import argparse
 import json
 import os
-import random
-import statistics
-import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import _episode_bench as EB
+import torch
 
 
 def write_episodes(tmp, mcfg, args):
-    rng = random.Random(0)
-    g = torch.Generator().manual_seed(0)
-    E, n, img = args.episodes, args.episode_len, mcfg.vit[0].img
-    T = E * n
-    lens = [rng.randint(27, 51) for _ in range(E)]
-    d = dict(frames_u8=torch.randint(0, 256, (T, args.n_img, img, img, 3), generator=g, dtype=torch.uint8),
-             actions_raw=torch.randn(T, mcfg.action_dim, generator=g), proprio_raw=torch.randn(T, mcfg.proprio_dim, generator=g),
-             episode_off=torch.arange(E + 1, dtype=torch.int64) * n,
-             prompt_flat=torch.randint(0, min(151000, mcfg.llm.vocab - 1), (sum(lens),), generator=g, dtype=torch.int64),
-             prompt_off=torch.tensor(np.cumsum([0] + lens), dtype=torch.int32), dataset_name="bench")
+    d = dict(EB.synthetic_episodes(mcfg, args, *EB.generators()), dataset_name="bench")
     path = os.path.join(tmp, "episodes.pt")
     torch.save(d, path)
     return path
@@ -48,29 +33,23 @@ def write_episodes(tmp, mcfg, args):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--backbone", default="config2")
-    ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--n_img", type=int, default=1)
+    EB.add_common_args(ap)
     ap.add_argument("--episodes", type=int, default=16)
     ap.add_argument("--episode_len", type=int, default=71)
     ap.add_argument("--fraction", type=float, default=0.25)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--max_seq_len", type=int, default=128)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_heldout needs a GPU"
-    from vla_adapter_amd import engine as E, finetune as F, synthetic as S
+    from vla_adapter_amd import finetune as F, synthetic as S
     from vla_adapter_amd.heldout import HeldOutSweep
     dev = "cuda:0"
-    mcfg = E.NAMED_CONFIGS[args.backbone]()
-    mcfg.n_img, mcfg.pro = args.n_img, True                      # as finetune() sets them (--use_pro_version defaults to True)
+    mcfg = EB.model_config(args)
     B, L = args.batch, args.max_seq_len
     with tempfile.TemporaryDirectory() as tmp:
         ep_file = write_episodes(tmp, mcfg, args)
         val_dir = os.path.join(tmp, "val")
         os.makedirs(val_dir)
-        common = ["--use_proprio", "True", "--use_fz", "True", "--batch_size", str(B), "--max_seq_len", str(L), "--num_images_in_input", str(args.n_img),
-                  "--episode_file", ep_file, "--use_val_set", "True"]
+        common = EB.common_flags(args) + ["--episode_file", ep_file, "--use_val_set", "True"]
         cfg_h = F.parse_args(common + ["--val_episode_fraction", str(args.fraction)])
         cfg_f = F.parse_args(common + ["--val_batch_file", val_dir])
         for c in (cfg_h, cfg_f):
@@ -81,10 +60,8 @@ def main():
         cur = F._pad_to(next(stream), L, pad_id)
         store = info["store"]
         assert store.Nv % B == 0, f"{store.Nv} held-out windows do not fill whole batches of {B}: the file-fed sweep would average a padded batch"
-        eng = E.VLAEngine(mcfg, S.make_weights(mcfg, dev, seed=0), dev)
-        static = {k: v.clone() for k, v in cur.items()}
-        noise = torch.zeros(mcfg.chunk, mcfg.action_dim * mcfg.llm.d, device=dev, dtype=torch.bfloat16)
-        eng.capture(static, noise, conservative_rows=True)          # prompts of 27-51 ids: the action block moves from batch to batch
+        eng = EB.new_engine(mcfg, dev)
+        static = EB.capture_step(eng, mcfg, cur, dev)
         sweeper = HeldOutSweep(cfg_h, mcfg, dev, 0, 1, eng, store, info["dataset_statistics"], static, L, True)
         for j in range(sweeper.n_batches):                           # the same windows, collated, as --val_batch_file batches
             b = sweeper.collate(sweeper.draw(j), j)
@@ -115,12 +92,7 @@ def main():
     out = dict(device=torch.cuda.get_device_name(0), backbone=args.backbone, batch=B, n_img=args.n_img, L=L, rounds=args.rounds,
                heldout_windows=store.Nv, batches_per_sweep=sweeper.n_batches,
                loss_value={"val_episode_fraction": a["loss_value"], "val_batch_file": b["loss_value"]})
-    for k, col in samples.items():
-        out[f"{k}.sweep_ms"] = round(statistics.median(col), 3)
-        out[f"{k}.sweep_ms.spread"] = [round(min(col), 3), round(max(col), 3)]
-    file_col = samples["val_batch_file"]
-    out["not_slower"] = statistics.median(samples["val_episode_fraction"]) - statistics.median(file_col) <= max(file_col) - min(file_col)
-    print(json.dumps(out), flush=True)
+    print(json.dumps(EB.report(out, samples, "sweep_ms", base="val_batch_file", other="val_episode_fraction")), flush=True)
 
 
 if __name__ == "__main__":

@@ -9,6 +9,7 @@
 // sample_position, permute_index, locate), which is what the kernel is tested against, bit for bit.
 #include "common.h"
 #include "permute.h"                            // feistel4 / permute_index: shared with mixture.hip
+#include "windows.h"                            // EPISODE_STREAM, clampll, last_not_above, emit_windows: shared with mixture.hip, heldout.hip
 #include "../../include/vla_episodes.h"
 
 namespace {
@@ -17,9 +18,6 @@ constexpr int SAMPLE_MAX_B = 1024;
 constexpr int GATHER_THREADS = 256;
 constexpr int GATHER_UNROLL = 4;                   // independent loads a thread has in flight
 constexpr int GATHER_MAX_BLOCKS = 2048;            // memory-bound grid: 256 CUs x 8 workgroups, the rest is strided
-constexpr u64 EPISODE_STREAM = 0xE9150DE5A391Eull;   // keeps the shuffle apart from the augmentation's and the collator's draws under equal seed words
-
-__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One workgroup; thread b < B draws sample b, then all threads scan the prompt lengths (Hillis-Steele in LDS).
 __global__ void __launch_bounds__(SAMPLE_MAX_B)
@@ -28,39 +26,20 @@ episode_sample_kernel(const long long* __restrict__ valid_off, const long long* 
                       int* __restrict__ ep, long long* __restrict__ row, int* __restrict__ out_off) {
   __shared__ int scan[SAMPLE_MAX_B];
   const int b = threadIdx.x;
-  int len = 0;
+  int e = 0;
+  long long t = 0;
   if (b < B) {
     const long long n_tab = valid_off[E];
-    int e = 0;
-    long long t = 0;
     if (n_tab >= 1) {
       const u64 n = (u64)n_tab;
       const u64 pos = (step * world + rank) * (u64)B + (u64)b;
       const u64 epoch = pos / n, i = pos % n;
       const long long j = (long long)permute_index(i, n, splitmix64_key(seed ^ EPISODE_STREAM, epoch));
-      int lo = 0, hi = E - 1;                      // the largest e in [0, E) with valid_off[e] <= j: ends inside [0, E) on any table
-      while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if (valid_off[mid] <= j) lo = mid; else hi = mid - 1;
-      }
-      e = lo;
+      e = last_not_above(valid_off, 0, E - 1, j);
       t = j - valid_off[e];
     }
-    const long long e0 = episode_off[e], e1 = episode_off[e + 1];
-    ep[b] = e;
-    row[b] = clampll(e0 + t, e0, e1 > e0 ? e1 - 1 : e0);
-    len = (int)clampll((long long)prompt_off[e + 1] - (long long)prompt_off[e], 0ll, (long long)Pmax);
   }
-  scan[b] = len;
-  __syncthreads();
-  for (int d = 1; d < (int)blockDim.x; d <<= 1) {
-    const int v = b >= d ? scan[b - d] : 0;
-    __syncthreads();
-    scan[b] += v;
-    __syncthreads();
-  }
-  if (b < B) out_off[b + 1] = scan[b];
-  if (b == 0) out_off[0] = 0;
+  emit_windows(b, B, e, t, episode_off, prompt_off, Pmax, scan, ep, row, out_off);
 }
 
 // grid (nbx + 1, B): workgroups x < nbx of sample b move its frame row in units of V (uint4: 16 B, unsigned char: 1 B), workgroup

@@ -8,6 +8,7 @@
 // written by exactly one thread (plain stores, no atomics).  Both rules are restated in Python (vla_adapter_amd/heldout.py:
 // sweep_windows, l1_accumulate_reference), which is what the kernels are tested against, bit for bit.
 #include "common.h"
+#include "windows.h"
 #include "../../include/vla_heldout.h"
 
 // The accumulation's additions round one by one, in the order the header states.
@@ -18,19 +19,7 @@ namespace {
 constexpr int SWEEP_MAX_B = 1024;
 constexpr int ACC_THREADS = 64;                    // one wave per workgroup: C * A cells are a few hundred at most (ALOHA: 25 x 14)
 
-__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// The largest i in [lo, hi] with tab[i] <= v (lo when there is none): ends inside [lo, hi] on any table.
-template <class T>
-__device__ __forceinline__ int last_not_above(const T* __restrict__ tab, int lo, int hi, long long v) {
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if ((long long)tab[mid] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// One workgroup; thread b < B locates window w_b, then all threads scan the prompt lengths (Hillis-Steele in LDS).
+// One workgroup; thread b < B locates window w_b, then all threads scan the prompt lengths (emit_windows).
 __global__ void __launch_bounds__(SWEEP_MAX_B)
 heldout_sweep_kernel(const long long* __restrict__ val_off, const long long* __restrict__ episode_off, const int* __restrict__ prompt_off,
                      const int* __restrict__ dataset_off, int E, int D, long long first, long long stride, int B, int Pmax,
@@ -38,31 +27,19 @@ heldout_sweep_kernel(const long long* __restrict__ val_off, const long long* __r
                      unsigned char* __restrict__ valid) {
   __shared__ int scan[SWEEP_MAX_B];
   const int b = threadIdx.x;
-  int len = 0;
+  int e = 0;
+  long long t = 0;
   if (b < B) {
     const long long nv = val_off[E];
     const long long w = (first + (long long)b) * stride;
     const bool ok = w < nv;                          // (nv < 1, a bad table: no sample is valid)
     const long long j = ok ? w : 0ll;                // a sample past the end takes window 0: everything downstream runs on in-range data
-    const int e = last_not_above(val_off, 0, E - 1, j);
-    const long long t = j - val_off[e];
-    const long long e0 = episode_off[e], e1 = episode_off[e + 1];
+    e = last_not_above(val_off, 0, E - 1, j);
+    t = j - val_off[e];
     ds[b] = dataset_off ? last_not_above(dataset_off, 0, D - 1, (long long)e) : 0;
-    ep[b] = e;
-    row[b] = clampll(e0 + t, e0, e1 > e0 ? e1 - 1 : e0);
     valid[b] = ok ? 1 : 0;
-    len = (int)clampll((long long)prompt_off[e + 1] - (long long)prompt_off[e], 0ll, (long long)Pmax);
   }
-  scan[b] = len;
-  __syncthreads();
-  for (int s = 1; s < (int)blockDim.x; s <<= 1) {
-    const int v = b >= s ? scan[b - s] : 0;
-    __syncthreads();
-    scan[b] += v;
-    __syncthreads();
-  }
-  if (b < B) out_off[b + 1] = scan[b];
-  if (b == 0) out_off[0] = 0;
+  emit_windows(b, B, e, t, episode_off, prompt_off, Pmax, scan, ep, row, out_off);
 }
 
 // Workgroups x < nbx: thread (x, tid) owns cell i = x * ACC_THREADS + tid of the C * A cells and walks the datasets and, per dataset,

@@ -8,6 +8,7 @@
 // sample_windows), which is what the kernel is tested against, bit for bit.
 #include "common.h"
 #include "permute.h"
+#include "windows.h"
 #include "../../include/vla_mixture.h"
 
 // Every product, quotient and difference of the normalisation rounds on its own, as in collate.hip.
@@ -17,22 +18,9 @@ namespace {
 
 constexpr int SAMPLE_MAX_B = 1024;
 constexpr int NORMALIZE_THREADS = 256;
-constexpr u64 EPISODE_STREAM = 0xE9150DE5A391Eull;   // episodes.hip: the datasets' own epochs are keyed as a single store's are
 constexpr u64 MIX_STREAM = 0x313D0DA7A5E75ull;       // keeps the period shuffle apart from the window shuffle, the augmentation and the collator
 
-__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// The largest i in [lo, hi] with tab[i] <= v (lo when there is none): ends inside [lo, hi] on any table.
-template <class T>
-__device__ __forceinline__ int last_not_above(const T* __restrict__ tab, int lo, int hi, long long v) {
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if ((long long)tab[mid] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// One workgroup; thread b < B draws sample b, then all threads scan the prompt lengths (Hillis-Steele in LDS).
+// One workgroup; thread b < B draws sample b, then all threads scan the prompt lengths (emit_windows).
 __global__ void __launch_bounds__(SAMPLE_MAX_B)
 mixture_sample_kernel(const long long* __restrict__ valid_off, const long long* __restrict__ episode_off,
                       const int* __restrict__ prompt_off, const int* __restrict__ dataset_off, const long long* __restrict__ quota_off,
@@ -40,7 +28,8 @@ mixture_sample_kernel(const long long* __restrict__ valid_off, const long long* 
                       int* __restrict__ ep, long long* __restrict__ row, int* __restrict__ out_off) {
   __shared__ int scan[SAMPLE_MAX_B];
   const int b = threadIdx.x;
-  int len = 0;
+  int e = 0;
+  long long t = 0;
   if (b < B) {
     const long long q_tab = quota_off[D];
     const u64 pos = (step * world + rank) * (u64)B + (u64)b;
@@ -56,8 +45,7 @@ mixture_sample_kernel(const long long* __restrict__ valid_off, const long long* 
     const int e_lo = min(max(dataset_off[d], 0), E - 1);             // dataset d's episodes [e_lo, e_hi), kept inside [0, E)
     const int e_hi = min(max(dataset_off[d + 1], e_lo + 1), E);
     const long long v0 = valid_off[e_lo], n_tab = valid_off[e_hi] - v0;
-    int e = e_lo;
-    long long t = 0;
+    e = e_lo;
     if (n_tab >= 1) {
       const u64 n = (u64)n_tab;
       const u64 epoch = c / n, i = c % n;
@@ -66,22 +54,9 @@ mixture_sample_kernel(const long long* __restrict__ valid_off, const long long* 
       e = last_not_above(valid_off, e_lo, e_hi - 1, j);
       t = j - valid_off[e];
     }
-    const long long e0 = episode_off[e], e1 = episode_off[e + 1];
     ds[b] = d;
-    ep[b] = e;
-    row[b] = clampll(e0 + t, e0, e1 > e0 ? e1 - 1 : e0);
-    len = (int)clampll((long long)prompt_off[e + 1] - (long long)prompt_off[e], 0ll, (long long)Pmax);
   }
-  scan[b] = len;
-  __syncthreads();
-  for (int w = 1; w < (int)blockDim.x; w <<= 1) {
-    const int v = b >= w ? scan[b - w] : 0;
-    __syncthreads();
-    scan[b] += v;
-    __syncthreads();
-  }
-  if (b < B) out_off[b + 1] = scan[b];
-  if (b == 0) out_off[0] = 0;
+  emit_windows(b, B, e, t, episode_off, prompt_off, Pmax, scan, ep, row, out_off);
 }
 
 // x [R, row_len] f32 -> y; element (r, i) with column d = i % D of set s = clamp(sel[r]): normalize_bounds_kernel of collate.hip

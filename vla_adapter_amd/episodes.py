@@ -23,6 +23,9 @@ An episode file is a ``.pt`` dict, or a directory of them (the shards are concat
 The sampling rule is stated here in plain Python - ``sample_position``, ``permute_index``, ``locate`` - and is the specification the
 kernel is tested against, bit for bit.
 
+``EpisodeTables`` is what the store shares with ``mixture.EpisodeMix``: the tables on the device, the window tables, the statistics,
+the raw-batch buffers and the gather.
+
 ``holdout=f`` sets every dataset's last episodes aside for validation without copying or reordering anything - ``holdout_count``,
 ``split_offsets``: two complementary window tables - and ``heldout.HeldOutSweep`` walks them.
 """
@@ -31,7 +34,7 @@ from __future__ import annotations
 import math
 import os
 from pathlib import Path
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -40,8 +43,8 @@ from .constants import NUM_ACTIONS_CHUNK
 from .finetune import RAW_BATCH_KEYS                # what sample() returns: the raw batch finetune.batch_stream collates
 
 EPISODE_KEYS = ("frames_u8", "actions_raw", "proprio_raw", "episode_off", "prompt_flat", "prompt_off")
-EPISODE_STREAM = 0xE9150DE5A391E        # csrc/episodes.hip: keeps the shuffle apart from the augmentation's and the collator's draws
-MAX_BATCH = 1024                        # vla_episode_sample is one workgroup
+EPISODE_STREAM = 0xE9150DE5A391E        # csrc/windows.h: keeps the shuffle apart from the augmentation's and the collator's draws
+MAX_BATCH = 1024                        # vla_episode_sample, vla_mixture_sample and vla_heldout_sweep are one workgroup each
 _M64 = (1 << 64) - 1
 
 
@@ -222,7 +225,105 @@ def check_split(train_off, val_off, e_lo: int, e_hi: int, H: int, chunk: int, na
     return dict(episodes=[e_hi - H, e_hi], num_episodes=H, train_windows=n_train, heldout_windows=n_val)
 
 
-class EpisodeStore:
+class EpisodeTables:
+    """What a store and a mix have in common: D >= 1 datasets back to back in one set of tables on the device, the training window
+    table ``valid_off`` (and, with ``holdout=f``, the complementary ``val_off``), the extents, the per-dataset statistics, the buffers
+    of a raw batch and the one ``vla_episode_gather`` call site.  ``EpisodeStore`` (below) and ``mixture.EpisodeMix`` add what is
+    their own: how the windows of a batch are drawn.
+
+    ``tables``: one episode-file dict per dataset; ``names``: the datasets' names (statistics and hold-out entries are keyed by them);
+    ``wheres``: what a ValueError about dataset d's tables calls them (default: its name)."""
+
+    mixed = False                           # a mix: the raw batch carries dataset_index, every sample its own dataset's statistics
+
+    def __init__(self, tables: List[dict], names: Sequence[str], device, chunk: int = NUM_ACTIONS_CHUNK, *, holdout: Optional[float] = None,
+                 wheres: Optional[Sequence[str]] = None):
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        wheres = list(wheres or names)
+        for d, w in zip(tables, wheres):
+            _check_shard(d, w)
+        self.device, self.chunk, self.names, self.D = device, int(chunk), tuple(names), len(tables)
+        self.action_masks = [torch.as_tensor(d["action_mask"]).tolist() if "action_mask" in d else None for d in tables]
+        ranges, self._stats = [0], {}                  # dataset d holds the episodes [ranges[d], ranges[d + 1])
+        for d, n, w, mask in zip(tables, self.names, wheres, self.action_masks):
+            E_d = int(d["episode_off"].numel() - 1)
+            if int(valid_offsets(d["episode_off"].cpu(), self.chunk)[-1]) < 1:
+                raise ValueError(f"{w}: no valid window - every one of the {E_d} episodes is shorter than the action chunk of {self.chunk} "
+                                 "steps (episode_off)")
+            ranges.append(ranges[-1] + E_d)
+            self._stats[n] = dataset_statistics(d["actions_raw"].cpu().numpy(), d["proprio_raw"].cpu().numpy(), E_d, mask)
+        self.episode_ranges = ranges
+        # one set of tables: the datasets' rows and episodes back to back (names and masks are kept per dataset, above)
+        all_ = tables[0]
+        if self.D > 1:
+            all_ = concat_shards([{k: v for k, v in d.items() if k not in ("dataset_name", "action_mask")} for d in tables], wheres, device)
+        act, pr, eo, po = all_["actions_raw"], all_["proprio_raw"], all_["episode_off"], all_["prompt_off"]
+        self.T, self.E = int(act.shape[0]), int(eo.numel() - 1)
+        # holdout=f: every dataset sets its own last H_d episodes aside.  The statistics (and a mix's transitions, p and quotas) stay
+        # over ALL episodes - the reference balances and normalises over split="all" (rlds/dataset.py:209-211)
+        valid, val = valid_offsets(eo.cpu(), self.chunk), None
+        self.holdout, self.heldout = holdout, None
+        if holdout is not None:
+            counts = [check_holdout(holdout, ranges[d + 1] - ranges[d], n) for d, n in enumerate(self.names)]
+            held = torch.zeros(self.E, dtype=torch.bool)
+            for d, H in enumerate(counts):
+                held[ranges[d + 1] - H:ranges[d + 1]] = True
+            valid, val = split_offsets(eo.cpu(), self.chunk, held)
+            self.heldout = {n: check_split(valid, val, ranges[d], ranges[d + 1], counts[d], self.chunk, n) for d, n in enumerate(self.names)}
+        self.N = int(valid[-1])
+        self.Nv = int(val[-1]) if val is not None else 0
+        self.A, self.Pd = int(act.shape[1]), int(pr.shape[1])
+        self.frame_shape = tuple(all_["frames_u8"].shape[1:])
+        self.row_bytes = int(np.prod(self.frame_shape))
+        self.Pmax = int(po.diff().max())
+        self.valid_off_host, self.val_off_host = valid, val
+        self.frames_u8, self.actions_raw, self.proprio_raw = self._upload(all_["frames_u8"]), self._upload(act), self._upload(pr)
+        self.episode_off, self.valid_off = self._upload(eo), self._upload(valid)
+        self.val_off = self._upload(val) if val is not None else None
+        self.prompt_flat, self.prompt_off = self._upload(all_["prompt_flat"]), self._upload(po)
+        self._out: Dict[int, dict] = {}
+
+    def _upload(self, t: torch.Tensor) -> torch.Tensor:
+        return t.to(self.device).contiguous()
+
+    def statistics(self) -> dict:
+        """One reference-shaped get_dataset_statistics entry per dataset, keyed by its name and taken from that dataset's rows alone:
+        what make_interleaved_dataset returns as all_dataset_statistics and --dataset_statistics_file would hold."""
+        return self._stats
+
+    # ---- the batch -----------------------------------------------------------------------------------------------------------
+    def _buffers(self, B: int) -> dict:
+        if B not in self._out:
+            dev, e = self.device, torch.empty
+            o = dict(ep=e(B, dtype=torch.int32, device=dev), row=e(B, dtype=torch.int64, device=dev),
+                     frames_u8=e((B,) + self.frame_shape, dtype=torch.uint8, device=dev),
+                     actions_raw=e(B, self.chunk, self.A, dtype=torch.float32, device=dev),
+                     proprio_raw=e(B, self.Pd, dtype=torch.float32, device=dev),
+                     prompt_flat=e(B * self.Pmax, dtype=torch.int64, device=dev), prompt_off=e(B + 1, dtype=torch.int32, device=dev))
+            if self.mixed:
+                o["dataset_index"] = e(B, dtype=torch.int32, device=dev)
+            self._out[B] = o
+        return self._out[B]
+
+    def _check_draw(self, B: int, rank: int, world: int, step: int) -> None:
+        """ValueError for a (B, rank, world, step) the samplers' entry points refuse."""
+        if not 1 <= B <= MAX_BATCH:
+            raise ValueError(f"sample: the batch size must lie in [1, {MAX_BATCH}] (one workgroup draws the batch), got {B}")
+        if not (world >= 1 and 0 <= rank < world and step >= 0):
+            raise ValueError(f"sample: need 0 <= rank < world and step >= 0, got rank {rank}, world {world}, step {step}")
+        check_position(B, rank, world, step)
+
+    def gather(self, ep: torch.Tensor, row: torch.Tensor, prompt_off: torch.Tensor, into: dict) -> dict:
+        """vla_episode_gather of the windows (ep, row, prompt_off) - a sampler's or the held-out sweep's - into the frames_u8 /
+        actions_raw / proprio_raw / prompt_flat of ``into``; -> the raw batch, RAW_BATCH_KEYS on the device."""
+        from . import ops
+        ops.episode_gather(self.frames_u8, self.actions_raw, self.proprio_raw, self.episode_off, self.prompt_flat, self.prompt_off, ep, row,
+                           prompt_off, into["frames_u8"], into["actions_raw"], into["proprio_raw"], into["prompt_flat"], self.Pmax)
+        return {k: prompt_off if k == "prompt_off" else into[k] for k in RAW_BATCH_KEYS}
+
+
+class EpisodeStore(EpisodeTables):
     """Episodes on the device; ``sample()`` draws one raw batch.  Build with ``EpisodeStore.load`` or ``EpisodeStore.from_dict``.
 
     ``holdout=f`` (0 < f < 1) sets the last ``holdout_count(E, f)`` episodes aside for validation (heldout.HeldOutSweep): the training
@@ -233,38 +334,9 @@ class EpisodeStore:
 
     def __init__(self, tables: dict, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, _where: str = "episode store",
                  *, holdout: Optional[float] = None):
-        if chunk < 1:
-            raise ValueError("chunk must be >= 1")
-        _check_shard(tables, _where)
-        self.device, self.chunk = device, int(chunk)
-        self.dataset_name = tables.get("dataset_name") or dataset_name or "episodes"
-        self.action_mask = torch.as_tensor(tables["action_mask"]).tolist() if "action_mask" in tables else None
-        act, pr, eo, po = tables["actions_raw"], tables["proprio_raw"], tables["episode_off"], tables["prompt_off"]
-        valid = valid_offsets(eo.cpu(), self.chunk)
-        if int(valid[-1]) < 1:
-            raise ValueError(f"{_where}: no valid window - every one of the {eo.numel() - 1} episodes is shorter than the action chunk of "
-                             f"{self.chunk} steps (episode_off)")
-        self.holdout, self.heldout, val = holdout, None, None
-        if holdout is not None:
-            E = int(eo.numel() - 1)
-            H = check_holdout(holdout, E, self.dataset_name)
-            valid, val = split_offsets(eo.cpu(), self.chunk, torch.arange(E) >= E - H)
-            self.heldout = {self.dataset_name: check_split(valid, val, 0, E, H, self.chunk, self.dataset_name)}
-        self.N = int(valid[-1])
-        self.Nv = int(val[-1]) if val is not None else 0
-        self.T, self.E = int(act.shape[0]), int(eo.numel() - 1)
-        self.A, self.Pd = int(act.shape[1]), int(pr.shape[1])
-        self.frame_shape = tuple(tables["frames_u8"].shape[1:])
-        self.row_bytes = int(np.prod(self.frame_shape))
-        self.Pmax = int(po.diff().max())
-        self._stats = {self.dataset_name: dataset_statistics(act.cpu().numpy(), pr.cpu().numpy(), self.E, self.action_mask)}
-        self.valid_off_host = valid
-        dv = lambda t: t.to(device).contiguous()
-        self.frames_u8, self.actions_raw, self.proprio_raw = dv(tables["frames_u8"]), dv(act), dv(pr)
-        self.episode_off, self.valid_off = dv(eo), dv(valid)
-        self.val_off_host, self.val_off = val, (dv(val) if val is not None else None)
-        self.prompt_flat, self.prompt_off = dv(tables["prompt_flat"]), dv(po)
-        self._out: Dict[int, dict] = {}
+        name = (tables.get("dataset_name") if isinstance(tables, dict) else None) or dataset_name or "episodes"
+        super().__init__([tables], [name], device, chunk, holdout=holdout, wheres=[_where])
+        self.dataset_name, self.action_mask = self.names[0], self.action_masks[0]
 
     # ---- construction --------------------------------------------------------------------------------------------------------
     @classmethod
@@ -280,30 +352,11 @@ class EpisodeStore:
         ``holdout``: the fraction of episodes - the last ones - set aside for validation (see the class)."""
         return cls(load_tables(path, device), device, chunk, dataset_name, _where=str(path), holdout=holdout)
 
-    # ---- the two products ----------------------------------------------------------------------------------------------------
-    def statistics(self) -> dict:
-        """The reference's get_dataset_statistics dict, keyed by the dataset's name: what --dataset_statistics_file would hold."""
-        return self._stats
-
-    def _buffers(self, B: int) -> dict:
-        if B not in self._out:
-            dev, e = self.device, torch.empty
-            self._out[B] = dict(ep=e(B, dtype=torch.int32, device=dev), row=e(B, dtype=torch.int64, device=dev),
-                                frames_u8=e((B,) + self.frame_shape, dtype=torch.uint8, device=dev),
-                                actions_raw=e(B, self.chunk, self.A, dtype=torch.float32, device=dev),
-                                proprio_raw=e(B, self.Pd, dtype=torch.float32, device=dev),
-                                prompt_flat=e(B * self.Pmax, dtype=torch.int64, device=dev),
-                                prompt_off=e(B + 1, dtype=torch.int32, device=dev))
-        return self._out[B]
-
+    # ---- the batch -----------------------------------------------------------------------------------------------------------
     def sample_indices(self, B: int, seed: int, rank: int, world: int, step: int):
         """vla_episode_sample into the store's buffers of batch size B -> (ep int32 [B], row int64 [B], prompt_off int32 [B + 1])."""
         from . import ops
-        if not 1 <= B <= MAX_BATCH:
-            raise ValueError(f"sample: the batch size must lie in [1, {MAX_BATCH}] (one workgroup draws the batch), got {B}")
-        if not (world >= 1 and 0 <= rank < world and step >= 0):
-            raise ValueError(f"sample: need 0 <= rank < world and step >= 0, got rank {rank}, world {world}, step {step}")
-        check_position(B, rank, world, step)
+        self._check_draw(B, rank, world, step)
         o = self._buffers(B)
         ops.episode_sample(self.valid_off, self.episode_off, self.prompt_off, seed, rank, world, step, self.Pmax, o["ep"], o["row"], o["prompt_off"])
         return o["ep"], o["row"], o["prompt_off"]
@@ -312,12 +365,7 @@ class EpisodeStore:
         """The raw batch of (rank, step): RAW_BATCH_KEYS on the device plus dataset_name, from the two kernels.  Every rank passes the
         same seed.  The tensors are the store's own buffers of this batch size: the next call with the same B overwrites them (in
         stream order), so consume - collate - a batch before drawing the next, or clone it."""
-        from . import ops
-        ep, row, off = self.sample_indices(B, seed, rank, world, step)
-        o = self._buffers(B)
-        ops.episode_gather(self.frames_u8, self.actions_raw, self.proprio_raw, self.episode_off, self.prompt_flat, self.prompt_off, ep, row, off,
-                           o["frames_u8"], o["actions_raw"], o["proprio_raw"], o["prompt_flat"], self.Pmax)
-        out = {k: o[k] for k in RAW_BATCH_KEYS}
+        out = self.gather(*self.sample_indices(B, seed, rank, world, step), self._buffers(B))
         out["dataset_name"] = self.dataset_name
         return out
 

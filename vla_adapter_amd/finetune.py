@@ -175,6 +175,7 @@ IMAGE_AUG_REFUSAL = ("--image_aug: already normalised pixel_values cannot be aug
 
 
 VAL_FLAGS = ("val_freq", "val_time_limit")
+EPISODE_FLAGS = ("episode_file", "episode_mix")     # the two device-resident batch sources: what either needs is stated once
 
 
 def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = False, val_batches: bool = False) -> None:
@@ -217,14 +218,11 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         if cfg.val_window_stride < 1:
             raise ValueError("--val_window_stride must be >= 1")
     if cfg.use_val_set:
-        if cfg.episode_file and not (cfg.val_batch_file or val_batches or heldout):
-            raise NotImplementedError("--use_val_set with --episode_file: no validation split is cut from the episodes (ValidationPass takes "
-                                      "collated batches); pass held-out batches with --val_batch_file.  Or hold a fraction of the "
-                                      "episodes out with --val_episode_fraction.")
-        if cfg.episode_mix and not (cfg.val_batch_file or val_batches or heldout):
-            raise NotImplementedError("--use_val_set with --episode_mix: no validation split is cut from the episodes (ValidationPass takes "
-                                      "collated batches); pass held-out batches with --val_batch_file.  Or hold a fraction of the "
-                                      "episodes out with --val_episode_fraction.")
+        for flag in EPISODE_FLAGS:
+            if getattr(cfg, flag) and not (cfg.val_batch_file or val_batches or heldout):
+                raise NotImplementedError(f"--use_val_set with --{flag}: no validation split is cut from the episodes (ValidationPass takes "
+                                          "collated batches); pass held-out batches with --val_batch_file.  Or hold a fraction of the "
+                                          "episodes out with --val_episode_fraction.")
         if not (cfg.val_batch_file or val_batches or heldout):
             raise NotImplementedError("--use_val_set needs held-out batches: pass --val_batch_file (a .pt dict or a directory of them) or "
                                       "finetune(val_batches=...); the RLDS val split is not read (out of scope, SURVEY section 2 #16)")
@@ -251,16 +249,12 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         raise ValueError(" and ".join("--" + n for n in sources) + f" are {len(sources)} batch sources: pass one")
     if cfg.raw_batch_file and not cfg.dataset_statistics_file:
         raise ValueError("--raw_batch_file carries un-normalised actions / proprio: pass the statistics with --dataset_statistics_file")
-    if cfg.episode_file and not cfg.max_seq_len:
-        raise ValueError("raw batches with prompt offsets on the device need --max_seq_len (the natural length would be read back): "
-                         "--episode_file draws its prompt offsets on the device")
-    if cfg.episode_file and not 1 <= cfg.batch_size <= 1024:
-        raise ValueError("--episode_file draws a batch in one workgroup: --batch_size must lie in [1, 1024]")
-    if cfg.episode_mix and not cfg.max_seq_len:
-        raise ValueError("raw batches with prompt offsets on the device need --max_seq_len (the natural length would be read back): "
-                         "--episode_mix draws its prompt offsets on the device")
-    if cfg.episode_mix and not 1 <= cfg.batch_size <= 1024:
-        raise ValueError("--episode_mix draws a batch in one workgroup: --batch_size must lie in [1, 1024]")
+    for flag in EPISODE_FLAGS:
+        if getattr(cfg, flag) and not cfg.max_seq_len:
+            raise ValueError("raw batches with prompt offsets on the device need --max_seq_len (the natural length would be read back): "
+                             f"--{flag} draws its prompt offsets on the device")
+        if getattr(cfg, flag) and not 1 <= cfg.batch_size <= 1024:
+            raise ValueError(f"--{flag} draws a batch in one workgroup: --batch_size must lie in [1, 1024]")
     if cfg.episode_mix:
         from .mixture import parse_mix
         parse_mix(cfg.episode_mix)                # ValueError for a weight that is no number or an entry without a path
@@ -623,44 +617,36 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
                 yield collate(b)
             if n == 0:
                 raise ValueError("empty batch iterable")
-    elif cfg.episode_file:
-        from .episodes import EpisodeStore
-        store = EpisodeStore.load(cfg.episode_file, dev, chunk=mcfg.chunk, dataset_name=cfg.dataset_name, holdout=cfg.val_episode_fraction)
-        if (store.A, store.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
-            raise ValueError(f"{cfg.episode_file}: actions_raw / proprio_raw have {store.A} / {store.Pd} columns, the model takes "
-                             f"{mcfg.action_dim} / {mcfg.proprio_dim}")
-        if store.frame_shape[0] != mcfg.n_img:
-            raise ValueError(f"{cfg.episode_file}: frames_u8 carries {store.frame_shape[0]} images per step, --num_images_in_input is {mcfg.n_img}")
-        if not cfg.dataset_statistics_file:
-            norm_stats = store.statistics()
-            if info is not None:
-                info["dataset_statistics"] = norm_stats
-        if info is not None:
-            info["store"] = store                 # (the held-out sweep walks the same device-resident tables)
-        while True:
-            yield collate_raw(store.sample(cfg.batch_size, cfg.seed, rank, world, step))
-    elif cfg.episode_mix:
-        from .mixture import EpisodeMix, parse_mix
-        mix = EpisodeMix.load(parse_mix(cfg.episode_mix), dev, chunk=mcfg.chunk, balance_weights=cfg.episode_mix_balance,
-                              holdout=cfg.val_episode_fraction)
-        if (mix.A, mix.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
-            raise ValueError(f"--episode_mix: actions_raw / proprio_raw have {mix.A} / {mix.Pd} columns, the model takes "
-                             f"{mcfg.action_dim} / {mcfg.proprio_dim}")
-        if mix.frame_shape[0] != mcfg.n_img:
-            raise ValueError(f"--episode_mix: frames_u8 carries {mix.frame_shape[0]} images per step, --num_images_in_input is {mcfg.n_img}")
-        if cfg.dataset_statistics_file:
-            mixture_stats(json.load(open(cfg.dataset_statistics_file)), mix.names)        # a missing entry is refused before the first step
+    elif cfg.episode_file or cfg.episode_mix:
+        if cfg.episode_file:
+            from .episodes import EpisodeStore
+            where = cfg.episode_file
+            src = EpisodeStore.load(cfg.episode_file, dev, chunk=mcfg.chunk, dataset_name=cfg.dataset_name, holdout=cfg.val_episode_fraction)
         else:
-            norm_stats = mix.statistics()
+            from .mixture import EpisodeMix, parse_mix
+            where = "--episode_mix"
+            src = EpisodeMix.load(parse_mix(cfg.episode_mix), dev, chunk=mcfg.chunk, balance_weights=cfg.episode_mix_balance,
+                                  holdout=cfg.val_episode_fraction)
+        if (src.A, src.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
+            raise ValueError(f"{where}: actions_raw / proprio_raw have {src.A} / {src.Pd} columns, the model takes "
+                             f"{mcfg.action_dim} / {mcfg.proprio_dim}")
+        if src.frame_shape[0] != mcfg.n_img:
+            raise ValueError(f"{where}: frames_u8 carries {src.frame_shape[0]} images per step, --num_images_in_input is {mcfg.n_img}")
+        if not cfg.dataset_statistics_file:
+            norm_stats = src.statistics()
             if info is not None:
                 info["dataset_statistics"] = norm_stats
+        elif src.mixed:
+            mixture_stats(json.load(open(cfg.dataset_statistics_file)), src.names)        # a missing entry is refused before the first step
         if info is not None:
-            info["mixture"] = mix.mixture_info()
-            info["store"] = mix
-        if rank == 0:
-            print(json.dumps(dict(mixture=mix.mixture_info())), flush=True)
+            info["store"] = src                   # (the held-out sweep walks the same device-resident tables)
+        if src.mixed:
+            if info is not None:
+                info["mixture"] = src.mixture_info()
+            if rank == 0:
+                print(json.dumps(dict(mixture=src.mixture_info())), flush=True)
         while True:
-            yield collate_raw(mix.sample(cfg.batch_size, cfg.seed, rank, world, step))
+            yield collate_raw(src.sample(cfg.batch_size, cfg.seed, rank, world, step))
     elif cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file:
         src = cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file
         files = sorted(str(p) for p in Path(src).glob("*.pt")) if os.path.isdir(src) else [src]

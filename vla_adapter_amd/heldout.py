@@ -22,11 +22,10 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .episodes import locate
+from .episodes import MAX_BATCH, locate     # one workgroup names the batch, as one draws a training batch
 
 HELDOUT_STREAM = 0x4E1D0075EE9A1        # the sweep's seed word for the collator's filler ids: apart from the training batches' under equal seeds
 SYNC_EVERY = 8                          # batches between two host waits (the --val_time_limit check): the overshoot is at most this many
-MAX_BATCH = 1024                        # vla_heldout_sweep is one workgroup
 
 
 # ---------------------------------------------------------------------------------------------------------------- the two rules
@@ -162,13 +161,13 @@ class HeldOutSweep:
             raise ValueError("--val_window_stride must be >= 1")
         self.cfg, self.mcfg, self.dev, self.rank, self.world, self.model, self.store = cfg, mcfg, dev, int(rank), int(world), model, store
         self.B, self.L, self.use_graph, self.group = B, int(L), bool(use_graph), group
-        self.mixed = hasattr(store, "dataset_off")
-        self.names = tuple(store.names) if self.mixed else (store.dataset_name,)
-        self.D, self.C, self.A = len(self.names), int(mcfg.chunk), int(mcfg.action_dim)
+        self.mixed, self.names, self.D = store.mixed, tuple(store.names), store.D
+        self.C, self.A = int(mcfg.chunk), int(mcfg.action_dim)
+        # per-dataset entries in the order ds indexes them; a single store's collate takes its one entry bare (no stats_index)
         if self.mixed:
             self.action_stats, self.proprio_stats = mixture_stats(norm_stats, self.names)
         else:
-            st = raw_batch_stats(norm_stats, store.dataset_name)
+            st = raw_batch_stats(norm_stats, self.names[0])
             self.action_stats, self.proprio_stats = st["action"], st["proprio"]
         self.windows = [store.heldout[n]["heldout_windows"] for n in self.names]
         self.Nv = int(store.Nv)
@@ -197,9 +196,7 @@ class HeldOutSweep:
         s, i, r = self.store, self.idx, self.raw
         ops.heldout_sweep(s.val_off, s.episode_off, s.prompt_off, s.dataset_off if self.mixed else None, self.rank, self.world, j, self.stride,
                           s.Pmax, i["ds"], i["ep"], i["row"], i["prompt_off"], i["valid"])
-        ops.episode_gather(s.frames_u8, s.actions_raw, s.proprio_raw, s.episode_off, s.prompt_flat, s.prompt_off, i["ep"], i["row"], i["prompt_off"],
-                           r["frames_u8"], r["actions_raw"], r["proprio_raw"], r["prompt_flat"], s.Pmax)
-        return dict(r, prompt_off=i["prompt_off"], dataset_index=i["ds"], valid=i["valid"])
+        return dict(s.gather(i["ep"], i["row"], i["prompt_off"], r), dataset_index=i["ds"], valid=i["valid"])
 
     def collate(self, raw: dict, j: int) -> dict:
         """The model's batch of a drawn raw batch: never augmented, every row normalised with its own dataset's statistics, filler ids

@@ -3,7 +3,7 @@
 ``RLDSDataset`` always builds a mixture (prismatic/vla/datasets/datasets.py:160-200); ``make_interleaved_dataset``
 (rlds/dataset.py:490-585) normalises every dataset with its own q01 / q99 statistics, interleaves the datasets frame by frame with
 ``sample_weights`` - multiplied by each dataset's transition count under ``balance_weights`` - and lets every dataset run through its
-own endless epochs.  ``EpisodeMix`` keeps D datasets back to back in one set of the tables of ``episodes.EpisodeStore`` and draws each
+own endless epochs.  ``EpisodeMix`` keeps D datasets back to back in one set of tables (``episodes.EpisodeTables``) and draws each
 step's batch with ``vla_mixture_sample`` (csrc/mixture.hip, include/vla_mixture.h) and the unchanged ``vla_episode_gather``; the batch
 carries ``dataset_index``, with which ``GPUInputStage.collate`` normalises every sample with its own dataset's statistics
 (``vla_normalize_bounds_rows``).  No host work per step: nothing is read back, synchronised or, after the first call, allocated.
@@ -16,15 +16,13 @@ from __future__ import annotations
 
 import math
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .constants import NUM_ACTIONS_CHUNK
-from .episodes import (MAX_BATCH, _M64, _check_shard, check_holdout, check_position, check_split, concat_shards, dataset_statistics, epoch_key, load_tables, locate, permute_index,
-                       sample_position, split_offsets, splitmix64_key, valid_offsets)
-from .finetune import RAW_BATCH_KEYS
+from .episodes import _M64, EpisodeTables, epoch_key, load_tables, locate, permute_index, sample_position, splitmix64_key
 
 MIX_STREAM = 0x313D0DA7A5E75            # csrc/mixture.hip: keeps the period shuffle apart from the window shuffle (EPISODE_STREAM), the
                                         # collator's (COLLATE_STREAM) and the augmentation's draws under equal seed words
@@ -109,9 +107,11 @@ def parse_mix(text: str) -> List[Tuple[str, float]]:
     return entries
 
 
-class EpisodeMix:
+class EpisodeMix(EpisodeTables):
     """D datasets on the device in one set of tables; ``sample()`` draws one raw batch of the weighted mixture.  Build with
     ``EpisodeMix.load`` or ``EpisodeMix.from_dicts``."""
+
+    mixed = True
 
     def __init__(self, tables: List[dict], weights: Sequence[float], names: Sequence[str], device, chunk: int = NUM_ACTIONS_CHUNK,
                  period: int = DEFAULT_PERIOD, balance_weights: bool = True, *, holdout: Optional[float] = None):
@@ -126,61 +126,18 @@ class EpisodeMix:
         for n, w in zip(names, weights):
             if not (isinstance(w, (int, float)) and float(w) > 0.0 and math.isfinite(float(w))):      # (NaN fails the comparison too)
                 raise ValueError(f"{n}: weight must be a finite number > 0, got {w!r}")
-        for d, n in zip(tables, names):
-            _check_shard(d, n)
-        self.device, self.chunk, self.names = device, int(chunk), tuple(names)
-        self.weights, self.balance_weights = [float(w) for w in weights], bool(balance_weights)
-        self.action_masks = [torch.as_tensor(d["action_mask"]).tolist() if "action_mask" in d else None for d in tables]
-        ds_off, self.transitions, self.windows, stats = [0], [], [], {}
-        for d, n, mask in zip(tables, names, self.action_masks):
-            E_d = int(d["episode_off"].numel() - 1)
-            N_d = int(valid_offsets(d["episode_off"].cpu(), self.chunk)[-1])
-            if N_d < 1:
-                raise ValueError(f"{n}: no valid window - every one of the {E_d} episodes is shorter than the action chunk of {self.chunk} "
-                                 "steps (episode_off)")
-            ds_off.append(ds_off[-1] + E_d)
-            self.transitions.append(int(d["actions_raw"].shape[0]))
-            self.windows.append(N_d)
-            stats[n] = dataset_statistics(d["actions_raw"].cpu().numpy(), d["proprio_raw"].cpu().numpy(), E_d, mask)
-        self._stats = stats
-        # one set of tables: the datasets' rows and episodes back to back (names and masks are the mix's own business)
-        bare = [{k: v for k, v in d.items() if k not in ("dataset_name", "action_mask")} for d in tables]
-        all_ = concat_shards(bare, list(names), device)
-        self.D, self.Q = len(tables), int(period)
+        super().__init__(tables, names, device, chunk, holdout=holdout)
+        # transitions, p and the quotas stay over ALL episodes under holdout=f (episodes.EpisodeTables); windows are the training
+        # windows N_d, which the sampler reads from valid_off on the device
+        self.weights, self.balance_weights, self.Q = [float(w) for w in weights], bool(balance_weights), int(period)
+        self.transitions = [int(d["actions_raw"].shape[0]) for d in tables]
+        ds_off, valid = self.episode_ranges, self.valid_off_host
+        self.windows = [int(valid[ds_off[d + 1]]) - int(valid[ds_off[d]]) for d in range(self.D)]
         self.p = probabilities(self.weights, self.transitions, self.balance_weights)
         self.quota = quotas(self.p, self.Q)
-        act, pr, eo, po = all_["actions_raw"], all_["proprio_raw"], all_["episode_off"], all_["prompt_off"]
-        valid = valid_offsets(eo.cpu(), self.chunk)
-        self.T, self.E = int(act.shape[0]), int(eo.numel() - 1)
-        # holdout=f: every dataset sets its own last H_d episodes aside (episodes.EpisodeStore).  transitions, p, the quotas and the
-        # statistics stay over ALL episodes - the reference balances and normalises over split="all" (rlds/dataset.py:209-211) -;
-        # windows becomes the training windows N_d, which the sampler reads from valid_off on the device
-        self.holdout, self.heldout, val = holdout, None, None
-        if holdout is not None:
-            held = torch.zeros(self.E, dtype=torch.bool)
-            counts = [check_holdout(holdout, ds_off[d + 1] - ds_off[d], n) for d, n in enumerate(names)]
-            for d, H in enumerate(counts):
-                held[ds_off[d + 1] - H:ds_off[d + 1]] = True
-            valid, val = split_offsets(eo.cpu(), self.chunk, held)
-            self.heldout = {n: check_split(valid, val, ds_off[d], ds_off[d + 1], counts[d], self.chunk, n) for d, n in enumerate(names)}
-            self.windows = [self.heldout[n]["train_windows"] for n in names]
-        self.N = int(valid[-1])
-        self.Nv = int(val[-1]) if val is not None else 0
-        self.val_off_host = val
-        self.A, self.Pd = int(act.shape[1]), int(pr.shape[1])
-        self.frame_shape = tuple(all_["frames_u8"].shape[1:])
-        self.row_bytes = int(np.prod(self.frame_shape))
-        self.Pmax = int(po.diff().max())
-        self.valid_off_host = valid
         self.dataset_off_host = torch.tensor(ds_off, dtype=torch.int32)
         self.quota_off_host = torch.tensor(np.cumsum([0] + self.quota), dtype=torch.int64)
-        dv = lambda t: t.to(device).contiguous()
-        self.frames_u8, self.actions_raw, self.proprio_raw = dv(all_["frames_u8"]), dv(act), dv(pr)
-        self.episode_off, self.valid_off = dv(eo), dv(valid)
-        self.val_off = dv(val) if val is not None else None
-        self.prompt_flat, self.prompt_off = dv(all_["prompt_flat"]), dv(po)
-        self.dataset_off, self.quota_off = dv(self.dataset_off_host), dv(self.quota_off_host)
-        self._out: Dict[int, dict] = {}
+        self.dataset_off, self.quota_off = self._upload(self.dataset_off_host), self._upload(self.quota_off_host)
 
     # ---- construction --------------------------------------------------------------------------------------------------------
     @classmethod
@@ -211,11 +168,6 @@ class EpisodeMix:
         return cls(tables, weights, names, device, chunk, period, balance_weights, holdout=holdout)
 
     # ---- what the mix is -----------------------------------------------------------------------------------------------------
-    def statistics(self) -> dict:
-        """One reference-shaped get_dataset_statistics entry per dataset, each from that dataset's rows alone: what
-        make_interleaved_dataset returns as all_dataset_statistics and --dataset_statistics_file would hold."""
-        return self._stats
-
     def mixture_info(self) -> dict:
         """Names, probabilities, quotas, the period, and the reference's dataset_len (rlds/dataset.py:512-522): the draws until every
         primary dataset - weight == 1.0 - has completed an epoch; None when no weight is 1.0 (the reference fails there)."""
@@ -225,26 +177,10 @@ class EpisodeMix:
                     dataset_len=int(max(primary)) if primary else None)
 
     # ---- the batch -----------------------------------------------------------------------------------------------------------
-    def _buffers(self, B: int) -> dict:
-        if B not in self._out:
-            dev, e = self.device, torch.empty
-            self._out[B] = dict(dataset_index=e(B, dtype=torch.int32, device=dev), ep=e(B, dtype=torch.int32, device=dev),
-                                row=e(B, dtype=torch.int64, device=dev),
-                                frames_u8=e((B,) + self.frame_shape, dtype=torch.uint8, device=dev),
-                                actions_raw=e(B, self.chunk, self.A, dtype=torch.float32, device=dev),
-                                proprio_raw=e(B, self.Pd, dtype=torch.float32, device=dev),
-                                prompt_flat=e(B * self.Pmax, dtype=torch.int64, device=dev),
-                                prompt_off=e(B + 1, dtype=torch.int32, device=dev))
-        return self._out[B]
-
     def sample_indices(self, B: int, seed: int, rank: int, world: int, step: int):
         """vla_mixture_sample into the mix's buffers of batch size B -> (ds int32 [B], ep int32 [B], row int64 [B], prompt_off int32 [B + 1])."""
         from . import ops
-        if not 1 <= B <= MAX_BATCH:
-            raise ValueError(f"sample: the batch size must lie in [1, {MAX_BATCH}] (one workgroup draws the batch), got {B}")
-        if not (world >= 1 and 0 <= rank < world and step >= 0):
-            raise ValueError(f"sample: need 0 <= rank < world and step >= 0, got rank {rank}, world {world}, step {step}")
-        check_position(B, rank, world, step)
+        self._check_draw(B, rank, world, step)
         o = self._buffers(B)
         ops.mixture_sample(self.valid_off, self.episode_off, self.prompt_off, self.dataset_off, self.quota_off, seed, rank, world, step, self.Pmax,
                            o["dataset_index"], o["ep"], o["row"], o["prompt_off"])
@@ -254,12 +190,8 @@ class EpisodeMix:
         """The raw batch of (rank, step): RAW_BATCH_KEYS on the device plus dataset_index int32 [B] (which dataset each sample came
         from) and dataset_names.  Every rank passes the same seed.  The tensors are the mix's own buffers of this batch size: the next
         call with the same B overwrites them (in stream order), so consume - collate - a batch before drawing the next, or clone it."""
-        from . import ops
-        _, ep, row, off = self.sample_indices(B, seed, rank, world, step)
-        o = self._buffers(B)
-        ops.episode_gather(self.frames_u8, self.actions_raw, self.proprio_raw, self.episode_off, self.prompt_flat, self.prompt_off, ep, row, off,
-                           o["frames_u8"], o["actions_raw"], o["proprio_raw"], o["prompt_flat"], self.Pmax)
-        out = {k: o[k] for k in RAW_BATCH_KEYS}
-        out["dataset_index"] = o["dataset_index"]
+        ds, ep, row, off = self.sample_indices(B, seed, rank, world, step)
+        out = self.gather(ep, row, off, self._buffers(B))
+        out["dataset_index"] = ds
         out["dataset_names"] = self.names
         return out

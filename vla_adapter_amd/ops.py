@@ -1027,13 +1027,19 @@ def serve_gather_hidden(hs: torch.Tensor, hid_row: torch.Tensor, Np: int, T: int
 
 
 # ---- device-resident episodes (include/vla_episodes.h, csrc/episodes.hip) -----------------------------------------------------------
+def _chk_vectors(op: str, dev, *operands) -> None:
+    """The window pickers' operand check: every (tensor, dtype, length) is 1-D, contiguous, on ``dev``; a None tensor is skipped."""
+    for t, dt, n in operands:
+        assert t is None or (t.is_cuda and t.device == dev and t.dtype == dt and t.dim() == 1 and t.numel() == n and t.is_contiguous()), \
+            f"{op}: bad operand"
+
+
 def episode_sample(valid_off: torch.Tensor, episode_off: torch.Tensor, prompt_off: torch.Tensor, seed: int, rank: int, world: int, step: int,
                    Pmax: int, ep: torch.Tensor, row: torch.Tensor, out_off: torch.Tensor) -> None:
     """vla_episode_sample: the windows of the batch of (rank, step) -> ep int32 [B], row int64 [B], out_off int32 [B + 1] (all given)."""
     E, B, dev = valid_off.numel() - 1, ep.numel(), valid_off.device
-    for t, dt, n in ((valid_off, torch.int64, E + 1), (episode_off, torch.int64, E + 1), (prompt_off, torch.int32, E + 1), (ep, torch.int32, B),
-                     (row, torch.int64, B), (out_off, torch.int32, B + 1)):
-        assert t.is_cuda and t.device == dev and t.dtype == dt and t.dim() == 1 and t.numel() == n and t.is_contiguous(), "episode_sample: bad operand"
+    _chk_vectors("episode_sample", dev, (valid_off, torch.int64, E + 1), (episode_off, torch.int64, E + 1), (prompt_off, torch.int32, E + 1),
+                 (ep, torch.int32, B), (row, torch.int64, B), (out_off, torch.int32, B + 1))
     N.check(_lib().vla_episode_sample(_st(), _p(valid_off), _p(episode_off), _p(prompt_off), E, int(seed) & (2 ** 64 - 1), int(rank), int(world),
                                       int(step), B, int(Pmax), _p(ep), _p(row), _p(out_off)), "episode_sample")
 
@@ -1067,10 +1073,9 @@ def mixture_sample(valid_off: torch.Tensor, episode_off: torch.Tensor, prompt_of
     """vla_mixture_sample: the windows of the batch of (rank, step) -> ds int32 [B], ep int32 [B], row int64 [B], out_off int32 [B + 1]
     (all given)."""
     E, D, B, dev = valid_off.numel() - 1, dataset_off.numel() - 1, ep.numel(), valid_off.device
-    for t, dt, n in ((valid_off, torch.int64, E + 1), (episode_off, torch.int64, E + 1), (prompt_off, torch.int32, E + 1),
-                     (dataset_off, torch.int32, D + 1), (quota_off, torch.int64, D + 1), (ds, torch.int32, B), (ep, torch.int32, B),
-                     (row, torch.int64, B), (out_off, torch.int32, B + 1)):
-        assert t.is_cuda and t.device == dev and t.dtype == dt and t.dim() == 1 and t.numel() == n and t.is_contiguous(), "mixture_sample: bad operand"
+    _chk_vectors("mixture_sample", dev, (valid_off, torch.int64, E + 1), (episode_off, torch.int64, E + 1), (prompt_off, torch.int32, E + 1),
+                 (dataset_off, torch.int32, D + 1), (quota_off, torch.int64, D + 1), (ds, torch.int32, B), (ep, torch.int32, B),
+                 (row, torch.int64, B), (out_off, torch.int32, B + 1))
     N.check(_lib().vla_mixture_sample(_st(), _p(valid_off), _p(episode_off), _p(prompt_off), _p(dataset_off), _p(quota_off), E, D,
                                       int(seed) & (2 ** 64 - 1), int(rank), int(world), int(step), B, int(Pmax), _p(ds), _p(ep), _p(row),
                                       _p(out_off)), "mixture_sample")
@@ -1102,11 +1107,9 @@ def heldout_sweep(val_off: torch.Tensor, episode_off: torch.Tensor, prompt_off: 
     [B], out_off int32 [B + 1], valid u8 [B] (all given).  dataset_off int32 [D + 1], or None for a single dataset."""
     E, B, dev = val_off.numel() - 1, ep.numel(), val_off.device
     D = 1 if dataset_off is None else dataset_off.numel() - 1
-    for t, dt, n in ((val_off, torch.int64, E + 1), (episode_off, torch.int64, E + 1), (prompt_off, torch.int32, E + 1),
-                     (dataset_off, torch.int32, D + 1), (ds, torch.int32, B), (ep, torch.int32, B), (row, torch.int64, B),
-                     (out_off, torch.int32, B + 1), (valid, torch.uint8, B)):
-        assert t is None or (t.is_cuda and t.device == dev and t.dtype == dt and t.dim() == 1 and t.numel() == n and t.is_contiguous()), \
-            "heldout_sweep: bad operand"
+    _chk_vectors("heldout_sweep", dev, (val_off, torch.int64, E + 1), (episode_off, torch.int64, E + 1), (prompt_off, torch.int32, E + 1),
+                 (dataset_off, torch.int32, D + 1), (ds, torch.int32, B), (ep, torch.int32, B), (row, torch.int64, B),
+                 (out_off, torch.int32, B + 1), (valid, torch.uint8, B))
     N.check(_lib().vla_heldout_sweep(_st(), _p(val_off), _p(episode_off), _p(prompt_off), _p(dataset_off), E, D, int(rank), int(world),
                                      int(batch_j), int(stride), B, int(Pmax), _p(ds), _p(ep), _p(row), _p(out_off), _p(valid)), "heldout_sweep")
 
