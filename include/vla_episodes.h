@@ -46,7 +46,8 @@ int vla_episode_sample(void* stream, const long long* valid_off, const long long
  *   out_proprio f32   [B, Pd]          = proprio[r]
  *   out_prompt  int64 [B * Pmax]       = the chosen prompts back to back at out_off[b], 0 behind out_off[B]
  * Prompt offsets of the store are clamped into [0, n_flat], those of the batch into [0, B * Pmax]; a destination range longer than its
- * prompt is zero-filled: no table makes the kernel read or write outside.  out_prompt may be NULL when Pmax == 0. */
+ * prompt is zero-filled: no table makes the kernel read or write outside.  out_prompt may be NULL when Pmax == 0.  row_bytes == 0 (a
+ * store that keeps its frames in another form, vla_jpeg.h): no frame is copied, frames and out_frames may be NULL. */
 int vla_episode_gather(void* stream, const unsigned char* frames, const float* actions, const float* proprio,
                        const long long* episode_off, const long long* prompt_flat, const int* prompt_off, const int* ep,
                        const long long* row, const int* out_off, unsigned char* out_frames, float* out_actions, float* out_proprio,

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "permute.h"                            // feistel4 / permute_index: shared with mixture.hip
 #include "windows.h"                            // EPISODE_STREAM, clampll, last_not_above, emit_windows: shared with mixture.hip, heldout.hip
+#include "episode_row.h"                        // episode_row: the row a sample reads, shared with jpeg.hip
 #include "../../include/vla_episodes.h"
 
 namespace {
@@ -53,10 +54,9 @@ episode_gather_kernel(const V* __restrict__ frames, const float* __restrict__ ac
                       float* __restrict__ out_proprio, long long* __restrict__ out_prompt, int B, int E, long long T, long long units,
                       int chunk, int A, int Pd, long long n_flat, int Pmax, int nbx) {
   const int b = blockIdx.y, tid = threadIdx.x;
-  const int e = min(max(ep[b], 0), E - 1);
-  const long long e0 = clampll(episode_off[e], 0ll, T - 1);
-  const long long e1 = clampll(episode_off[e + 1], e0 + 1, T);
-  const long long r = clampll(row[b], e0, e1 - 1);
+  const EpisodeRow w = episode_row(episode_off, ep, row, b, E, T);
+  const int e = w.e;
+  const long long e1 = w.e1, r = w.r;
   if ((int)blockIdx.x < nbx) {
     const V* __restrict__ src = frames + r * units;
     V* __restrict__ dst = out_frames + (long long)b * units;
@@ -112,9 +112,11 @@ extern "C" int vla_episode_gather(void* stream, const unsigned char* frames, con
                                   const long long* row, const int* out_off, unsigned char* out_frames, float* out_actions,
                                   float* out_proprio, long long* out_prompt, int B, int E, long long T, long long row_bytes, int chunk,
                                   int A, int Pd, long long n_flat, int Pmax) {
-  VLA_REQUIRE(frames && actions && proprio && episode_off && prompt_off && ep && row && out_off, "episode_gather: null input pointer");
-  VLA_REQUIRE(out_frames && out_actions && out_proprio, "episode_gather: null output pointer");
-  VLA_REQUIRE(B >= 1 && B <= 65535 && E >= 1 && T >= 1 && row_bytes >= 1, "episode_gather: 1 <= B <= 65535, E, T, row_bytes >= 1");
+  VLA_REQUIRE(actions && proprio && episode_off && prompt_off && ep && row && out_off, "episode_gather: null input pointer");
+  VLA_REQUIRE(out_actions && out_proprio, "episode_gather: null output pointer");
+  VLA_REQUIRE(B >= 1 && B <= 65535 && E >= 1 && T >= 1 && row_bytes >= 0, "episode_gather: 1 <= B <= 65535, E, T >= 1, row_bytes >= 0");
+  // row_bytes == 0: a store whose frames are not raw pixels (JPEG: vla_jpeg_decode_rows fills the frames) - no frame workgroup runs
+  VLA_REQUIRE((frames && out_frames) || row_bytes == 0, "episode_gather: null frames / out_frames with row_bytes > 0");
   VLA_REQUIRE(chunk >= 1 && A >= 1 && Pd >= 1 && n_flat >= 0 && Pmax >= 0, "episode_gather: chunk, A, Pd >= 1, n_flat, Pmax >= 0");
   VLA_REQUIRE((long long)chunk * A <= 0x7fffffffll && (long long)B * Pmax <= 0x7fffffffll, "episode_gather: chunk * A and B * Pmax must fit int32");
   VLA_REQUIRE(out_prompt || Pmax == 0, "episode_gather: null out_prompt with Pmax > 0");

@@ -20,6 +20,10 @@ An episode file is a ``.pt`` dict, or a directory of them (the shards are concat
   dataset_name  str, optional
   action_mask   bool    [A], optional         the reference's action_normalization_mask
 
+In place of ``frames_u8`` a file may carry its frames as JPEG files - ``frames_jpeg``, ``frame_off``, ``frame_shape`` (jpeg_store.py) -
+which ``gather`` then decodes on the device, batch by batch, into the same ``frames_u8`` buffer; a dict carries
+exactly one of the two forms, and the shards of a dataset and the datasets of a mix all the same one.
+
 The sampling rule is stated here in plain Python - ``sample_position``, ``permute_index``, ``locate`` - and is the specification the
 kernel is tested against, bit for bit.
 
@@ -41,6 +45,7 @@ import torch
 
 from .constants import NUM_ACTIONS_CHUNK
 from .finetune import RAW_BATCH_KEYS                # what sample() returns: the raw batch finetune.batch_stream collates
+from .jpeg_store import JPEG_KEYS, STATUS_TEXT, JpegFrames, check_jpeg_shard, concat_jpeg, storage_form
 
 EPISODE_KEYS = ("frames_u8", "actions_raw", "proprio_raw", "episode_off", "prompt_flat", "prompt_off")
 EPISODE_STREAM = 0xE9150DE5A391E        # csrc/windows.h: keeps the shuffle apart from the augmentation's and the collator's draws
@@ -151,13 +156,19 @@ def _check_shard(d: dict, where: str) -> None:
     """ValueError naming the key for every table that does not fit the others."""
     if not isinstance(d, dict):
         raise ValueError(f"{where}: an episode file is a dict of {EPISODE_KEYS}")
-    for k in EPISODE_KEYS:
+    jpeg = storage_form(d, where) == "jpeg"             # (ValueError for both forms in one dict; neither: frames_u8 is missing, below)
+    for k in EPISODE_KEYS[1:] if jpeg else EPISODE_KEYS:
         if k not in d or not isinstance(d[k], torch.Tensor):
-            raise ValueError(f"{where}: {k} is missing (an episode file carries {EPISODE_KEYS})")
-    fr, act, pr, eo, pf, po = (d[k] for k in EPISODE_KEYS)
-    if fr.dtype != torch.uint8 or fr.dim() != 5 or fr.shape[-1] != 3 or fr.shape[0] < 1:
-        raise ValueError(f"{where}: frames_u8 must be uint8 [T, n_img, H, W, 3] with T >= 1, got {fr.dtype} {tuple(fr.shape)}")
-    T = fr.shape[0]
+            raise ValueError(f"{where}: {k} is missing (an episode file carries {EPISODE_KEYS}, or {JPEG_KEYS} in place of frames_u8)")
+    act, pr, eo, pf, po = (d[k] for k in EPISODE_KEYS[1:])
+    if jpeg:
+        T = act.shape[0] if act.dim() == 2 else 0
+        check_jpeg_shard(d, T, where)
+    else:
+        fr = d["frames_u8"]
+        if fr.dtype != torch.uint8 or fr.dim() != 5 or fr.shape[-1] != 3 or fr.shape[0] < 1:
+            raise ValueError(f"{where}: frames_u8 must be uint8 [T, n_img, H, W, 3] with T >= 1, got {fr.dtype} {tuple(fr.shape)}")
+        T = fr.shape[0]
     if act.dtype != torch.float32 or act.dim() != 2 or act.shape[0] != T or act.shape[1] < 1:
         raise ValueError(f"{where}: actions_raw must be float32 [T = {T}, A], got {act.dtype} {tuple(act.shape)}")
     if pr.dtype != torch.float32 or pr.dim() != 2 or pr.shape[0] != T or pr.shape[1] < 1:
@@ -179,6 +190,17 @@ def _check_shard(d: dict, where: str) -> None:
             raise ValueError(f"{where}: action_mask must be bool [A = {act.shape[1]}], got {m.dtype} {tuple(m.shape)}")
     if "dataset_name" in d and not isinstance(d["dataset_name"], str):
         raise ValueError(f"{where}: dataset_name must be a str")
+
+
+def check_one_form(tables: Sequence[dict], names: Sequence[str]) -> bool:
+    """True when every one of the tables keeps its frames as JPEG files, False when every one keeps raw pixels; ValueError naming
+    the first that differs from the first (shards of a dataset, datasets of a mix: mixed storage is not supported)."""
+    forms = [storage_form(d, n) for d, n in zip(tables, names)]
+    for f, n in zip(forms[1:], names[1:]):
+        if f != forms[0]:
+            raise ValueError(f"{n}: stores its frames as {f}, {names[0]} as {forms[0]}: one run keeps all its frames in one form "
+                             f"(frames_u8, or {JPEG_KEYS})")
+    return forms[0] == "jpeg"
 
 
 def valid_offsets(episode_off: torch.Tensor, chunk: int) -> torch.Tensor:
@@ -243,6 +265,7 @@ class EpisodeTables:
         wheres = list(wheres or names)
         for d, w in zip(tables, wheres):
             _check_shard(d, w)
+        check_one_form(tables, wheres)
         self.device, self.chunk, self.names, self.D = device, int(chunk), tuple(names), len(tables)
         self.action_masks = [torch.as_tensor(d["action_mask"]).tolist() if "action_mask" in d else None for d in tables]
         ranges, self._stats = [0], {}                  # dataset d holds the episodes [ranges[d], ranges[d + 1])
@@ -274,15 +297,19 @@ class EpisodeTables:
         self.N = int(valid[-1])
         self.Nv = int(val[-1]) if val is not None else 0
         self.A, self.Pd = int(act.shape[1]), int(pr.shape[1])
-        self.frame_shape = tuple(all_["frames_u8"].shape[1:])
+        # the frames: raw pixels (frames_u8), or JPEG files that gather() decodes (jpeg: their bytes and tables on the device)
+        self.jpeg = JpegFrames(all_, device, wheres[0] if self.D == 1 else "episode mix") if "frames_jpeg" in all_ else None
+        self.frame_shape = (self.jpeg.n_img, self.jpeg.H, self.jpeg.W, 3) if self.jpeg else tuple(all_["frames_u8"].shape[1:])
         self.row_bytes = int(np.prod(self.frame_shape))
         self.Pmax = int(po.diff().max())
         self.valid_off_host, self.val_off_host = valid, val
-        self.frames_u8, self.actions_raw, self.proprio_raw = self._upload(all_["frames_u8"]), self._upload(act), self._upload(pr)
+        self.frames_u8 = None if self.jpeg else self._upload(all_["frames_u8"])
+        self.actions_raw, self.proprio_raw = self._upload(act), self._upload(pr)
         self.episode_off, self.valid_off = self._upload(eo), self._upload(valid)
         self.val_off = self._upload(val) if val is not None else None
         self.prompt_flat, self.prompt_off = self._upload(all_["prompt_flat"]), self._upload(po)
         self._out: Dict[int, dict] = {}
+        self._no_frames, self.decode_status = None, None   # (JPEG: the gather's zero-length frame table; the last batch's status)
 
     def _upload(self, t: torch.Tensor) -> torch.Tensor:
         return t.to(self.device).contiguous()
@@ -303,6 +330,8 @@ class EpisodeTables:
                      prompt_flat=e(B * self.Pmax, dtype=torch.int64, device=dev), prompt_off=e(B + 1, dtype=torch.int32, device=dev))
             if self.mixed:
                 o["dataset_index"] = e(B, dtype=torch.int32, device=dev)
+            if self.jpeg:                   # the decode's workspace and status of this batch size (gather takes them from there: the
+                self.jpeg.buffers(B)        # held-out sweep gathers into buffers of its own)
             self._out[B] = o
         return self._out[B]
 
@@ -318,9 +347,50 @@ class EpisodeTables:
         """vla_episode_gather of the windows (ep, row, prompt_off) - a sampler's or the held-out sweep's - into the frames_u8 /
         actions_raw / proprio_raw / prompt_flat of ``into``; -> the raw batch, RAW_BATCH_KEYS on the device."""
         from . import ops
-        ops.episode_gather(self.frames_u8, self.actions_raw, self.proprio_raw, self.episode_off, self.prompt_flat, self.prompt_off, ep, row,
-                           prompt_off, into["frames_u8"], into["actions_raw"], into["proprio_raw"], into["prompt_flat"], self.Pmax)
+        if self.jpeg:                       # actions, proprio and prompts by the same gather over zero-length frame rows, then the frames
+            if self._no_frames is None:
+                self._no_frames = torch.empty(self.T, 0, dtype=torch.uint8, device=self.device)
+            buf = self.jpeg.buffers(int(ep.numel()))
+            frames, out_frames = self._no_frames, buf["no_frames"]
+        else:
+            frames, out_frames = self.frames_u8, into["frames_u8"]
+        ops.episode_gather(frames, self.actions_raw, self.proprio_raw, self.episode_off, self.prompt_flat, self.prompt_off, ep, row,
+                           prompt_off, out_frames, into["actions_raw"], into["proprio_raw"], into["prompt_flat"], self.Pmax)
+        if self.jpeg:
+            self.decode_status = self.jpeg.decode(self.episode_off, self.T, ep, row, into["frames_u8"], buf)
         return {k: prompt_off if k == "prompt_off" else into[k] for k in RAW_BATCH_KEYS}
+
+    def bad_segments(self) -> torch.Tensor:
+        """f32 [1] on the device: how many segments of the last gathered batch did not decode (no read-back here)."""
+        return (self.decode_status != 0).sum().to(torch.float32).view(1)
+
+    def verify_frames(self, batch: int = 64) -> int:
+        """Decode every frame of a JPEG store once, ``batch`` steps at a time, and raise a ValueError that names the first frame with a
+        segment that did not decode (one read-back, behind the last batch); -> the number of frames decoded.  0 for a raw store."""
+        if not self.jpeg:
+            return 0
+        j, dev = self.jpeg, self.device
+        rows = torch.arange(self.T, dtype=torch.int64, device=dev)
+        eps = (torch.bucketize(rows, self.episode_off, right=True) - 1).clamp_(0, self.E - 1).to(torch.int32)
+        B = min(int(batch), self.T)
+        buf = j.buffers(B)
+        frames = torch.empty((B,) + self.frame_shape, dtype=torch.uint8, device=dev)
+        first = torch.full((1,), self.T * j.n_img * j.max_seg, dtype=torch.int64, device=dev)       # smallest (frame, segment) with a status
+        code = torch.zeros(1, dtype=torch.uint8, device=dev)
+        for t0 in range(0, self.T, B):
+            t0 = min(t0, self.T - B)                                                                # (the last batch overlaps the one before)
+            st = j.decode(self.episode_off, self.T, eps[t0:t0 + B], rows[t0:t0 + B], frames, buf).view(-1)
+            bad = st != 0
+            idx = torch.where(bad, torch.arange(st.numel(), device=dev) + t0 * j.n_img * j.max_seg, first).min().view(1)
+            hit = idx < first
+            code = torch.where(hit, st[(idx - t0 * j.n_img * j.max_seg).clamp(0, st.numel() - 1)], code)
+            first = torch.minimum(first, idx)
+        at, c = int(first), int(code)                                                               # the one read-back
+        if at < self.T * j.n_img * j.max_seg:
+            frame, seg = divmod(at, j.max_seg)
+            raise ValueError(f"verify_frames: frame {frame} (step {frame // j.n_img}, image {frame % j.n_img}), segment {seg}: "
+                             f"{STATUS_TEXT.get(c, f'status {c}')}")
+        return self.T * j.n_img
 
 
 class EpisodeStore(EpisodeTables):
@@ -389,8 +459,9 @@ def concat_shards(shards: List[dict], names: Optional[List[str]] = None, device=
     frames are assembled on ``device`` shard by shard (the host never holds a second copy of them)."""
     names = names or [f"shard {i}" for i in range(len(shards))]
     first = shards[0]
+    jpeg = check_one_form(shards, names)
     for d, n in zip(shards[1:], names[1:]):
-        for k in ("frames_u8", "actions_raw", "proprio_raw"):
+        for k in ("actions_raw", "proprio_raw") if jpeg else ("frames_u8", "actions_raw", "proprio_raw"):
             if d[k].shape[1:] != first[k].shape[1:]:
                 raise ValueError(f"{n}: {k} has rows of shape {tuple(d[k].shape[1:])}, {names[0]} of {tuple(first[k].shape[1:])}")
         if d.get("dataset_name") != first.get("dataset_name"):
@@ -400,13 +471,17 @@ def concat_shards(shards: List[dict], names: Optional[List[str]] = None, device=
     if len(shards) == 1:
         return first
     out = {k: torch.cat([d[k] for d in shards]) for k in ("actions_raw", "proprio_raw", "prompt_flat")}
-    out["frames_u8"] = torch.empty((out["actions_raw"].shape[0],) + tuple(first["frames_u8"].shape[1:]), dtype=torch.uint8, device=device)
+    if jpeg:
+        out.update(concat_jpeg(shards, names, device))
+    else:
+        out["frames_u8"] = torch.empty((out["actions_raw"].shape[0],) + tuple(first["frames_u8"].shape[1:]), dtype=torch.uint8, device=device)
     eo, po, t0, p0 = [first["episode_off"][:1]], [first["prompt_off"][:1].to(torch.int64)], 0, 0
     for d in shards:
-        out["frames_u8"][t0:t0 + d["frames_u8"].shape[0]].copy_(d["frames_u8"])
+        if not jpeg:
+            out["frames_u8"][t0:t0 + d["frames_u8"].shape[0]].copy_(d["frames_u8"])
         eo.append(d["episode_off"][1:] + t0)
         po.append(d["prompt_off"][1:].to(torch.int64) + p0)
-        t0 += d["frames_u8"].shape[0]
+        t0 += d["actions_raw"].shape[0]
         p0 += d["prompt_flat"].numel()
     if p0 > 2 ** 31 - 1:
         raise ValueError(f"prompt_off: {p0} prompt ids in all do not fit its int32 offsets")

@@ -131,6 +131,8 @@ class FinetuneConfig:
                                           # reference's: weights only, everything else from zero) is unchanged
     log_state_digest: bool = False        # every logged step also carries state_digest: the 64-bit digests (ops.state_digest) of data, m and v of
                                           # every flat buffer as hex strings, read in the log line's own read-back
+    verify_frames: bool = False           # --episode_file / --episode_mix whose frames are JPEG files (jpeg_store.py): decode every frame once at
+                                          # load and refuse the run, naming the frame, when a scan does not decode (DESIGN.md section 18 has the cost)
     # fmt: on
 
 
@@ -638,6 +640,8 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
                 info["dataset_statistics"] = norm_stats
         elif src.mixed:
             mixture_stats(json.load(open(cfg.dataset_statistics_file)), src.names)        # a missing entry is refused before the first step
+        if cfg.verify_frames:                     # (a raw store has nothing to verify)
+            src.verify_frames()
         if info is not None:
             info["store"] = src                   # (the held-out sweep walks the same device-resident tables)
         if src.mixed:
@@ -817,6 +821,10 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None, o
             # token-CE: the four metrics of the reference's trainer (base_strategy.py:350-356; this rank's batch, as there) ride the
             # loss's read-back - one copy, one sync
             parts = [loss3] + ([trainer.ce_metrics] if ce else [])
+            store = info.get("store")
+            jpeg = store is not None and store.jpeg is not None and store.decode_status is not None
+            if jpeg:    # JPEG frames: how many segments of the batch drawn last did not decode rides the same read-back
+                parts.append(store.bad_segments())
             if clip:    # the norm of this step's update rides the same read-back (the captured adapter step leaves its update pending: apply it)
                 eng.flush()
                 parts.append((trainer or eng).grad_norm.view(1))
@@ -827,7 +835,7 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None, o
             if cfg.log_state_digest:
                 nd = parts[-1].numel()
                 l, digests = l[:-nd], owner.state_digest_dict(TS.from_limbs(l[-nd:]))
-            l, tm, gn = l[:3], l[3:7] if ce else [], l[-1]
+            l, tm, gn, bad = l[:3], l[3:7] if ce else [], l[-1], l[7 if ce else 3] if jpeg else None
             if not all(x == x for x in l):
                 raise FloatingPointError(f"non-finite loss at step {log_step}: {l} (a captured step replayed on a batch whose action "
                                          "block starts before the frozen live-row window poisons the loss: --conservative_rows true)")
@@ -837,6 +845,8 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None, o
                 log[-1].update(zip(TOKEN_METRIC_NAMES, tm))
             if clip:
                 log[-1]["grad_norm"] = gn
+            if jpeg:
+                log[-1]["jpeg_bad_segments"] = int(bad)
             if cfg.log_state_digest:
                 log[-1]["state_digest"] = digests
             if rank == 0:

@@ -1066,6 +1066,38 @@ def episode_gather(frames: torch.Tensor, actions: torch.Tensor, proprio: torch.T
             "episode_gather")
 
 
+# ---- JPEG frames of a device-resident store (include/vla_jpeg.h, csrc/jpeg.hip) --------------------------------------------------------
+def jpeg_workspace_bytes(slots: int, H: int, W: int, h2v2: int) -> int:
+    """vla_jpeg_workspace_bytes: what vla_jpeg_decode_rows needs for ``slots`` = B * n_img images (host arithmetic)."""
+    n = _lib().vla_jpeg_workspace_bytes(int(slots), int(H), int(W), int(h2v2))
+    if n < 0:
+        raise ValueError(f"jpeg_workspace_bytes: {slots} images of {H} x {W} (sampling flag {h2v2}) are refused: H and W are multiples of 16")
+    return n
+
+
+def jpeg_decode_rows(data: torch.Tensor, img_seg: torch.Tensor, seg_tab: torch.Tensor, img_tab: torch.Tensor, qt_pool: torch.Tensor,
+                     ht_pool: torch.Tensor, episode_off: torch.Tensor, T: int, ep: torch.Tensor, row: torch.Tensor, n_img: int, H: int, W: int,
+                     h2v2: int, max_seg: int, mapping: int, workspace: torch.Tensor, out_frames: torch.Tensor, status: torch.Tensor) -> None:
+    """vla_jpeg_decode_rows: the store's bytes and tables (jpeg_store.JpegFrames) + the sampler's index vectors -> out_frames u8
+    [B, n_img, H, W, 3] and status u8 [B, n_img, max_seg] (both given; out_frames may be strided between images)."""
+    B, E, dev, n_all = ep.numel(), episode_off.numel() - 1, data.device, int(T) * int(n_img)
+    for t in (data, img_seg, seg_tab, img_tab, qt_pool, ht_pool, episode_off, ep, row, workspace, status):
+        assert t.is_cuda and t.device == dev and t.is_contiguous(), "jpeg_decode_rows: operands are contiguous tensors on one device"
+    assert data.dtype == torch.uint8 and data.dim() == 1 and workspace.dtype == torch.uint8
+    assert img_seg.dtype == torch.int64 and img_seg.numel() == n_all + 1 and seg_tab.dtype == torch.int64 and seg_tab.dim() == 2 and seg_tab.shape[1] == 4
+    assert img_tab.dtype == torch.int32 and tuple(img_tab.shape) == (n_all, 12)
+    assert qt_pool.dtype == torch.int16 and qt_pool.dim() == 2 and qt_pool.shape[1] == 64 and ht_pool.dtype == torch.int32 and ht_pool.dim() == 2 and ht_pool.shape[1] == 548
+    assert episode_off.dtype == torch.int64 and ep.dtype == torch.int32 and row.dtype == torch.int64 and row.numel() == B
+    assert status.dtype == torch.uint8 and tuple(status.shape) == (B, n_img, max_seg)
+    assert out_frames.is_cuda and out_frames.device == dev and out_frames.dtype == torch.uint8 and tuple(out_frames.shape) == (B, n_img, H, W, 3)
+    image = out_frames.stride(1) if n_img > 1 else (out_frames.stride(0) if B > 1 else H * W * 3)          # elements between two images
+    assert out_frames[0, 0].is_contiguous() and (B == 1 or out_frames.stride(0) == n_img * image), "jpeg_decode_rows: out_frames: contiguous images, one stride between them"
+    N.check(_lib().vla_jpeg_decode_rows(_st(), _p(data), data.numel(), _p(img_seg), _p(seg_tab), seg_tab.shape[0], _p(img_tab), _p(qt_pool),
+                                        qt_pool.shape[0], _p(ht_pool), ht_pool.shape[0], _p(episode_off), E, int(T), _p(ep), _p(row), B, int(n_img),
+                                        int(H), int(W), int(h2v2), int(max_seg), int(mapping), _p(workspace), workspace.numel(), _p(out_frames),
+                                        int(image), _p(status)), "jpeg_decode_rows")
+
+
 # ---- a weighted mixture of device-resident datasets (include/vla_mixture.h, csrc/mixture.hip) ----------------------------------------
 def mixture_sample(valid_off: torch.Tensor, episode_off: torch.Tensor, prompt_off: torch.Tensor, dataset_off: torch.Tensor,
                    quota_off: torch.Tensor, seed: int, rank: int, world: int, step: int, Pmax: int, ds: torch.Tensor, ep: torch.Tensor,
