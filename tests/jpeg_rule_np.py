@@ -25,8 +25,18 @@ class Bits:
     """The bits of an entropy-coded segment, 0xFF 0x00 unstuffed."""
 
     def __init__(self, data: bytes):
+        self.data = data
         self.bits = "".join(f"{b:08b}" for b in data.replace(b"\xff\x00", b"\xff"))
         self.pos = 0
+        self.by_length = [0] * 17          # symbols decoded so far, by the length of their code
+
+    def bytes_consumed(self) -> int:
+        """How many bytes of the segment, stuffed zeros included, hold the bits taken so far."""
+        left, i = (self.pos + 7) // 8, 0
+        while left:
+            i += 2 if self.data[i] == 0xFF else 1
+            left -= 1
+        return i
 
     def take(self, n: int) -> int:
         if n == 0:
@@ -42,6 +52,7 @@ class Bits:
         for l in range(1, 17):
             code = (code << 1) | self.take(1)
             if (l, code) in table:
+                self.by_length[l] += 1
                 return table[(l, code)]
         raise ValueError("a code that is in no table")
 
@@ -56,6 +67,8 @@ def parse(data: bytes) -> dict:
     out, pos = dict(qt={}, ht={}, dri=0), 2
     while True:
         assert data[pos] == 0xFF
+        while data[pos + 1] == 0xFF:             # fill bytes in front of a marker
+            pos += 1
         m, L = data[pos + 1], (data[pos + 2] << 8) | data[pos + 3]
         seg = data[pos + 4:pos + 2 + L]
         if m == 0xDB:
@@ -82,14 +95,17 @@ def parse(data: bytes) -> dict:
             assert m not in (0xC1, 0xC2, 0xC3, 0xC9, 0xCA, 0xCB), "baseline files only"
         pos += 2 + L
     segs, start, i = [], pos, pos
-    while True:                                  # 0xFF 0x00 is data, 0xFF RSTn splits, any other marker (EOI) ends the scan
-        i = data.index(b"\xff", i)
-        nxt = data[i + 1]
+    while True:                                  # 0xFF 0x00 is data, 0xFF RSTn splits, any other marker (EOI) ends the scan;
+        i = j = data.index(b"\xff", i)           # a marker may have 0xFF fill bytes in front of it
+        while data[j + 1] == 0xFF:
+            j += 1
+        nxt = data[j + 1]
         if nxt == 0:
+            assert j == i, "fill bytes in front of a stuffed byte"
             i += 2
         elif 0xD0 <= nxt <= 0xD7:
             segs.append(data[start:i])
-            start = i = i + 2
+            start = i = j + 2
         else:
             segs.append(data[start:i])
             break
@@ -143,8 +159,11 @@ def ycc_to_rgb(y, cb, cr):
     return np.clip(np.stack([r, g, b], -1), 0, 255).astype(np.uint8)
 
 
-def decode(data: bytes) -> np.ndarray:
-    """A baseline 4:2:0 or 4:4:4 file whose sides are multiples of 16 -> uint8 [H, W, 3]."""
+def decode(data: bytes, stats: dict = None) -> np.ndarray:
+    """A baseline 4:2:0 or 4:4:4 file whose sides are multiples of 16 -> uint8 [H, W, 3].  ``stats``, when given, receives what only
+    a decode can count: "by_length" [17], the symbols decoded by the length of their code, and "consumed", per segment the bytes that
+    hold the bits its MCUs took, "blocks" [(component, [the DC symbol, the AC symbols ...])] in coding order, and "quantised", the
+    coefficients before dequantisation."""
     p = parse(data)
     H, W, comps = p["H"], p["W"], p["comps"]
     h2v2 = (comps[0][1], comps[0][2]) == (2, 2)
@@ -161,11 +180,13 @@ def decode(data: bytes) -> np.ndarray:
                 q, (td, ta) = p["qt"][comps[c][3]], p["scan"][c]
                 blk = planes[c][(2 * my + dy, 2 * mx + dx) if (h2v2 and c == 0) else (my, mx)]
                 s = bits.symbol(p["ht"][td])
+                syms = [s]
                 pred[c] += extend(bits.take(s), s)
                 blk[0] = pred[c] * q[0]
                 k = 1
                 while k < 64:
                     rs = bits.symbol(p["ht"][0x10 | ta])
+                    syms.append(rs)
                     r, s = rs >> 4, rs & 15
                     if s:
                         k += r
@@ -175,6 +196,13 @@ def decode(data: bytes) -> np.ndarray:
                     else:
                         break
                     k += 1
+                if stats is not None:
+                    stats.setdefault("blocks", []).append((c, syms))
+        if stats is not None:
+            stats.setdefault("consumed", []).append(bits.bytes_consumed())
+            stats["by_length"] = [a + b for a, b in zip(stats.get("by_length", [0] * 17), bits.by_length)]
+    if stats is not None:                        # the quantised coefficients as the file codes them: [Y, Cb, Cr], zigzag order
+        stats["quantised"] = [pl[..., ZIGZAG] // p["qt"][comps[c][3]] for c, pl in enumerate(planes)]
     pix = []
     for pl in planes:
         bh, bw = pl.shape[:2]

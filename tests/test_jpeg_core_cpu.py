@@ -39,6 +39,20 @@ def test_the_core_matches_pillow_on_224_frames(exe, tmp_path):
         assert np.array_equal(px[i], JC.pillow_decode(f))
 
 
+CRAFTED_STORES = {**JC.crafted_stores(JC.crafted_corpus()), **JC.crafted_stores(JC.long_corpus())}
+
+
+@pytest.mark.parametrize("sanitized", [False, True], ids=["plain", "sanitized"])
+@pytest.mark.parametrize("key", sorted(CRAFTED_STORES), ids=lambda k: f"{k[0]}x{k[1]}-{'420' if k[2] else '444'}")
+def test_the_core_matches_pillow_on_the_crafted_corpus(exe, exe_san, tmp_path, key, sanitized):
+    H, W, h2v2 = key
+    cases = CRAFTED_STORES[key]
+    px, st, ix = JC.run_core(exe_san if sanitized else exe, tmp_path, JC.pack([c.data for c in cases], 1, H, W), "crafted")
+    assert ix.h2v2 == h2v2 and ix.N == len(cases) and not st.any(), "every segment of a crafted file decodes"
+    for i, c in enumerate(cases):
+        assert np.array_equal(px[i], c.pixels), f"{c.name}: {(px[i] != c.pixels).sum()} of {c.pixels.size} values differ from Pillow's"
+
+
 @pytest.mark.parametrize("shape", sorted(JC.corrupt_corpus()), ids=lambda s: f"{s[0]}x{s[1]}")
 def test_the_corrupt_corpus_under_the_sanitizers(exe_san, exe, tmp_path, shape):
     H, W = shape

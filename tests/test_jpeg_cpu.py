@@ -1,7 +1,8 @@
 """CPU checks of the JPEG frame store (vla_adapter_amd/jpeg_store.py, include/vla_jpeg.h): the written-down decode rule
-(tests/jpeg_rule_np.py) against Pillow, bit for bit, on the matrix of tests/jpeg_cases.py; the parser - its pools, its segment
-tables, its refusals, each naming the frame; the two storage forms of an episode dict; concat_shards on JPEG shards; the seventh
-header against its signature table and the built library; the flag."""
+(tests/jpeg_rule_np.py) against Pillow, bit for bit, on the matrix of tests/jpeg_cases.py and on its crafted corpus - files no run of
+Pillow's encoder writes, from the coefficient-level writer tests/jpeg_writer.py, which is pinned here too; the parser - its pools, its
+segment tables, its refusals, each naming the frame, RGB-coded files among them; fill bytes in front of RSTn; the two storage forms
+of an episode dict; concat_shards on JPEG shards; the seventh header against its signature table and the built library; the flag."""
 import dataclasses
 import os
 import re
@@ -12,6 +13,7 @@ import torch
 
 from tests import jpeg_cases as JC
 from tests import jpeg_rule_np as R
+from tests import jpeg_writer as JW
 from tests.test_episodes_cpu import make_tables
 from vla_adapter_amd import episodes as EP
 from vla_adapter_amd import jpeg_store as JS
@@ -45,7 +47,133 @@ def test_the_rule_on_a_224_frame():
     assert np.array_equal(R.decode(data), JC.pillow_decode(data))
 
 
+# ---------------------------------------------------------------------------------------------------------------- the crafted corpus
+CRAFTED = JC.crafted_corpus() + JC.long_corpus()
+
+
+def test_the_writer_round_trips_pillows_files():
+    """A Pillow file's coefficients, read by the rule's entropy decode and written again with the file's own tables: the same
+    entropy-coded bytes - codes, value bits, stuffing, padding and restart markers are T.81's - and the same pixels from Pillow."""
+    for kw in (dict(quality=90, subsampling=2), dict(quality=85, subsampling=0, optimize=True), dict(quality=90, subsampling=2, restart_marker_blocks=5),
+               dict(quality=80, subsampling=0, restart_marker_rows=1)):
+        data = JC.encode(JC.content("ramp", 32, 48) // 2 + JC.content("noise", 32, 48) // 16 + 50, **kw)
+        st, p = {}, R.parse(data)
+        R.decode(data, st)
+        ids = sorted({t for pair in p["scan"] for t in pair})
+        spec = JW.Spec(H=32, W=48, h2v2=kw["subsampling"] == 2, qtables={i: [int(q) for q in t] for i, t in p["qt"].items()},
+                       dc_tables={i: JW.tables_from_codes(p["ht"][i]) for i in ids}, ac_tables={i: JW.tables_from_codes(p["ht"][0x10 | i]) for i in ids},
+                       comp_ids=[c[0] for c in p["comps"]], comp_tq=[c[3] for c in p["comps"]], comp_td=[t[0] for t in p["scan"]],
+                       comp_ta=[t[1] for t in p["scan"]], restart=p["dri"] or None)
+        again = JW.write(spec, st["quantised"])
+        assert R.parse(again)["segments"] == p["segments"] and len(p["segments"]) == (1 if not p["dri"] else -(-(6 if spec.h2v2 else 24) // p["dri"]))
+        assert np.array_equal(JC.pillow_decode(again), JC.pillow_decode(data))
+
+
+def test_the_writer_refuses_blocks_beyond_its_bound_and_tables_that_are_no_prefix_code():
+    s = JC._spec(16, 16, 1)
+    b = JC._blocks(s, 1)
+    JW.write(JC.with_tables(s, b), b)
+    b[0][0, 0, 0] = 1001                                                  # x quantiser 2: the block's sum passes 2000 by its DC alone
+    with pytest.raises(AssertionError, match="> 2000"):
+        JW.write(JC.with_tables(s, b), b)
+    assert JW.BOUND == 2000
+    JW.huffman_from_lengths([(0, 1), (1, 2), (2, 3), (3, 3)][:3] + [(3, 16)])
+    with pytest.raises(AssertionError, match="all-ones"):
+        JW.huffman_from_lengths([(0, 1), (1, 2), (2, 3), (3, 3)])       # Kraft sum 1: the last code would be 111
+    with pytest.raises(AssertionError, match="all-ones"):
+        JW.code_table([1, 2] + [0] * 14, [0, 1, 2])                        # 0, 10 and 11
+
+
+@pytest.mark.parametrize("i", range(len(CRAFTED)), ids=[c.name for c, _ in CRAFTED])
+def test_a_crafted_case_has_its_property_and_the_rule_decodes_it_as_pillow_does(i):
+    case, checks = CRAFTED[i]
+    f = JC.crafted_facts(case.name)
+    listed = checks(f)
+    assert listed, "a case without a property"
+    for what, got, want in listed:
+        assert got >= want if isinstance(want, JC.AtLeast) else got == want, \
+            f"{case.name}: {what}: {got}, the case needs {'at least ' if isinstance(want, JC.AtLeast) else ''}{int(want)}"
+    assert f["rule"].shape == case.shape + (3,) and np.array_equal(f["rule"], case.pixels), \
+        f"{case.name}: {(f['rule'] != case.pixels).sum()} of {case.pixels.size} values differ"
+
+
+def test_the_crafted_corpus_covers_the_issues_list():
+    names = [c.name for c, _ in JC.crafted_corpus()]
+    for part in ("codes-of-9-to-16-bits", "commonest-symbols-16-bits", "lengths-1-to-16-mixed", "three-table-pairs", "three-quantisation-tables", "ac-only-at-zigzag-63",
+                 "all-63-ac-nonzero", "eob-straight-after-dc", "run-of-15", "zrl-then-eob", "every-category", "runs-of-ones", "restart-every-2", "restart-every-5",
+                 "past-the-last-mcu", "dri-0-written", "fill-bytes-in-front-of-rstn", "one-dht-and-one-dqt", "dqt-after-sof0", "defined-twice",
+                 "fill-bytes-in-front-of-header", "payloads-full-of-marker-bytes", "no-app0-ids-1-2-3", "jfif-ids-0-1-2", "bytes-behind-eoi", "jfif-with-ids-r-g-b",
+                 "adobe-transform-1-without-jfif"):
+        assert [n for n in names if part in n], part
+    assert {c.shape for c, _ in JC.crafted_corpus()} == {(16, 16), (32, 48)} and {c.shape for c, _ in JC.long_corpus()} == {(224, 224)}
+    for key, cases in {**JC.crafted_stores(JC.crafted_corpus()), **JC.crafted_stores(JC.long_corpus())}.items():
+        t = JC.pack([c.data for c in cases], 1, key[0], key[1])
+        ix = JS.parse_frames(t["frames_jpeg"], t["frame_off"], t["frame_shape"])
+        assert ix.h2v2 == key[2] and ix.N == len(cases), "the parser accepts every crafted file"
+
+
+def test_stage_bytes_is_what_the_long_corpus_is_built_around():
+    assert JC.stage_bytes() == 32768, "STAGE_BYTES of csrc/jpeg.hip moved: the padded files and the long noise files must move with it"
+    cases = {c.name: c for c, _ in JC.long_corpus()}
+    t = JC.pack([cases[n].data for n in sorted(cases) if "padded" in n], 1, 224, 224)
+    ix = JS.parse_frames(t["frames_jpeg"], t["frame_off"], t["frame_shape"])
+    assert sorted((ix.seg_tab[:, 1] - ix.seg_tab[:, 0]).tolist()) == [32767, 32768, 32769], "one segment on either side of the staging limit and one at it"
+
+
 # ---------------------------------------------------------------------------------------------------------------- the parser
+def test_rgb_coded_files_are_refused_and_the_refusal_names_the_frame():
+    """libjpeg reads these as RGB - its pixels are far from a YCbCr decode of the same coefficients - so the YCbCr kernels must not."""
+    good = {sub: JC.encode(JC.content("ramp", 32, 48), quality=90, subsampling=sub) for sub in (0, 2)}
+    seen = JC.refused_colour()
+    assert [n for n, *_ in seen] == ["pillow-keep-rgb", "ids-r-g-b-without-jfif-or-adobe", "pillow-420-app0-removed-ids-r-g-b", "adobe-transform-0-ids-1-2-3"]
+    for name, shape, data, why in seen:
+        want, as_ycc = JC.pillow_decode(data), R.decode(data)
+        assert (as_ycc != want).mean() > 0.5, f"{name}: Pillow does not read this file as RGB"
+        ok = good[2 if R.parse(data)["comps"][0][1] == 2 else 0]              # (of the file's own sampling: nothing else to refuse)
+        msg = _refused([ok, ok, data], shape, r"the store: frame 2 \(step 2, image 0\): the file stores RGB")
+        assert why in msg and "not YCbCr: not supported" in msg, msg
+
+
+def test_the_colour_rule_is_libjpegs():
+    rgb, ycc = [82, 71, 66], [1, 2, 3]
+    for jfif, adobe, ids, says_rgb in ((True, None, rgb, False), (True, 0, rgb, False), (False, 0, ycc, True), (False, 1, rgb, False), (False, 2, rgb, False),
+                                       (False, None, rgb, True), (False, None, ycc, False), (False, None, [0, 1, 2], False), (False, None, [82, 71, 67], False)):
+        assert bool(JS._stores_rgb(jfif, adobe, ids)) == says_rgb, (jfif, adobe, ids)
+    # a marker too short for libjpeg to examine counts as not seen: "JFIF" in 13 bytes, "Adobe" in 11
+    s = JC._spec(16, 16, 1, comp_ids=rgb, layout=[("APP", 0, b"JFIF\0" + bytes(8)), ("DQT", [0, 1]), ("SOF",), ("DHT", [(0, 0), (1, 0), (0, 1), (1, 1)])])
+    b = JC._blocks(s, 1)
+    data = JW.write(JC.with_tables(s, b), b)
+    assert (R.decode(data) != JC.pillow_decode(data)).mean() > 0.5 and "component ids 'R', 'G', 'B'" in _refused([data], (16, 16), "frame 0 ")
+    s.layout[0] = ("APP", 14, b"Adobe\0\x64" + bytes(4))
+    s.comp_ids = ycc
+    data = JW.write(s, b)
+    assert np.array_equal(R.decode(data), JC.pillow_decode(data))
+    t = JC.pack([data], 1, 16, 16)
+    assert JS.parse_frames(t["frames_jpeg"], t["frame_off"], t["frame_shape"]).N == 1
+
+
+def test_fill_bytes_in_front_of_rstn_and_eoi_are_accepted():
+    case = next(c for c, _ in JC.crafted_corpus() if c.name == "32x48-444-fill-bytes-in-front-of-rstn")
+    t = JC.pack([case.data], 1, 32, 48)
+    ix = JS.parse_frames(t["frames_jpeg"], t["frame_off"], t["frame_shape"])
+    p = R.parse(case.data)
+    assert ix.max_seg == 12 == len(p["segments"])
+    for k, seg in enumerate(p["segments"]):
+        lo, hi, m0, m1 = ix.seg_tab[k].tolist()
+        assert case.data[lo:hi] == seg and (m0, m1) == (2 * k, 2 * k + 2)
+        assert case.data[hi:hi + 3] == b"\xff\xff\xff" if k < 11 else case.data[hi:] == b"\xff\xff\xd9", "hi is the first 0xFF of the run"
+        assert k == 0 or (0xD0 <= case.data[lo - 1] <= 0xD7 and case.data[lo - 2] == 0xFF), "lo is the byte behind the marker code"
+
+
+def test_fill_bytes_in_front_of_a_stuffed_byte_are_refused_by_name():
+    """0xFF 0xFF 0x00 inside entropy-coded data: libjpeg reads one data byte, the decode core the end of the segment - refused."""
+    case = next(c for c, _ in JC.crafted_corpus() if c.name == "32x48-420-codes-that-are-runs-of-ones")
+    head, scan, tail = JC.split_scan(case.data)
+    i = scan.index(b"\xff\x00")
+    msg = _refused([case.data, head + scan[:i] + b"\xff" + scan[i:] + tail], (32, 48), r"frame 1 \(step 1, image 0\)")
+    assert "1 0xFF fill byte(s) in front of a stuffed 0xFF 0x00" in msg and f"scan byte {i}" in msg and "missing EOI" not in msg
+
+
 def mixed_store(H=32, W=48):
     """Six frames that mix three table sets: q50, q95 and q95 with optimised Huffman tables."""
     kws = [dict(quality=50), dict(quality=95), dict(quality=95, optimize=True)]

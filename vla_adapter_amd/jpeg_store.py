@@ -11,7 +11,13 @@ and every batch's frames are then decoded on the device (csrc/jpeg.hip, include/
 section 18).
 
 Accepted: baseline sequential (SOF0), 8 bit, the three components Y, Cb, Cr in one scan, sampled 4:2:0 or 4:4:4, one sampling per
-store, H and W multiples of 16 and equal to ``frame_shape``.  Everything else is refused at load by a ValueError that names the frame.
+store, H and W multiples of 16 and equal to ``frame_shape``.  Everything else is refused at load by a ValueError that names the frame:
+other codings (extended, progressive, lossless, hierarchical, arithmetic), 12-bit samples, one or four components, other samplings,
+16-bit quantisation tables, a table that is used and never defined, a second scan or a missing EOI, a size mismatch, Huffman counts
+that overflow their code space, and three components that store RGB.  Whether they do is libjpeg's rule (``_stores_rgb``): a JFIF
+marker says YCbCr; without one an Adobe marker says RGB with transform 0; without either the ids 'R', 'G', 'B' say RGB.  0xFF fill
+bytes are accepted in front of every marker, RSTn and EOI included; in front of a stuffed 0xFF 0x00 they are refused (T.81 has
+none there; libjpeg reads them as one data byte, the decode core as the end of the segment).
 
 ``parse_frames`` walks the markers of every file once: it pools the quantisation and Huffman tables by content (the latter in the
 derived form the kernel reads), finds the entropy-coded segments - one per image, or one per restart interval - and writes the small
@@ -142,12 +148,24 @@ class _Pools:
         return self.h[key]
 
 
+def _stores_rgb(jfif: bool, adobe, ids) -> str:
+    """libjpeg's rule for the colour coding of three components (jdapimin.c, default_decompress_parms): a JFIF marker says YCbCr;
+    without one an Adobe marker says RGB with transform 0 and YCbCr with any other; without either the component ids 'R', 'G', 'B'
+    say RGB and any others YCbCr.  -> what says RGB, or "" for YCbCr."""
+    if jfif:
+        return ""
+    if adobe is not None:
+        return "Adobe transform 0" if adobe == 0 else ""
+    return "component ids 'R', 'G', 'B' and neither a JFIF nor an Adobe marker" if list(ids) == [0x52, 0x47, 0x42] else ""
+
+
 def _parse_one(buf: np.ndarray, base: int, H: int, W: int, pools: _Pools):
     """One file (buf: its bytes; base: its offset in the store) -> (img row, [segment rows]); ValueError with the reason alone."""
     n = int(buf.shape[0])
     if n < 4 or buf[0] != 0xFF or buf[1] != 0xD8:
         raise ValueError("no SOI marker at its start: not a JPEG file")
     qt, ht, sof, dri, pos = {}, {}, None, 0, 2
+    jfif, adobe = False, None                           # a JFIF APP0 marker was seen; the transform flag of an Adobe APP14 marker
     while True:
         if pos + 2 > n:
             raise ValueError("the header is truncated: no SOS marker (the file ends inside its header)")
@@ -170,7 +188,11 @@ def _parse_one(buf: np.ndarray, base: int, H: int, W: int, pools: _Pools):
         seg = buf[pos + 4:pos + 2 + L].tobytes()
         if m in _SOF_REFUSED:
             raise ValueError(f"{_SOF_REFUSED[m]} is not supported: baseline sequential (SOF0) files only")
-        if m == 0xDB:
+        if m == 0xE0 and len(seg) >= 14 and seg[:5] == b"JFIF\0":          # (jdmarker.c: 14 and 12 bytes are what it examines)
+            jfif = True
+        elif m == 0xEE and len(seg) >= 12 and seg[:5] == b"Adobe":
+            adobe = seg[11]
+        elif m == 0xDB:
             i = 0
             while i < len(seg):
                 if seg[i] >> 4:
@@ -224,6 +246,9 @@ def _parse_one(buf: np.ndarray, base: int, H: int, W: int, pools: _Pools):
                 raise ValueError("the scan does not list the three components in the frame's order")
             if (seg[7], seg[8], seg[9]) != (0, 63, 0):
                 raise ValueError("a scan with spectral selection or successive approximation: sequential scans only")
+            rgb = _stores_rgb(jfif, adobe, [c[0] for c in comps])
+            if rgb:
+                raise ValueError(f"the file stores RGB ({rgb}), not YCbCr: not supported")
             rec = np.zeros(IMG_WORDS, dtype=np.int32)
             for c in range(3):
                 td, ta, tq = seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15, comps[c][3]
@@ -236,25 +261,30 @@ def _parse_one(buf: np.ndarray, base: int, H: int, W: int, pools: _Pools):
             start = pos + 2 + L
             break
         pos += 2 + L
-    # the scan: entropy-coded bytes, in which 0xFF is followed by 0x00 (a data byte 0xFF) or, with DRI, by RSTn; anything else ends it
+    # the scan: entropy-coded bytes, in which 0xFF is followed by 0x00 (a data byte 0xFF) or, with DRI, by RSTn; anything else ends it.
+    # A marker may have 0xFF fill bytes in front of it (T.81 B.1.1.2), so the scan is walked run of 0xFF by run: `s` the first byte of
+    # a run, `e` the byte behind it, which is the marker code (a run at the very end of the file has none and marks nothing).
     data = buf[start:]
-    ff = np.flatnonzero(data[:-1] == 0xFF) if data.shape[0] > 1 else np.zeros(0, dtype=np.int64)
-    nxt = data[ff + 1]
-    ff, nxt = ff[nxt != 0], nxt[nxt != 0]
-    is_rst = (nxt >= 0xD0) & (nxt <= 0xD7) if dri else np.zeros(nxt.shape, dtype=bool)
+    isff = data == 0xFF
+    prev = np.concatenate([[False], isff])[:-1]
+    s, e = np.flatnonzero(isff & ~prev), np.flatnonzero(~isff & prev)
+    s = s[:e.shape[0]]
+    code = data[e]
+    keep = ~((code == 0) & (e - s == 1))                          # a single 0xFF and 0x00: a stuffed data byte
+    s, e, code = s[keep], e[keep], code[keep]
+    is_rst = (code >= 0xD0) & (code <= 0xD7) if dri else np.zeros(code.shape, dtype=bool)
     ends = np.flatnonzero(~is_rst)
     if ends.size == 0:
         raise ValueError("missing EOI: the scan runs to the end of the file")
-    end = int(ff[ends[0]])
-    k = end
-    while k + 1 < data.shape[0] and data[k + 1] == 0xFF:          # fill bytes in front of the marker code
-        k += 1
-    if k + 1 >= data.shape[0] or data[k + 1] != 0xD9:
-        raise ValueError(f"missing EOI: the scan is followed by marker 0xFF{int(data[k + 1]) if k + 1 < data.shape[0] else 0:02X} "
-                         "(a second scan, or stray bytes)")
-    rst = ff[:ends[0]]                                            # the RSTn markers inside the scan
-    los = np.concatenate([[0], rst + 2]).astype(np.int64)
-    his = np.concatenate([rst, [end]]).astype(np.int64)
+    j = int(ends[0])
+    if code[j] == 0:
+        raise ValueError(f"{int(e[j] - s[j] - 1)} 0xFF fill byte(s) in front of a stuffed 0xFF 0x00 inside the entropy-coded data (scan byte "
+                         f"{int(s[j])}): fill bytes are accepted in front of markers only")
+    if code[j] != 0xD9:
+        raise ValueError(f"missing EOI: the scan is followed by marker 0xFF{int(code[j]):02X} (a second scan, or stray bytes)")
+    end = int(s[j])
+    los = np.concatenate([[0], e[:j] + 1]).astype(np.int64)       # a segment starts behind the code of its RSTn marker
+    his = np.concatenate([s[:j], [end]]).astype(np.int64)         # and ends at the first 0xFF - a fill byte, if there are any - of the next
     n_mcu = (H // 16) * (W // 16) if h2v2 else (H // 8) * (W // 8)
     segs = np.zeros((los.shape[0], SEG_WORDS), dtype=np.int64)
     segs[:, 0], segs[:, 1] = los + (base + start), his + (base + start)
