@@ -1,4 +1,5 @@
-// Training from JPEG-compressed episodes: the frames of a batch decoded where the data lives.  Declared in include/vla_jpeg.h; the
+// Training from JPEG-compressed episodes: the frames of a batch decoded where the data lives.  Declared in include/vla_jpeg.h (and
+// include/vla_jpeg_index.h: the same decode with an entry state per segment, for stores that carry a scan index); the
 // decode itself - bit reader, Huffman symbols, blocks, inverse DCT, upsampling, colour - is csrc/jpeg_core.h, which the host compiles
 // too (tests/test_jpeg_core_cpu.py runs it under the sanitizers).  Three launches on the caller's stream, nothing allocated or read
 // back: a captured graph may hold them.
@@ -12,6 +13,7 @@
 #include "episode_row.h"                        // episode_row: the row a sample reads, shared with episodes.hip
 #include "jpeg_core.h"
 #include "../../include/vla_jpeg.h"
+#include "../../include/vla_jpeg_index.h"
 
 namespace {
 
@@ -40,18 +42,20 @@ __device__ __forceinline__ ItemId item_id(i64 item, int max_seg, int n_img, cons
 constexpr int STAGE_BYTES = 32 * 1024;           // a wave stages a segment of up to this many bytes in LDS (a 256 x 256 q95 frame fits)
 
 // One lane per item: grid ceil(B * n_img * max_seg / 64) workgroups of one wave.  Item = (slot, k): segment k of the image in slot
-// b * n_img + cam.  Every lane reads its own stream and its own image's tables from global memory.
+// b * n_img + cam.  Every lane reads its own stream and its own image's tables from global memory.  seg_ent: the entry state of every
+// segment (include/vla_jpeg_index.h), or null - every segment starts behind a marker, with no bit consumed and zero predictors.
 __global__ void __launch_bounds__(ENTROPY_THREADS)
 jpeg_entropy_lane_kernel(const u8* __restrict__ bytes, i64 n_bytes, const i64* __restrict__ img_seg, const i64* __restrict__ seg_tab, i64 S,
                          const int* __restrict__ img_tab, const unsigned short* __restrict__ qt_pool, int nQ, const int* __restrict__ ht_pool,
                          int nH, const i64* __restrict__ episode_off, int E, i64 T, const int* __restrict__ ep, const i64* __restrict__ row,
-                         int B, int n_img, int H, int W, int h2v2, int max_seg, short* __restrict__ coef, u8* __restrict__ status) {
+                         int B, int n_img, int H, int W, int h2v2, int max_seg, const int* __restrict__ seg_ent, short* __restrict__ coef,
+                         u8* __restrict__ status) {
   const i64 item = (i64)blockIdx.x * ENTROPY_THREADS + threadIdx.x;
   if (item >= (i64)B * n_img * max_seg) return;
   const ItemId id = item_id(item, max_seg, n_img, episode_off, E, T, ep, row);
   const int slot = id.slot, k = id.k;
   const i64 img = id.img;
-  const Store st{bytes, n_bytes, img_seg, seg_tab, S, img_tab, qt_pool, nQ, ht_pool, nH};
+  const Store st{bytes, n_bytes, img_seg, seg_tab, S, img_tab, qt_pool, nQ, ht_pool, nH, seg_ent};
   const int rc = decode_item(st, img, k, H, W, h2v2, coef + (i64)slot * blocks_per_image(H, W, h2v2) * 64);
   status[item] = (u8)(rc < 0 ? ST_OK : rc);             // (no segment k in this image: nothing to decode)
 }
@@ -64,7 +68,8 @@ __global__ void __launch_bounds__(ENTROPY_THREADS)
 jpeg_entropy_wave_kernel(const u8* __restrict__ bytes, i64 n_bytes, const i64* __restrict__ img_seg, const i64* __restrict__ seg_tab, i64 S,
                          const int* __restrict__ img_tab, const unsigned short* __restrict__ qt_pool, int nQ, const int* __restrict__ ht_pool,
                          int nH, const i64* __restrict__ episode_off, int E, i64 T, const int* __restrict__ ep, const i64* __restrict__ row,
-                         int B, int n_img, int H, int W, int h2v2, int max_seg, short* __restrict__ coef, u8* __restrict__ status) {
+                         int B, int n_img, int H, int W, int h2v2, int max_seg, const int* __restrict__ seg_ent, short* __restrict__ coef,
+                         u8* __restrict__ status) {
   __shared__ int s_ht[6 * HT_WORDS];
   __shared__ unsigned short s_q[3 * 64];
   __shared__ u8 s_bytes[STAGE_BYTES];
@@ -73,7 +78,7 @@ jpeg_entropy_wave_kernel(const u8* __restrict__ bytes, i64 n_bytes, const i64* _
   const ItemId id = item_id(item, max_seg, n_img, episode_off, E, T, ep, row);
   const int slot = id.slot, k = id.k;
   const i64 img = id.img;
-  const Store st{bytes, n_bytes, img_seg, seg_tab, S, img_tab, qt_pool, nQ, ht_pool, nH};
+  const Store st{bytes, n_bytes, img_seg, seg_tab, S, img_tab, qt_pool, nQ, ht_pool, nH, seg_ent};
   Item it;
   if (!resolve_item(st, img, k, H, W, h2v2, it)) {      // (uniform over the wave: no segment k in this image)
     if (lane == 0) status[item] = ST_OK;
@@ -101,9 +106,9 @@ jpeg_entropy_wave_kernel(const u8* __restrict__ bytes, i64 n_bytes, const i64* _
   short* __restrict__ out = coef + (i64)slot * blocks_per_image(H, W, h2v2) * 64;
   int rc;
   if (staged)
-    rc = decode_segment(s_bytes, 0, len, it.mcu0, it.mcu1, H, W, h2v2, t, out);
+    rc = decode_segment(s_bytes, 0, len, it.e, it.mcu0, it.mcu1, H, W, h2v2, t, out);
   else
-    rc = decode_segment(bytes, it.lo, it.hi, it.mcu0, it.mcu1, H, W, h2v2, t, out);
+    rc = decode_segment(bytes, it.lo, it.hi, it.e, it.mcu0, it.mcu1, H, W, h2v2, t, out);
   status[item] = (u8)rc;
 }
 
@@ -159,12 +164,12 @@ extern "C" long long vla_jpeg_workspace_bytes(long long slots, int H, int W, int
   return coef_bytes(slots, H, W, h2v2) + slots * plane_bytes_of(H, W, h2v2);
 }
 
-extern "C" int vla_jpeg_decode_rows(void* stream, const unsigned char* bytes, long long n_bytes, const long long* img_seg,
-                                    const long long* seg_tab, long long S, const int* img_tab, const unsigned short* qt_pool, int nQ,
-                                    const int* ht_pool, int nH, const long long* episode_off, int E, long long T, const int* ep,
-                                    const long long* row, int B, int n_img, int H, int W, int h2v2, int max_seg, int mapping,
-                                    void* workspace, long long workspace_bytes, unsigned char* out_frames, long long out_stride,
-                                    unsigned char* status) {
+// vla_jpeg_decode_rows and vla_jpeg_decode_rows_at: the same three launches, the entropy stage with or without an entry table
+static int decode_rows(void* stream, const unsigned char* bytes, long long n_bytes, const long long* img_seg, const long long* seg_tab,
+                       long long S, const int* seg_ent, const int* img_tab, const unsigned short* qt_pool, int nQ, const int* ht_pool, int nH,
+                       const long long* episode_off, int E, long long T, const int* ep, const long long* row, int B, int n_img, int H, int W,
+                       int h2v2, int max_seg, int mapping, void* workspace, long long workspace_bytes, unsigned char* out_frames,
+                       long long out_stride, unsigned char* status) {
   VLA_REQUIRE(bytes && img_seg && seg_tab && img_tab && qt_pool && ht_pool && episode_off && ep && row, "jpeg_decode_rows: null input pointer");
   VLA_REQUIRE(workspace && out_frames && status, "jpeg_decode_rows: null output pointer");
   VLA_REQUIRE(B >= 1 && B <= 65535 && n_img >= 1 && n_img <= 16 && E >= 1 && T >= 1, "jpeg_decode_rows: 1 <= B <= 65535, 1 <= n_img <= 16, E, T >= 1");
@@ -184,11 +189,11 @@ extern "C" int vla_jpeg_decode_rows(void* stream, const unsigned char* bytes, lo
   const hipStream_t st = (hipStream_t)stream;
   if (mapping)
     hipLaunchKernelGGL(jpeg_entropy_wave_kernel, dim3((unsigned)items), dim3(ENTROPY_THREADS), 0, st, bytes, n_bytes, img_seg, seg_tab, S, img_tab,
-                       qt_pool, nQ, ht_pool, nH, episode_off, E, T, ep, row, B, n_img, H, W, h2v2, max_seg, coef, status);
+                       qt_pool, nQ, ht_pool, nH, episode_off, E, T, ep, row, B, n_img, H, W, h2v2, max_seg, seg_ent, coef, status);
   else
     hipLaunchKernelGGL(jpeg_entropy_lane_kernel, dim3((unsigned)((items + ENTROPY_THREADS - 1) / ENTROPY_THREADS)), dim3(ENTROPY_THREADS), 0, st, bytes,
                        n_bytes, img_seg, seg_tab, S, img_tab, qt_pool, nQ, ht_pool, nH, episode_off, E, T, ep, row, B, n_img, H, W, h2v2, max_seg,
-                       coef, status);
+                       seg_ent, coef, status);
   VLA_CHECK_LAUNCH("jpeg_decode_rows (entropy)");
   const long long n_blocks = slots * per_image;
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((n_blocks + IDCT_THREADS - 1) / IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, coef, planes,
@@ -202,4 +207,25 @@ extern "C" int vla_jpeg_decode_rows(void* stream, const unsigned char* bytes, lo
     hipLaunchKernelGGL(jpeg_pixels_kernel<false>, grid_c, dim3(PIXEL_THREADS), 0, st, planes, out_frames, n_quads, plane_bytes, out_stride, H, W, h2v2);
   VLA_CHECK_LAUNCH("jpeg_decode_rows (pixels)");
   return VLA_OK;
+}
+
+extern "C" int vla_jpeg_decode_rows(void* stream, const unsigned char* bytes, long long n_bytes, const long long* img_seg,
+                                    const long long* seg_tab, long long S, const int* img_tab, const unsigned short* qt_pool, int nQ,
+                                    const int* ht_pool, int nH, const long long* episode_off, int E, long long T, const int* ep,
+                                    const long long* row, int B, int n_img, int H, int W, int h2v2, int max_seg, int mapping,
+                                    void* workspace, long long workspace_bytes, unsigned char* out_frames, long long out_stride,
+                                    unsigned char* status) {
+  return decode_rows(stream, bytes, n_bytes, img_seg, seg_tab, S, nullptr, img_tab, qt_pool, nQ, ht_pool, nH, episode_off, E, T, ep, row, B, n_img,
+                     H, W, h2v2, max_seg, mapping, workspace, workspace_bytes, out_frames, out_stride, status);
+}
+
+extern "C" int vla_jpeg_decode_rows_at(void* stream, const unsigned char* bytes, long long n_bytes, const long long* img_seg,
+                                       const long long* seg_tab, const int* seg_ent, long long S, const int* img_tab,
+                                       const unsigned short* qt_pool, int nQ, const int* ht_pool, int nH, const long long* episode_off, int E,
+                                       long long T, const int* ep, const long long* row, int B, int n_img, int H, int W, int h2v2,
+                                       int max_seg, int mapping, void* workspace, long long workspace_bytes, unsigned char* out_frames,
+                                       long long out_stride, unsigned char* status) {
+  VLA_REQUIRE(seg_ent, "jpeg_decode_rows_at: null entry table");
+  return decode_rows(stream, bytes, n_bytes, img_seg, seg_tab, S, seg_ent, img_tab, qt_pool, nQ, ht_pool, nH, episode_off, E, T, ep, row, B, n_img,
+                     H, W, h2v2, max_seg, mapping, workspace, workspace_bytes, out_frames, out_stride, status);
 }

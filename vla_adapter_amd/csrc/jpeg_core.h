@@ -1,4 +1,4 @@
-// The baseline JPEG decode, stated once for the device (csrc/jpeg.hip) and for the host (the stand-alone program of
+// The baseline JPEG decode, stated once for the device (csrc/jpeg.hip, csrc/jpeg_index.hip) and for the host (the stand-alone program of
 // tests/test_jpeg_core_cpu.py, which runs it under the sanitizers): bit reader, symbol decode, block decode, IDCT, chroma upsample and
 // colour conversion.  Every function is plain integer C++ and compiles with hipcc for both sides and with any host compiler.
 //
@@ -37,6 +37,9 @@ constexpr int HT_MAXCODE = 0, HT_VALOFF = 18, HT_LOOK = 36, HT_VAL = 36 + 256, H
 constexpr int IMG_Q = 0, IMG_DC = 3, IMG_AC = 6, IMG_RESTART = 9, IMG_H2V2 = 10, IMG_WORDS = 12;
 // a row of the segment table (int64 [S, SEG_WORDS]): the entropy-coded bytes [lo, hi) and the MCUs [mcu0, mcu1) they hold
 constexpr int SEG_LO = 0, SEG_HI = 1, SEG_MCU0 = 2, SEG_MCU1 = 3, SEG_WORDS = 4;
+// a row of the optional entry table (int32 [S, ENT_WORDS], include/vla_jpeg_index.h): how many bits of the byte at `lo` are already
+// consumed, and the DC predictors of Y, Cb, Cr there
+constexpr int ENT_BIT = 0, ENT_P0 = 1, ENT_P1 = 2, ENT_P2 = 3, ENT_WORDS = 4;
 
 VLA_JPEG_HD int natural_order(int k) {
   // jpeg_natural_order: zigzag position -> position in the 8 x 8 block
@@ -53,6 +56,8 @@ VLA_JPEG_HD int natural_order(int k) {
 struct BitReader {
   const u8* bytes;
   i64 pos, end;
+  i64 fed;          // bytes pushed into `acc` so far, supplied ones included: 8 * fed - n bits are consumed.  Only the index walk reads
+                    // it; in the per-batch decode it is a dead store, which the compiler drops once the reader is inlined
   u64 acc;          // the low `n` bits are unread, the oldest on top
   int n, pad;       // `pad` of them, the youngest, are supplied zeros
   int truncated;
@@ -63,6 +68,7 @@ VLA_JPEG_HD void br_init(BitReader& br, const u8* bytes, i64 lo, i64 hi) {
   br.pos = lo;
   br.end = hi > lo ? hi : lo;
   br.acc = 0;
+  br.fed = 0;
   br.n = br.pad = br.truncated = 0;
 }
 
@@ -85,6 +91,7 @@ VLA_JPEG_HD void br_fill(BitReader& br) {
     }
     br.acc = (br.acc << 8) | b;
     br.n += 8;
+    ++br.fed;
   }
 }
 
@@ -140,7 +147,7 @@ VLA_JPEG_HD int decode_block(BitReader& br, const int* __restrict dc, const int*
   if (s < 0 || s > 15) return ST_BAD_CODE;
   if (s) {
     br_fill(br);
-    pred += receive_extend(br, s);
+    pred = (int)((unsigned)pred + (unsigned)receive_extend(br, s));          // (wraps: an entry table may hand in any predictor)
   }
   if (br.truncated) return ST_TRUNCATED;
   out[0] = saturate16((i64)pred * q[0]);
@@ -169,17 +176,15 @@ VLA_JPEG_HD int decode_block(BitReader& br, const int* __restrict dc, const int*
 
 // Where block `blk` of MCU `mcu` stands in an image's coefficient (and plane) layout: the Y blocks in raster order, then Cb, then Cr.
 // bw = W / 8 blocks per Y row, bh = H / 8.  4:2:0: blk 0 .. 3 are the MCU's Y blocks (raster), 4 Cb, 5 Cr; 4:4:4: Y, Cb, Cr.
+VLA_JPEG_HD int block_component(int blk, int h2v2) { return h2v2 ? (blk < 4 ? 0 : blk - 3) : blk; }
+
 VLA_JPEG_HD int block_index(int mcu, int blk, int bw, int bh, int h2v2, int& comp) {
+  comp = block_component(blk, h2v2);
   if (h2v2) {
     const int mw = bw >> 1, my = mcu / mw, mx = mcu - my * mw;
-    if (blk < 4) {
-      comp = 0;
-      return (2 * my + (blk >> 1)) * bw + 2 * mx + (blk & 1);
-    }
-    comp = blk - 3;
+    if (blk < 4) return (2 * my + (blk >> 1)) * bw + 2 * mx + (blk & 1);
     return bw * bh + (comp - 1) * (mw * (bh >> 1)) + my * mw + mx;
   }
-  comp = blk;
   return blk * bw * bh + mcu;
 }
 
@@ -199,14 +204,32 @@ VLA_JPEG_HD const unsigned short* table_q(const Tables& t, int c) { return t.q +
 VLA_JPEG_HD const int* table_dc(const Tables& t, int c) { return t.ht + (c == 0 ? t.dc0 : (c == 1 ? t.dc1 : t.dc2)); }
 VLA_JPEG_HD const int* table_ac(const Tables& t, int c) { return t.ht + (c == 0 ? t.ac0 : (c == 1 ? t.ac1 : t.ac2)); }
 
-// One segment: the MCUs [mcu0, mcu1) of an image from bytes[lo, hi), into the image's coefficient blocks `coef` (64 shorts each, laid
-// out by block_index).  The caller has clamped lo <= hi into the byte array and mcu0 <= mcu1 into the image's MCUs.  `img`: the
-// image's row of the per-image table, its table ids already clamped into the pools.  Every block of the range is written; -> ST_*.
-VLA_JPEG_HD int decode_segment(const u8* bytes, i64 lo, i64 hi, int mcu0, int mcu1, int H, int W, int h2v2,
+// Where a segment's decode begins: `bit` (0 .. 7) bits of the byte at `lo` are already consumed, and the DC predictors of Y, Cb, Cr
+// are p0, p1, p2.  Behind a marker - the start of every segment the parser finds - it is all zero; index_segment() records the state
+// at MCUs inside a segment, which makes a piece of a segment a segment of its own.
+struct Entry {
+  int bit, p0, p1, p2;
+};
+
+VLA_JPEG_HD Entry entry_at(const int* ent) {          // (null: no entry table; the row as it stands: decode_segment masks the bit)
+  return ent ? Entry{ent[ENT_BIT], ent[ENT_P0], ent[ENT_P1], ent[ENT_P2]} : Entry{0, 0, 0, 0};
+}
+
+// One segment: the MCUs [mcu0, mcu1) of an image from bytes[lo, hi), begun in state `e`, into the image's coefficient blocks `coef`
+// (64 shorts each, laid out by block_index).  The caller has clamped lo <= hi into the byte array and mcu0 <= mcu1 into the image's
+// MCUs.  `img`: the image's row of the per-image table, its table ids already clamped into the pools.  Every block of the range is
+// written; -> ST_*.  The entry's bit is masked to 0 .. 7 here, the one place every caller - the kernels and the host program - passes
+// through; the predictors feed arithmetic only (a wrapping add, a saturating product): any value is safe.
+VLA_JPEG_HD int decode_segment(const u8* bytes, i64 lo, i64 hi, const Entry& e, int mcu0, int mcu1, int H, int W, int h2v2,
                                const Tables& t, short* __restrict coef) {
   BitReader br;
   br_init(br, bytes, lo, hi);
-  int p0 = 0, p1 = 0, p2 = 0;                           // the DC predictors of Y, Cb, Cr
+  const int bit = e.bit & 7;
+  if (bit) {                                            // (the bits of the byte at `lo` that the piece in front consumed)
+    br_fill(br);
+    br_skip(br, bit);
+  }
+  int p0 = e.p0, p1 = e.p1, p2 = e.p2;                  // the DC predictors of Y, Cb, Cr
   int status = ST_OK;
   const int bw = W >> 3, bh = H >> 3, nb = blocks_per_mcu(h2v2);
   for (int mcu = mcu0; mcu < mcu1; ++mcu) {
@@ -236,6 +259,7 @@ struct Store {
   int nQ;
   const int* ht_pool;
   int nH;
+  const int* seg_ent = nullptr;     // int32 [S, ENT_WORDS]: the entry state of every segment, or null when every segment starts behind a marker
 };
 
 VLA_JPEG_HD i64 clamp_i64(i64 v, i64 lo, i64 hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -244,15 +268,16 @@ VLA_JPEG_HD i64 clamp_i64(i64 v, i64 lo, i64 hi) { return v < lo ? lo : (v > hi 
 struct Item {
   i64 lo, hi;
   int mcu0, mcu1;
+  Entry e;
   Tables t;
 };
 
-// -> false when image img (0 <= img < N, the caller's duty) has no segment k.  Every value read from a table is clamped before it is
-// used: segment rows into [0, S], byte ranges into [0, n_bytes], MCU ranges into the image, ids into the pools.
-VLA_JPEG_HD bool resolve_item(const Store& st, i64 img, int k, int H, int W, int h2v2, Item& it) {
-  const i64 s0 = clamp_i64(st.img_seg[img], 0, st.S), s1 = clamp_i64(st.img_seg[img + 1], s0, st.S);
-  if (k < 0 || k >= s1 - s0) return false;
-  const i64* seg = st.seg_tab + (s0 + k) * SEG_WORDS;
+// Row s of the segment table (0 <= s < S, the caller's duty) as a segment of image img (0 <= img < N, likewise).  Every value read
+// from a table is clamped before it is used: byte ranges into [0, n_bytes], MCU ranges into the image, ids into the pools (the entry
+// bit is masked where it is used, in decode_segment).
+VLA_JPEG_HD void resolve_segment(const Store& st, i64 img, i64 s, int H, int W, int h2v2, Item& it) {
+  const i64* seg = st.seg_tab + s * SEG_WORDS;
+  it.e = entry_at(st.seg_ent ? st.seg_ent + s * ENT_WORDS : nullptr);
   const int n_mcu = mcus_per_image(H, W, h2v2);
   it.lo = clamp_i64(seg[SEG_LO], 0, st.n_bytes);
   it.hi = clamp_i64(seg[SEG_HI], it.lo, st.n_bytes);
@@ -266,6 +291,13 @@ VLA_JPEG_HD bool resolve_item(const Store& st, i64 img, int k, int H, int W, int
     ac[c] = clamp_i64(rec[IMG_AC + c], 0, st.nH - 1) * HT_WORDS;
   }
   it.t = Tables{st.qt_pool, st.ht_pool, q[0], q[1], q[2], dc[0], dc[1], dc[2], ac[0], ac[1], ac[2]};
+}
+
+// -> false when image img (0 <= img < N, the caller's duty) has no segment k; the image's segment rows are clamped into [0, S].
+VLA_JPEG_HD bool resolve_item(const Store& st, i64 img, int k, int H, int W, int h2v2, Item& it) {
+  const i64 s0 = clamp_i64(st.img_seg[img], 0, st.S), s1 = clamp_i64(st.img_seg[img + 1], s0, st.S);
+  if (k < 0 || k >= s1 - s0) return false;
+  resolve_segment(st, img, s0 + k, H, W, h2v2, it);
   return true;
 }
 
@@ -273,7 +305,102 @@ VLA_JPEG_HD bool resolve_item(const Store& st, i64 img, int k, int H, int W, int
 VLA_JPEG_HD int decode_item(const Store& st, i64 img, int k, int H, int W, int h2v2, short* __restrict coef) {
   Item it;
   if (!resolve_item(st, img, k, H, W, h2v2, it)) return -1;
-  return decode_segment(st.bytes, it.lo, it.hi, it.mcu0, it.mcu1, H, W, h2v2, it.t, coef);
+  return decode_segment(st.bytes, it.lo, it.hi, it.e, it.mcu0, it.mcu1, H, W, h2v2, it.t, coef);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the scan index
+// The walk that makes pieces of a segment (include/vla_jpeg_index.h): the Huffman decode of the MCUs [mcu0, mcu1) from bytes[lo, hi),
+// coefficients discarded, and at every MCU whose distance from mcu0 is a multiple of piece_mcus (>= 1) a record of where the reader
+// stands - a row of the segment table (`seg`: lo, hi, mcu0, mcu1) and one of the entry table (`ent`: bit, p0, p1, p2), `rows` of
+// each, every word of them written, and no more whatever the stream holds.  `base` is added to the byte positions written (the
+// caller may hand in a copy of the segment's bytes that starts at 0).  -> the walk's ST_*.
+//
+// Position: the reader refills up to 8 bytes ahead, so `pos` is not where the next bit lies.  8 * fed - n bits are consumed, and at
+// a record all of them are bits of the data (no MCU in front ended truncated), so the next bit is bit c & 7 of data byte c >> 3; a
+// cursor steps from byte to byte, over a stuffed 0x00 together with its 0xFF, and so never rests on one.  The cursor only moves
+// forward: the whole walk reads every byte twice.
+//
+// hi: piece j ends where piece j + 1 begins - at its lo; one byte later when it begins inside a byte, which the two share; two when
+// that byte is 0xFF, whose stuffed 0x00 must be inside the range or the reader takes the pair for a marker.  The last piece keeps the
+// segment's hi.  A piece's decode consumes exactly the bits in front of the next piece's entry, all of them inside its range; what the
+// reader supplies behind the range is zero bits that only a lookahead sees.  decode_symbol() settles on a code of length l by
+// its first l bits alone (the lookup table has one entry for every continuation of a short code, and the search compares l-bit
+// prefixes), and those l bits are bits of the data, so every symbol is the one the whole segment's decode reads there.
+//
+// A walk that stops with a non-zero status inside piece j has written pieces 0 .. j; piece j keeps the segment's hi, so its decode
+// meets the same bits and fails at the same block.  Every later piece gets lo = hi = the segment's hi and a zero entry: its decode
+// runs out of bytes at once, reports it and writes zero coefficients, which is what the whole segment's decode leaves behind a failure.
+VLA_JPEG_HD int index_segment(const u8* bytes, i64 lo, i64 hi, i64 base, int mcu0, int mcu1, int h2v2, const Tables& t, int piece_mcus,
+                              i64 rows, i64* __restrict seg, int* __restrict ent) {
+  BitReader br;
+  br_init(br, bytes, lo, hi);
+  hi = br.end;
+  int p0 = 0, p1 = 0, p2 = 0, status = ST_OK, left = 0;
+  i64 j = 0, at = lo, at_byte = 0;                      // rows written; the cursor: data byte `at_byte` of the segment is bytes[at]
+  short blk[64];
+  const int nb = blocks_per_mcu(h2v2);
+  for (int mcu = mcu0; (mcu < mcu1 || mcu == mcu0) && status == ST_OK; ++mcu) {         // (an empty segment is one empty piece)
+    if (left == 0) {
+      if (j >= rows) break;
+      const i64 c = 8 * br.fed - br.n, bit = c & 7;
+      for (; at_byte < (c >> 3) && at < hi; ++at_byte) at += (bytes[at] == 0xFF && at + 1 < hi) ? 2 : 1;
+      if (j) seg[(j - 1) * SEG_WORDS + SEG_HI] = base + clamp_i64(at + (bit ? (at < hi && bytes[at] == 0xFF ? 2 : 1) : 0), lo, hi);
+      const i64 m1 = clamp_i64((i64)mcu + piece_mcus, mcu0, mcu1);
+      seg[j * SEG_WORDS + SEG_LO] = base + at;
+      seg[j * SEG_WORDS + SEG_HI] = base + hi;
+      seg[j * SEG_WORDS + SEG_MCU0] = mcu;
+      seg[j * SEG_WORDS + SEG_MCU1] = m1;
+      ent[j * ENT_WORDS + ENT_BIT] = (int)bit;
+      ent[j * ENT_WORDS + ENT_P0] = p0;
+      ent[j * ENT_WORDS + ENT_P1] = p1;
+      ent[j * ENT_WORDS + ENT_P2] = p2;
+      ++j;
+      left = piece_mcus;
+    }
+    --left;
+    for (int b = 0; b < nb && mcu < mcu1 && status == ST_OK; ++b) {
+      const int comp = block_component(b, h2v2);
+      int& pred = comp == 0 ? p0 : (comp == 1 ? p1 : p2);
+      status = decode_block(br, table_dc(t, comp), table_ac(t, comp), table_q(t, comp), pred, blk);
+    }
+  }
+  for (; j < rows; ++j) {                               // pieces behind a failure (or rows the segment has no MCUs for): nothing to read
+    const i64 m0 = clamp_i64((i64)mcu0 + j * piece_mcus, mcu0, mcu1), m1 = clamp_i64(m0 + piece_mcus, mcu0, mcu1);
+    seg[j * SEG_WORDS + SEG_LO] = seg[j * SEG_WORDS + SEG_HI] = base + hi;
+    seg[j * SEG_WORDS + SEG_MCU0] = m0;
+    seg[j * SEG_WORDS + SEG_MCU1] = m1;
+    ent[j * ENT_WORDS + ENT_BIT] = ent[j * ENT_WORDS + ENT_P0] = ent[j * ENT_WORDS + ENT_P1] = ent[j * ENT_WORDS + ENT_P2] = 0;
+  }
+  return status;
+}
+
+// Work item s of the index build (0 <= s < S, the caller's duty), resolved from the tables: the segment as a segment of its image -
+// the last image whose first segment row is not behind s, by a binary search that ends whatever img_seg holds - and the rows of the
+// output it owns, piece_off[s] .. piece_off[s + 1] clamped into [0, S_out] and made monotone.
+struct IndexItem {
+  Item it;
+  i64 r0, rows;
+};
+
+VLA_JPEG_HD IndexItem resolve_index_item(const Store& st, i64 N, i64 s, int H, int W, int h2v2, const i64* __restrict piece_off, i64 S_out) {
+  i64 a = 0, b = N - 1;                                 // the answer lies in [a, b]
+  while (a < b) {
+    const i64 m = a + (b - a + 1) / 2;
+    if (clamp_i64(st.img_seg[m], 0, st.S) <= s) a = m; else b = m - 1;
+  }
+  IndexItem w;
+  resolve_segment(st, a, s, H, W, h2v2, w.it);
+  w.r0 = clamp_i64(piece_off[s], 0, S_out);
+  w.rows = clamp_i64(piece_off[s + 1], w.r0, S_out) - w.r0;
+  return w;
+}
+
+// Segment s of the store walked and cut: -> the walk's ST_*
+VLA_JPEG_HD int index_item(const Store& st, i64 N, i64 s, int H, int W, int h2v2, int piece_mcus, const i64* __restrict piece_off, i64 S_out,
+                           i64* __restrict out_seg_tab, int* __restrict out_seg_ent) {
+  const IndexItem w = resolve_index_item(st, N, s, H, W, h2v2, piece_off, S_out);
+  return index_segment(st.bytes, w.it.lo, w.it.hi, 0, w.it.mcu0, w.it.mcu1, h2v2, w.it.t, piece_mcus, w.rows, out_seg_tab + w.r0 * SEG_WORDS,
+                       out_seg_ent + w.r0 * ENT_WORDS);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the inverse DCT

@@ -254,12 +254,14 @@ class EpisodeTables:
     their own: how the windows of a batch are drawn.
 
     ``tables``: one episode-file dict per dataset; ``names``: the datasets' names (statistics and hold-out entries are keyed by them);
-    ``wheres``: what a ValueError about dataset d's tables calls them (default: its name)."""
+    ``wheres``: what a ValueError about dataset d's tables calls them (default: its name).  ``jpeg_scan_index``: frames that are
+    JPEG files without a restart marker per MCU row get a scan index at load (jpeg_store.JpegFrames.build_scan_index) - the same
+    pixels, decoded a row per work item; nothing changes for raw frames."""
 
     mixed = False                           # a mix: the raw batch carries dataset_index, every sample its own dataset's statistics
 
     def __init__(self, tables: List[dict], names: Sequence[str], device, chunk: int = NUM_ACTIONS_CHUNK, *, holdout: Optional[float] = None,
-                 wheres: Optional[Sequence[str]] = None):
+                 wheres: Optional[Sequence[str]] = None, jpeg_scan_index: bool = False):
         if chunk < 1:
             raise ValueError("chunk must be >= 1")
         wheres = list(wheres or names)
@@ -299,6 +301,8 @@ class EpisodeTables:
         self.A, self.Pd = int(act.shape[1]), int(pr.shape[1])
         # the frames: raw pixels (frames_u8), or JPEG files that gather() decodes (jpeg: their bytes and tables on the device)
         self.jpeg = JpegFrames(all_, device, wheres[0] if self.D == 1 else "episode mix") if "frames_jpeg" in all_ else None
+        if self.jpeg and jpeg_scan_index:
+            self.jpeg.build_scan_index()
         self.frame_shape = (self.jpeg.n_img, self.jpeg.H, self.jpeg.W, 3) if self.jpeg else tuple(all_["frames_u8"].shape[1:])
         self.row_bytes = int(np.prod(self.frame_shape))
         self.Pmax = int(po.diff().max())
@@ -361,12 +365,15 @@ class EpisodeTables:
         return {k: prompt_off if k == "prompt_off" else into[k] for k in RAW_BATCH_KEYS}
 
     def bad_segments(self) -> torch.Tensor:
-        """f32 [1] on the device: how many segments of the last gathered batch did not decode (no read-back here)."""
+        """f32 [1] on the device: how many segments of the last gathered batch did not decode (no read-back here).  In a store with
+        a scan index a segment is a piece, and this counts pieces."""
         return (self.decode_status != 0).sum().to(torch.float32).view(1)
 
     def verify_frames(self, batch: int = 64) -> int:
         """Decode every frame of a JPEG store once, ``batch`` steps at a time, and raise a ValueError that names the first frame with a
-        segment that did not decode (one read-back, behind the last batch); -> the number of frames decoded.  0 for a raw store."""
+        segment that did not decode (one read-back, behind the last batch); -> the number of frames decoded.  0 for a raw store.
+        In a store with a scan index the segment it names is the piece: pieces in front of a damaged one decode, those behind it
+        report that they ran out of bytes."""
         if not self.jpeg:
             return 0
         j, dev = self.jpeg, self.device
@@ -403,24 +410,25 @@ class EpisodeStore(EpisodeTables):
     batch is what it is without the argument."""
 
     def __init__(self, tables: dict, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, _where: str = "episode store",
-                 *, holdout: Optional[float] = None):
+                 *, holdout: Optional[float] = None, jpeg_scan_index: bool = False):
         name = (tables.get("dataset_name") if isinstance(tables, dict) else None) or dataset_name or "episodes"
-        super().__init__([tables], [name], device, chunk, holdout=holdout, wheres=[_where])
+        super().__init__([tables], [name], device, chunk, holdout=holdout, wheres=[_where], jpeg_scan_index=jpeg_scan_index)
         self.dataset_name, self.action_mask = self.names[0], self.action_masks[0]
 
     # ---- construction --------------------------------------------------------------------------------------------------------
     @classmethod
     def from_dict(cls, tables: dict, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, *,
-                  holdout: Optional[float] = None) -> "EpisodeStore":
-        return cls(tables, device, chunk, dataset_name, holdout=holdout)
+                  holdout: Optional[float] = None, jpeg_scan_index: bool = False) -> "EpisodeStore":
+        return cls(tables, device, chunk, dataset_name, holdout=holdout, jpeg_scan_index=jpeg_scan_index)
 
     @classmethod
     def load(cls, path, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, *,
-             holdout: Optional[float] = None) -> "EpisodeStore":
+             holdout: Optional[float] = None, jpeg_scan_index: bool = False) -> "EpisodeStore":
         """``path``: a .pt episode file or a directory of them (concatenated in sorted order).  Validates the tables (ValueError that
         names the key), moves everything to the device and builds valid_off; ``dataset_name``: used when the file names none;
-        ``holdout``: the fraction of episodes - the last ones - set aside for validation (see the class)."""
-        return cls(load_tables(path, device), device, chunk, dataset_name, _where=str(path), holdout=holdout)
+        ``holdout``: the fraction of episodes - the last ones - set aside for validation (see the class); ``jpeg_scan_index``: JPEG
+        frames get a scan index (EpisodeTables)."""
+        return cls(load_tables(path, device), device, chunk, dataset_name, _where=str(path), holdout=holdout, jpeg_scan_index=jpeg_scan_index)
 
     # ---- the batch -----------------------------------------------------------------------------------------------------------
     def sample_indices(self, B: int, seed: int, rank: int, world: int, step: int):

@@ -133,6 +133,9 @@ class FinetuneConfig:
                                           # every flat buffer as hex strings, read in the log line's own read-back
     verify_frames: bool = False           # --episode_file / --episode_mix whose frames are JPEG files (jpeg_store.py): decode every frame once at
                                           # load and refuse the run, naming the frame, when a scan does not decode (DESIGN.md section 18 has the cost)
+    jpeg_scan_index: bool = False         # --episode_file / --episode_mix whose frames are JPEG files: walk every scan once at load and record
+                                          # where each MCU row starts, so that files without restart markers decode a row per work item - the
+                                          # same pixels, hence the same run; nothing to do for raw frames
     # fmt: on
 
 
@@ -623,12 +626,13 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
         if cfg.episode_file:
             from .episodes import EpisodeStore
             where = cfg.episode_file
-            src = EpisodeStore.load(cfg.episode_file, dev, chunk=mcfg.chunk, dataset_name=cfg.dataset_name, holdout=cfg.val_episode_fraction)
+            src = EpisodeStore.load(cfg.episode_file, dev, chunk=mcfg.chunk, dataset_name=cfg.dataset_name, holdout=cfg.val_episode_fraction,
+                                    jpeg_scan_index=cfg.jpeg_scan_index)
         else:
             from .mixture import EpisodeMix, parse_mix
             where = "--episode_mix"
             src = EpisodeMix.load(parse_mix(cfg.episode_mix), dev, chunk=mcfg.chunk, balance_weights=cfg.episode_mix_balance,
-                                  holdout=cfg.val_episode_fraction)
+                                  holdout=cfg.val_episode_fraction, jpeg_scan_index=cfg.jpeg_scan_index)
         if (src.A, src.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
             raise ValueError(f"{where}: actions_raw / proprio_raw have {src.A} / {src.Pd} columns, the model takes "
                              f"{mcfg.action_dim} / {mcfg.proprio_dim}")
@@ -640,6 +644,10 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
                 info["dataset_statistics"] = norm_stats
         elif src.mixed:
             mixture_stats(json.load(open(cfg.dataset_statistics_file)), src.names)        # a missing entry is refused before the first step
+        if src.jpeg is not None and src.jpeg.seg_ent is not None and rank == 0:      # (a raw store, or a marker per row already: no index)
+            j = src.jpeg
+            print(json.dumps(dict(jpeg_scan_index=dict(pieces_per_frame=round(int(j.seg_tab.shape[0]) / j.N, 2), index_bytes=j.index_bytes(),
+                                                       jpeg_index_bad_scans=int((j.index_status != 0).sum())))), flush=True)
         if cfg.verify_frames:                     # (a raw store has nothing to verify)
             src.verify_frames()
         if info is not None:

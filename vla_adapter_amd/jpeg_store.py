@@ -23,6 +23,12 @@ none there; libjpeg reads them as one data byte, the decode core as the end of t
 derived form the kernel reads), finds the entropy-coded segments - one per image, or one per restart interval - and writes the small
 per-image and per-segment tables that ``JpegFrames`` uploads beside the bytes.  Only the scan is validated structurally (its markers);
 whether its bits decode is the kernel's ``status``, and ``EpisodeStore.verify_frames`` reads it for the whole store.
+
+The decode is serial per segment, and a file without restart markers is one segment.  ``JpegFrames.build_scan_index`` (asked for by
+``jpeg_scan_index=True`` of the stores, ``--jpeg_scan_index`` of ``finetune``) walks such segments once on the device and cuts them
+into pieces of one MCU row, each with the byte, the bit and the DC predictors at which it begins (``plan_pieces``,
+include/vla_jpeg_index.h): the files stay as they are, the pixels too, and the decode gets a work item per row.
+A piece is a segment in every respect - in ``seg_tab``, in ``max_seg``, in ``status`` and in what ``verify_frames`` names.
 """
 from __future__ import annotations
 
@@ -325,11 +331,35 @@ def parse_frames(frames_jpeg, frame_off, frame_shape, where: str = "episode stor
                      qt_pool=np.stack(pools.q_rows), ht_pool=np.stack(pools.h_rows), max_seg=int(max(counts)))
 
 
+# ---------------------------------------------------------------------------------------------------------------- the scan index
+def plan_pieces(index: JpegIndex, piece_mcus: int):
+    """How the segments of a store are cut into pieces of ``piece_mcus`` MCUs (include/vla_jpeg_index.h; numpy only): segment
+    [m0, m1) gets max(1, ceil((m1 - m0) / piece_mcus)) pieces that tile it without gap or overlap, the last one shorter.
+    -> (piece_off int64 [S + 1]: the pieces of segment s are rows piece_off[s] .. piece_off[s + 1] of the new tables, the new img_seg
+    int64 [N + 1] = piece_off[img_seg], S' = the number of pieces, the new max_seg)."""
+    piece_mcus = int(piece_mcus)
+    if piece_mcus < 1:
+        raise ValueError(f"piece_mcus must be >= 1, got {piece_mcus}")
+    n = np.maximum(index.seg_tab[:, 3] - index.seg_tab[:, 2], 0)
+    pieces = np.maximum(1, (n + piece_mcus - 1) // piece_mcus)
+    piece_off = np.concatenate([[0], np.cumsum(pieces)]).astype(np.int64)
+    img_seg = piece_off[index.img_seg]
+    return piece_off, img_seg, int(piece_off[-1]), int(np.diff(img_seg).max())
+
+
+# vla_jpeg_index_build walks segments serially, a lane a 224 x 224 scan in 12 - 25 ms (DESIGN.md section 18).  4096 segments are 64
+# waves of the lane mapping - fewer than the device has compute units - so a launch of one slice lasts about as long as one walk, tens
+# of milliseconds, however large the store: no single launch holds a shared device for long.
+BUILD_SLICE = 4096
+
+
 # ---------------------------------------------------------------------------------------------------------------- on the device
 class JpegFrames:
     """The JPEG frames of a store on the device: the bytes, the tables parse_frames wrote, and the decode of a batch's frames."""
 
     mapping = 1                 # vla_jpeg_decode_rows: 0 one lane per segment, 1 one wave per segment (DESIGN.md section 18)
+    build_mapping = 0           # vla_jpeg_index_build: likewise; the build is bound by throughput, and a lane per scan is the faster
+                                # one for a store of more than one slice (DESIGN.md section 19)
 
     def __init__(self, tables: dict, device, where: str = "episode store"):
         self.device = device
@@ -340,6 +370,43 @@ class JpegFrames:
         self.qt_pool, self.ht_pool = up(ix.qt_pool.view(np.int16)), up(ix.ht_pool)          # (torch has no uint16 arithmetic: same bits)
         self.n_img, self.H, self.W, self.h2v2, self.max_seg, self.N = ix.n_img, ix.H, ix.W, ix.h2v2, ix.max_seg, ix.N
         self._ws: Dict[int, torch.Tensor] = {}
+        self.seg_ent, self.index_status, self.piece_mcus = None, None, None        # (set by build_scan_index)
+
+    def build_scan_index(self, piece_mcus: int = None, mapping: int = None, slice_segments: int = BUILD_SLICE) -> int:
+        """Cut every segment longer than ``piece_mcus`` MCUs (default: one MCU row) into pieces the decode starts in parallel
+        (include/vla_jpeg_index.h): one serial walk per segment on the device, ``slice_segments`` segments per launch.  Swaps in the
+        new img_seg / seg_tab / max_seg and the entry table seg_ent, drops the buffers sized by the old max_seg, and keeps
+        ``index_status`` u8 [S] (the walk's status of every original segment) on the device - nothing is read back; how many walks
+        stopped early is ``(index_status != 0).sum()`` for whoever logs it.  -> the number of pieces, or 0 when no segment is longer
+        than piece_mcus and the store stays as it is."""
+        from . import ops
+        ix = self.index
+        if piece_mcus is None:
+            piece_mcus = ix.W // 16 if ix.h2v2 else ix.W // 8
+        if self.seg_ent is not None:
+            raise ValueError("build_scan_index: the store already has a scan index")
+        piece_off, img_seg, S2, max_seg = plan_pieces(ix, piece_mcus)
+        S = int(ix.seg_tab.shape[0])
+        if S2 == S:
+            return 0
+        dev = self.device
+        po = torch.from_numpy(piece_off).to(dev)
+        seg_tab = torch.empty(S2, SEG_WORDS, dtype=torch.int64, device=dev)
+        seg_ent = torch.empty(S2, 4, dtype=torch.int32, device=dev)
+        status = torch.empty(S, dtype=torch.uint8, device=dev)
+        step = max(1, int(slice_segments))
+        for s0 in range(0, S, step):
+            ops.jpeg_index_build(self.bytes, self.img_seg, self.seg_tab, self.img_tab, self.qt_pool, self.ht_pool, self.H, self.W, self.h2v2,
+                                 int(piece_mcus), po, s0, min(s0 + step, S), self.build_mapping if mapping is None else mapping,
+                                 seg_tab, seg_ent, status)
+        self.img_seg, self.seg_tab, self.seg_ent, self.max_seg = torch.from_numpy(img_seg).to(dev), seg_tab, seg_ent, max_seg
+        self.index_status, self.piece_mcus = status, int(piece_mcus)
+        self._ws = {}
+        return S2
+
+    def index_bytes(self) -> int:
+        """The bytes of the scan index on the device: a row of seg_tab (32) and one of seg_ent (16) per piece."""
+        return 0 if self.seg_ent is None else int(self.seg_tab.shape[0]) * (SEG_WORDS * 8 + 16)
 
     def buffers(self, B: int) -> dict:
         """workspace and status for batches of B samples, and the zero-length frame rows the store's gather writes (allocated once
@@ -354,12 +421,13 @@ class JpegFrames:
 
     def decode(self, episode_off: torch.Tensor, T: int, ep: torch.Tensor, row: torch.Tensor, out_frames: torch.Tensor, buf: dict = None,
                mapping: int = None) -> torch.Tensor:
-        """vla_jpeg_decode_rows of the windows (ep, row) into out_frames u8 [B, n_img, H, W, 3]; -> status u8 [B, n_img, max_seg]."""
+        """vla_jpeg_decode_rows (vla_jpeg_decode_rows_at for a store with a scan index) of the windows (ep, row) into out_frames u8
+        [B, n_img, H, W, 3]; -> status u8 [B, n_img, max_seg]."""
         from . import ops
         buf = buf or self.buffers(int(ep.numel()))
         ops.jpeg_decode_rows(self.bytes, self.img_seg, self.seg_tab, self.img_tab, self.qt_pool, self.ht_pool, episode_off, T, ep, row,
                              self.n_img, self.H, self.W, self.h2v2, self.max_seg, self.mapping if mapping is None else mapping,
-                             buf["workspace"], out_frames, buf["status"])
+                             buf["workspace"], out_frames, buf["status"], self.seg_ent)
         return buf["status"]
 
 

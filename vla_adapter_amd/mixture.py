@@ -114,7 +114,7 @@ class EpisodeMix(EpisodeTables):
     mixed = True
 
     def __init__(self, tables: List[dict], weights: Sequence[float], names: Sequence[str], device, chunk: int = NUM_ACTIONS_CHUNK,
-                 period: int = DEFAULT_PERIOD, balance_weights: bool = True, *, holdout: Optional[float] = None):
+                 period: int = DEFAULT_PERIOD, balance_weights: bool = True, *, holdout: Optional[float] = None, jpeg_scan_index: bool = False):
         if chunk < 1:
             raise ValueError("chunk must be >= 1")
         if not tables:
@@ -126,7 +126,7 @@ class EpisodeMix(EpisodeTables):
         for n, w in zip(names, weights):
             if not (isinstance(w, (int, float)) and float(w) > 0.0 and math.isfinite(float(w))):      # (NaN fails the comparison too)
                 raise ValueError(f"{n}: weight must be a finite number > 0, got {w!r}")
-        super().__init__(tables, names, device, chunk, holdout=holdout)
+        super().__init__(tables, names, device, chunk, holdout=holdout, jpeg_scan_index=jpeg_scan_index)
         # transitions, p and the quotas stay over ALL episodes under holdout=f (episodes.EpisodeTables); windows are the training
         # windows N_d, which the sampler reads from valid_off on the device
         self.weights, self.balance_weights, self.Q = [float(w) for w in weights], bool(balance_weights), int(period)
@@ -142,16 +142,17 @@ class EpisodeMix(EpisodeTables):
     # ---- construction --------------------------------------------------------------------------------------------------------
     @classmethod
     def from_dicts(cls, entries, device, chunk: int = NUM_ACTIONS_CHUNK, period: int = DEFAULT_PERIOD, balance_weights: bool = True, *,
-                   holdout: Optional[float] = None) -> "EpisodeMix":
+                   holdout: Optional[float] = None, jpeg_scan_index: bool = False) -> "EpisodeMix":
         """``entries``: [(tables dict, weight)]; a dict without dataset_name is called dataset_<index>."""
-        return cls.load(entries, device, chunk, period, balance_weights, holdout=holdout)
+        return cls.load(entries, device, chunk, period, balance_weights, holdout=holdout, jpeg_scan_index=jpeg_scan_index)
 
     @classmethod
     def load(cls, entries, device, chunk: int = NUM_ACTIONS_CHUNK, period: int = DEFAULT_PERIOD, balance_weights: bool = True, *,
-             holdout: Optional[float] = None) -> "EpisodeMix":
+             holdout: Optional[float] = None, jpeg_scan_index: bool = False) -> "EpisodeMix":
         """``entries``: [(path or tables dict, weight)]; a path is anything ``EpisodeStore.load`` takes.  A dataset is called by its
         file's dataset_name, else by the path's stem.  ``holdout``: the fraction of every dataset's episodes - its last ones - set aside
-        for validation (episodes.EpisodeStore); None: every table and batch is what it is without the argument."""
+        for validation (episodes.EpisodeStore); None: every table and batch is what it is without the argument.  ``jpeg_scan_index``:
+        JPEG frames get a scan index at load (episodes.EpisodeTables)."""
         tables, weights, names = [], [], []
         for i, entry in enumerate(entries):
             src, w = entry if isinstance(entry, (tuple, list)) else (entry, 1.0)
@@ -165,7 +166,7 @@ class EpisodeMix(EpisodeTables):
             tables.append(d)
             weights.append(w)
             names.append(name if isinstance(name, str) and name else fallback)
-        return cls(tables, weights, names, device, chunk, period, balance_weights, holdout=holdout)
+        return cls(tables, weights, names, device, chunk, period, balance_weights, holdout=holdout, jpeg_scan_index=jpeg_scan_index)
 
     # ---- what the mix is -----------------------------------------------------------------------------------------------------
     def mixture_info(self) -> dict:

@@ -202,6 +202,14 @@ JPEG_PROTOS = {
 }
 JPEG_SYMBOLS = sorted(JPEG_PROTOS)
 
+# the scan index of the JPEG frame store (include/vla_jpeg_index.h, csrc/jpeg_index.hip and csrc/jpeg.hip): an eighth table, bound by
+# name in the same way (tests/test_jpeg_index_cpu.py checks header, table and library against each other)
+JPEG_INDEX_PROTOS = {
+    "vla_jpeg_index_build": ([_P, _P, _L, _P, _P, _L, _P, _P, _I, _P, _I, _L, _I, _I, _I, _I, _P, _L, _L, _I, _P, _P, _L, _P], _I),
+    "vla_jpeg_decode_rows_at": ([_P, _P, _L, _P, _P, _P, _L, _P, _P, _I, _P, _I, _P, _I, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P], _I),
+}
+JPEG_INDEX_SYMBOLS = sorted(JPEG_INDEX_PROTOS)
+
 _lib = None
 
 
@@ -215,7 +223,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()) + list(HELDOUT_PROTOS.items()) + list(DIGEST_PROTOS.items()) + list(JPEG_PROTOS.items()):
+    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()) + list(HELDOUT_PROTOS.items()) + list(DIGEST_PROTOS.items()) + list(JPEG_PROTOS.items()) + list(JPEG_INDEX_PROTOS.items()):
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

@@ -1077,9 +1077,11 @@ def jpeg_workspace_bytes(slots: int, H: int, W: int, h2v2: int) -> int:
 
 def jpeg_decode_rows(data: torch.Tensor, img_seg: torch.Tensor, seg_tab: torch.Tensor, img_tab: torch.Tensor, qt_pool: torch.Tensor,
                      ht_pool: torch.Tensor, episode_off: torch.Tensor, T: int, ep: torch.Tensor, row: torch.Tensor, n_img: int, H: int, W: int,
-                     h2v2: int, max_seg: int, mapping: int, workspace: torch.Tensor, out_frames: torch.Tensor, status: torch.Tensor) -> None:
+                     h2v2: int, max_seg: int, mapping: int, workspace: torch.Tensor, out_frames: torch.Tensor, status: torch.Tensor,
+                     seg_ent: Optional[torch.Tensor] = None) -> None:
     """vla_jpeg_decode_rows: the store's bytes and tables (jpeg_store.JpegFrames) + the sampler's index vectors -> out_frames u8
-    [B, n_img, H, W, 3] and status u8 [B, n_img, max_seg] (both given; out_frames may be strided between images)."""
+    [B, n_img, H, W, 3] and status u8 [B, n_img, max_seg] (both given; out_frames may be strided between images).  ``seg_ent`` (int32
+    [S, 4], the entry state of every segment: a store with a scan index): vla_jpeg_decode_rows_at (include/vla_jpeg_index.h)."""
     B, E, dev, n_all = ep.numel(), episode_off.numel() - 1, data.device, int(T) * int(n_img)
     for t in (data, img_seg, seg_tab, img_tab, qt_pool, ht_pool, episode_off, ep, row, workspace, status):
         assert t.is_cuda and t.device == dev and t.is_contiguous(), "jpeg_decode_rows: operands are contiguous tensors on one device"
@@ -1092,10 +1094,37 @@ def jpeg_decode_rows(data: torch.Tensor, img_seg: torch.Tensor, seg_tab: torch.T
     assert out_frames.is_cuda and out_frames.device == dev and out_frames.dtype == torch.uint8 and tuple(out_frames.shape) == (B, n_img, H, W, 3)
     image = out_frames.stride(1) if n_img > 1 else (out_frames.stride(0) if B > 1 else H * W * 3)          # elements between two images
     assert out_frames[0, 0].is_contiguous() and (B == 1 or out_frames.stride(0) == n_img * image), "jpeg_decode_rows: out_frames: contiguous images, one stride between them"
-    N.check(_lib().vla_jpeg_decode_rows(_st(), _p(data), data.numel(), _p(img_seg), _p(seg_tab), seg_tab.shape[0], _p(img_tab), _p(qt_pool),
-                                        qt_pool.shape[0], _p(ht_pool), ht_pool.shape[0], _p(episode_off), E, int(T), _p(ep), _p(row), B, int(n_img),
-                                        int(H), int(W), int(h2v2), int(max_seg), int(mapping), _p(workspace), workspace.numel(), _p(out_frames),
-                                        int(image), _p(status)), "jpeg_decode_rows")
+    tail = (_p(img_tab), _p(qt_pool), qt_pool.shape[0], _p(ht_pool), ht_pool.shape[0], _p(episode_off), E, int(T), _p(ep), _p(row), B, int(n_img),
+            int(H), int(W), int(h2v2), int(max_seg), int(mapping), _p(workspace), workspace.numel(), _p(out_frames), int(image), _p(status))
+    if seg_ent is None:
+        N.check(_lib().vla_jpeg_decode_rows(_st(), _p(data), data.numel(), _p(img_seg), _p(seg_tab), seg_tab.shape[0], *tail), "jpeg_decode_rows")
+        return
+    assert seg_ent.is_cuda and seg_ent.device == dev and seg_ent.is_contiguous() and seg_ent.dtype == torch.int32 and tuple(seg_ent.shape) == (seg_tab.shape[0], 4)
+    N.check(_lib().vla_jpeg_decode_rows_at(_st(), _p(data), data.numel(), _p(img_seg), _p(seg_tab), _p(seg_ent), seg_tab.shape[0], *tail),
+            "jpeg_decode_rows_at")
+
+
+def jpeg_index_build(data: torch.Tensor, img_seg: torch.Tensor, seg_tab: torch.Tensor, img_tab: torch.Tensor, qt_pool: torch.Tensor,
+                     ht_pool: torch.Tensor, H: int, W: int, h2v2: int, piece_mcus: int, piece_off: torch.Tensor, s_begin: int, s_end: int,
+                     mapping: int, out_seg_tab: torch.Tensor, out_seg_ent: torch.Tensor, out_status: torch.Tensor) -> None:
+    """vla_jpeg_index_build (include/vla_jpeg_index.h): the segments [s_begin, s_end) of the store walked once and cut into pieces of
+    ``piece_mcus`` MCUs - rows piece_off[s] .. piece_off[s + 1] of out_seg_tab int64 [S', 4] and out_seg_ent int32 [S', 4], and
+    out_status u8 [S] (all given; only the slice's rows are written)."""
+    dev, S, n_all = data.device, seg_tab.shape[0], img_tab.shape[0]
+    for t in (data, img_seg, seg_tab, img_tab, qt_pool, ht_pool, piece_off, out_seg_tab, out_seg_ent, out_status):
+        assert t.is_cuda and t.device == dev and t.is_contiguous(), "jpeg_index_build: operands are contiguous tensors on one device"
+    assert data.dtype == torch.uint8 and data.dim() == 1
+    assert img_seg.dtype == torch.int64 and img_seg.numel() == n_all + 1 and seg_tab.dtype == torch.int64 and seg_tab.dim() == 2 and seg_tab.shape[1] == 4
+    assert img_tab.dtype == torch.int32 and img_tab.dim() == 2 and img_tab.shape[1] == 12
+    assert qt_pool.dtype == torch.int16 and qt_pool.dim() == 2 and qt_pool.shape[1] == 64 and ht_pool.dtype == torch.int32 and ht_pool.dim() == 2 and ht_pool.shape[1] == 548
+    assert piece_off.dtype == torch.int64 and piece_off.numel() == S + 1
+    assert out_seg_tab.dtype == torch.int64 and out_seg_tab.dim() == 2 and out_seg_tab.shape[1] == 4
+    assert out_seg_ent.dtype == torch.int32 and tuple(out_seg_ent.shape) == tuple(out_seg_tab.shape)
+    assert out_status.dtype == torch.uint8 and out_status.numel() == S
+    N.check(_lib().vla_jpeg_index_build(_st(), _p(data), data.numel(), _p(img_seg), _p(seg_tab), S, _p(img_tab), _p(qt_pool), qt_pool.shape[0],
+                                        _p(ht_pool), ht_pool.shape[0], n_all, int(H), int(W), int(h2v2), int(piece_mcus), _p(piece_off),
+                                        int(s_begin), int(s_end), int(mapping), _p(out_seg_tab), _p(out_seg_ent), out_seg_tab.shape[0],
+                                        _p(out_status)), "jpeg_index_build")
 
 
 # ---- a weighted mixture of device-resident datasets (include/vla_mixture.h, csrc/mixture.hip) ----------------------------------------
