@@ -6,12 +6,15 @@
 //   jpeg_entropy_*_kernel one work item per (image of the batch, segment): Huffman decode -> dequantised int16 blocks in workspace
 //   jpeg_idct_kernel      one thread per 8 x 8 block: islow inverse DCT -> the u8 planes Y, Cb, Cr in workspace
 //   jpeg_pixels_kernel    one thread per 4 pixels of a row: fancy upsampling, YCbCr -> RGB -> out_frames
+// The last two are stage B, launched through vlajpeg::stage_b (jpeg_stage_b.h): the JPEG round trip of csrc/policy_image.hip puts its
+// own coefficient blocks in front of the same two kernels.
 // Entropy decode is serial per segment and lanes diverge (every lane follows its own stream), so the mapping of items to lanes is a
 // launch argument: one lane per item (64 segments share a wave and its instruction stream) or one wave per item (the first lane
 // decodes; no divergence, 64 times the waves).  DESIGN.md section 18 has the measurements of both.
 #include "common.h"
 #include "episode_row.h"                        // episode_row: the row a sample reads, shared with episodes.hip
 #include "jpeg_core.h"
+#include "jpeg_stage_b.h"
 #include "../../include/vla_jpeg.h"
 #include "../../include/vla_jpeg_index.h"
 
@@ -164,6 +167,27 @@ extern "C" long long vla_jpeg_workspace_bytes(long long slots, int H, int W, int
   return coef_bytes(slots, H, W, h2v2) + slots * plane_bytes_of(H, W, h2v2);
 }
 
+bool vlajpeg::stage_b_fits(long long slots, int H, int W) { return slots * H * (W / 4) <= 0x7fffffffll * PIXEL_THREADS; }
+
+// Stage B (jpeg_stage_b.h): coefficient blocks -> planes -> pixels, two launches.  The callers have checked the shape (shape_ok's rule),
+// the pointers and that the grids fit.
+int vlajpeg::stage_b(hipStream_t st, const short* coef, unsigned char* planes, long long slots, int H, int W, int h2v2, unsigned char* out_frames,
+                     long long out_stride) {
+  const long long per_image = blocks_per_image(H, W, h2v2), plane_bytes = plane_bytes_of(H, W, h2v2);
+  const long long n_blocks = slots * per_image;
+  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((n_blocks + IDCT_THREADS - 1) / IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, coef, planes,
+                     n_blocks, per_image, plane_bytes, H, W, h2v2);
+  VLA_CHECK_LAUNCH("jpeg stage B (idct)");
+  const long long n_quads = slots * H * (W / 4);
+  const dim3 grid_c((unsigned)((n_quads + PIXEL_THREADS - 1) / PIXEL_THREADS));
+  if ((uintptr_t)out_frames % 4 == 0 && out_stride % 4 == 0)
+    hipLaunchKernelGGL(jpeg_pixels_kernel<true>, grid_c, dim3(PIXEL_THREADS), 0, st, planes, out_frames, n_quads, plane_bytes, out_stride, H, W, h2v2);
+  else
+    hipLaunchKernelGGL(jpeg_pixels_kernel<false>, grid_c, dim3(PIXEL_THREADS), 0, st, planes, out_frames, n_quads, plane_bytes, out_stride, H, W, h2v2);
+  VLA_CHECK_LAUNCH("jpeg stage B (pixels)");
+  return VLA_OK;
+}
+
 // vla_jpeg_decode_rows and vla_jpeg_decode_rows_at: the same three launches, the entropy stage with or without an entry table
 static int decode_rows(void* stream, const unsigned char* bytes, long long n_bytes, const long long* img_seg, const long long* seg_tab,
                        long long S, const int* seg_ent, const int* img_tab, const unsigned short* qt_pool, int nQ, const int* ht_pool, int nH,
@@ -181,11 +205,10 @@ static int decode_rows(void* stream, const unsigned char* bytes, long long n_byt
   VLA_REQUIRE((uintptr_t)workspace % 16 == 0 && workspace_bytes >= vla_jpeg_workspace_bytes(slots, H, W, h2v2),
               "jpeg_decode_rows: workspace must be 16-byte aligned and hold vla_jpeg_workspace_bytes");
   const long long items = slots * max_seg;
-  VLA_REQUIRE(items <= 0x7fffffffll && slots * H * (W / 4) <= 0x7fffffffll * PIXEL_THREADS,
+  VLA_REQUIRE(items <= 0x7fffffffll && vlajpeg::stage_b_fits(slots, H, W),
               "jpeg_decode_rows: B * n_img * max_seg or B * n_img * H * W is too large for one grid");
   short* coef = (short*)workspace;
   unsigned char* planes = (unsigned char*)workspace + coef_bytes(slots, H, W, h2v2);
-  const long long per_image = blocks_per_image(H, W, h2v2), plane_bytes = plane_bytes_of(H, W, h2v2);
   const hipStream_t st = (hipStream_t)stream;
   if (mapping)
     hipLaunchKernelGGL(jpeg_entropy_wave_kernel, dim3((unsigned)items), dim3(ENTROPY_THREADS), 0, st, bytes, n_bytes, img_seg, seg_tab, S, img_tab,
@@ -195,18 +218,7 @@ static int decode_rows(void* stream, const unsigned char* bytes, long long n_byt
                        n_bytes, img_seg, seg_tab, S, img_tab, qt_pool, nQ, ht_pool, nH, episode_off, E, T, ep, row, B, n_img, H, W, h2v2, max_seg,
                        seg_ent, coef, status);
   VLA_CHECK_LAUNCH("jpeg_decode_rows (entropy)");
-  const long long n_blocks = slots * per_image;
-  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((n_blocks + IDCT_THREADS - 1) / IDCT_THREADS)), dim3(IDCT_THREADS), 0, st, coef, planes,
-                     n_blocks, per_image, plane_bytes, H, W, h2v2);
-  VLA_CHECK_LAUNCH("jpeg_decode_rows (idct)");
-  const long long n_quads = slots * H * (W / 4);
-  const dim3 grid_c((unsigned)((n_quads + PIXEL_THREADS - 1) / PIXEL_THREADS));
-  if ((uintptr_t)out_frames % 4 == 0 && out_stride % 4 == 0)
-    hipLaunchKernelGGL(jpeg_pixels_kernel<true>, grid_c, dim3(PIXEL_THREADS), 0, st, planes, out_frames, n_quads, plane_bytes, out_stride, H, W, h2v2);
-  else
-    hipLaunchKernelGGL(jpeg_pixels_kernel<false>, grid_c, dim3(PIXEL_THREADS), 0, st, planes, out_frames, n_quads, plane_bytes, out_stride, H, W, h2v2);
-  VLA_CHECK_LAUNCH("jpeg_decode_rows (pixels)");
-  return VLA_OK;
+  return vlajpeg::stage_b(st, coef, planes, slots, H, W, h2v2, out_frames, out_stride);
 }
 
 extern "C" int vla_jpeg_decode_rows(void* stream, const unsigned char* bytes, long long n_bytes, const long long* img_seg,

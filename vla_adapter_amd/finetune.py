@@ -136,6 +136,9 @@ class FinetuneConfig:
     jpeg_scan_index: bool = False         # --episode_file / --episode_mix whose frames are JPEG files: walk every scan once at load and record
                                           # where each MCU row starts, so that files without restart markers decode a row per work item - the
                                           # same pixels, hence the same run; nothing to do for raw frames
+    frame_resize: str = "bicubic"         # how frames that are not at the model's size get there (every GPUInputStage of the run): "bicubic", the
+                                          # processor's Pillow resize, or "lanczos3", the RLDS stage's tf.image.resize(method="lanczos3",
+                                          # antialias=True) (obs_transforms.py:75).  Frames at the model's size: no effect
     # fmt: on
 
 
@@ -201,6 +204,8 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         raise ValueError("--ddp_algo is allreduce or rs_ag")
     if cfg.objective not in ("l1", "token_ce"):
         raise ValueError("--objective is l1 or token_ce")
+    if cfg.frame_resize not in ("bicubic", "lanczos3"):
+        raise ValueError(f"--frame_resize is bicubic or lanczos3, got {cfg.frame_resize!r}")
     if cfg.objective == "token_ce" and train_mode(cfg) == "adapter":
         raise NotImplementedError("--objective token_ce trains the VLM (LoRA or full fine-tune); --use_fz True freezes it")
     if cfg.backbone is not None:
@@ -372,7 +377,7 @@ class ValidationPass:
             if fr.dtype != torch.uint8 or fr.dim() != 5 or fr.shape[-1] != 3:
                 raise ValueError(f"frames_u8 must be uint8 [B, n_img, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
             if self.stage is None:
-                self.stage = GPUInputStage(self.dev, backbones=backbone_norms(self.mcfg), image_size=self.mcfg.vit[0].img)
+                self.stage = GPUInputStage(self.dev, backbones=backbone_norms(self.mcfg), image_size=self.mcfg.vit[0].img, resize=self.cfg.frame_resize)
             b["pixel_values"] = self.stage.pixels(fr)              # never augmented (rlds/dataset.py:412: train=False)
         B = self.shapes["input_ids"][0][0]
         if b["input_ids"].shape[0] != B:
@@ -581,7 +586,7 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
             st = raw_batch_stats(norm_stats, b.get("dataset_name"))
             act_st, pr_st, index = st["action"], st["proprio"], None
         if stage is None:
-            stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img)
+            stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img, resize=cfg.frame_resize)
         aug = ImageAugment(seed=cfg.seed, rank=rank, step=step) if cfg.image_aug else None
         L = cfg.max_seq_len or None
         if L is None and b["prompt_off"].is_cuda:
@@ -604,7 +609,7 @@ def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, e
         if fr.dtype != torch.uint8 or fr.dim() != 5 or fr.shape[-1] != 3:
             raise ValueError(f"frames_u8 must be uint8 [B, n_img, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
         if stage is None:
-            stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img)
+            stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img, resize=cfg.frame_resize)
         aug = ImageAugment(seed=cfg.seed, rank=rank, step=step) if cfg.image_aug else None
         b["pixel_values"] = stage.pixels(fr, augment=aug)
         step += 1

@@ -173,7 +173,7 @@ class HeldOutSweep:
         self.Nv = int(store.Nv)
         self.n_batches = sweep_batches(self.Nv, self.stride, B, self.rank, self.world)
         self.shapes = {k: (tuple(v.shape), v.dtype) for k, v in static.items()}
-        self.stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img)
+        self.stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img, resize=getattr(cfg, "frame_resize", "bicubic"))
         self.training_phase = cfg.phase == "Training"
         e = torch.empty
         self.idx = dict(ds=e(B, dtype=torch.int32, device=dev), ep=e(B, dtype=torch.int32, device=dev), row=e(B, dtype=torch.int64, device=dev),

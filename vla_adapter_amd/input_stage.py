@@ -128,6 +128,72 @@ def pil_bicubic_coeffs(in_size: int, out_size: int):
     return bounds, coefs
 
 
+# ---- the evaluator's frame pipeline: resize_image_for_policy (experiments/robot/openvla_utils.py:542-565), DESIGN.md section 20 ----
+RESIZE_MODES = ("bicubic", "lanczos3")
+# libjpeg's two standard quantisation tables (jcparam.c: std_luminance_quant_tbl, std_chrominance_quant_tbl), natural order
+JPEG_STD_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+JPEG_STD_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+
+
+def jpeg_quant_tables(quality: int = 95) -> np.ndarray:
+    """uint16 [2, 64]: the luminance and the chrominance quantisation table of a baseline file of ``quality`` (1 .. 100), natural
+    order - libjpeg's jpeg_set_quality: its standard tables scaled by jpeg_quality_scaling (5000 / quality below 50, else 200 - 2 *
+    quality), q = clamp((base * scale + 50) / 100, 1, 255), integer arithmetic.  95 is tf.image.encode_jpeg's default."""
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_quant_tables: quality is 1 .. 100, got {quality}")
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    base = np.array([JPEG_STD_LUMA, JPEG_STD_CHROMA], dtype=np.int64)
+    return np.clip((base * scale + 50) // 100, 1, 255).astype(np.uint16)
+
+
+_SPANS = {}
+
+
+def tf_lanczos3_spans(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The spans of tf.image.resize(method="lanczos3", antialias=True) along one side, n_in -> n_out samples (TF's ScaleAndTranslate:
+    ComputeSpansCore with the Lanczos3 kernel, scale = n_out / n_in, translation 0), float32 throughout -> (starts int32 [n_out],
+    weights f32 [n_out, span], zero-padded behind a span that the source's edge cuts short).  Cached per (n_in, n_out).
+
+    scale = f32(n_out) / f32(n_in), inv = 1 / scale, ks = max(inv, 1) (the kernel widens with the downscale factor: the antialiasing);
+    span = min(2 ceil(3 ks) + 1, n_in).  Output x samples the source at s = (x + 0.5) inv; its span is [ceil(s - 3 ks - 0.5), floor(s +
+    3 ks - 0.5)] clamped into the source; source i weighs k(|(i + 0.5 - s) (1 / ks)|), k(x) = 0 beyond 3, 1 up to 1e-3, else 3 sin(pi x)
+    sin(pi x / 3) / (pi^2 x^2) with pi = f32(3.14159265359); the weights are summed one after the other in float32 and every one is
+    multiplied by 1 / sum (when |sum| >= 1000 FLT_MIN).  numpy's float32 sin stands where TF calls sinf: their last bits may differ."""
+    key = (int(n_in), int(n_out))
+    if key in _SPANS:
+        return _SPANS[key]
+    n_in, n_out = key
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"tf_lanczos3_spans: sizes must be positive, got {n_in} -> {n_out}")
+    f32 = np.float32
+    scale = f32(n_out) / f32(n_in)
+    inv = f32(1.0) / scale
+    ks = max(inv, f32(1.0))
+    oks, rad, pi = f32(1.0) / ks, f32(3.0), f32(3.14159265359)
+    span = min(2 * int(np.ceil(rad * ks)) + 1, n_in)
+    s = (np.arange(n_out, dtype=f32) + f32(0.5)) * inv                                # f32 [n_out]
+    first = np.clip(np.ceil((s - rad * ks) - f32(0.5)).astype(np.int64), 0, n_in - 1)
+    last = np.clip(np.floor((s + rad * ks) - f32(0.5)).astype(np.int64), 0, n_in - 1)
+    src = first[:, None] + np.arange(span)[None, :]                                    # [n_out, span]
+    x = np.abs(((src.astype(f32) + f32(0.5)) - s[:, None]) * oks).astype(f32)
+    with np.errstate(all="ignore"):
+        v = (rad * np.sin(pi * x) * np.sin(pi * x / rad) / (pi * pi * x * x)).astype(f32)
+    w = np.where(x > rad, f32(0), np.where(x <= f32(1e-3), f32(1), v)).astype(f32)
+    w[src > last[:, None]] = 0                                                        # behind the span: padding
+    tot = np.zeros(n_out, f32)
+    for k in range(span):                                                              # summed one after the other, as TF does
+        tot = (tot + w[:, k]).astype(f32)
+    norm = np.where(np.abs(tot) >= f32(1000.0) * np.finfo(f32).tiny, f32(1.0) / np.where(tot == 0, f32(1), tot), f32(1.0)).astype(f32)
+    w = (w * norm[:, None]).astype(f32)
+    out = (np.ascontiguousarray(first.astype(np.int32)), np.ascontiguousarray(w))
+    for a in out:
+        a.setflags(write=False)
+    _SPANS[key] = out
+    return out
+
+
 NORMALIZATION_KINDS = ("bounds", "bounds_q99")     # NormalizationType.BOUNDS / BOUNDS_Q99 (rlds/utils/data_utils.py:44-49)
 
 
@@ -187,7 +253,13 @@ SERVE_STATS_KINDS = {"bounds": ("min", "max"), "bounds_q99": ("q01", "q99")}    
 class GPUInputStage:
     def __init__(self, device="cuda", tokenizer_len: int = 151643, n_bins: int = 256, min_action: float = -1.0, max_action: float = 1.0,
                  pad_token_id: int = PAD_TOKEN_ID, model_max_length: int = 2048, backbones: Sequence[str] = ("siglip",),
-                 out_dtype=torch.bfloat16, image_size: int = 224):
+                 out_dtype=torch.bfloat16, image_size: int = 224, resize: str = "bicubic"):
+        """``resize``: how pixels() brings frames that are not at ``image_size`` there - "bicubic", the processor's Pillow resize
+        (resize()), or "lanczos3", the RLDS stage's tf.image.resize(method="lanczos3", antialias=True) (lanczos3_resize(), DESIGN.md
+        section 20)."""
+        if resize not in RESIZE_MODES:
+            raise ValueError(f"GPUInputStage: resize is one of {RESIZE_MODES}, got {resize!r}")
+        self.resize_mode = resize
         self.device, self.tokenizer_len, self.pad, self.max_len = device, tokenizer_len, pad_token_id, model_max_length
         self.lo, self.hi = float(min_action), float(max_action)
         self.bins = torch.from_numpy(np.linspace(min_action, max_action, n_bins)).to(device)       # f64, numpy's own edges
@@ -198,6 +270,8 @@ class GPUInputStage:
         self.image_size = image_size
         self._taps = {}
         self._stats = {}
+        self._spans = {}
+        self._qtabs = {}
 
     def resize(self, frames_u8: torch.Tensor, out_h: int = 224, out_w: int = 224) -> torch.Tensor:
         """uint8 [B, H, W, 3] -> uint8 [B, out_h, out_w, 3], bit-identical to PIL.Image.resize((out_w, out_h), BICUBIC): horizontal
@@ -225,6 +299,60 @@ class GPUInputStage:
             cur = nxt
         return cur
 
+    def lanczos3_resize(self, frames_u8: torch.Tensor, out_h: int = 224, out_w: int = 224) -> torch.Tensor:
+        """uint8 [B, H, W, 3] -> uint8 [B, out_h, out_w, 3]: tf.image.resize(method="lanczos3", antialias=True), rounded half to even
+        and clipped, as the reference's RLDS stage (obs_transforms.py:75) and its evaluators (resize_image_for_policy) apply it.  Two
+        HIP passes, the vertical one first, float32 sums over the spans of tf_lanczos3_spans(); bit-identical to the numpy rule of
+        tests/policy_image_rule_np.py.  TF itself is not pinned: its last bits and its pass order are unconfirmed (DESIGN.md section
+        20).  A side that does not change is not resampled; frames already at the size come back as they are, nothing launched."""
+        fr = frames_u8.to(self.device)
+        if fr.dim() != 4 or fr.dtype != torch.uint8 or fr.shape[3] != 3:
+            raise ValueError(f"lanczos3_resize: frames are uint8 [B, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
+        B, H, W, _ = fr.shape
+        if (H, W) == (out_h, out_w):
+            return fr
+
+        def spans(n_in, n_out):
+            if n_in == n_out:
+                return None
+            key = (n_in, n_out)
+            if key not in self._spans:
+                st, w = tf_lanczos3_spans(n_in, n_out)
+                self._spans[key] = (torch.from_numpy(st.copy()).to(self.device), torch.from_numpy(w.copy()).to(self.device))
+            return self._spans[key]
+        return ops.policy_lanczos3_resize(fr.contiguous(), out_h, out_w, spans(H, out_h), spans(W, out_w))
+
+    def jpeg_round_trip(self, frames_u8: torch.Tensor, quality: int = 95) -> torch.Tensor:
+        """uint8 [B, H, W, 3] -> uint8 of the same shape: what saving every frame as a baseline 4:2:0 JPEG file of ``quality`` and
+        decoding it again gives (tf.image.encode_jpeg, then tf.io.decode_image, of resize_image_for_policy), bit-identical to Pillow /
+        libjpeg-turbo.  No file is written: the entropy coding is lossless and left out.  H and W must be multiples of 16 (ValueError)."""
+        fr = frames_u8.to(self.device)
+        if fr.dim() != 4 or fr.dtype != torch.uint8 or fr.shape[3] != 3:
+            raise ValueError(f"jpeg_round_trip: frames are uint8 [B, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
+        if fr.shape[1] % 16 or fr.shape[2] % 16 or fr.shape[1] < 16 or fr.shape[2] < 16:
+            raise ValueError(f"jpeg_round_trip: frames of {fr.shape[1]} x {fr.shape[2]}: H and W must be multiples of 16 (libjpeg's edge "
+                             "replication for partial MCUs is not built)")
+        q = int(quality)
+        if q not in self._qtabs:
+            self._qtabs[q] = torch.from_numpy(jpeg_quant_tables(q).view(np.int16).copy()).to(self.device)
+        return ops.policy_jpeg_round_trip(fr.contiguous(), self._qtabs[q])
+
+    def policy_frames(self, frames_u8, size: Optional[int] = None, quality: int = 95) -> torch.Tensor:
+        """The evaluator's resize_image_for_policy (experiments/robot/openvla_utils.py:542-565) for a batch, on the device: frames_u8
+        uint8 [B, n_img, H, W, 3], or the list form pixels() takes -> uint8 [B, n_img, size, size, 3] (default size: image_size):
+        jpeg_round_trip(quality), then lanczos3_resize.  Nothing is read back.  Pinned: the round trip to Pillow / libjpeg-turbo, the
+        resize to the numpy rule; not pinned: TF's own bits."""
+        size = self.image_size if size is None else int(size)
+        if isinstance(frames_u8, torch.Tensor) and frames_u8.dim() == 5:
+            fr = frames_u8.to(self.device)
+        else:
+            fr = torch.stack([f.to(self.device) for f in frames_u8], 1)
+        if fr.dim() != 5 or fr.dtype != torch.uint8 or fr.shape[4] != 3:
+            raise ValueError(f"policy_frames: frames are uint8 [B, n_img, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
+        B, n_img, H, W, _ = fr.shape
+        flat = fr.contiguous().view(B * n_img, H, W, 3)
+        return self.lanczos3_resize(self.jpeg_round_trip(flat, quality), size, size).view(B, n_img, size, size, 3)
+
     def tokenize_actions(self, actions: torch.Tensor) -> torch.Tensor:
         """[..., action_dim] f32 on the device -> int64 token ids (same shape)."""
         return ops.action_tokenize(actions.to(self.device, torch.float32).contiguous(), self.bins, self.tokenizer_len, self.lo, self.hi)
@@ -250,7 +378,8 @@ class GPUInputStage:
         else:
             stacked = None
         if tuple(frames_u8[0].shape[1:3]) != (self.image_size, self.image_size):       # apply_transform: resize first
-            frames_u8 = [self.resize(f, self.image_size, self.image_size) for f in frames_u8]
+            first = self.lanczos3_resize if self.resize_mode == "lanczos3" else self.resize
+            frames_u8 = [first(f, self.image_size, self.image_size) for f in frames_u8]
             stacked = None
         B, H, W, _ = frames_u8[0].shape
         nb = len(self.norm)

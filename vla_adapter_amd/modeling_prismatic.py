@@ -182,7 +182,7 @@ class OpenVLAForActionPrediction:
 
     def predict_actions(self, prompt_ids, *, pixel_values=None, frames_u8=None, center_crop: bool = False, proprio=None,
                         proprio_normalized: bool = False, unnorm_key=None, action_head=True, proprio_projector=True, L=None,
-                        return_tensors: bool = False, use_film: bool = False, noisy_action_projector=None):
+                        return_tensors: bool = False, use_film: bool = False, noisy_action_projector=None, policy_resize: bool = False):
         """predict_action for a batch: B observations, prompts of different lengths, one forward.  Returns (un-normalised actions
         float64 ndarray [B, chunk, action_dim], action hidden states [B, 1, 64, D] of the last layer) - row b is what
         predict_action returns for sample b alone (same layout per row; the bf16 sums of the head run in a batch-dependent order, so
@@ -194,9 +194,16 @@ class OpenVLAForActionPrediction:
         one that does not fit L raise ValueError; with offsets already on the device nothing is read back, L must be given, and such a
         row comes back as NaN actions (row_ok, include/vla_serve.h).
         Exactly one of pixel_values ([B, C, H, W], already processed) / frames_u8 (raw uint8 frames as GPUInputStage.pixels takes
-        them; center_crop: the evaluator's crop first).  Frames are resized by the Pillow-bicubic path of the input stage
-        ("resize-naive", the processor's own); the evaluator's TF lanczos3 resize after a JPEG round trip
-        (experiments/robot/openvla_utils.py: resize_image_for_policy) is NOT reproduced.
+        them; center_crop: the evaluator's crop first).  Frames that are not at the model's size are resized by the Pillow-bicubic path
+        of the input stage ("resize-naive", the processor's own).
+        policy_resize (frames_u8 only; with pixel_values: ValueError): the evaluator's resize_image_for_policy
+        (experiments/robot/openvla_utils.py:542-565) runs on the frames first - GPUInputStage.policy_frames: a JPEG round trip at quality
+        95, then TF's lanczos3 resize with antialiasing to the model's size - and then center_crop and the processor, which is the
+        evaluator's order.  Pinned: the round trip, bit for bit, to Pillow / libjpeg-turbo (4:2:0, islow, fancy upsampling); the resize,
+        bit for bit, to the float32 numpy rule of tests/policy_image_rule_np.py, which stays within one grey level of Pillow's LANCZOS on
+        band-limited frames.  Not pinned (TensorFlow is not available to compare with): TF's own last bits, the order of the two
+        resize passes (vertical first here), numpy's sin against glibc's sinf in the weights, and that tf.image.encode_jpeg /
+        tf.io.decode_image run libjpeg with exactly those defaults.  H and W of the frames must be multiples of 16.
         proprio [B, Pd]: raw, normalised on the device with norm_stats[key]["proprio"] (the evaluator's normalize_proprio), or
         already normalised (proprio_normalized=True).  action_head / proprio_projector: as in predict_action.
         return_tensors: device tensors (actions f64 [B, chunk, action_dim]) and no host synchronisation on a replayed shape."""
@@ -207,6 +214,8 @@ class OpenVLAForActionPrediction:
             raise NotImplementedError("discrete-token action prediction needs the lm_head (SURVEY 8f-4); pass the L1 regression head")
         if (pixel_values is None) == (frames_u8 is None):
             raise ValueError("predict_actions: pass exactly one of pixel_values / frames_u8")
+        if policy_resize and frames_u8 is None:
+            raise ValueError("predict_actions: policy_resize works on raw frames (frames_u8); pixel_values are already processed")
         if proprio is None or proprio_projector is None:
             raise ValueError("predict_actions: the regression head dereferences proprio and its projector (action_heads.py:53-54)")
         from . import input_stage as IS
@@ -217,6 +226,8 @@ class OpenVLAForActionPrediction:
         key = self._check_unnorm_key(self.norm_stats, unnorm_key)
         kind = K.ACTION_PROPRIO_NORMALIZATION_TYPE
         B = tok["input_ids"].shape[0]
+        if policy_resize:
+            frames_u8 = stage.policy_frames(frames_u8)
         px = stage.pixels(frames_u8, center_crop=center_crop) if frames_u8 is not None else pixel_values.to(dev).contiguous()
         if proprio_normalized:
             import numpy as np

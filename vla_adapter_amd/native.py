@@ -210,6 +210,15 @@ JPEG_INDEX_PROTOS = {
 }
 JPEG_INDEX_SYMBOLS = sorted(JPEG_INDEX_PROTOS)
 
+# the evaluator's frame pipeline (include/vla_policy_image.h, csrc/policy_image.hip): a ninth table, bound by name in the same way
+# (tests/test_policy_image_cpu.py checks header, table and library against each other)
+POLICY_IMAGE_PROTOS = {
+    "vla_policy_image_workspace_bytes": ([_L, _I, _I, _I, _I, _I], _L),
+    "vla_policy_jpeg_round_trip": ([_P, _P, _L, _L, _I, _I, _P, _P, _L, _P, _L], _I),
+    "vla_policy_lanczos3_resize": ([_P, _P, _L, _L, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _L, _P], _I),
+}
+POLICY_IMAGE_SYMBOLS = sorted(POLICY_IMAGE_PROTOS)
+
 _lib = None
 
 
@@ -223,7 +232,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()) + list(HELDOUT_PROTOS.items()) + list(DIGEST_PROTOS.items()) + list(JPEG_PROTOS.items()) + list(JPEG_INDEX_PROTOS.items()):
+    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()) + list(HELDOUT_PROTOS.items()) + list(DIGEST_PROTOS.items()) + list(JPEG_PROTOS.items()) + list(JPEG_INDEX_PROTOS.items()) + list(POLICY_IMAGE_PROTOS.items()):
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

@@ -1218,3 +1218,67 @@ def state_digest(t: torch.Tensor, salt: int = 0, out: Optional[torch.Tensor] = N
 def digest_value(d) -> int:
     """The unsigned 64-bit value of a digest (an int64 [1] tensor of state_digest, or its .item()): a host sync for a tensor."""
     return int(d.item() if isinstance(d, torch.Tensor) else d) & (2 ** 64 - 1)
+
+
+# ---- the evaluator's frame pipeline (include/vla_policy_image.h, csrc/policy_image.hip) ----------------------------------------------
+def _frames_nhwc(frames: torch.Tensor, what: str):
+    """uint8 [N, H, W, 3] on the device whose images are contiguous (the images themselves may be a stride apart) -> (N, H, W, stride)."""
+    if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3):
+        raise ValueError(f"{what}: frames are uint8 [N, H, W, 3] on the device, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
+    n, H, W, _ = frames.shape
+    if n < 1 or frames.stride()[1:] != (W * 3, 3, 1) or (n > 1 and frames.stride(0) < H * W * 3):
+        raise ValueError(f"{what}: every image must be contiguous ({H} x {W} x 3), at least one image apart; strides {frames.stride()}")
+    return n, H, W, (frames.stride(0) if n > 1 else H * W * 3)
+
+
+def policy_jpeg_round_trip(frames: torch.Tensor, qtab: torch.Tensor, out: Optional[torch.Tensor] = None,
+                           workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vla_policy_jpeg_round_trip: uint8 [N, H, W, 3] (images a stride apart) -> uint8 of the same shape, the pixels a 4:2:0 baseline
+    JPEG file of each frame decodes to.  qtab: int16 [2, 64] on the device, the luminance and chrominance quantisation tables in
+    natural order (input_stage.jpeg_quant_tables).  H and W must be multiples of 16: ValueError otherwise."""
+    n, H, W, stride = _frames_nhwc(frames, "policy_jpeg_round_trip")
+    need = _lib().vla_policy_image_workspace_bytes(n, H, W, 0, 0, 1)
+    if need < 0:
+        raise ValueError(f"policy_jpeg_round_trip: {n} frames of {H} x {W} are refused: H and W must be multiples of 16 inside [16, 4096] "
+                         "(a frame whose edge MCUs are partial would need libjpeg's edge replication, which is not built)")
+    assert qtab.is_cuda and qtab.dtype == torch.int16 and tuple(qtab.shape) == (2, 64) and qtab.is_contiguous(), "qtab: int16 [2, 64] on the device"
+    if out is None:
+        out = torch.empty(n, H, W, 3, device=frames.device, dtype=torch.uint8)
+    _, oh, ow, ostride = _frames_nhwc(out, "policy_jpeg_round_trip (out)")
+    assert (out.shape[0], oh, ow) == (n, H, W) and out.device == frames.device
+    if workspace is None:
+        workspace = torch.empty(need, device=frames.device, dtype=torch.uint8)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == frames.device
+    N.check(_lib().vla_policy_jpeg_round_trip(_st(), _p(frames), stride, n, H, W, _p(qtab), _p(workspace), workspace.numel(), _p(out), ostride),
+            "policy_jpeg_round_trip")
+    return out
+
+
+def policy_lanczos3_resize(frames: torch.Tensor, out_h: int, out_w: int, spans_v, spans_h, out: Optional[torch.Tensor] = None,
+                           workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vla_policy_lanczos3_resize: uint8 [N, H, W, 3] (images a stride apart) -> uint8 [N, out_h, out_w, 3], tf.image.resize(method =
+    "lanczos3", antialias=True) rounded and clamped.  spans_v / spans_h: (starts int32 [out_len], weights f32 [out_len, span]) on the
+    device for H -> out_h and W -> out_w (input_stage.tf_lanczos3_spans); None for a side that does not change.  At least one side
+    must change (the caller returns the frames as they are otherwise)."""
+    n, H, W, stride = _frames_nhwc(frames, "policy_lanczos3_resize")
+    need = _lib().vla_policy_image_workspace_bytes(n, H, W, int(out_h), int(out_w), 0)
+    if need < 0:
+        raise ValueError(f"policy_lanczos3_resize: {n} frames of {H} x {W} -> {out_h} x {out_w} are refused (sides inside [1, 4096], one must change)")
+
+    def tab(sp, n_out, changes):
+        if not changes:
+            return None, None, 0
+        st, w = sp
+        assert st.is_cuda and st.dtype == torch.int32 and st.is_contiguous() and st.numel() == n_out, "starts: int32 [out_len] on the device"
+        assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 2 and w.shape[0] == n_out, "weights: f32 [out_len, span]"
+        return st, w, int(w.shape[1])
+    sv, wv, kv = tab(spans_v, out_h, H != out_h)
+    sh, wh, kh = tab(spans_h, out_w, W != out_w)
+    if out is None:
+        out = torch.empty(n, out_h, out_w, 3, device=frames.device, dtype=torch.uint8)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, out_h, out_w, 3)
+    if workspace is None and need:
+        workspace = torch.empty(need, device=frames.device, dtype=torch.uint8)
+    N.check(_lib().vla_policy_lanczos3_resize(_st(), _p(frames), stride, n, H, W, int(out_h), int(out_w), _p(sv), _p(wv), kv, _p(sh), _p(wh), kh,
+                                              _p(workspace), workspace.numel() if workspace is not None else 0, _p(out)), "policy_lanczos3_resize")
+    return out

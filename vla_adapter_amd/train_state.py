@@ -103,7 +103,7 @@ def fingerprint(cfg, mode: str, world: int, n_img: int, batches_given: bool = Fa
     """The flags that define the trajectory.  Two runs with equal fingerprints, equal weights and equal state take the same steps."""
     kind, path = source_of(cfg, batches_given)
     lora = mode == "lora"
-    return dict(
+    fp = dict(
         seed=int(cfg.seed), batch_size=int(cfg.batch_size), grad_accumulation_steps=int(cfg.grad_accumulation_steps),
         learning_rate=float(cfg.learning_rate), lr_warmup_steps=float(cfg.lr_warmup_steps), num_steps_before_decay=int(cfg.num_steps_before_decay),
         mode=mode, lora_rank=int(cfg.lora_rank) if lora else None, lora_dropout=float(cfg.lora_dropout) if lora else None,
@@ -116,6 +116,9 @@ def fingerprint(cfg, mode: str, world: int, n_img: int, batches_given: bool = Fa
         world_size=int(world), phase=str(cfg.phase), use_graph=bool(cfg.use_graph), conservative_rows=bool(cfg.conservative_rows),
         backbone=cfg.backbone, tiny=bool(cfg.tiny), use_pro_version=bool(cfg.use_pro_version), num_images_in_input=int(n_img),
         ddp_algo=str(cfg.ddp_algo))
+    if getattr(cfg, "frame_resize", "bicubic") != "bicubic":      # (only when it is not the default: a state written before the flag existed resumes)
+        fp["frame_resize"] = str(cfg.frame_resize)
+    return fp
 
 
 def fingerprint_differences(recorded: dict, current: dict) -> list:
