@@ -1,5 +1,4 @@
-"""The arena helper's own tests, on CPU tensors (tests/arena.py), and the completeness guard of the memory-contract module: every
-symbol of the native signature table is named by a case there or by its EXEMPT table."""
+"""The arena helper's own tests, on CPU tensors (tests/arena.py)."""
 import pytest
 import torch
 
@@ -134,19 +133,3 @@ def test_set_records_a_new_state():
     a.set(torch.full((3, 8), 2.0, dtype=BF))
     a.assert_unchanged()
     assert a.ptr(1, 2) == a.view.data_ptr() + (16 + 2) * 2
-
-
-# ---------------------------------------------------------------------------------------------------------------- completeness guard
-def test_every_native_symbol_has_a_memory_contract_case_or_an_exemption():
-    from tests import test_memory_contract_gpu as M
-    from vla_adapter_amd import native
-    table = set(native._PROTOS)
-    covered, exempt = set(M.COVERED), set(M.EXEMPT)
-    assert not (covered | exempt) - table, f"names that are no entry points: {sorted((covered | exempt) - table)}"
-    assert not covered & exempt, f"both tested and exempt: {sorted(covered & exempt)}"
-    assert not table - covered - exempt, f"entry points with neither a case nor an exemption: {sorted(table - covered - exempt)}"
-    for name, reason in M.EXEMPT.items():
-        assert isinstance(reason, str) and 4 <= len(reason) and "\n" not in reason, f"{name}: a one-line reason"
-    for name, tests in M.COVERED.items():
-        for t in tests:
-            assert callable(getattr(M, t, None)), f"{name}: case {t} does not exist"

@@ -1,6 +1,5 @@
 """Image augmentation without a GPU: the fine-tune flags, the ABI 7 entry points and their host-side argument validation."""
 import ctypes
-import os
 
 import pytest
 
@@ -9,11 +8,8 @@ from vla_adapter_amd import finetune as F
 
 @pytest.fixture(scope="module")
 def lib():
-    from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return native.load()
+    from tests.abi_headers import load_library
+    return load_library()
 
 
 def test_image_aug_is_honoured_with_a_frame_source(tmp_path):
@@ -69,7 +65,7 @@ def test_library_exports_the_augment_entry_points_at_abi_8(lib):
     from vla_adapter_amd import native
     assert lib.vla_version() == native.ABI_VERSION == 8          # (the augment entry points arrived in ABI 7)
     for name in ("vla_augment_slab_floats", "vla_augment_stats", "vla_augment_apply"):
-        assert name in native.ABI_SYMBOLS and hasattr(lib, name)
+        assert name in native.family("native").protos and hasattr(lib, name)
     # 224 x 224: 28 units of 8 pixels per row, 224 rows -> 25 chunks of 256 units per image, 3 channel sums each
     assert lib.vla_augment_slab_floats(64, 224, 224) == 64 * 25 * 3
     assert lib.vla_augment_slab_floats(0, 224, 224) == -1

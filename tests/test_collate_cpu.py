@@ -10,17 +10,14 @@ import pytest
 from vla_adapter_amd import finetune as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("vla_normalize_bounds", "vla_collate_tokens")
+NEW_ENTRY_POINTS = ("vla_normalize_bounds", "vla_collate_tokens")
 PROMPT_LENS = [2, 3, 9, 40, 51]
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return native.load()
+    from tests.abi_headers import load_library
+    return load_library()
 
 
 def test_raw_batch_file_is_accepted_with_statistics(tmp_path):
@@ -88,9 +85,9 @@ def test_new_symbols_in_header_binding_and_library(lib):
     from vla_adapter_amd import native
     txt = open(os.path.join(ROOT, "include", "vla_native.h")).read()
     code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    for name in NEW_SYMBOLS:
+    for name in NEW_ENTRY_POINTS:
         assert re.search(r"\b%s\s*\(" % name, code), f"{name} is not declared in vla_native.h"
-        assert name in native.ABI_SYMBOLS and hasattr(lib, name)
+        assert name in native.family("native").protos and hasattr(lib, name)
         assert name in re.search(r"Added since without a version change.*?\*/", txt, flags=re.S).group(0)
     assert lib.vla_version() == native.ABI_VERSION == int(re.search(r"#define VLA_ABI_VERSION (\d+)", txt).group(1))
 

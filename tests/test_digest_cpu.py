@@ -1,26 +1,13 @@
-"""CPU checks of the state digest (include/vla_digest.h): the sixth header against its signature table and the
-built library, the untouched earlier tables, the host wrapper's refusals, and the rule itself in numpy (tests/digest_rule_np.py) -
+"""CPU checks of the state digest (include/vla_digest.h): the ordered token-CE sum's signature beside
+vla_token_ce_metrics', the entry points' and the host wrapper's refusals, and the rule itself in numpy (tests/digest_rule_np.py) -
 vectorised form against plain Python integers, sensitivity to a swap, to a +1 / -1 pair and to an appended zero word, independence of
 the summation order, independence of where the view lies."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 from tests import digest_rule_np as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "vla_digest.h")
 SIZES = [1, 3, 4, 5, 7, 8, 9, 65539]
-
-
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def header_symbols():
-    return sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", header_text())))
 
 
 def words(n, seed=0):
@@ -29,61 +16,17 @@ def words(n, seed=0):
 
 @pytest.fixture(scope="module")
 def lib():
+    from tests.abi_headers import load_library
+    return load_library()
+
+
+def test_the_ordered_sum_takes_token_ce_metrics_operands_and_the_per_row_terms():
     from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return native.load()
-
-
-# ---------------------------------------------------------------------------------------------------------------- the six tables
-def test_digest_header_and_binding_agree():
-    from vla_adapter_amd import native
-    assert header_symbols() == native.DIGEST_SYMBOLS == sorted(native.DIGEST_PROTOS) == ["vla_state_digest", "vla_state_digest_slots", "vla_token_ce_metrics_ordered"]
-    for other in (native._PROTOS, native.SERVE_PROTOS, native.EPISODE_PROTOS, native.MIXTURE_PROTOS, native.HELDOUT_PROTOS):
-        assert not set(native.DIGEST_PROTOS) & set(other), "an entry point belongs to one header"
-
-
-def test_digest_signatures_match_the_header_argument_counts():
-    from vla_adapter_amd import native
-    protos = re.findall(r"\bint\s+(vla_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header_text())
-    assert sorted(n for n, _ in protos) == native.DIGEST_SYMBOLS
-    for name, params in protos:
-        count = 0 if params.strip() in ("", "void") else len(params.split(","))
-        assert count == len(native.DIGEST_PROTOS[name][0]), name
-    assert len(native.DIGEST_PROTOS["vla_state_digest"][0]) == 7 and len(native.DIGEST_PROTOS["vla_state_digest_slots"][0]) == 0
-    # the ordered token-CE sum takes vla_token_ce_metrics' operands and one more: the per-row terms
-    assert native.DIGEST_PROTOS["vla_token_ce_metrics_ordered"][0][:-1] == native._PROTOS["vla_token_ce_metrics"][0]
-    assert len(native.DIGEST_PROTOS["vla_token_ce_metrics_ordered"][0]) == 13
-
-
-def test_the_earlier_tables_are_unchanged():
-    from vla_adapter_amd import native
-    txt = open(os.path.join(ROOT, "include", "vla_native.h")).read()
-    assert native.ABI_VERSION == 8 == int(re.search(r"#define VLA_ABI_VERSION (\d+)", txt).group(1))
-    tabs = (native._PROTOS, native.SERVE_PROTOS, native.EPISODE_PROTOS, native.MIXTURE_PROTOS, native.HELDOUT_PROTOS)
-    assert tuple(len(t) for t in tabs) == (69, 4, 2, 2, 2)
-    for tab in tabs:
-        assert not [k for k in tab if "digest" in k]
-
-
-def test_library_exports_both_symbols(lib):
-    from vla_adapter_amd import native
-    for name in header_symbols():
-        fn = getattr(lib, name, None)
-        assert fn is not None, f"libvla_native.so does not export {name}"
-        args, res = native.DIGEST_PROTOS[name]
-        assert list(fn.argtypes) == list(args) and fn.restype is res, f"{name}: native.load() binds the table's signature"
-    mk = open(os.path.join(ROOT, "vla_adapter_amd", "csrc", "Makefile")).read()
-    assert "digest.hip" in mk and "vla_digest.h" in mk
-    assert lib.vla_state_digest_slots() >= 1
-    P = 64
-    assert lib.vla_token_ce_metrics_ordered(None, P, 16, P, P, 3, 11, P, P, None, 12, 8, None) == -1 and b"terms" in lib.vla_last_error()
-    assert lib.vla_token_ce_metrics_ordered(None, P, 16, P, P, 0, 11, P, P, None, 12, 8, P) == -1
+    assert native.family("digest").protos["vla_token_ce_metrics_ordered"][0][:-1] == native.family("native").protos["vla_token_ce_metrics"][0]
 
 
 def test_host_checks_refuse_bad_arguments(lib):
-    """The entry point's own argument checks answer before anything is launched (no device needed)."""
+    """The entry points' own argument checks answer before anything is launched (no device needed)."""
     P = 64
     dg = lambda **kw: lib.vla_state_digest(None, kw.get("x", P), kw.get("n", 8), 0, kw.get("scratch", P), kw.get("slots", 4), kw.get("out", P))
     assert dg(n=0) == -1 and b"n >= 1" in lib.vla_last_error()
@@ -95,6 +38,9 @@ def test_host_checks_refuse_bad_arguments(lib):
     assert dg(scratch=68) == -1 and b"8-byte" in lib.vla_last_error()
     assert dg(scratch=None, slots=4) == -1 and b"null scratch" in lib.vla_last_error()
     assert dg(slots=-1) == -1
+    assert lib.vla_state_digest_slots() >= 1
+    assert lib.vla_token_ce_metrics_ordered(None, P, 16, P, P, 3, 11, P, P, None, 12, 8, None) == -1 and b"terms" in lib.vla_last_error()
+    assert lib.vla_token_ce_metrics_ordered(None, P, 16, P, P, 0, 11, P, P, None, 12, 8, P) == -1
 
 
 def test_the_wrapper_refuses_an_empty_or_wide_operand():
@@ -200,15 +146,3 @@ def test_the_digest_does_not_depend_on_where_the_view_lies():
         buf = words(1001 + 8, seed=10)
         buf[off:off + 1001] = w
         assert R.digest(buf[off:off + 1001]) == R.digest(w)
-
-
-def test_every_digest_symbol_has_a_memory_contract_case_or_an_exemption():
-    from tests import test_digest_gpu as M
-    from vla_adapter_amd import native
-    table = set(native.DIGEST_PROTOS)
-    covered, exempt = set(M.COVERED), set(M.EXEMPT)
-    assert not (covered | exempt) - table and not covered & exempt and not table - covered - exempt
-    assert "test_state_digest_contract" in M.COVERED["vla_state_digest"] and "test_token_ce_metrics_ordered_contract" in M.COVERED["vla_token_ce_metrics_ordered"]
-    for name, tests in M.COVERED.items():
-        for t in tests:
-            assert callable(getattr(M, t, None)), f"{name}: case {t} does not exist"

@@ -4,13 +4,13 @@ starting 0, 1, 3 and 8 words into a buffer (16-byte loads / word by word), two s
 on poisoned arenas by the procedure of tests/test_memory_contract_gpu.py - nothing outside ``out`` and the scratch is written, no
 input changes, a read past the view would meet a NaN.  The header's third entry, vla_token_ce_metrics_ordered, against the atomic
 form on the same operands, against its fixed summation order restated in numpy (bit for bit, run after run), and its memory contract.
-COVERED / EXEMPT: tests/test_digest_cpu.py checks on the CPU that they cover native.DIGEST_PROTOS."""
+COVERED / EXEMPT: tests/test_abi_families.py checks on the CPU that they cover the "digest" family of native.FAMILIES."""
 import numpy as np
 import pytest
 import torch
 
 from tests import digest_rule_np as R
-from tests.test_memory_contract_gpu import F32, I32, I64, U8, call, contract, gen, st2
+from tests.test_memory_contract_gpu import F32, I32, I64, U8, call, case_for, contract, gen, st2
 from vla_adapter_amd import ops
 
 COVERED = {}
@@ -19,12 +19,7 @@ SIZES = [1, 3, 4, 5, 7, 8, 9, 65539, 2 ** 22 + 5]
 SALTS = (0, 0xDEADBEEFCAFEF00D)
 
 
-def case(*symbols):
-    def deco(fn):
-        for s in symbols:
-            COVERED.setdefault(s, []).append(fn.__name__)
-        return pytest.mark.gpu(fn)
-    return deco
+case = case_for(COVERED)
 
 
 _WORDS = {}

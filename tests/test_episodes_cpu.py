@@ -1,7 +1,6 @@
-"""CPU checks of training from device-resident episodes (vla_adapter_amd/episodes.py, include/vla_episodes.h): the third header against
-its signature table and the built library, the untouched training ABI, the sampling rule in plain Python - bijection, exactly-once
-epochs, the reference's action windows - the statistics against numpy, the refusals that need no device, and the completeness guard
-of tests/test_episodes_memory_contract_gpu.py."""
+"""CPU checks of training from device-resident episodes (vla_adapter_amd/episodes.py, include/vla_episodes.h): the sampling rule in plain
+Python - bijection, exactly-once epochs, the reference's action windows - the statistics against numpy, and the refusals that need no
+device."""
 import os
 import re
 
@@ -12,26 +11,14 @@ import torch
 from vla_adapter_amd import episodes as EP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "vla_episodes.h")
 LENGTHS = [1, 7, 8, 9, 20]                 # episodes of the issue's store: 0, 0, 1, 2 and 13 windows at chunk 8
 CHUNK = 8
 
 
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def header_symbols():
-    return sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", header_text())))
-
-
 @pytest.fixture(scope="module")
 def lib():
-    from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return native.load()
+    from tests.abi_headers import load_library
+    return load_library()
 
 
 def make_tables(lengths=LENGTHS, prompt_lens=(3, 0, 11, 5, 7), n_img=2, hw=8, A=7, Pd=8, seed=0, **extra):
@@ -45,43 +32,6 @@ def make_tables(lengths=LENGTHS, prompt_lens=(3, 0, 11, 5, 7), n_img=2, hw=8, A=
              prompt_off=torch.tensor(np.cumsum([0] + list(prompt_lens)), dtype=torch.int32))
     d.update(extra)
     return d
-
-
-# ---------------------------------------------------------------------------------------------------------------- the three tables
-def test_episode_header_and_binding_agree():
-    from vla_adapter_amd import native
-    assert header_symbols() == native.EPISODE_SYMBOLS == sorted(native.EPISODE_PROTOS) == ["vla_episode_gather", "vla_episode_sample"]
-    assert not set(native.EPISODE_PROTOS) & set(native._PROTOS), "an entry point belongs to one header"
-    assert not set(native.EPISODE_PROTOS) & set(native.SERVE_PROTOS), "an entry point belongs to one header"
-
-
-def test_library_exports_every_episode_symbol(lib):
-    from vla_adapter_amd import native
-    for name in header_symbols():
-        fn = getattr(lib, name, None)
-        assert fn is not None, f"libvla_native.so does not export {name}"
-        args, res = native.EPISODE_PROTOS[name]
-        assert list(fn.argtypes) == list(args) and fn.restype is res, f"{name}: native.load() binds the table's signature"
-
-
-def test_episode_signatures_match_the_header_argument_counts():
-    """Each prototype of the header has as many parameters as its ctypes signature (a dropped or added argument shifts every later one)."""
-    from vla_adapter_amd import native
-    protos = re.findall(r"\bint\s+(vla_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header_text())
-    assert sorted(n for n, _ in protos) == native.EPISODE_SYMBOLS
-    for name, params in protos:
-        assert len(params.split(",")) == len(native.EPISODE_PROTOS[name][0]), name
-
-
-def test_training_abi_is_unchanged():
-    from vla_adapter_amd import native
-    txt = open(os.path.join(ROOT, "include", "vla_native.h")).read()
-    assert native.ABI_VERSION == 8 == int(re.search(r"#define VLA_ABI_VERSION (\d+)", txt).group(1))
-    assert native.ABI_SYMBOLS == sorted(list(native._PROTOS) + ["vla_last_error"])
-    assert len(native._PROTOS) == 69 and not [k for k in native._PROTOS if "episode" in k]
-    assert len(native.SERVE_PROTOS) == 4 and not [k for k in native.SERVE_PROTOS if "episode" in k]
-    stripped = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    assert sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", stripped))) == native.ABI_SYMBOLS, "vla_native.h declares the training table only"
 
 
 def largest_step(B, rank, world):
@@ -112,21 +62,6 @@ def test_the_store_refuses_the_overflowing_step_before_the_device():
     st = EP.EpisodeStore.from_dict(make_tables(), "cpu", chunk=CHUNK)
     with pytest.raises(ValueError, match="stream position overflows 63 bits"):
         st.sample_indices(4, 0, 2, 3, largest_step(4, 2, 3) + 1)
-
-
-def test_every_episode_symbol_has_a_memory_contract_case_or_an_exemption():
-    from tests import test_episodes_memory_contract_gpu as M
-    from vla_adapter_amd import native
-    table = set(native.EPISODE_PROTOS)
-    covered, exempt = set(M.COVERED), set(M.EXEMPT)
-    assert not (covered | exempt) - table, f"names that are no episode entry points: {sorted((covered | exempt) - table)}"
-    assert not covered & exempt, f"both tested and exempt: {sorted(covered & exempt)}"
-    assert not table - covered - exempt, f"entry points with neither a case nor an exemption: {sorted(table - covered - exempt)}"
-    for name, reason in M.EXEMPT.items():
-        assert isinstance(reason, str) and 4 <= len(reason) and "\n" not in reason, f"{name}: a one-line reason"
-    for name, tests in M.COVERED.items():
-        for t in tests:
-            assert callable(getattr(M, t, None)), f"{name}: case {t} does not exist"
 
 
 def test_the_window_tail_and_the_tables_are_stated_once():

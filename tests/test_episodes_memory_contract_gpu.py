@@ -2,25 +2,20 @@
 runs on compact operands and then with every device operand a view inside a poisoned arena (tests/arena.py) at the minimum alignment
 its host check accepts; outputs must be bit-equal, inputs unchanged, and nothing written outside the declared extent.  The gather runs
 on both arms: 16-byte chunks (384-byte rows, frames 16-B aligned) and bytes (150-byte rows; and 384-byte rows at a 1-B aligned base).
-COVERED / EXEMPT: tests/test_episodes_cpu.py checks on the CPU that they cover native.EPISODE_PROTOS."""
+COVERED / EXEMPT: tests/test_abi_families.py checks on the CPU that they cover the "episodes" family of native.FAMILIES."""
 import pytest
 import torch
 
 from tests.arena import assert_bits_equal
 from tests.test_episodes_cpu import CHUNK, LENGTHS, make_tables
-from tests.test_memory_contract_gpu import DEV, F32, I32, I64, U8, call, contract
+from tests.test_memory_contract_gpu import DEV, F32, I32, I64, U8, call, case_for, contract
 from vla_adapter_amd import episodes as EP
 
 COVERED = {}
 EXEMPT = {}                      # both entry points have a device footprint
 
 
-def case(*symbols):
-    def deco(fn):
-        for s in symbols:
-            COVERED.setdefault(s, []).append(fn.__name__)
-        return pytest.mark.gpu(fn)
-    return deco
+case = case_for(COVERED)
 
 
 @case("vla_episode_sample")

@@ -7,17 +7,14 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("vla_grad_sumsq_slots", "vla_grad_sumsq", "vla_grad_norm_finalise", "vla_adamw_clipped_bf16")
+NEW_ENTRY_POINTS = ("vla_grad_sumsq_slots", "vla_grad_sumsq", "vla_grad_norm_finalise", "vla_adamw_clipped_bf16")
 BASE = ["--tiny", "true", "--use_proprio", "True"]
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return native.load()
+    from tests.abi_headers import load_library
+    return load_library()
 
 
 def test_config_field_and_flag():
@@ -70,9 +67,9 @@ def test_slot_count_is_monotone_host_arithmetic(lib, monkeypatch):
 def test_new_symbols_in_header_binding_and_library(lib):
     from vla_adapter_amd import native
     txt = open(os.path.join(ROOT, "include", "vla_native.h")).read()
-    for name in NEW_SYMBOLS:
+    for name in NEW_ENTRY_POINTS:
         assert re.search(r"\b%s\s*\(" % name, re.sub(r"/\*.*?\*/", "", txt, flags=re.S)), f"{name} is not declared in vla_native.h"
-        assert name in native.ABI_SYMBOLS and hasattr(lib, name)
+        assert name in native.family("native").protos and hasattr(lib, name)
     assert int(re.search(r"#define VLA_ABI_VERSION (\d+)", txt).group(1)) == native.ABI_VERSION == 8, "added without a version change"
     assert "vla_adamw_clipped_bf16" in re.search(r"Added since without a version change.*?\*/", txt, flags=re.S).group(0)
 

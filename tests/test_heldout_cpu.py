@@ -1,11 +1,8 @@
-"""CPU checks of validation on held-out episodes (vla_adapter_amd/heldout.py, include/vla_heldout.h): the fifth header against its
-signature table and the built library, the untouched earlier tables, the split rule and its refusals, training epochs that never touch
-a held-out episode, the ordered sweep in plain Python - every strided held-out window exactly once over ranks and batches, for a store
-and a mix -, the flags, the report's derivation from hand-made sums, the two-rank merge on gloo, and the completeness guard of
-tests/test_heldout_memory_contract_gpu.py."""
+"""CPU checks of validation on held-out episodes (vla_adapter_amd/heldout.py, include/vla_heldout.h): the entry points' own
+refusals, the split rule and its refusals, training epochs that never touch a held-out episode, the ordered sweep in plain Python - every strided held-out window exactly once over ranks and batches, for a store
+and a mix -, the flags, the report's derivation from hand-made sums, and the two-rank merge on gloo."""
 import math
 import os
-import re
 import socket
 
 import numpy as np
@@ -19,8 +16,6 @@ from vla_adapter_amd import episodes as EP
 from vla_adapter_amd import heldout as HO
 from vla_adapter_amd import mixture as MX
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "vla_heldout.h")
 LENGTHS = [9, 1, 20, 8, 7, 12, 10]          # the issue's store: 2, 0, 13, 1, 0, 5 and 3 windows at chunk 8
 PROMPTS = (3, 0, 11, 5, 7, 2, 6)
 F = 0.4                                     # holds the last 3 episodes out
@@ -50,58 +45,10 @@ def make_pair(device="cpu", holdout=F, **kw):
     return tables, MX.EpisodeMix.from_dicts([(tables[0], 1.0), (tables[1], 1.0)], device, chunk=CHUNK, period=16, holdout=holdout)
 
 
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def header_symbols():
-    return sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", header_text())))
-
-
 @pytest.fixture(scope="module")
 def lib():
-    from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return native.load()
-
-
-# ---------------------------------------------------------------------------------------------------------------- the five tables
-def test_heldout_header_and_binding_agree():
-    from vla_adapter_amd import native
-    assert header_symbols() == native.HELDOUT_SYMBOLS == sorted(native.HELDOUT_PROTOS) == ["vla_heldout_l1_accumulate", "vla_heldout_sweep"]
-    for other in (native._PROTOS, native.SERVE_PROTOS, native.EPISODE_PROTOS, native.MIXTURE_PROTOS):
-        assert not set(native.HELDOUT_PROTOS) & set(other), "an entry point belongs to one header"
-
-
-def test_heldout_signatures_match_the_header_argument_counts():
-    from vla_adapter_amd import native
-    protos = re.findall(r"\bint\s+(vla_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header_text())
-    assert sorted(n for n, _ in protos) == native.HELDOUT_SYMBOLS
-    for name, params in protos:
-        assert len(params.split(",")) == len(native.HELDOUT_PROTOS[name][0]), name
-    assert len(native.HELDOUT_PROTOS["vla_heldout_sweep"][0]) == 18 and len(native.HELDOUT_PROTOS["vla_heldout_l1_accumulate"][0]) == 11
-
-
-def test_the_earlier_tables_are_unchanged():
-    from vla_adapter_amd import native
-    txt = open(os.path.join(ROOT, "include", "vla_native.h")).read()
-    assert native.ABI_VERSION == 8 == int(re.search(r"#define VLA_ABI_VERSION (\d+)", txt).group(1))
-    assert (len(native._PROTOS), len(native.SERVE_PROTOS), len(native.EPISODE_PROTOS), len(native.MIXTURE_PROTOS)) == (69, 4, 2, 2)
-    for tab in (native._PROTOS, native.SERVE_PROTOS, native.EPISODE_PROTOS, native.MIXTURE_PROTOS):
-        assert not [k for k in tab if "heldout" in k]
-
-
-def test_library_exports_both_symbols(lib):
-    from vla_adapter_amd import native
-    for name in header_symbols():
-        fn = getattr(lib, name, None)
-        assert fn is not None, f"libvla_native.so does not export {name}"
-        args, res = native.HELDOUT_PROTOS[name]
-        assert list(fn.argtypes) == list(args) and fn.restype is res, f"{name}: native.load() binds the table's signature"
-    mk = open(os.path.join(ROOT, "vla_adapter_amd", "csrc", "Makefile")).read()
-    assert "heldout.hip" in mk and "vla_heldout.h" in mk
+    from tests.abi_headers import load_library
+    return load_library()
 
 
 def test_host_checks_refuse_bad_arguments(lib):
@@ -119,21 +66,6 @@ def test_host_checks_refuse_bad_arguments(lib):
     assert sweep(j=2 ** 61, stride=8) == -1 and b"overflows" in lib.vla_last_error()
     assert lib.vla_heldout_l1_accumulate(None, P, P, None, P, 0, 8, 7, 1, P, P) == -1 and b">= 1" in lib.vla_last_error()
     assert lib.vla_heldout_l1_accumulate(None, P, P, None, None, 4, 8, 7, 1, P, P) == -1 and b"null" in lib.vla_last_error()
-
-
-def test_every_heldout_symbol_has_a_memory_contract_case_or_an_exemption():
-    from tests import test_heldout_memory_contract_gpu as M
-    from vla_adapter_amd import native
-    table = set(native.HELDOUT_PROTOS)
-    covered, exempt = set(M.COVERED), set(M.EXEMPT)
-    assert not (covered | exempt) - table, f"names that are no held-out entry points: {sorted((covered | exempt) - table)}"
-    assert not covered & exempt, f"both tested and exempt: {sorted(covered & exempt)}"
-    assert not table - covered - exempt, f"entry points with neither a case nor an exemption: {sorted(table - covered - exempt)}"
-    for name, reason in M.EXEMPT.items():
-        assert isinstance(reason, str) and 4 <= len(reason) and "\n" not in reason, f"{name}: a one-line reason"
-    for name, tests in M.COVERED.items():
-        for t in tests:
-            assert callable(getattr(M, t, None)), f"{name}: case {t} does not exist"
 
 
 # ---------------------------------------------------------------------------------------------------------------- the split rule

@@ -3,25 +3,20 @@ tests/test_memory_contract_gpu.py: each runs on compact operands and then with e
 (tests/arena.py) at the minimum alignment its host check accepts - acc at 8 bytes, valid at 1; outputs must be bit-equal, inputs
 unchanged, and nothing written outside the declared extent.  The index tables' arenas are poisoned with in-range values that would
 change the result, pred / target with NaN and valid with 1, so a read one element past an operand shows.
-COVERED / EXEMPT: tests/test_heldout_cpu.py checks on the CPU that they cover native.HELDOUT_PROTOS."""
+COVERED / EXEMPT: tests/test_abi_families.py checks on the CPU that they cover the "heldout" family of native.FAMILIES."""
 import numpy as np
 import pytest
 import torch
 
 from tests.test_heldout_cpu import make_pair, make_store
-from tests.test_memory_contract_gpu import F64, I32, I64, U8, call, contract, gen
+from tests.test_memory_contract_gpu import F64, I32, I64, U8, call, case_for, contract, gen
 from vla_adapter_amd import heldout as HO
 
 COVERED = {}
 EXEMPT = {}                      # both entry points have a device footprint
 
 
-def case(*symbols):
-    def deco(fn):
-        for s in symbols:
-            COVERED.setdefault(s, []).append(fn.__name__)
-        return pytest.mark.gpu(fn)
-    return deco
+case = case_for(COVERED)
 
 
 @case("vla_heldout_sweep")

@@ -2,10 +2,9 @@
 (tests/jpeg_rule_np.py) against Pillow, bit for bit, on the matrix of tests/jpeg_cases.py and on its crafted corpus - files no run of
 Pillow's encoder writes, from the coefficient-level writer tests/jpeg_writer.py, which is pinned here too; the parser - its pools, its
 segment tables, its refusals, each naming the frame, RGB-coded files among them; fill bytes in front of RSTn; the two storage forms
-of an episode dict; concat_shards on JPEG shards; the seventh header against its signature table and the built library; the flag."""
+of an episode dict; concat_shards on JPEG shards; the workspace arithmetic; the flag."""
 import dataclasses
 import os
-import re
 
 import numpy as np
 import pytest
@@ -19,7 +18,6 @@ from vla_adapter_amd import episodes as EP
 from vla_adapter_amd import jpeg_store as JS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "vla_jpeg.h")
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rule
@@ -328,31 +326,7 @@ def test_a_raw_store_is_what_it_was():
     assert st.jpeg is None and torch.equal(st.frames_u8, d["frames_u8"]) and st.frame_shape == (2, 8, 8, 3)
 
 
-# ---------------------------------------------------------------------------------------------------------------- header, table, flag
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def test_jpeg_header_binding_and_library_agree():
-    from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = native.load()
-    names = sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", header_text())))
-    assert names == native.JPEG_SYMBOLS == sorted(native.JPEG_PROTOS) == ["vla_jpeg_decode_rows", "vla_jpeg_workspace_bytes"]
-    for other in (native._PROTOS, native.SERVE_PROTOS, native.EPISODE_PROTOS, native.MIXTURE_PROTOS, native.HELDOUT_PROTOS, native.DIGEST_PROTOS):
-        assert not set(native.JPEG_PROTOS) & set(other), "an entry point belongs to one header"
-    protos = re.findall(r"\b(?:int|long long)\s+(vla_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header_text())
-    assert sorted(n for n, _ in protos) == native.JPEG_SYMBOLS
-    for name, params in protos:
-        args, res = native.JPEG_PROTOS[name]
-        assert len(params.split(",")) == len(args), name
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == list(args) and fn.restype is res
-    assert native.ABI_VERSION == 8 and len(native._PROTOS) == 69 and not [k for k in native._PROTOS if "jpeg" in k]
-
-
+# ---------------------------------------------------------------------------------------------------------------- the entry points, the flag
 def test_workspace_bytes_is_host_arithmetic():
     from vla_adapter_amd import ops
     assert ops.jpeg_workspace_bytes(64, 224, 224, 1) == 64 * 224 * 224 * 3 // 2 * 3        # 1.5 samples per pixel, 2 + 1 bytes each
@@ -372,8 +346,6 @@ def test_the_core_is_stated_once_and_shares_the_row_clamp():
         assert "episode_off[w.e" not in txt and "row[b]" not in txt, "the clamp is episode_row's alone"
     for const in ("4433", "15137", "25172", "91881", "116130"):
         assert const not in jpeg, "the arithmetic lives in jpeg_core.h"
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert "jpeg.hip" in mk and "jpeg_core.h" in mk and "episode_row.h" in mk and "vla_jpeg.h" in mk
 
 
 def test_verify_frames_flag_defaults_to_off():

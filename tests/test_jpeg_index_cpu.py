@@ -1,13 +1,12 @@
 """The scan index of the JPEG store on the host (include/vla_jpeg_index.h, csrc/jpeg_core.h: index_segment and the entry state of
-decode_segment): header, binding and library agree; plan_pieces tiles every segment; a stand-alone program with its own main
-(tests/jpeg_index_cases.py: INDEX_MAIN, compiled with g++ here), plain and with -fsanitize=address,undefined, builds the index of the
-matrix, the crafted corpus and the long corpus at four piece lengths - its entries equal the plain-Python rule's, the piece-wise decode
+decode_segment): the indexed decode takes the plain one's arguments and the entry table; plan_pieces tiles every segment; a stand-alone
+program with its own main (tests/jpeg_index_cases.py: INDEX_MAIN, compiled with g++ here), plain and with
+-fsanitize=address,undefined, builds the index of the matrix, the crafted corpus and the long corpus at four piece lengths - its entries equal the plain-Python rule's, the piece-wise decode
 gives the whole-segment decode's coefficients and Pillow's pixels, every status is 0; the sanitized program ends without a report on
 damaged scans and on hostile tables, with the whole-segment decode's pixels for the former.  Nothing is loaded into Python: the
 sanitizers see the program alone.  What this program computes is what the kernels must compute (tests/test_jpeg_index_gpu.py)."""
 import dataclasses
 import os
-import re
 
 import numpy as np
 import pytest
@@ -16,37 +15,12 @@ from tests import jpeg_cases as JC
 from tests import jpeg_index_cases as IC
 from vla_adapter_amd import jpeg_store as JS
 
-HEADER = os.path.join(JC.ROOT, "include", "vla_jpeg_index.h")
-NAMES = ["vla_jpeg_decode_rows_at", "vla_jpeg_index_build"]
 
-
-# ---------------------------------------------------------------------------------------------------------------- header, table, library
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def test_jpeg_index_header_binding_and_library_agree():
+# ---------------------------------------------------------------------------------------------------------------- the entry points
+def test_the_indexed_decode_takes_the_decodes_arguments_and_the_entry_table():
     from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = native.load()
-    names = sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", header_text())))
-    assert names == native.JPEG_INDEX_SYMBOLS == sorted(native.JPEG_INDEX_PROTOS) == NAMES
-    for other in (native._PROTOS, native.SERVE_PROTOS, native.EPISODE_PROTOS, native.MIXTURE_PROTOS, native.HELDOUT_PROTOS, native.DIGEST_PROTOS, native.JPEG_PROTOS):
-        assert not set(native.JPEG_INDEX_PROTOS) & set(other), "an entry point belongs to one header"
-    protos = re.findall(r"\b(?:int|long long)\s+(vla_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header_text())
-    assert sorted(n for n, _ in protos) == NAMES
-    for name, params in protos:
-        args, res = native.JPEG_INDEX_PROTOS[name]
-        assert len(params.split(",")) == len(args), name
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == list(args) and fn.restype is res
-    # the indexed decode takes the decode's arguments and the entry table
-    at, plain = native.JPEG_INDEX_PROTOS["vla_jpeg_decode_rows_at"][0], native.JPEG_PROTOS["vla_jpeg_decode_rows"][0]
+    at, plain = native.family("jpeg_index").protos["vla_jpeg_decode_rows_at"][0], native.family("jpeg").protos["vla_jpeg_decode_rows"][0]
     assert len(at) == len(plain) + 1 and at[:5] + at[6:] == plain
-    mk = open(os.path.join(JC.ROOT, "vla_adapter_amd", "csrc", "Makefile")).read()
-    assert "jpeg_index.hip" in mk and "vla_jpeg_index.h" in mk
 
 
 def test_the_block_walk_is_stated_once():

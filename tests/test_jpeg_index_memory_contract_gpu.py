@@ -11,21 +11,17 @@ import torch
 
 from tests import jpeg_cases as JC
 from tests import jpeg_index_cases as IC
-from tests.test_memory_contract_gpu import I32, I64, U8, call, contract
+from tests.test_memory_contract_gpu import I32, I64, U8, call, case_for, contract
 from vla_adapter_amd import jpeg_store as JS
 from vla_adapter_amd import ops
 
 COVERED = {}
+EXEMPT = {}                      # both entry points have a device footprint
 H, W, N_IMG, LENGTHS = 32, 48, 2, (1, 3)
 SEG_POISON, ENT_POISON, ST_POISON = 5, 0x01010101, 0x7F
 
 
-def case(*symbols):
-    def deco(fn):
-        for s in symbols:
-            COVERED.setdefault(s, []).append(fn.__name__)
-        return pytest.mark.gpu(fn)
-    return deco
+case = case_for(COVERED)
 
 
 def store(h2v2):
@@ -159,8 +155,3 @@ def test_hostile_tables_give_in_range_results(mapping):
             e = ent[(ent != ENT_POISON).any(1)]
             assert (e[:, 0] >= 0).all() and (e[:, 0] <= 7).all(), f"{name}: entry bits inside a byte"
             assert (st <= 3).all() and (status <= 3).all(), f"{name}: every status is one of the four"
-
-
-def test_every_jpeg_index_symbol_has_a_memory_contract_case():
-    from vla_adapter_amd import native
-    assert set(COVERED) == set(native.JPEG_INDEX_PROTOS)

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from tests import jpeg_cases as JC
-from tests.test_memory_contract_gpu import DEV, I32, I64, U8, call, contract
+from tests.test_memory_contract_gpu import DEV, I32, I64, U8, call, case_for, contract
 from vla_adapter_amd import jpeg_store as JS
 from vla_adapter_amd import ops
 
@@ -16,12 +16,7 @@ COVERED = {}
 EXEMPT = {"vla_jpeg_workspace_bytes": "host arithmetic only: it takes no pointer"}
 
 
-def case(*symbols):
-    def deco(fn):
-        for s in symbols:
-            COVERED.setdefault(s, []).append(fn.__name__)
-        return pytest.mark.gpu(fn)
-    return deco
+case = case_for(COVERED)
 
 
 @case("vla_jpeg_decode_rows")
@@ -59,10 +54,3 @@ def test_jpeg_decode_rows_contract(h2v2, align, pad, mapping):
     assert not rc["status"].any()
     got = rc["frames_u8"].cpu().numpy().reshape(B, n_img, H, W, 3)
     assert np.array_equal(got, want[[0, 3, 2, 0, 3]])
-
-
-def test_every_jpeg_symbol_has_a_memory_contract_case_or_an_exemption():
-    from vla_adapter_amd import native
-    table = set(native.JPEG_PROTOS)
-    covered, exempt = set(COVERED), set(EXEMPT)
-    assert not (covered | exempt) - table and not covered & exempt and not table - covered - exempt

@@ -17,7 +17,7 @@ No case hands an entry point a pointer it should refuse, none places a view at t
 at the end (one row, eight columns too many) stay inside the arenas' margins.
 
 COVERED names the entry points the cases exercise (filled by @case), EXEMPT those without a device footprint;
-tests/test_arena_cpu.py checks on the CPU that the two tables cover the binding's signature table.
+tests/test_abi_families.py checks on the CPU that the two tables cover the family's signature table.
 """
 import ctypes as C
 import math
@@ -46,13 +46,18 @@ EXEMPT = {
 }
 
 
-def case(*symbols):
-    """Marks a GPU case and records the entry points it exercises."""
-    def deco(fn):
-        for s in symbols:
-            COVERED.setdefault(s, []).append(fn.__name__)
-        return pytest.mark.gpu(fn)
-    return deco
+def case_for(covered):
+    """-> the decorator case(*symbols) of one module: it marks a GPU case and records in `covered` the entry points it exercises."""
+    def case(*symbols):
+        def deco(fn):
+            for s in symbols:
+                covered.setdefault(s, []).append(fn.__name__)
+            return pytest.mark.gpu(fn)
+        return deco
+    return case
+
+
+case = case_for(COVERED)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the procedure

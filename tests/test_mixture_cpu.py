@@ -1,8 +1,6 @@
-"""CPU checks of training on a weighted mixture of episode datasets (vla_adapter_amd/mixture.py, include/vla_mixture.h): the fourth
-header against its signature table and the built library, the untouched earlier tables, the quotas, the sampling rule in plain Python -
-exact quotas per period, every ordinal once, every window of a dataset once per N_d ordinals, ranks without gap or overlap - the
-per-dataset statistics, the reference's dataset_len, the refusals that need no device, and the completeness guard of
-tests/test_mixture_memory_contract_gpu.py."""
+"""CPU checks of training on a weighted mixture of episode datasets (vla_adapter_amd/mixture.py, include/vla_mixture.h): the quotas, the
+sampling rule in plain Python - exact quotas per period, every ordinal once, every window of a dataset once per N_d ordinals, ranks without gap or overlap - the
+per-dataset statistics, the reference's dataset_len, and the refusals that need no device."""
 import json
 import math
 import os
@@ -17,7 +15,6 @@ from vla_adapter_amd import episodes as EP
 from vla_adapter_amd import mixture as MX
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "vla_mixture.h")
 NAMES = ("suite_a", "suite_b", "suite_c")
 MIX_LENGTHS = (LENGTHS, [12, 8], [30])      # 16, 6 and 23 windows at chunk 8; 45, 20 and 30 transitions
 WEIGHTS = (1.0, 1.0, 0.5)                   # balanced: p = (45, 20, 15) / 80
@@ -51,61 +48,15 @@ def host_tables(mix):
     return mix.valid_off_host.tolist(), mix.dataset_off_host.tolist(), mix.quota_off_host.tolist()
 
 
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def header_symbols():
-    return sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", header_text())))
-
-
 @pytest.fixture(scope="module")
 def lib():
-    from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return native.load()
+    from tests.abi_headers import load_library
+    return load_library()
 
 
 @pytest.fixture(scope="module")
 def mix():
     return make_mix()
-
-
-# ---------------------------------------------------------------------------------------------------------------- the four tables
-def test_mixture_header_and_binding_agree():
-    from vla_adapter_amd import native
-    assert header_symbols() == native.MIXTURE_SYMBOLS == sorted(native.MIXTURE_PROTOS) == ["vla_mixture_sample", "vla_normalize_bounds_rows"]
-    for other in (native._PROTOS, native.SERVE_PROTOS, native.EPISODE_PROTOS):
-        assert not set(native.MIXTURE_PROTOS) & set(other), "an entry point belongs to one header"
-
-
-def test_library_exports_every_mixture_symbol(lib):
-    from vla_adapter_amd import native
-    for name in header_symbols():
-        fn = getattr(lib, name, None)
-        assert fn is not None, f"libvla_native.so does not export {name}"
-        args, res = native.MIXTURE_PROTOS[name]
-        assert list(fn.argtypes) == list(args) and fn.restype is res, f"{name}: native.load() binds the table's signature"
-
-
-def test_mixture_signatures_match_the_header_argument_counts():
-    from vla_adapter_amd import native
-    protos = re.findall(r"\bint\s+(vla_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header_text())
-    assert sorted(n for n, _ in protos) == native.MIXTURE_SYMBOLS
-    for name, params in protos:
-        assert len(params.split(",")) == len(native.MIXTURE_PROTOS[name][0]), name
-    assert len(native.MIXTURE_PROTOS["vla_mixture_sample"][0]) == 18 and len(native.MIXTURE_PROTOS["vla_normalize_bounds_rows"][0]) == 12
-
-
-def test_the_earlier_tables_are_unchanged():
-    from vla_adapter_amd import native
-    txt = open(os.path.join(ROOT, "include", "vla_native.h")).read()
-    assert native.ABI_VERSION == 8 == int(re.search(r"#define VLA_ABI_VERSION (\d+)", txt).group(1))
-    assert len(native._PROTOS) == 69 and len(native.SERVE_PROTOS) == 4 and len(native.EPISODE_PROTOS) == 2
-    for tab in (native._PROTOS, native.SERVE_PROTOS, native.EPISODE_PROTOS):
-        assert not [k for k in tab if "mixture" in k or k == "vla_normalize_bounds_rows"]
 
 
 def test_host_checks_refuse_bad_arguments(lib):
@@ -134,21 +85,6 @@ def test_sample_refuses_a_stream_position_beyond_63_bits(lib, mix, B, rank, worl
     _, m = mix
     with pytest.raises(ValueError, match="stream position overflows 63 bits"):
         m.sample_indices(B, 0, rank, world, step + 1)
-
-
-def test_every_mixture_symbol_has_a_memory_contract_case_or_an_exemption():
-    from tests import test_mixture_memory_contract_gpu as M
-    from vla_adapter_amd import native
-    table = set(native.MIXTURE_PROTOS)
-    covered, exempt = set(M.COVERED), set(M.EXEMPT)
-    assert not (covered | exempt) - table, f"names that are no mixture entry points: {sorted((covered | exempt) - table)}"
-    assert not covered & exempt, f"both tested and exempt: {sorted(covered & exempt)}"
-    assert not table - covered - exempt, f"entry points with neither a case nor an exemption: {sorted(table - covered - exempt)}"
-    for name, reason in M.EXEMPT.items():
-        assert isinstance(reason, str) and 4 <= len(reason) and "\n" not in reason, f"{name}: a one-line reason"
-    for name, tests in M.COVERED.items():
-        for t in tests:
-            assert callable(getattr(M, t, None)), f"{name}: case {t} does not exist"
 
 
 def test_the_feistel_network_is_stated_once():

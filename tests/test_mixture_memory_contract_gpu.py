@@ -2,11 +2,11 @@
 runs on compact operands and then with every device operand a view inside a poisoned arena (tests/arena.py) at the minimum alignment
 its host check accepts; outputs must be bit-equal, inputs unchanged, and nothing written outside the declared extent.  The index
 tables' arenas are poisoned with in-range values that would change the result, so a read one element past a table shows.
-COVERED / EXEMPT: tests/test_mixture_cpu.py checks on the CPU that they cover native.MIXTURE_PROTOS."""
+COVERED / EXEMPT: tests/test_abi_families.py checks on the CPU that they cover the "mixture" family of native.FAMILIES."""
 import pytest
 import torch
 
-from tests.test_memory_contract_gpu import DEV, F32, I32, I64, U8, call, contract, gen
+from tests.test_memory_contract_gpu import DEV, F32, I32, I64, U8, call, case_for, contract, gen
 from tests.test_mixture_cpu import PERIOD, make_mix
 from vla_adapter_amd import mixture as MX
 from vla_adapter_amd import ops
@@ -15,12 +15,7 @@ COVERED = {}
 EXEMPT = {}                      # both entry points have a device footprint
 
 
-def case(*symbols):
-    def deco(fn):
-        for s in symbols:
-            COVERED.setdefault(s, []).append(fn.__name__)
-        return pytest.mark.gpu(fn)
-    return deco
+case = case_for(COVERED)
 
 
 @case("vla_mixture_sample")

@@ -1,7 +1,7 @@
 """The evaluator's frame pipeline on the host (include/vla_policy_image.h, csrc/jpeg_forward.h, input_stage.tf_lanczos3_spans): the
 numpy rule of the JPEG round trip (tests/policy_image_rule_np.py) equals Pillow bit for bit - the quantised coefficients of Pillow's
-file and the pixels of Pillow's decode - and the host's quantisation tables are the file's; header, binding and library agree; a
-stand-alone program with its own main around csrc/jpeg_forward.h + csrc/jpeg_core.h, compiled with g++ plain and with
+file and the pixels of Pillow's decode - and the host's quantisation tables are the file's; vla_native.h does not name
+these calls; a stand-alone program with its own main around csrc/jpeg_forward.h + csrc/jpeg_core.h, compiled with g++ plain and with
 -fsanitize=address,undefined, reproduces the rule's coefficients and pixels (nothing is loaded into Python: the sanitizers see the
 program alone); the lanczos3 rule keeps a flat image flat, has weight rows that sum to 1, returns the input at equal sizes and stays
 within one grey level of Pillow's LANCZOS on a band-limited image; the flag parses, is refused when unknown and enters the fingerprint
@@ -9,7 +9,6 @@ only when it is not the default.  TensorFlow is not installed: its own last bits
 import dataclasses
 import functools
 import os
-import re
 import struct
 import subprocess
 
@@ -23,8 +22,6 @@ from tests import jpeg_rule_np as R
 from tests import policy_image_rule_np as P
 from vla_adapter_amd import input_stage as IS
 
-HEADER = os.path.join(JC.ROOT, "include", "vla_policy_image.h")
-NAMES = ["vla_policy_image_workspace_bytes", "vla_policy_jpeg_round_trip", "vla_policy_lanczos3_resize"]
 QUALITIES = (30, 75, 95, 100)
 
 
@@ -76,41 +73,16 @@ def test_the_hosts_quantisation_tables_are_the_files(quality):
             IS.jpeg_quant_tables(bad)
 
 
-# ---------------------------------------------------------------------------------------------------------------- header, table, library
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def test_policy_image_header_binding_and_library_agree():
+# ---------------------------------------------------------------------------------------------------------------- the entry points
+def test_the_training_header_does_not_name_these_calls():
+    from tests.abi_headers import header_text
     from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = native.load()
-    names = sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", header_text())))
-    assert names == native.POLICY_IMAGE_SYMBOLS == sorted(native.POLICY_IMAGE_PROTOS) == NAMES
-    for other in (native._PROTOS, native.SERVE_PROTOS, native.EPISODE_PROTOS, native.MIXTURE_PROTOS, native.HELDOUT_PROTOS, native.DIGEST_PROTOS,
-                  native.JPEG_PROTOS, native.JPEG_INDEX_PROTOS):
-        assert not set(native.POLICY_IMAGE_PROTOS) & set(other), "an entry point belongs to one header"
-    protos = re.findall(r"\b(?:int|long long)\s+(vla_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header_text())
-    assert sorted(n for n, _ in protos) == NAMES
-    for name, params in protos:
-        args, res = native.POLICY_IMAGE_PROTOS[name]
-        assert len(params.split(",")) == len(args), name
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == list(args) and fn.restype is res
-    native_h = open(os.path.join(JC.ROOT, "include", "vla_native.h")).read()
-    assert not [n for n in NAMES if n in native_h], "the training ABI's header does not move for these calls"
-    mk = open(os.path.join(JC.ROOT, "vla_adapter_amd", "csrc", "Makefile")).read()
-    assert "policy_image.hip" in mk and "vla_policy_image.h" in mk and "jpeg_forward.h" in mk and "jpeg_stage_b.h" in mk
+    assert not [n for n in native.family("policy_image").protos if n in header_text("vla_native.h")], "the training ABI's header does not move for these calls"
 
 
 def test_the_size_function_refuses_what_the_calls_refuse():
-    from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    ws = native.load().vla_policy_image_workspace_bytes
+    from tests.abi_headers import load_library
+    ws = load_library().vla_policy_image_workspace_bytes
     assert ws(2, 256, 256, 0, 0, 1) == 2 * (256 * 256 * 3 // 2) * 3, "int16 coefficients and u8 planes of a 4:2:0 image"
     for H, W in ((250, 256), (256, 8), (0, 16), (16, 4112)):
         assert ws(1, H, W, 0, 0, 1) == -1, (H, W)

@@ -11,7 +11,7 @@ import torch
 
 from tests import jpeg_cases as JC
 from tests import policy_image_rule_np as P
-from tests.test_memory_contract_gpu import F32, I32, U8, call, contract
+from tests.test_memory_contract_gpu import F32, I32, U8, call, case_for, contract
 from vla_adapter_amd import input_stage as IS
 from vla_adapter_amd import ops
 
@@ -20,12 +20,7 @@ EXEMPT = {"vla_policy_image_workspace_bytes": "host arithmetic only: it takes no
 I16 = torch.int16
 
 
-def case(*symbols):
-    def deco(fn):
-        for s in symbols:
-            COVERED.setdefault(s, []).append(fn.__name__)
-        return pytest.mark.gpu(fn)
-    return deco
+case = case_for(COVERED)
 
 
 def frames_of(N, H, W):
@@ -84,10 +79,3 @@ def test_policy_lanczos3_resize_contract(H, W, oh, ow):
     assert np.array_equal(rc["out"].cpu().numpy(), want)
     if not n_ws:
         assert (rc["workspace_untouched"] == 0x7F).all(), "a single pass goes from u8 to u8: the workspace is not written"
-
-
-def test_every_policy_image_symbol_has_a_memory_contract_case_or_an_exemption():
-    from vla_adapter_amd import native
-    table = set(native.POLICY_IMAGE_PROTOS)
-    covered, exempt = set(COVERED), set(EXEMPT)
-    assert not (covered | exempt) - table and not covered & exempt and not table - covered - exempt

@@ -1,28 +1,7 @@
-"""CPU checks of the serving batch (predict_actions): the host-side layout, the second header against its signature table and the
-built library, the untouched training ABI, the completeness guard of tests/test_serve_memory_contract_gpu.py, and the refusals of
-the public call that need no device."""
-import os
-import re
-
+"""CPU checks of the serving batch (predict_actions): the host-side layout and the refusals of the public call that need no device
+(tests/test_abi_families.py checks include/vla_serve.h against the binding, the library and the memory-contract cases)."""
 import pytest
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def serve_header_symbols():
-    txt = open(os.path.join(ROOT, "include", "vla_serve.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", txt)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from vla_adapter_amd import native
-    if not os.path.exists(native.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return native.load()
 
 
 # ---------------------------------------------------------------------------------------------------------------- layout
@@ -48,56 +27,6 @@ def test_serve_layout_lands_a_stream_of_calls_on_few_shapes():
     assert len({serve_layout([p, 7])[1] for p in range(8, 31)}) == 1            # rows of 73 .. 95 ids: all L = 96
     with pytest.raises(ValueError):
         serve_layout([3], 0)
-
-
-# ---------------------------------------------------------------------------------------------------------------- the two tables
-def test_serve_header_and_binding_agree():
-    from vla_adapter_amd import native
-    assert serve_header_symbols() == native.SERVE_SYMBOLS == sorted(native.SERVE_PROTOS)
-    assert {"vla_serve_tokens", "vla_normalize_proprio_serve", "vla_unnormalize_actions"} <= set(native.SERVE_PROTOS)
-    assert not set(native.SERVE_PROTOS) & set(native._PROTOS), "an entry point belongs to one header"
-
-
-def test_library_exports_every_serve_symbol(lib):
-    from vla_adapter_amd import native
-    for name in serve_header_symbols():
-        fn = getattr(lib, name, None)
-        assert fn is not None, f"libvla_native.so does not export {name}"
-        args, res = native.SERVE_PROTOS[name]
-        assert list(fn.argtypes) == list(args) and fn.restype is res, f"{name}: native.load() binds the table's signature"
-
-
-def test_serve_signatures_match_the_header_argument_counts():
-    """Each prototype of the header has as many parameters as its ctypes signature (a dropped or added argument shifts every later one)."""
-    from vla_adapter_amd import native
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vla_serve.h")).read(), flags=re.S)
-    for name, params in re.findall(r"\bint\s+(vla_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt):
-        assert len(params.split(",")) == len(native.SERVE_PROTOS[name][0]), name
-
-
-def test_training_abi_is_unchanged():
-    from vla_adapter_amd import native
-    txt = open(os.path.join(ROOT, "include", "vla_native.h")).read()
-    assert native.ABI_VERSION == 8 == int(re.search(r"#define VLA_ABI_VERSION (\d+)", txt).group(1))
-    assert native.ABI_SYMBOLS == sorted(list(native._PROTOS) + ["vla_last_error"])
-    assert len(native._PROTOS) == 69 and not [k for k in native._PROTOS if "serve" in k or k == "vla_unnormalize_actions"]
-    stripped = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    assert sorted(set(re.findall(r"\b(vla_[a-z0-9_]+)\s*\(", stripped))) == native.ABI_SYMBOLS, "vla_native.h declares the training table only"
-
-
-def test_every_serve_symbol_has_a_memory_contract_case_or_an_exemption():
-    from tests import test_serve_memory_contract_gpu as M
-    from vla_adapter_amd import native
-    table = set(native.SERVE_PROTOS)
-    covered, exempt = set(M.COVERED), set(M.EXEMPT)
-    assert not (covered | exempt) - table, f"names that are no serving entry points: {sorted((covered | exempt) - table)}"
-    assert not covered & exempt, f"both tested and exempt: {sorted(covered & exempt)}"
-    assert not table - covered - exempt, f"entry points with neither a case nor an exemption: {sorted(table - covered - exempt)}"
-    for name, reason in M.EXEMPT.items():
-        assert isinstance(reason, str) and 4 <= len(reason) and "\n" not in reason, f"{name}: a one-line reason"
-    for name, tests in M.COVERED.items():
-        for t in tests:
-            assert callable(getattr(M, t, None)), f"{name}: case {t} does not exist"
 
 
 # ---------------------------------------------------------------------------------------------------------------- refusals

@@ -1,23 +1,18 @@
 """The memory contract of the serving entry points (include/vla_serve.h), by the procedure of tests/test_memory_contract_gpu.py: each
 runs on compact operands and then with every device operand a view inside a poisoned arena (tests/arena.py) at the minimum alignment
 its host check accepts - strided where the entry point takes a stride; outputs must be bit-equal, inputs unchanged, and nothing written
-outside the declared extent.  COVERED / EXEMPT: tests/test_serve_cpu.py checks on the CPU that they cover native.SERVE_PROTOS."""
+outside the declared extent.  COVERED / EXEMPT: tests/test_abi_families.py checks on the CPU that they cover the "serve" family of native.FAMILIES."""
 import pytest
 import torch
 
 from tests.arena import assert_bits_equal
-from tests.test_memory_contract_gpu import BF, DEV, F32, F64, I32, I64, U8, call, contract, gen, ld_of
+from tests.test_memory_contract_gpu import BF, DEV, F32, F64, I32, I64, U8, call, case_for, contract, gen, ld_of
 
 COVERED = {}
 EXEMPT = {}                      # every serving entry point has a device footprint
 
 
-def case(*symbols):
-    def deco(fn):
-        for s in symbols:
-            COVERED.setdefault(s, []).append(fn.__name__)
-        return pytest.mark.gpu(fn)
-    return deco
+case = case_for(COVERED)
 
 
 @case("vla_serve_tokens")

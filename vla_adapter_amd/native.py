@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = (os.environ.get("VLA_NATIVE_LIB") or None) or os.path.join(_HERE, "libvla_native.so")   # override: same-box A/B of two builds
@@ -75,149 +76,144 @@ class HeadAttnDesc(C.Structure):
 
 
 _P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double
-_PROTOS = {
-    "vla_version": ([], _I),
-    "vla_desc_size": ([_I], _I),
-    "vla_gemm256_extent_ok": ([C.POINTER(GemmDesc)], _I),
-    "vla_gemm_nt_plan": ([C.POINTER(GemmDesc), _I, _I, C.POINTER(C.c_int)], _I),
-    "vla_gemm_tn_plan": ([C.POINTER(GemmTnDesc), _I, C.POINTER(C.c_int)], _I),
-    "vla_gemm_latency_hint": ([C.c_int], _I),
-    "vla_gemm_bf16_tn": ([_P, C.POINTER(GemmTnDesc)], _I),
-    "vla_gemm_bf16_tn_grouped": ([_P, C.POINTER(GemmTnDesc), _I], _I),
-    "vla_copy_rows3d": ([_P, _P, _P, _I, _I, _I, _L, _L, _L, _L], _I),
-    "vla_layerscale_fwd": ([_P, _P, _P, _P, _P, _L, _I], _I),
-    "vla_layerscale_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I], _I),
-    "vla_gemm_bf16_nt": ([_P, C.POINTER(GemmDesc)], _I),
-    "vla_transpose_bf16": ([_P, _P, _P, _I, _I, _I, _I, _I, _L, _L], _I),
-    "vla_layernorm_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F], _I),
-    "vla_layernorm_bwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
-    "vla_rmsnorm_fwd": ([_P, _P, _P, _P, _P, _I, _I, _F], _I),
-    "vla_rmsnorm_bwd": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
-    "vla_attn_fwd": ([_P, C.POINTER(AttnDesc)], _I),
-    "vla_attn_bwd": ([_P, C.POINTER(AttnDesc)], _I),
-    "vla_rope_half": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I], _I),
-    "vla_rope_interleaved": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I], _I),
-    "vla_im2col_patch": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I], _I),
-    "vla_image_normalize_u8": ([_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I], _I),
-    "vla_action_tokenize": ([_P, _P, _P, _P, _L, _I, _F, _F, _L], _I),
-    "vla_action_mask": ([_P, _P, _P, _P, _P, _I, _I, _I], _I),
-    "vla_embed_splice": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
-    "vla_action_query_grad": ([_P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
-    "vla_gather_rows": ([_P, _P, _P, _P, _I, _I, _I, _I], _I),
-    "vla_scatter_add_rows": ([_P, _P, _P, _P, _I, _I, _I, _I], _I),
-    "vla_add_bf16": ([_P, _P, _P, _P, _L], _I),
-    "vla_gelu_fwd": ([_P, _P, _P, _L], _I),
-    "vla_gelu_bwd": ([_P, _P, _P, _P, _L], _I),
-    "vla_relu_bwd": ([_P, _P, _P, _P, _L], _I),
-    "vla_swiglu_bwd": ([_P, _P, _P, _P, _I, _I], _I),
-    "vla_swiglu_fwd": ([_P, _P, _P, _I, _I], _I),
-    "vla_colsum_bf16": ([_P, _P, _P, _I, _I, _I, _I, _L, _L], _I),
-    "vla_cast_f32_bf16": ([_P, _P, _P, _L], _I),
-    "vla_cast_bf16_f32": ([_P, _P, _P, _L], _I),
-    "vla_rmsnorm_dw": ([_P, _P, _P, _P, _P, _I, _I], _I),
-    "vla_embed_grad": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
-    "vla_resample_u8": ([_P, _P, _P, _L, _I, _I, _I, _P, _P, _I], _I),
-    "vla_augment_slab_floats": ([_I, _I, _I], _L),
-    "vla_augment_stats": ([_P, _P, _P, _P, _I, _I, _I, _I, C.c_uint, C.POINTER(C.c_float), C.c_ulonglong, _L, _L], _I),
-    "vla_augment_apply": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, C.c_uint,
-                           C.POINTER(C.c_float), C.c_ulonglong, _L, _L], _I),
-    "vla_token_ce": ([_P, _P, _L, _P, _I, _I, _P], _I),
-    "vla_token_ce_bwd": ([_P, _P, _L, _P, _I, _I, _P, _F, _P, _L], _I),
-    "vla_token_ce_metrics": ([_P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _L, _I], _I),
-    "vla_token_metrics_finish": ([_P, _P, _D, _P], _I),
-    "vla_token_row_class": ([_P, _P, _P, _I, _I, _I, _L, _I], _I),
-    "vla_copy2d": ([_P, _P, _P, _L, _I, _L, _L, _I, _I, _I, _I, _L], _I),
-    "vla_fill_zero": ([_P, _P, _L], _I),
-    "vla_dropout_bf16": ([_P, _P, _P, _L, C.c_int, _L, _L, C.c_float, C.c_ulonglong, _P], _I),
-    "vla_dropout_bwd_add_bf16": ([_P, _P, _P, _L, C.c_int, _L, _L, C.c_float, C.c_ulonglong, _P], _I),
-    "vla_inc_i32": ([_P, _P], _I),
-    "vla_quant_fp8_rows": ([_P, _P, _P, _P, _I, _I, _I, _I], _I),
-    "vla_rmsnorm_fwd_q8": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F], _I),
-    "vla_layernorm_fwd_q8": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F], _I),
-    "vla_head_index_prep": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I], _I),
-    "vla_add_scalar_f32": ([_P, _P, _P, _I], _I),
-    "vla_head_attn_fwd": ([_P, C.POINTER(HeadAttnDesc)], _I),
-    "vla_head_attn_bwd": ([_P, C.POINTER(HeadAttnDesc)], _I),
-    "vla_l1_loss": ([_P, _P, _P, _P, _P, _I, _I, _I, _F], _I),
-    "vla_adamw_bf16": ([_P, _P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _I, _I, _F], _I),
-    "vla_adamw_clipped_bf16": ([_P, _P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _I, _I, _F, _P], _I),
-    "vla_grad_sumsq_slots": ([_L], _L),
-    "vla_grad_sumsq": ([_P, _P, _L, _I, _F, _P], _I),
-    "vla_grad_norm_finalise": ([_P, _P, _L, _F, _P], _I),
-    "vla_normalize_bounds": ([_P, _P, _P, _L, _I, _P, _P, _P, _P], _I),
-    "vla_collate_tokens": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _L, _L, _L, _I, C.c_ulonglong, _L, _L], _I),
-}
-# symbols include/vla_native.h declares (checked by tests/test_abi.py without touching a GPU)
-ABI_SYMBOLS = sorted(list(_PROTOS) + ["vla_last_error"])
 
 
-# the serving entry points (include/vla_serve.h, csrc/serve.hip): a table of their own, bound beside _PROTOS - the training ABI above
-# (its header, its version) does not move for them (tests/test_serve_cpu.py checks header, table and library against each other)
-SERVE_PROTOS = {
-    "vla_serve_tokens": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L], _I),
-    "vla_normalize_proprio_serve": ([_P, _P, _I, _P, _L, _I, _P, _P, _P], _I),
-    "vla_unnormalize_actions": ([_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P], _I),
-    "vla_serve_gather_hidden": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I], _I),
-}
-SERVE_SYMBOLS = sorted(SERVE_PROTOS)
+class Family(NamedTuple):
+    """The entry points that one header under include/ declares: name -> (argtypes, restype)."""
+    key: str
+    header: str
+    protos: dict
 
-# the episode sampler (include/vla_episodes.h, csrc/episodes.hip): a third table, bound by name in the same way
-# (tests/test_episodes_cpu.py checks header, table and library against each other)
-EPISODE_PROTOS = {
-    "vla_episode_sample": ([_P, _P, _P, _P, _I, C.c_ulonglong, _L, _L, _L, _I, _I, _P, _P, _P], _I),
-    "vla_episode_gather": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _I, _I, _L, _I], _I),
-}
-EPISODE_SYMBOLS = sorted(EPISODE_PROTOS)
 
-# the dataset mixture (include/vla_mixture.h, csrc/mixture.hip): a fourth table, bound by name in the same way
-# (tests/test_mixture_cpu.py checks header, table and library against each other)
-MIXTURE_PROTOS = {
-    "vla_mixture_sample": ([_P, _P, _P, _P, _P, _P, _I, _I, C.c_ulonglong, _L, _L, _L, _I, _I, _P, _P, _P, _P], _I),
-    "vla_normalize_bounds_rows": ([_P, _P, _P, _L, _I, _I, _P, _I, _P, _P, _P, _P], _I),
-}
-MIXTURE_SYMBOLS = sorted(MIXTURE_PROTOS)
+# One family per header, in the order the headers were added.  Every family lives in the same library and is bound by name in load();
+# the later ones were added without moving vla_native.h or its ABI version.  tests/test_abi_families.py checks every signature against
+# its header type for type, and the library's exports against both.
+FAMILIES = (
+    # the training ABI (csrc/*.hip): its version and the four descriptors are checked by load()
+    Family("native", "vla_native.h", {
+        "vla_version": ([], _I),
+        "vla_desc_size": ([_I], _I),
+        "vla_gemm256_extent_ok": ([C.POINTER(GemmDesc)], _I),
+        "vla_gemm_nt_plan": ([C.POINTER(GemmDesc), _I, _I, C.POINTER(C.c_int)], _I),
+        "vla_gemm_tn_plan": ([C.POINTER(GemmTnDesc), _I, C.POINTER(C.c_int)], _I),
+        "vla_gemm_latency_hint": ([C.c_int], _I),
+        "vla_gemm_bf16_tn": ([_P, C.POINTER(GemmTnDesc)], _I),
+        "vla_gemm_bf16_tn_grouped": ([_P, C.POINTER(GemmTnDesc), _I], _I),
+        "vla_copy_rows3d": ([_P, _P, _P, _I, _I, _I, _L, _L, _L, _L], _I),
+        "vla_layerscale_fwd": ([_P, _P, _P, _P, _P, _L, _I], _I),
+        "vla_layerscale_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I], _I),
+        "vla_gemm_bf16_nt": ([_P, C.POINTER(GemmDesc)], _I),
+        "vla_transpose_bf16": ([_P, _P, _P, _I, _I, _I, _I, _I, _L, _L], _I),
+        "vla_layernorm_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F], _I),
+        "vla_layernorm_bwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
+        "vla_rmsnorm_fwd": ([_P, _P, _P, _P, _P, _I, _I, _F], _I),
+        "vla_rmsnorm_bwd": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
+        "vla_attn_fwd": ([_P, C.POINTER(AttnDesc)], _I),
+        "vla_attn_bwd": ([_P, C.POINTER(AttnDesc)], _I),
+        "vla_rope_half": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I], _I),
+        "vla_rope_interleaved": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I], _I),
+        "vla_im2col_patch": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I], _I),
+        "vla_image_normalize_u8": ([_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I], _I),
+        "vla_action_tokenize": ([_P, _P, _P, _P, _L, _I, _F, _F, _L], _I),
+        "vla_action_mask": ([_P, _P, _P, _P, _P, _I, _I, _I], _I),
+        "vla_embed_splice": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
+        "vla_action_query_grad": ([_P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
+        "vla_gather_rows": ([_P, _P, _P, _P, _I, _I, _I, _I], _I),
+        "vla_scatter_add_rows": ([_P, _P, _P, _P, _I, _I, _I, _I], _I),
+        "vla_add_bf16": ([_P, _P, _P, _P, _L], _I),
+        "vla_gelu_fwd": ([_P, _P, _P, _L], _I),
+        "vla_gelu_bwd": ([_P, _P, _P, _P, _L], _I),
+        "vla_relu_bwd": ([_P, _P, _P, _P, _L], _I),
+        "vla_swiglu_bwd": ([_P, _P, _P, _P, _I, _I], _I),
+        "vla_swiglu_fwd": ([_P, _P, _P, _I, _I], _I),
+        "vla_colsum_bf16": ([_P, _P, _P, _I, _I, _I, _I, _L, _L], _I),
+        "vla_cast_f32_bf16": ([_P, _P, _P, _L], _I),
+        "vla_cast_bf16_f32": ([_P, _P, _P, _L], _I),
+        "vla_rmsnorm_dw": ([_P, _P, _P, _P, _P, _I, _I], _I),
+        "vla_embed_grad": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I], _I),
+        "vla_resample_u8": ([_P, _P, _P, _L, _I, _I, _I, _P, _P, _I], _I),
+        "vla_augment_slab_floats": ([_I, _I, _I], _L),
+        "vla_augment_stats": ([_P, _P, _P, _P, _I, _I, _I, _I, C.c_uint, C.POINTER(C.c_float), C.c_ulonglong, _L, _L], _I),
+        "vla_augment_apply": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, C.c_uint,
+                               C.POINTER(C.c_float), C.c_ulonglong, _L, _L], _I),
+        "vla_token_ce": ([_P, _P, _L, _P, _I, _I, _P], _I),
+        "vla_token_ce_bwd": ([_P, _P, _L, _P, _I, _I, _P, _F, _P, _L], _I),
+        "vla_token_ce_metrics": ([_P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _L, _I], _I),
+        "vla_token_metrics_finish": ([_P, _P, _D, _P], _I),
+        "vla_token_row_class": ([_P, _P, _P, _I, _I, _I, _L, _I], _I),
+        "vla_copy2d": ([_P, _P, _P, _L, _I, _L, _L, _I, _I, _I, _I, _L], _I),
+        "vla_fill_zero": ([_P, _P, _L], _I),
+        "vla_dropout_bf16": ([_P, _P, _P, _L, C.c_int, _L, _L, C.c_float, C.c_ulonglong, _P], _I),
+        "vla_dropout_bwd_add_bf16": ([_P, _P, _P, _L, C.c_int, _L, _L, C.c_float, C.c_ulonglong, _P], _I),
+        "vla_inc_i32": ([_P, _P], _I),
+        "vla_quant_fp8_rows": ([_P, _P, _P, _P, _I, _I, _I, _I], _I),
+        "vla_rmsnorm_fwd_q8": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F], _I),
+        "vla_layernorm_fwd_q8": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F], _I),
+        "vla_head_index_prep": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I], _I),
+        "vla_add_scalar_f32": ([_P, _P, _P, _I], _I),
+        "vla_head_attn_fwd": ([_P, C.POINTER(HeadAttnDesc)], _I),
+        "vla_head_attn_bwd": ([_P, C.POINTER(HeadAttnDesc)], _I),
+        "vla_l1_loss": ([_P, _P, _P, _P, _P, _I, _I, _I, _F], _I),
+        "vla_adamw_bf16": ([_P, _P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _I, _I, _F], _I),
+        "vla_adamw_clipped_bf16": ([_P, _P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _I, _I, _F, _P], _I),
+        "vla_grad_sumsq_slots": ([_L], _L),
+        "vla_grad_sumsq": ([_P, _P, _L, _I, _F, _P], _I),
+        "vla_grad_norm_finalise": ([_P, _P, _L, _F, _P], _I),
+        "vla_normalize_bounds": ([_P, _P, _P, _L, _I, _P, _P, _P, _P], _I),
+        "vla_collate_tokens": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _L, _L, _L, _I, C.c_ulonglong, _L, _L], _I),
+    }),
+    # the serving entry points (csrc/serve.hip)
+    Family("serve", "vla_serve.h", {
+        "vla_serve_tokens": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L], _I),
+        "vla_normalize_proprio_serve": ([_P, _P, _I, _P, _L, _I, _P, _P, _P], _I),
+        "vla_unnormalize_actions": ([_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P], _I),
+        "vla_serve_gather_hidden": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I], _I),
+    }),
+    # the episode sampler (csrc/episodes.hip)
+    Family("episodes", "vla_episodes.h", {
+        "vla_episode_sample": ([_P, _P, _P, _P, _I, C.c_ulonglong, _L, _L, _L, _I, _I, _P, _P, _P], _I),
+        "vla_episode_gather": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _I, _I, _L, _I], _I),
+    }),
+    # the dataset mixture (csrc/mixture.hip)
+    Family("mixture", "vla_mixture.h", {
+        "vla_mixture_sample": ([_P, _P, _P, _P, _P, _P, _I, _I, C.c_ulonglong, _L, _L, _L, _I, _I, _P, _P, _P, _P], _I),
+        "vla_normalize_bounds_rows": ([_P, _P, _P, _L, _I, _I, _P, _I, _P, _P, _P, _P], _I),
+    }),
+    # validation on held-out episodes (csrc/heldout.hip)
+    Family("heldout", "vla_heldout.h", {
+        "vla_heldout_sweep": ([_P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P], _I),
+        "vla_heldout_l1_accumulate": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
+    }),
+    # the state digest (csrc/digest.hip)
+    Family("digest", "vla_digest.h", {
+        "vla_state_digest_slots": ([], _I),
+        "vla_state_digest": ([_P, _P, _L, C.c_ulonglong, _P, _L, _P], _I),
+        "vla_token_ce_metrics_ordered": ([_P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _L, _I, _P], _I),
+    }),
+    # the JPEG frame store (csrc/jpeg.hip)
+    Family("jpeg", "vla_jpeg.h", {
+        "vla_jpeg_workspace_bytes": ([_L, _I, _I, _I], _L),
+        "vla_jpeg_decode_rows": ([_P, _P, _L, _P, _P, _L, _P, _P, _I, _P, _I, _P, _I, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P], _I),
+    }),
+    # the scan index of the JPEG frame store (csrc/jpeg_index.hip and csrc/jpeg.hip)
+    Family("jpeg_index", "vla_jpeg_index.h", {
+        "vla_jpeg_index_build": ([_P, _P, _L, _P, _P, _L, _P, _P, _I, _P, _I, _L, _I, _I, _I, _I, _P, _L, _L, _I, _P, _P, _L, _P], _I),
+        "vla_jpeg_decode_rows_at": ([_P, _P, _L, _P, _P, _P, _L, _P, _P, _I, _P, _I, _P, _I, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P], _I),
+    }),
+    # the evaluator's frame pipeline (csrc/policy_image.hip)
+    Family("policy_image", "vla_policy_image.h", {
+        "vla_policy_image_workspace_bytes": ([_L, _I, _I, _I, _I, _I], _L),
+        "vla_policy_jpeg_round_trip": ([_P, _P, _L, _L, _I, _I, _P, _P, _L, _P, _L], _I),
+        "vla_policy_lanczos3_resize": ([_P, _P, _L, _L, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _L, _P], _I),
+    }),
+)
+PROTOS = {name: sig for fam in FAMILIES for name, sig in fam.protos.items()}
+assert len(PROTOS) == sum(len(fam.protos) for fam in FAMILIES), "an entry point belongs to one header"
 
-# validation on held-out episodes (include/vla_heldout.h, csrc/heldout.hip): a fifth table, bound by name in the same way
-# (tests/test_heldout_cpu.py checks header, table and library against each other)
-HELDOUT_PROTOS = {
-    "vla_heldout_sweep": ([_P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P], _I),
-    "vla_heldout_l1_accumulate": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
-}
-HELDOUT_SYMBOLS = sorted(HELDOUT_PROTOS)
 
-# the state digest (include/vla_digest.h, csrc/digest.hip): a sixth table, bound by name in the same way
-# (tests/test_digest_cpu.py checks header, table and library against each other)
-DIGEST_PROTOS = {
-    "vla_state_digest_slots": ([], _I),
-    "vla_state_digest": ([_P, _P, _L, C.c_ulonglong, _P, _L, _P], _I),
-    "vla_token_ce_metrics_ordered": ([_P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _L, _I, _P], _I),
-}
-DIGEST_SYMBOLS = sorted(DIGEST_PROTOS)
+def family(key: str) -> Family:
+    return next(fam for fam in FAMILIES if fam.key == key)
 
-# the JPEG frame store (include/vla_jpeg.h, csrc/jpeg.hip): a seventh table, bound by name in the same way
-# (tests/test_jpeg_cpu.py checks header, table and library against each other)
-JPEG_PROTOS = {
-    "vla_jpeg_workspace_bytes": ([_L, _I, _I, _I], _L),
-    "vla_jpeg_decode_rows": ([_P, _P, _L, _P, _P, _L, _P, _P, _I, _P, _I, _P, _I, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P], _I),
-}
-JPEG_SYMBOLS = sorted(JPEG_PROTOS)
-
-# the scan index of the JPEG frame store (include/vla_jpeg_index.h, csrc/jpeg_index.hip and csrc/jpeg.hip): an eighth table, bound by
-# name in the same way (tests/test_jpeg_index_cpu.py checks header, table and library against each other)
-JPEG_INDEX_PROTOS = {
-    "vla_jpeg_index_build": ([_P, _P, _L, _P, _P, _L, _P, _P, _I, _P, _I, _L, _I, _I, _I, _I, _P, _L, _L, _I, _P, _P, _L, _P], _I),
-    "vla_jpeg_decode_rows_at": ([_P, _P, _L, _P, _P, _P, _L, _P, _P, _I, _P, _I, _P, _I, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P], _I),
-}
-JPEG_INDEX_SYMBOLS = sorted(JPEG_INDEX_PROTOS)
-
-# the evaluator's frame pipeline (include/vla_policy_image.h, csrc/policy_image.hip): a ninth table, bound by name in the same way
-# (tests/test_policy_image_cpu.py checks header, table and library against each other)
-POLICY_IMAGE_PROTOS = {
-    "vla_policy_image_workspace_bytes": ([_L, _I, _I, _I, _I, _I], _L),
-    "vla_policy_jpeg_round_trip": ([_P, _P, _L, _L, _I, _I, _P, _P, _L, _P, _L], _I),
-    "vla_policy_lanczos3_resize": ([_P, _P, _L, _L, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _L, _P], _I),
-}
-POLICY_IMAGE_SYMBOLS = sorted(POLICY_IMAGE_PROTOS)
 
 _lib = None
 
@@ -232,7 +228,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in list(_PROTOS.items()) + list(SERVE_PROTOS.items()) + list(EPISODE_PROTOS.items()) + list(MIXTURE_PROTOS.items()) + list(HELDOUT_PROTOS.items()) + list(DIGEST_PROTOS.items()) + list(JPEG_PROTOS.items()) + list(JPEG_INDEX_PROTOS.items()) + list(POLICY_IMAGE_PROTOS.items()):
+    for name, (args, res) in PROTOS.items():
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")
