@@ -74,7 +74,7 @@ def _recompute(backbone, mode, d, step, val, L, rank=0, seed=0, phase_training=T
     n = len(val)
     vals = []
     for j, i in enumerate(list(range(rank % n, n)) + list(range(rank % n))):
-        b = F._pad_to(val[i], L, pad)
+        b = F.pad_to(val[i], L, pad)
         noise = F.validation_noise(F.FinetuneConfig(seed=seed), mcfg, rank, step, j).to(DEV) if phase_training else None
         pred = model.forward(b, noise)
         vals.append(ops.l1_loss(pred, eng._to_bf16(b["actions"]), want_grad=False)[0].tolist())
@@ -195,7 +195,7 @@ def test_val_batch_file_directory_and_the_command_line(tmp_path):
     for name, bs in (("train", train), ("val", val)):
         os.makedirs(tmp_path / name)
         for i, b in enumerate(bs):
-            torch.save({k: v.cpu() for k, v in F._pad_to(b, L, 0).items()}, tmp_path / name / f"{i:03d}.pt")
+            torch.save({k: v.cpu() for k, v in F.pad_to(b, L, 0).items()}, tmp_path / name / f"{i:03d}.pt")
     r = subprocess.run([sys.executable, os.path.join("vla-scripts", "finetune.py"), "--tiny", "true", "--use_fz", "True", "--use_proprio", "True",
                         "--batch_size", "4", "--batch_file", str(tmp_path / "train"), "--use_val_set", "True", "--val_batch_file", str(tmp_path / "val"),
                         "--val_freq", "5", "--max_steps", "10", "--save_freq", "1000", "--run_root_dir", str(tmp_path / "runs")],

@@ -57,12 +57,12 @@ def new_engine(mcfg, dev: str):
     return E.VLAEngine(mcfg, S.make_weights(mcfg, dev, seed=0), dev)
 
 
-def capture_step(eng, mcfg, first: dict, dev: str) -> dict:
-    """Captures the adapter-only training step on a copy of the padded batch ``first``, as ``finetune()`` does; -> the static batch."""
-    static = {k: v.clone() for k, v in first.items()}
-    noise = torch.zeros(mcfg.chunk, mcfg.action_dim * mcfg.llm.d, device=dev, dtype=torch.bfloat16)
-    eng.capture(static, noise, conservative_rows=True)              # prompts of 27-51 ids: the action block moves from batch to batch
-    return static
+def capture_step(eng, mcfg, first: dict, dev: str):
+    """``finetune()``'s own runner of the adapter-only step, captured on a copy of the padded batch ``first`` (``runner.static``)."""
+    from vla_adapter_amd.finetune import StepRunner
+    runner = StepRunner(eng, None, mcfg, dev, True, conservative_rows=True)   # prompts of 27-51 ids: the action block moves from batch to batch
+    runner.capture(first)
+    return runner
 
 
 def time_sources(args, mcfg, cfgs: dict, base: str, dev: str = "cuda:0"):
@@ -77,21 +77,17 @@ def time_sources(args, mcfg, cfgs: dict, base: str, dev: str = "cuda:0"):
     eng = new_engine(mcfg, dev)
     pad_id = min(S.PAD_ID, mcfg.llm.vocab - 1)
     L, lr = args.max_seq_len, 1e-4
-    cur = {k: F._pad_to(next(s), L, pad_id) for k, s in streams.items()}
-    static = capture_step(eng, mcfg, cur[base], dev)
+    cur = {k: F.pad_to(next(s), L, pad_id) for k, s in streams.items()}
+    runner = capture_step(eng, mcfg, cur[base], dev)
 
     def run(which, steps):
-        """finetune()'s captured adapter-only loop: copy the current batch's small tensors, stage the next batch's pixels, replay."""
+        """finetune()'s loop around its captured adapter-only step: one batch of look-ahead, whose pixels the step stages."""
         stream = streams[which]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            nxt = F._pad_to(next(stream), L, pad_id)
-            for k in static:
-                if k != "pixel_values":
-                    static[k].copy_(cur[which][k])
-            eng.stage_next_pixels(nxt["pixel_values"])
-            loss3 = eng.train_step_graphed(lr)
+            nxt = F.pad_to(next(stream), L, pad_id)
+            loss3 = runner.step(cur[which], nxt, lr)
             cur[which] = nxt
         eng.flush()
         torch.cuda.synchronize()

@@ -6,7 +6,7 @@ per step), on the same box, in one process, on ONE engine and one captured graph
 The tool writes a synthetic episode file (``--episodes`` episodes of ``--episode_len`` steps, ``--n_img`` views of the model's image
 size, prompts of 27-51 ids) and ``--files`` raw batches drawn from it into a temporary directory, builds the engine of ``--backbone``
 (random weights) and runs the loop of ``finetune()``'s captured adapter-only branch - one batch of look-ahead, its vision stage staged
-for the next step - over ``finetune.batch_stream`` of either source.  Both go through the same ``collate_raw`` (normalisation, token
+for the next step - over ``finetune.batch_stream`` of either source.  Both go through the same ``batches.Collator.raw`` (normalisation, token
 assembly, augmentation).
 
 Per source, milliseconds per step: host clock around ``--steps`` steps that end in a device synchronise, after ``--warmup`` steps.

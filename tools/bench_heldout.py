@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times one validation sweep fed from the held-out split of a device-resident episode store (``--val_episode_fraction``:
 heldout.HeldOutSweep - windows named and gathered on the device, sums kept on the device, one read-back per sweep) against the same
-windows pre-collated into ``--val_batch_file`` batches and swept by ``finetune.ValidationPass`` (one torch.load, a host-to-device copy
+windows pre-collated into ``--val_batch_file`` batches and swept by ``validation.ValidationPass`` (one torch.load, a host-to-device copy
 and a three-float read-back per batch), on the same box, in one process, on ONE captured engine and one set of captured validation
 graphs: only the source and the reduction differ.
 
@@ -57,18 +57,18 @@ def main():
         info = {}
         stream = F.batch_stream(cfg_h, mcfg, dev, 0, None, cfg_h._explicit, world=1, info=info)
         pad_id = min(S.PAD_ID, mcfg.llm.vocab - 1)
-        cur = F._pad_to(next(stream), L, pad_id)
+        cur = F.pad_to(next(stream), L, pad_id)
         store = info["store"]
         assert store.Nv % B == 0, f"{store.Nv} held-out windows do not fill whole batches of {B}: the file-fed sweep would average a padded batch"
         eng = EB.new_engine(mcfg, dev)
-        static = EB.capture_step(eng, mcfg, cur, dev)
+        static = EB.capture_step(eng, mcfg, cur, dev).static
         sweeper = HeldOutSweep(cfg_h, mcfg, dev, 0, 1, eng, store, info["dataset_statistics"], static, L, True)
         for j in range(sweeper.n_batches):                           # the same windows, collated, as --val_batch_file batches
             b = sweeper.collate(sweeper.draw(j), j)
             torch.save({k: v.cpu() for k, v in b.items()}, os.path.join(val_dir, f"batch_{j:04d}.pt"))
         first = sweeper.sweep(1)                                     # captures the validation graphs on the sweeper's static batch
         files = F.ValidationPass(cfg_f, mcfg, dev, 0, eng, static, L, pad_id, True)
-        files.static, files.noise = sweeper.static, sweeper.noise    # one set of captured graphs: both sources replay it on the same buffers
+        files.feed.static, files.noise = sweeper.feed.static, sweeper.noise   # one set of captured graphs: both sources replay it on the same buffers
         runs = {"val_batch_file": files.sweep, "val_episode_fraction": sweeper.sweep}
 
         def run(which):

@@ -8,7 +8,7 @@ The tool writes ``--datasets`` synthetic episode files (``--episodes`` episodes 
 the model's image size, prompts of 27-51 ids) and one file that holds all of them as a single dataset into a temporary directory,
 builds the engine of ``--backbone`` (random weights) and runs the loop of ``finetune()``'s captured adapter-only branch - one batch of
 look-ahead, its vision stage staged for the next step - over ``finetune.batch_stream`` of either source.  Both go through the same
-``collate_raw`` (token assembly, augmentation).
+``batches.Collator.raw`` (token assembly, augmentation).
 
 Per source, milliseconds per step: host clock around ``--steps`` steps that end in a device synchronise, after ``--warmup`` steps.
 The sources alternate over ``--rounds`` rounds; the figures are the medians over the rounds with the spread (min - max) beside them.

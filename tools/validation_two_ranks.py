@@ -15,7 +15,7 @@ from vla_adapter_amd import engine as E, finetune as F, synthetic as S  # noqa: 
 
 def batches(n, seed0, L):
     cfg, pad = E.tiny_config(), min(S.PAD_ID, E.tiny_config().llm.vocab - 1)
-    return [F._pad_to(S.make_batch(cfg, 4, "cuda:0", seed=seed0 + i, P=32, ragged=True), L, pad) for i in range(n)]
+    return [F.pad_to(S.make_batch(cfg, 4, "cuda:0", seed=seed0 + i, P=32, ragged=True), L, pad) for i in range(n)]
 
 
 def main(out_dir: str, L: int):

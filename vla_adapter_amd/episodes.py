@@ -44,7 +44,7 @@ import numpy as np
 import torch
 
 from .constants import NUM_ACTIONS_CHUNK
-from .finetune import RAW_BATCH_KEYS                # what sample() returns: the raw batch finetune.batch_stream collates
+from .batches import RAW_BATCH_KEYS                 # what sample() returns: the raw batch batches.batch_stream collates
 from .jpeg_store import JPEG_KEYS, STATUS_TEXT, JpegFrames, check_jpeg_shard, concat_jpeg, storage_form
 
 EPISODE_KEYS = ("frames_u8", "actions_raw", "proprio_raw", "episode_off", "prompt_flat", "prompt_off")

@@ -24,9 +24,15 @@ import os
 import time
 from dataclasses import dataclass
 from pathlib import Path
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
+
+from .batches import IMAGE_AUG_REFUSAL, RAW_BATCH_KEYS, batch_stream, mixture_stats, pad_to, raw_batch_stats  # noqa: F401  (re-exported)
+from .validation import ValidationPass, validation_due, validation_noise  # noqa: F401  (re-exported)
+
+_pad_to = pad_to                      # the name it had here: callers written against it keep resolving
 
 
 @dataclass
@@ -178,10 +184,6 @@ def train_mode(cfg: FinetuneConfig) -> str:
     return "lora" if cfg.use_lora else ("adapter" if cfg.use_fz else "full")
 
 
-IMAGE_AUG_REFUSAL = ("--image_aug: already normalised pixel_values cannot be augmented; pass raw uint8 frames (frames_u8) with "
-                     "--frame_batch_file, or in the batches handed to finetune()")
-
-
 VAL_FLAGS = ("val_freq", "val_time_limit")
 EPISODE_FLAGS = ("episode_file", "episode_mix")     # the two device-resident batch sources: what either needs is stated once
 
@@ -316,115 +318,6 @@ def loop_plan(cfg: FinetuneConfig, start=None):
         batch_idx += 1
 
 
-def validation_due(cfg: FinetuneConfig, item) -> bool:
-    """Does the validation pass run behind this loop_plan item?  The reference: ``log_step > 0 and log_step % val_freq == 0``
-    after the optimizer step and the checkpoint save (finetune.py:1101), on EVERY micro-batch of such a gradient step.  Here
-    once per gradient step, as for the checkpoint: behind the optimizer step that completes it - or behind the last micro-batch
-    of the run, where the reference breaks before that optimizer step (loop_plan)."""
-    _, _, log_step, boundary, _, last = item
-    return bool(cfg.use_val_set) and (boundary or last) and log_step > 0 and log_step % cfg.val_freq == 0
-
-
-def validation_noise(cfg: FinetuneConfig, mcfg, rank: int, log_step: int, j: int) -> torch.Tensor:
-    """The head's N(0, 0.02^2) input perturbation (action_heads.py:64-72) of validation batch j of the sweep at log_step, phase
-    "Training": bf16 [chunk, action_dim * D] on the host, from a generator of its own keyed by (seed, rank, log_step, j) - the
-    training stream's draws do not depend on whether (or how long) validation ran.  (The reference draws both from torch's
-    global generator.)"""
-    key = (((int(cfg.seed) * 1_000_003 + int(rank)) * 1_000_033 + int(log_step)) * 10_007 + int(j)) % (2 ** 63 - 1)
-    g = torch.Generator().manual_seed(key)
-    return (torch.randn(mcfg.chunk, mcfg.action_dim * mcfg.llm.d, generator=g) * 0.02).to(torch.bfloat16)
-
-
-class ValidationPass:
-    """The reference's run_validation (finetune.py:605-685) on held-out batches: eval mode (no LoRA dropout, no image
-    augmentation), no gradient; per batch the three L1 values of run_forward_pass, each averaged over the batches of the sweep
-    as the reference does (sum / count of Python floats).  A sweep is ONE pass over the source from this rank's own offset,
-    ended early behind the first batch at which --val_time_limit seconds have passed; a finite source is not cycled to fill the
-    time limit (the reference's RLDS val iterator repeats for ever: the same batches would count twice).  No collective: every
-    rank validates on its own, as every rank of the reference does."""
-
-    def __init__(self, cfg: FinetuneConfig, mcfg, dev: str, rank: int, model, static: dict, L: int, pad_id: int, use_graph: bool,
-                 val_batches=None):
-        self.cfg, self.mcfg, self.dev, self.rank, self.model, self.L, self.pad_id = cfg, mcfg, dev, rank, model, L, pad_id
-        self.use_graph = use_graph
-        self.shapes = {k: (tuple(v.shape), v.dtype) for k, v in static.items()}   # the captured step's batch: shape contract
-        if val_batches is not None:
-            self.items, self.files = list(val_batches), None
-            if not self.items:
-                raise ValueError("empty validation batch iterable")
-        else:
-            src = cfg.val_batch_file
-            self.files = sorted(str(p) for p in Path(src).glob("*.pt")) if os.path.isdir(src) else [src]
-            if not self.files or not os.path.isfile(self.files[0]):
-                raise FileNotFoundError(f"no .pt validation batch files under {src}")
-            self.items = None
-        self.stage, self.static, self.noise = None, None, None
-        self.training_phase = cfg.phase == "Training"
-
-    def _order(self):
-        n = len(self.items if self.items is not None else self.files)
-        o = self.rank % n
-        for i in list(range(o, n)) + list(range(o)):
-            yield self.items[i] if self.items is not None else torch.load(self.files[i], weights_only=True)
-
-    def prepare(self, b: dict) -> dict:
-        """Host collate of one validation batch: frames -> plain normalised pixels, right-padding to the captured length, the
-        training batch's shapes enforced."""
-        from .input_stage import GPUInputStage, backbone_norms
-        b = {k: v.to(self.dev) for k, v in b.items()}
-        if "frames_u8" in b:
-            fr = b.pop("frames_u8")
-            if fr.dtype != torch.uint8 or fr.dim() != 5 or fr.shape[-1] != 3:
-                raise ValueError(f"frames_u8 must be uint8 [B, n_img, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
-            if self.stage is None:
-                self.stage = GPUInputStage(self.dev, backbones=backbone_norms(self.mcfg), image_size=self.mcfg.vit[0].img, resize=self.cfg.frame_resize)
-            b["pixel_values"] = self.stage.pixels(fr)              # never augmented (rlds/dataset.py:412: train=False)
-        B = self.shapes["input_ids"][0][0]
-        if b["input_ids"].shape[0] != B:
-            raise ValueError(f"validation batch of {b['input_ids'].shape[0]} samples: the validation pass runs at the training batch size "
-                             f"({B}, --batch_size)")
-        b = _pad_to(b, self.L, self.pad_id)
-        out = {}
-        for k, (shape, dt) in self.shapes.items():
-            if k not in b:
-                raise ValueError(f"validation batch without {k!r} (the training batches carry {sorted(self.shapes)})")
-            if tuple(b[k].shape) != shape:
-                raise ValueError(f"validation batch {k!r} of shape {tuple(b[k].shape)}: the training step's is {shape}")
-            out[k] = b[k] if b[k].dtype == dt else b[k].to(dt)
-        return out
-
-    def sweep(self, log_step: int) -> dict:
-        model, t0 = self.model, time.time()
-        model.begin_validation()
-        values = []
-        for j, b in enumerate(self._order()):
-            b = self.prepare(b)
-            noise = None
-            if self.training_phase:
-                nz = validation_noise(self.cfg, self.mcfg, self.rank, log_step, j)
-                if self.noise is None:
-                    self.noise = torch.empty(nz.shape, device=self.dev, dtype=nz.dtype)
-                self.noise.copy_(nz)
-                noise = self.noise
-            if self.use_graph:
-                if self.static is None:
-                    self.static = {k: v.clone() for k, v in b.items()}
-                else:
-                    for k in self.static:
-                        self.static[k].copy_(b[k])
-                loss3 = model.val_step_graphed(self.static, noise)
-            else:
-                loss3 = model.val_forward(b, noise)
-            values.append(loss3.tolist())              # host sync on this batch's completion (the reference's .item())
-            if time.time() - t0 > self.cfg.val_time_limit:
-                break
-        model.end_validation()
-        n = len(values)
-        mean = [sum(v[i] for v in values) / n for i in range(3)]
-        return dict(step=log_step, loss_value=mean[0], loss=mean[0], curr_action_l1_loss=mean[1], next_actions_l1_loss=mean[2],
-                    val_batches_count=n)
-
-
 def save_training_checkpoint(cfg: FinetuneConfig, run_dir: Path, step: int, eng, dataset_statistics: Optional[dict] = None,
                              trainer=None, train_state=None) -> Path:
     """File names / key layout of finetune.py:527-572 (rank 0).  Where the VLM goes follows the reference: ``use_fz`` ->
@@ -482,225 +375,75 @@ def save_training_checkpoint(cfg: FinetuneConfig, run_dir: Path, step: int, eng,
     return d
 
 
-def _pad_to(batch: dict, L: int, pad_id: int) -> dict:
-    """Right-pad (collator semantics, data_utils.py:114-134) a batch to the static sequence length of the captured step."""
-    cur = batch["input_ids"].shape[1]
-    if cur == L:
-        return batch
-    if cur > L:
-        raise ValueError(f"batch with {cur} tokens exceeds the captured sequence length {L}: raise --max_seq_len")
-    out = dict(batch)
-    pad = lambda t, v: torch.nn.functional.pad(t, (0, L - cur), value=v)
-    out["input_ids"], out["labels"] = pad(batch["input_ids"], pad_id), pad(batch["labels"], -100)
-    out["attention_mask"] = pad(batch["attention_mask"].to(torch.bool), False)
-    return out
+class StepRunner:
+    """One training step in each of its four forms - trainer (LoRA / full fine-tune) or the adapter-only engine, captured or eager.
+    It owns what the forms need between steps: the static batch of the captured step, the head-noise buffer (``training``: the caller
+    refills it before a step; else no noise is fed) and whether a step has run."""
 
+    def __init__(self, eng, trainer, mcfg, dev: str, use_graph: bool, training: bool = True, conservative_rows: bool = False):
+        self.eng, self.trainer, self.owner = eng, trainer, trainer or eng
+        self.use_graph, self.conservative_rows = bool(use_graph), conservative_rows
+        self.noise = torch.zeros(mcfg.chunk, mcfg.action_dim * mcfg.llm.d, device=dev, dtype=torch.bfloat16)
+        self.fed_noise = self.noise if training else None
+        self.static, self.first = None, True
 
-RAW_BATCH_KEYS = ("frames_u8", "prompt_flat", "prompt_off", "actions_raw", "proprio_raw")
-
-
-def raw_batch_stats(norm_stats: dict, dataset_name: Optional[str] = None) -> dict:
-    """The dataset_statistics.json entry a raw batch is normalised with: the one its ``dataset_name`` names, else the file's only one."""
-    if dataset_name is None and len(norm_stats) == 1:
-        dataset_name = next(iter(norm_stats))
-    if dataset_name not in norm_stats:
-        raise KeyError(f"dataset statistics hold no entry {dataset_name!r} (the batch's dataset_name; without one the file must hold a "
-                       f"single entry): its keys are {sorted(norm_stats)}")
-    st = norm_stats[dataset_name]
-    if "action" not in st or "proprio" not in st:
-        raise KeyError(f"dataset statistics entry {dataset_name!r} needs 'action' and 'proprio', got {sorted(st)}")
-    return st
-
-
-def mixture_stats(norm_stats: dict, dataset_names) -> tuple:
-    """(action entries, proprio entries) in the order of a mixed raw batch's ``dataset_names``: what its ``dataset_index`` indexes.
-    KeyError naming the dataset the statistics hold no entry for."""
-    for n in dataset_names:
-        if n not in norm_stats:
-            raise KeyError(f"dataset statistics hold no entry {n!r} (one of the batch's dataset_names {tuple(dataset_names)}): their keys "
-                           f"are {sorted(norm_stats)}")
-    sts = [raw_batch_stats(norm_stats, n) for n in dataset_names]
-    return tuple(st["action"] for st in sts), tuple(st["proprio"] for st in sts)
-
-
-def batch_stream(cfg: FinetuneConfig, mcfg, dev: str, rank: int, batches=None, explicit=(), world: int = 1, info: Optional[dict] = None,
-                 start: int = 0):
-    """Endless iterator over collated batches: an explicit iterable, ``--batch_file`` / ``--frame_batch_file`` / ``--raw_batch_file``
-    (one .pt dict, or a directory of them, cycled in sorted order; every rank starts at its own offset - the reference's ranks draw independent
-    shuffles, finetune.py:988-994), ``--episode_file``, ``--episode_mix``, or seeded synthetic batches (a new one every micro-step).
-
-    ``--episode_file``: the episodes are loaded once into an ``episodes.EpisodeStore`` on the device; micro-step s of this rank collates
-    ``store.sample(batch_size, seed, rank, world, s)`` - a raw batch as below, keyed by the same (seed, rank, step).  Without
-    --dataset_statistics_file it is normalised with ``store.statistics()``, which is then also left in ``info["dataset_statistics"]``
-    (the caller's dict) for the checkpoints.
-
-    ``--val_episode_fraction f``: store and mix are built with ``holdout=f`` - every dataset's last episodes are never drawn here (the
-    training table counts no window of theirs) and wait for ``heldout.HeldOutSweep``; the statistics stay over all episodes.
-    ``info["store"]`` hands the store / mix to the caller.
-
-    ``--episode_mix``: the same over a weighted mixture of datasets (``mixture.EpisodeMix``): the raw batch then carries
-    ``dataset_index`` (int32 [B]) and ``dataset_names``, and every sample is normalised with its own dataset's entry - of the mix's
-    statistics, or of --dataset_statistics_file, which must then hold every name (KeyError naming the missing one).  Such a batch
-    is collated the same way when it comes from ``--raw_batch_file`` or ``batches``.  ``info["mixture"]`` holds ``mixture_info()``.
-
-    A batch carrying ``frames_u8`` (uint8 [B, n_img, H, W, 3]) instead of ``pixel_values`` goes through the GPU input stage here:
-    with --image_aug (default True, as in the reference) the training augmentation of the reference's RLDS pipeline
-    (datasets.py:204-218, drawn per image from --seed, the rank and this rank's micro-step counter), else a plain normalise.  The
-    normalisation per backbone follows the model config (input_stage.backbone_norms: DINOv2-like ViTs ImageNet, others SigLIP).
-    Frames not at the model's image size go through the Pillow-exact bicubic resize of the processor first; the reference's RLDS
-    stage resizes with TF's lanczos3 there, which is not reproduced.
-
-    A raw batch (``actions_raw`` ...: RAW_BATCH_KEYS) is collated on the device by ``GPUInputStage.collate``: actions and proprio
-    normalised with the statistics of ``--dataset_statistics_file`` (the entry named by the batch's ``dataset_name``, or the file's
-    only one), token length --max_seq_len (0: the batch's own), filler tokens and augmentation keyed by the same (seed, rank, step).
-
-    ``start`` (--resume_train_state): the micro-step the first batch belongs to.  Every source is a function of that position - the
-    samplers', the augmentation's and the collator's step, the file sources' cyclic index, the synthetic source's counter - so the
-    stream yields what the stream of a run from 0 yields from its ``start``-th batch on; an explicit iterable is advanced by
-    cycling through it without collating."""
-    from . import synthetic as S
-    from .input_stage import GPUInputStage, ImageAugment, backbone_norms
-    start = int(start)
-    assert start >= 0
-    stage, step, norm_stats, mix_stats = None, start, None, {}
-
-    def collate_raw(b):
-        nonlocal stage, step, norm_stats
-        missing = [k for k in RAW_BATCH_KEYS if k not in b]
-        if missing:
-            raise ValueError(f"raw batch lacks {missing}: it carries {RAW_BATCH_KEYS} and optionally dataset_name")
-        mixed = "dataset_index" in b or "dataset_names" in b
-        if mixed and not ("dataset_index" in b and "dataset_names" in b):
-            raise ValueError("a raw batch of a dataset mixture carries both dataset_index (int32 [B]) and dataset_names")
-        if norm_stats is None:
-            if not cfg.dataset_statistics_file:
-                raise ValueError("raw batches carry un-normalised actions / proprio: pass the statistics with --dataset_statistics_file")
-            norm_stats = json.load(open(cfg.dataset_statistics_file))
-        if mixed:               # every sample with its own dataset's statistics; the entry lists are built once per tuple of names
-            names = tuple(b["dataset_names"])
-            if names not in mix_stats:
-                mix_stats[names] = mixture_stats(norm_stats, names)
-            act_st, pr_st = mix_stats[names]
-            index = b["dataset_index"].to(dev, torch.int32)
+    def capture(self, first_batch: dict, resume_state: Optional[dict] = None) -> None:
+        """use_graph: captures the step on a copy of the padded ``first_batch``, the static batch; eager: nothing to do."""
+        if not self.use_graph:
+            return
+        self.static = {k: v.clone() for k, v in first_batch.items()}
+        if self.trainer is not None:  # LoRA / full fine-tune: forward + backward as one captured graph (trainers.BackboneTrainer.capture)
+            self.trainer.capture(self.static, self.fed_noise)
         else:
-            st = raw_batch_stats(norm_stats, b.get("dataset_name"))
-            act_st, pr_st, index = st["action"], st["proprio"], None
-        if stage is None:
-            stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img, resize=cfg.frame_resize)
-        aug = ImageAugment(seed=cfg.seed, rank=rank, step=step) if cfg.image_aug else None
-        L = cfg.max_seq_len or None
-        if L is None and b["prompt_off"].is_cuda:
-            raise ValueError("raw batches with prompt offsets on the device need --max_seq_len (the natural length would be read back)")
-        out = stage.collate(b["frames_u8"], (b["prompt_flat"], b["prompt_off"]), b["actions_raw"], b["proprio_raw"], action_stats=act_st,
-                            proprio_stats=pr_st, L=L, seed=cfg.seed, rank=rank, step=step, augment=aug, stats_index=index)
-        step += 1
-        return out
+            ts = resume_state
+            self.eng.capture(self.static, self.fed_noise, conservative_rows=self.conservative_rows,
+                             row0=ts["row0"] if ts is not None and ts["row0"] >= 0 else None)    # (the window of the run this one continues)
 
-    def collate(b):
-        nonlocal stage, step
-        if "actions_raw" in b:
-            return collate_raw(b)
-        b = {k: v.to(dev) for k, v in b.items()}
-        if "frames_u8" not in b:
-            if "image_aug" in explicit:
-                raise NotImplementedError(IMAGE_AUG_REFUSAL)
-            return b
-        fr = b.pop("frames_u8")
-        if fr.dtype != torch.uint8 or fr.dim() != 5 or fr.shape[-1] != 3:
-            raise ValueError(f"frames_u8 must be uint8 [B, n_img, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
-        if stage is None:
-            stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img, resize=cfg.frame_resize)
-        aug = ImageAugment(seed=cfg.seed, rank=rank, step=step) if cfg.image_aug else None
-        b["pixel_values"] = stage.pixels(fr, augment=aug)
-        step += 1
-        return b
-
-    if batches is not None:
-        skip = start
-        while True:
-            n = 0
-            for b in batches:
-                n += 1
-                if skip > 0:
-                    skip -= 1
-                    continue
-                yield collate(b)
-            if n == 0:
-                raise ValueError("empty batch iterable")
-    elif cfg.episode_file or cfg.episode_mix:
-        if cfg.episode_file:
-            from .episodes import EpisodeStore
-            where = cfg.episode_file
-            src = EpisodeStore.load(cfg.episode_file, dev, chunk=mcfg.chunk, dataset_name=cfg.dataset_name, holdout=cfg.val_episode_fraction,
-                                    jpeg_scan_index=cfg.jpeg_scan_index)
-        else:
-            from .mixture import EpisodeMix, parse_mix
-            where = "--episode_mix"
-            src = EpisodeMix.load(parse_mix(cfg.episode_mix), dev, chunk=mcfg.chunk, balance_weights=cfg.episode_mix_balance,
-                                  holdout=cfg.val_episode_fraction, jpeg_scan_index=cfg.jpeg_scan_index)
-        if (src.A, src.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
-            raise ValueError(f"{where}: actions_raw / proprio_raw have {src.A} / {src.Pd} columns, the model takes "
-                             f"{mcfg.action_dim} / {mcfg.proprio_dim}")
-        if src.frame_shape[0] != mcfg.n_img:
-            raise ValueError(f"{where}: frames_u8 carries {src.frame_shape[0]} images per step, --num_images_in_input is {mcfg.n_img}")
-        if not cfg.dataset_statistics_file:
-            norm_stats = src.statistics()
-            if info is not None:
-                info["dataset_statistics"] = norm_stats
-        elif src.mixed:
-            mixture_stats(json.load(open(cfg.dataset_statistics_file)), src.names)        # a missing entry is refused before the first step
-        if src.jpeg is not None and src.jpeg.seg_ent is not None and rank == 0:      # (a raw store, or a marker per row already: no index)
-            j = src.jpeg
-            print(json.dumps(dict(jpeg_scan_index=dict(pieces_per_frame=round(int(j.seg_tab.shape[0]) / j.N, 2), index_bytes=j.index_bytes(),
-                                                       jpeg_index_bad_scans=int((j.index_status != 0).sum())))), flush=True)
-        if cfg.verify_frames:                     # (a raw store has nothing to verify)
-            src.verify_frames()
-        if info is not None:
-            info["store"] = src                   # (the held-out sweep walks the same device-resident tables)
-        if src.mixed:
-            if info is not None:
-                info["mixture"] = src.mixture_info()
-            if rank == 0:
-                print(json.dumps(dict(mixture=src.mixture_info())), flush=True)
-        while True:
-            yield collate_raw(src.sample(cfg.batch_size, cfg.seed, rank, world, step))
-    elif cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file:
-        src = cfg.batch_file or cfg.frame_batch_file or cfg.raw_batch_file
-        files = sorted(str(p) for p in Path(src).glob("*.pt")) if os.path.isdir(src) else [src]
-        if not files:
-            raise FileNotFoundError(f"no .pt batch files under {src}")
-        i = (rank + start) % len(files)
-        while True:
-            b = torch.load(files[i], weights_only=True)
-            if cfg.frame_batch_file and "frames_u8" not in b:
-                raise ValueError(f"{files[i]}: --frame_batch_file batches carry frames_u8 (uint8 [B, n_img, H, W, 3])")
-            if cfg.raw_batch_file and "actions_raw" not in b:
-                raise ValueError(f"{files[i]}: --raw_batch_file batches carry {RAW_BATCH_KEYS}")
-            yield collate(b)
-            i = (i + 1) % len(files)
-    else:
-        i = start
-        while True:
-            yield S.make_batch(mcfg, cfg.batch_size, dev, seed=1_000_003 * cfg.seed + 7919 * rank + i, P=32, ragged=True)
-            i += 1
+    def step(self, cur: dict, nxt: dict, lr: float):
+        """Trains on ``cur``; ``nxt`` is the batch after it, whose vision stage the captured adapter-only step runs inside this one.
+        -> the three loss values on the device."""
+        first, self.first = self.first, False
+        if not self.use_graph:
+            return self.owner.train_step(cur, lr, self.fed_noise)
+        if self.trainer is not None:
+            for k in self.static:
+                self.static[k].copy_(cur[k])
+            return self.trainer.train_step_graphed(lr)
+        for k in self.static:         # (the pixels reach the vision stage through stage_next_pixels: the first step's copy is spare)
+            if k != "pixel_values" or first:
+                self.static[k].copy_(cur[k])
+        self.eng.stage_next_pixels(nxt["pixel_values"])
+        return self.eng.train_step_graphed(lr)
 
 
-def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None, on_finish=None) -> dict:
-    """``batches``: optional iterable of collated batch dicts (util/data_utils.py:165-172 contract); ``explicit``: names of
-    the flags given on the command line (parse_args records them); ``val_batches``: optional held-out batches of the same form
-    for --use_val_set (iterated once per validation sweep; instead of --val_batch_file); ``on_finish(engine, trainer or None)``:
-    called once behind the last step and the final save, with every update applied and the device idle (a caller that wants
-    to look at the trained model itself, not at its checkpoint files)."""
-    from . import ddp, engine as E, synthetic as S
-    explicit = explicit or getattr(cfg, "_explicit", ())
-    check_supported(cfg, explicit, frame_batches=batches is not None, val_batches=val_batches is not None)
+class LogReadback:
+    """The logged step's one host read-back: 1-D device tensors added by name, concatenated in that order (a lone part as it is),
+    read with one ``tolist`` and handed back by name."""
+
+    def __init__(self):
+        self.parts = {}
+
+    def add(self, name: str, part) -> None:
+        self.parts[name] = part
+
+    def read(self) -> dict:
+        parts = list(self.parts.values())
+        flat = iter((torch.cat(parts) if len(parts) > 1 else parts[0]).tolist())
+        return {name: [next(flat) for _ in range(part.numel())] for name, part in self.parts.items()}
+
+
+def setup_run(cfg: FinetuneConfig, explicit, given_batches: bool, given_val_batches: bool) -> SimpleNamespace:
+    """Everything in front of the first batch: the flags checked, the process group, the model config, the weights (random, --vlm_path,
+    --resume), the --resume_train_state file, the engine and the trainer of the mode with their step controls and, resumed, their
+    optimizer state.  -> what the loop needs, by name."""
+    from . import checkpoints as CK, ddp, engine as E, synthetic as S, train_state as TS
+    check_supported(cfg, explicit, frame_batches=given_batches, val_batches=given_val_batches)
     rank, local, world = ddp.init_process_group_from_env()
     torch.cuda.set_device(local)
     dev = f"cuda:{local}"
-    from . import checkpoints as CK
+    vlm_sd = CK.load_file(cfg.vlm_path) if (cfg.vlm_path and os.path.isfile(cfg.vlm_path)) else None
     # model geometry: explicit --backbone, else read off the --vlm_path state dict (which backbones, widths, depths), else BASELINE
     # configs[1].  The reference builds the model from the checkpoint's config.json (finetune.py:777-816); --tiny is the plumbing size.
-    vlm_sd = CK.load_file(cfg.vlm_path) if (cfg.vlm_path and os.path.isfile(cfg.vlm_path)) else None
     if cfg.tiny:
         mcfg = E.NAMED_CONFIGS[cfg.backbone or "tiny"]()
     elif cfg.backbone is not None:
@@ -716,9 +459,8 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None, o
     if vlm_sd is not None:                                        # local VLM state dict (HF-style or native Prismatic keys)
         W.update(CK.split_reference_state_dict(vlm_sd, mcfg))
     lora_sd = None
-    from . import train_state as TS
     # the flags that define the trajectory (--save_train_state writes them, --resume_train_state compares them), and the state to go on from
-    fp = TS.fingerprint(cfg, mode, world, mcfg.n_img, batches is not None) if (cfg.save_train_state or cfg.resume_train_state) else None
+    fp = TS.fingerprint(cfg, mode, world, mcfg.n_img, given_batches) if (cfg.save_train_state or cfg.resume_train_state) else None
     ts, start = None, None
     if cfg.resume:                    # head / proprio (finetune.py:275-278) + the action queries + whatever else this mode trained
         if not (cfg.resum_vla_path and os.path.isdir(cfg.resum_vla_path)):
@@ -753,115 +495,107 @@ def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None, o
     elif mode == "full":
         from .trainers import FullFinetune
         trainer = FullFinetune(eng)
-    use_graph = cfg.use_graph
-    (trainer or eng).set_grad_accumulation(cfg.grad_accumulation_steps)
+    owner = trainer or eng
+    owner.set_grad_accumulation(cfg.grad_accumulation_steps)
     if cfg.objective != "l1":
         trainer.set_objective(cfg.objective)
-    clip = cfg.max_grad_norm is not None
-    if clip:
-        (trainer or eng).set_max_grad_norm(cfg.max_grad_norm)
-    owner = trainer or eng
+    if cfg.max_grad_norm is not None:
+        owner.set_max_grad_norm(cfg.max_grad_norm)
     if ts is not None:                # the loaded weights are the ones the state was written beside (digests), then m, v and the step count
         owner.verify_data_digests(ts)
         owner.load_optimizer_state(ts)
+    return SimpleNamespace(rank=rank, world=world, dev=dev, mcfg=mcfg, mode=mode, eng=eng, trainer=trainer, owner=owner, fp=fp, ts=ts,
+                           start=start, pad_id=min(S.PAD_ID, mcfg.llm.vocab - 1))
+
+
+def finetune(cfg: FinetuneConfig, batches=None, explicit=(), val_batches=None, on_finish=None) -> dict:
+    """``batches``: optional iterable of collated batch dicts (util/data_utils.py:165-172 contract); ``explicit``: names of
+    the flags given on the command line (parse_args records them); ``val_batches``: optional held-out batches of the same form
+    for --use_val_set (iterated once per validation sweep; instead of --val_batch_file); ``on_finish(engine, trainer or None)``:
+    called once behind the last step and the final save, with every update applied and the device idle (a caller that wants
+    to look at the trained model itself, not at its checkpoint files)."""
+    from . import ddp, train_state as TS
+    explicit = explicit or getattr(cfg, "_explicit", ())
+    run = setup_run(cfg, explicit, batches is not None, val_batches is not None)
+    rank, world, dev, mcfg, mode, eng, trainer, owner, ts, start, pad_id = (run.rank, run.world, run.dev, run.mcfg, run.mode, run.eng,
+                                                                          run.trainer, run.owner, run.ts, run.start, run.pad_id)
     info = {}
     stream = batch_stream(cfg, mcfg, dev, rank, batches, explicit, world=world, info=info, start=start[0] if start else 0)
-    pad_id = min(S.PAD_ID, mcfg.llm.vocab - 1)
     cur = next(stream)
     L = cfg.max_seq_len or cur["input_ids"].shape[1]
-    cur = _pad_to(cur, L, pad_id)
+    cur = pad_to(cur, L, pad_id)
     training = cfg.phase == "Training"
     gen = torch.Generator(device=dev).manual_seed(cfg.seed * 7919 + rank)
-    noise = torch.zeros(mcfg.chunk, mcfg.action_dim * mcfg.llm.d, device=dev, dtype=torch.bfloat16)
     run_dir = Path(cfg.run_root_dir) / (cfg.run_id_override or f"native+{cfg.dataset_name}+b{cfg.batch_size * world}+lr-{cfg.learning_rate}")
     stats = json.load(open(cfg.dataset_statistics_file)) if cfg.dataset_statistics_file else info.get("dataset_statistics")
-    static = None
-    if use_graph:
-        static = {k: v.clone() for k, v in cur.items()}
-        if trainer is not None:       # LoRA / full fine-tune: forward + backward as one captured graph (trainers.BackboneTrainer.capture)
-            trainer.capture(static, noise if training else None)
-        else:
-            eng.capture(static, noise if training else None, conservative_rows=cfg.conservative_rows,
-                        row0=ts["row0"] if ts is not None and ts["row0"] >= 0 else None)     # (the window of the run this one continues)
+    runner = StepRunner(eng, trainer, mcfg, dev, cfg.use_graph, training, cfg.conservative_rows)
+    runner.capture(cur, ts)
     if ts is not None:                # behind capture and its warm-up, which move the dropout counter: the counters, the head-noise generator
         owner.load_device_counters(ts)
         TS.restore_generator(gen, ts, writer=rank == 0)
-    validator = None
+    validator, shaped = None, runner.static if runner.static is not None else cur
     if cfg.use_val_set and cfg.val_episode_fraction is not None:
         from .heldout import HeldOutSweep
-        validator = HeldOutSweep(cfg, mcfg, dev, rank, world, trainer or eng, info["store"], stats, static if static is not None else cur, L,
-                                 use_graph)
+        validator = HeldOutSweep(cfg, mcfg, dev, rank, world, owner, info["store"], stats, shaped, L, cfg.use_graph)
         info["heldout"] = validator.info()
         if rank == 0:
             print(json.dumps(dict(heldout=info["heldout"])), flush=True)
     elif cfg.use_val_set:
-        validator = ValidationPass(cfg, mcfg, dev, rank, trainer or eng, static if static is not None else cur, L, pad_id, use_graph,
-                                   val_batches)
-    log, val_log, t0, saved_at, steps_done, first = [], [], time.time(), None, 0, True
+        validator = ValidationPass(cfg, mcfg, dev, rank, owner, shaped, L, pad_id, cfg.use_graph, val_batches)
+    clip, ce = cfg.max_grad_norm is not None, cfg.objective == "token_ce"
+    store = info.get("store")
+    log, val_log, t0, saved_at, steps_done = [], [], time.time(), None, 0
 
     def state_after(batch_idx, g, log_step):
         """--save_train_state: the state behind the optimizer step that closes micro-step batch_idx (every update applied)."""
-        return lambda: TS.collect(owner, mode=mode, fp=fp, next_grad_step=g + 1, next_micro_step=batch_idx + 1, log_step=log_step,
+        return lambda: TS.collect(owner, mode=mode, fp=run.fp, next_grad_step=g + 1, next_micro_step=batch_idx + 1, log_step=log_step,
                                   generator=gen, row0=eng.frozen_row0)
+
+    def log_entry(log_step, lr, loss3) -> dict:
+        """The log line of a step: the only host sync, one read-back that everything the line carries rides."""
+        rb = LogReadback()
+        rb.add("loss", loss3)
+        if ce:      # the four metrics of the reference's trainer (base_strategy.py:350-356; this rank's batch, as there)
+            rb.add("ce", trainer.ce_metrics)
+        if store is not None and store.jpeg is not None and store.decode_status is not None:
+            rb.add("jpeg", store.bad_segments())   # JPEG frames: how many segments of the batch drawn last did not decode
+        if clip:    # the norm of this step's update (the captured adapter step leaves its update pending: apply it)
+            eng.flush()
+            rb.add("grad_norm", owner.grad_norm.view(1))
+        if cfg.log_state_digest:        # the digests as 16-bit limbs (exact in f32); they are of the state behind this step's update
+            eng.flush()
+            rb.add("digest", TS.limbs_f32(owner.state_digests_device()))
+        got = rb.read()
+        l = got["loss"]
+        if not all(x == x for x in l):
+            raise FloatingPointError(f"non-finite loss at step {log_step}: {l} (a captured step replayed on a batch whose action "
+                                     "block starts before the frozen live-row window poisons the loss: --conservative_rows true)")
+        entry = dict(step=log_step, loss_value=l[0], curr_action_l1_loss=l[1], next_actions_l1_loss=l[2], lr=lr)
+        if ce:      # (next_actions_l1_loss: the reference's name for the decoded next-actions L1 replaces the copy of the loss)
+            from .ops import TOKEN_METRIC_NAMES
+            entry.update(zip(TOKEN_METRIC_NAMES, got["ce"]))
+        if clip:
+            entry["grad_norm"] = got["grad_norm"][0]
+        if "jpeg" in got:
+            entry["jpeg_bad_segments"] = int(got["jpeg"][0])
+        if cfg.log_state_digest:
+            entry["state_digest"] = owner.state_digest_dict(TS.from_limbs(got["digest"]))
+        return entry
+
     for item in loop_plan(cfg, start):
         batch_idx, g, log_step, boundary, save, last = item
-        nxt = _pad_to(next(stream), L, pad_id)                    # one batch of look-ahead: its vision stage runs inside this step
+        nxt = pad_to(next(stream), L, pad_id)                     # one batch of look-ahead: its vision stage runs inside this step
         if training:   # fresh N(0, 0.02^2) perturbation every call (action_heads.py:14-17, 69-72)
-            noise.copy_((torch.randn(noise.shape, device=dev, generator=gen) * 0.02).to(torch.bfloat16))
+            runner.noise.copy_((torch.randn(runner.noise.shape, device=dev, generator=gen) * 0.02).to(torch.bfloat16))
         lr = lr_at(g, cfg)
-        if trainer is not None and use_graph:
-            for k in static:
-                static[k].copy_(cur[k])
-            loss3 = trainer.train_step_graphed(lr)
-        elif trainer is not None:
-            loss3 = trainer.train_step(cur, lr, noise if training else None)
-        elif use_graph:
-            for k in static:
-                if k != "pixel_values" or first:
-                    static[k].copy_(cur[k])
-            eng.stage_next_pixels(nxt["pixel_values"])
-            loss3 = eng.train_step_graphed(lr)
-        else:
-            loss3 = eng.train_step(cur, lr, noise if training else None)
+        loss3 = runner.step(cur, nxt, lr)
         steps_done += int(boundary)
-        first = False
         if boundary and world > 1 and cfg.sync_check_freq > 0 and steps_done % cfg.sync_check_freq == 0:
             eng.flush()                      # (the captured adapter step leaves its update pending: compare what the ranks really hold)
             flats = [eng.head.P.data] + ([trainer.P.data] if trainer is not None else [])
             ddp.assert_ranks_in_sync(flats, what=f"parameters after optimizer step {steps_done}")
-        if boundary and (log_step % cfg.wandb_log_freq == 0 or last):          # the only host sync, every log_freq gradient steps
-            ce = cfg.objective == "token_ce"
-            # token-CE: the four metrics of the reference's trainer (base_strategy.py:350-356; this rank's batch, as there) ride the
-            # loss's read-back - one copy, one sync
-            parts = [loss3] + ([trainer.ce_metrics] if ce else [])
-            store = info.get("store")
-            jpeg = store is not None and store.jpeg is not None and store.decode_status is not None
-            if jpeg:    # JPEG frames: how many segments of the batch drawn last did not decode rides the same read-back
-                parts.append(store.bad_segments())
-            if clip:    # the norm of this step's update rides the same read-back (the captured adapter step leaves its update pending: apply it)
-                eng.flush()
-                parts.append((trainer or eng).grad_norm.view(1))
-            if cfg.log_state_digest:        # the digests ride it too, as 16-bit limbs (exact in f32); they are of the state behind this step's update
-                eng.flush()
-                parts.append(TS.limbs_f32(owner.state_digests_device()))
-            l = (torch.cat(parts) if len(parts) > 1 else loss3).tolist()
-            if cfg.log_state_digest:
-                nd = parts[-1].numel()
-                l, digests = l[:-nd], owner.state_digest_dict(TS.from_limbs(l[-nd:]))
-            l, tm, gn, bad = l[:3], l[3:7] if ce else [], l[-1], l[7 if ce else 3] if jpeg else None
-            if not all(x == x for x in l):
-                raise FloatingPointError(f"non-finite loss at step {log_step}: {l} (a captured step replayed on a batch whose action "
-                                         "block starts before the frozen live-row window poisons the loss: --conservative_rows true)")
-            log.append(dict(step=log_step, loss_value=l[0], curr_action_l1_loss=l[1], next_actions_l1_loss=l[2], lr=lr))
-            if ce:      # (next_actions_l1_loss: the reference's name for the decoded next-actions L1 replaces the copy of the loss)
-                from .ops import TOKEN_METRIC_NAMES
-                log[-1].update(zip(TOKEN_METRIC_NAMES, tm))
-            if clip:
-                log[-1]["grad_norm"] = gn
-            if jpeg:
-                log[-1]["jpeg_bad_segments"] = int(bad)
-            if cfg.log_state_digest:
-                log[-1]["state_digest"] = digests
+        if boundary and (log_step % cfg.wandb_log_freq == 0 or last):          # every log_freq gradient steps
+            log.append(log_entry(log_step, lr, loss3))
             if rank == 0:
                 print(json.dumps(log[-1]), flush=True)
         if save:

@@ -22,7 +22,9 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .batches import batch_stats, input_stage
 from .episodes import MAX_BATCH, locate     # one workgroup names the batch, as one draws a training batch
+from .validation import ValidationFeed, validation_noise
 
 HELDOUT_STREAM = 0x4E1D0075EE9A1        # the sweep's seed word for the collator's filler ids: apart from the training batches' under equal seeds
 SYNC_EVERY = 8                          # batches between two host waits (the --val_time_limit check): the overshoot is at most this many
@@ -145,12 +147,10 @@ class HeldOutSweep:
     batches are normalised with.  The sweep owns its index, raw-batch, noise and sum buffers: the store's ``_out[B]`` buffers hold the
     next training batch at the same B and are not touched.  With use_graph the model's captured validation graphs hold the addresses
     of the first static batch they were replayed on: one sweeper (or ValidationPass) per model, or hand the same ``static`` buffers on
-    (``sweeper.static``)."""
+    (``sweeper.feed.static``)."""
 
     def __init__(self, cfg, mcfg, dev: str, rank: int, world: int, model, store, norm_stats: dict, static: dict, L: int,
                  use_graph: bool, group=None):
-        from .finetune import mixture_stats, raw_batch_stats
-        from .input_stage import GPUInputStage, backbone_norms
         if getattr(store, "val_off", None) is None:
             raise ValueError("HeldOutSweep: the store holds nothing out (build it with holdout=f)")
         B = int(cfg.batch_size)
@@ -160,20 +160,16 @@ class HeldOutSweep:
         if self.stride < 1:
             raise ValueError("--val_window_stride must be >= 1")
         self.cfg, self.mcfg, self.dev, self.rank, self.world, self.model, self.store = cfg, mcfg, dev, int(rank), int(world), model, store
-        self.B, self.L, self.use_graph, self.group = B, int(L), bool(use_graph), group
+        self.B, self.L, self.group = B, int(L), group
         self.mixed, self.names, self.D = store.mixed, tuple(store.names), store.D
         self.C, self.A = int(mcfg.chunk), int(mcfg.action_dim)
         # per-dataset entries in the order ds indexes them; a single store's collate takes its one entry bare (no stats_index)
-        if self.mixed:
-            self.action_stats, self.proprio_stats = mixture_stats(norm_stats, self.names)
-        else:
-            st = raw_batch_stats(norm_stats, self.names[0])
-            self.action_stats, self.proprio_stats = st["action"], st["proprio"]
+        self.action_stats, self.proprio_stats = batch_stats(norm_stats, self.names, self.mixed)
         self.windows = [store.heldout[n]["heldout_windows"] for n in self.names]
         self.Nv = int(store.Nv)
         self.n_batches = sweep_batches(self.Nv, self.stride, B, self.rank, self.world)
-        self.shapes = {k: (tuple(v.shape), v.dtype) for k, v in static.items()}
-        self.stage = GPUInputStage(dev, backbones=backbone_norms(mcfg), image_size=mcfg.vit[0].img, resize=getattr(cfg, "frame_resize", "bicubic"))
+        self.feed = ValidationFeed(model, static, use_graph, "held-out")
+        self.stage = input_stage(cfg, mcfg, dev)
         self.training_phase = cfg.phase == "Training"
         e = torch.empty
         self.idx = dict(ds=e(B, dtype=torch.int32, device=dev), ep=e(B, dtype=torch.int32, device=dev), row=e(B, dtype=torch.int64, device=dev),
@@ -186,7 +182,7 @@ class HeldOutSweep:
         self.sums = torch.zeros(n + self.D, dtype=torch.float64, device=dev)
         self.acc, self.cnt = self.sums[:n].view(self.D, self.C, self.A), self.sums[n:].view(torch.int64)
         self.sums_host = torch.empty(n + self.D, dtype=torch.float64).pin_memory()
-        self.static, self.noise, self.noise_host, self.event = None, None, None, torch.cuda.Event()
+        self.noise, self.noise_host, self.event = None, None, torch.cuda.Event()
         self.batches_run = 0
 
     # ---- one batch -------------------------------------------------------------------------------------------------------------
@@ -205,21 +201,15 @@ class HeldOutSweep:
                                action_stats=self.action_stats, proprio_stats=self.proprio_stats, L=self.L,
                                seed=(int(self.cfg.seed) ^ HELDOUT_STREAM) & (2 ** 64 - 1), rank=self.rank, step=j, augment=None,
                                stats_index=raw["dataset_index"] if self.mixed else None)
-        for k, (shape, _) in self.shapes.items():
-            if k not in b:
-                raise ValueError(f"held-out batch without {k!r} (the training batches carry {sorted(self.shapes)})")
-            if tuple(b[k].shape) != shape:
-                raise ValueError(f"held-out batch {k!r} of shape {tuple(b[k].shape)}: the training step's is {shape}")
-        return {k: b[k] for k in self.shapes}
+        return self.feed.enforce(b)
 
     def _noise(self, log_step: int, j: int) -> Optional[torch.Tensor]:
-        """finetune.validation_noise of batch j, keyed by the batch's place in the whole sweep (global batch j world + rank, rank word 0):
+        """validation.validation_noise of batch j, keyed by the batch's place in the whole sweep (global batch j world + rank, rank word 0):
         a batch's perturbation belongs to its windows, not to the rank that happens to run it, so a sweep gives the same sums on any
         number of ranks.  It goes through a ring of SYNC_EVERY pinned host buffers: the copy is asynchronous, and slot j % SYNC_EVERY
         is rewritten only behind the host wait that follows batch j."""
         if not self.training_phase:
             return None
-        from .finetune import validation_noise
         nz = validation_noise(self.cfg, self.mcfg, 0, log_step, j * self.world + self.rank)
         if self.noise is None:
             self.noise = torch.empty(nz.shape, device=self.dev, dtype=nz.dtype)
@@ -236,17 +226,7 @@ class HeldOutSweep:
         raw = self.draw(j)
         b = self.collate(raw, j)
         noise = self._noise(log_step, j)
-        if self.use_graph:
-            if self.static is None:
-                self.static = {k: b[k].clone() if b[k].dtype == dt else b[k].to(dt) for k, (_, dt) in self.shapes.items()}
-            else:
-                for k in self.static:
-                    self.static[k].copy_(b[k])
-            model.val_step_graphed(self.static, noise)
-            target = self.static["actions"]
-        else:
-            model.val_forward(b, noise)
-            target = b["actions"]
+        target = self.feed.forward(b, noise)[1]["actions"]
         to_bf16 = getattr(model, "eng", model)._to_bf16
         ops.heldout_l1_accumulate(model.val_pred.contiguous(), to_bf16(target), raw["dataset_index"] if self.mixed else None, raw["valid"], self.acc, self.cnt)
 
