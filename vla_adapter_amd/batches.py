@@ -169,16 +169,17 @@ def episode_batches(cfg, mcfg, dev: str, rank: int, world: int, info: Optional[d
     """``--episode_file`` / ``--episode_mix``: loads the store / mix, checks it against the model and the statistics file, fills ``info``
     (dataset_statistics, store, mixture), prints rank 0's lines; then the raw batch of every micro-step, drawn on the device at the
     collator's own step and normalised with the source's own statistics where no file gives them."""
+    jpeg_quality = int(getattr(cfg, "episode_jpeg_quality", 0)) or None          # (0: off - the frames stay in the form their files have)
     if cfg.episode_file:
         from .episodes import EpisodeStore
         where = cfg.episode_file
         src = EpisodeStore.load(cfg.episode_file, dev, chunk=mcfg.chunk, dataset_name=cfg.dataset_name, holdout=cfg.val_episode_fraction,
-                                jpeg_scan_index=cfg.jpeg_scan_index)
+                                jpeg_scan_index=cfg.jpeg_scan_index, jpeg_quality=jpeg_quality)
     else:
         from .mixture import EpisodeMix, parse_mix
         where = "--episode_mix"
         src = EpisodeMix.load(parse_mix(cfg.episode_mix), dev, chunk=mcfg.chunk, balance_weights=cfg.episode_mix_balance,
-                              holdout=cfg.val_episode_fraction, jpeg_scan_index=cfg.jpeg_scan_index)
+                              holdout=cfg.val_episode_fraction, jpeg_scan_index=cfg.jpeg_scan_index, jpeg_quality=jpeg_quality)
     if (src.A, src.Pd) != (mcfg.action_dim, mcfg.proprio_dim):
         raise ValueError(f"{where}: actions_raw / proprio_raw have {src.A} / {src.Pd} columns, the model takes "
                          f"{mcfg.action_dim} / {mcfg.proprio_dim}")

@@ -8,7 +8,9 @@
 // The forward kernel is integer only; the resize sums in float32 with no contraction, as the numpy rule does
 // (tests/policy_image_rule_np.py).  Nothing is allocated, read back or synchronised.
 #include "common.h"
+#include "jpeg_encode_core.h"
 #include "jpeg_forward.h"
+#include "jpeg_stage_a.h"
 #include "jpeg_stage_b.h"
 #include "../../include/vla_jpeg.h"
 #include "../../include/vla_policy_image.h"
@@ -33,8 +35,9 @@ struct McuLds {
 };
 
 // WIDE: frames and in_stride are multiples of 16, so every 16 bytes of an MCU's row (48 bytes, at a multiple of 48 inside an image
-// whose rows are multiples of 48) load as one uint4.
-template <bool WIDE>
+// whose rows are multiples of 48) load as one uint4.  QUANT (the encoder's stage 1, jpeg_stage_a.h): the quantised values, not the
+// dequantised ones, every block in zigzag order, the MCUs one behind the other in coding order.
+template <bool WIDE, bool QUANT = false>
 __global__ void __launch_bounds__(FWD_THREADS)
 policy_forward_kernel(const u8* __restrict__ frames, i64 in_stride, i64 n_mcus, int H, int W, const unsigned short* __restrict__ qtab,
                       short* __restrict__ coef) {
@@ -104,14 +107,19 @@ policy_forward_kernel(const u8* __restrict__ frames, i64 in_stride, i64 n_mcus, 
     fdct_1d(in, o, false);
     const unsigned short* q = s_q + (blk < 4 ? 0 : 64);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) s.out[blk * 64 + r * 8 + k] = requantise((int)o[r], q[r * 8 + k]);
+    for (int r = 0; r < 8; ++r) {
+      if (QUANT)
+        s.out[blk * 64 + zigzag_of(r * 8 + k)] = (short)quantise((int)o[r], q[r * 8 + k]);
+      else
+        s.out[blk * 64 + r * 8 + k] = requantise((int)o[r], q[r * 8 + k]);
+    }
   }
   __syncthreads();
 
   // the six blocks to their places in the image's coefficient layout, 16 bytes a lane (the workspace is 16-byte aligned)
   if (live && lane < 48) {
     int comp;
-    const i64 at = (img * (i64)per_image * 6 + block_index(mcu, blk, W >> 3, H >> 3, 1, comp)) * 64 + k * 8;
+    const i64 at = QUANT ? (g * 6 + blk) * 64 + k * 8 : (img * (i64)per_image * 6 + block_index(mcu, blk, W >> 3, H >> 3, 1, comp)) * 64 + k * 8;
     *reinterpret_cast<uint4*>(coef + at) = *reinterpret_cast<const uint4*>(s.out + blk * 64 + k * 8);
   }
 }
@@ -219,6 +227,18 @@ bool resize_shape_ok(long long N, int H, int W, int out_h, int out_w) {
 long long intermediate_bytes(long long N, int H, int W, int out_h, int out_w) { return (H != out_h && W != out_w) ? N * out_h * W * 3 * 4 : 0; }
 
 }  // namespace
+
+int vlajpeg::stage_a_quantised(hipStream_t st, const unsigned char* frames, long long in_stride, long long N, int H, int W,
+                               const unsigned short* qtab, short* quant) {
+  const long long n_mcus = N * mcus_per_image(H, W, 1), grid = (n_mcus + FWD_WAVES - 1) / FWD_WAVES;
+  VLA_REQUIRE(grid <= 0x7fffffffll, "jpeg_encode: N * H * W is too large for one grid");
+  if ((uintptr_t)frames % 16 == 0 && in_stride % 16 == 0)
+    hipLaunchKernelGGL((policy_forward_kernel<true, true>), dim3((unsigned)grid), dim3(FWD_THREADS), 0, st, frames, in_stride, n_mcus, H, W, qtab, quant);
+  else
+    hipLaunchKernelGGL((policy_forward_kernel<false, true>), dim3((unsigned)grid), dim3(FWD_THREADS), 0, st, frames, in_stride, n_mcus, H, W, qtab, quant);
+  VLA_CHECK_LAUNCH("jpeg_encode (forward)");
+  return VLA_OK;
+}
 
 extern "C" long long vla_policy_image_workspace_bytes(long long N, int H, int W, int out_h, int out_w, int round_trip) {
   if (round_trip) return vla_jpeg_workspace_bytes(N, H, W, 1);

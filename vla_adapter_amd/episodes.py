@@ -423,12 +423,14 @@ class EpisodeStore(EpisodeTables):
 
     @classmethod
     def load(cls, path, device, chunk: int = NUM_ACTIONS_CHUNK, dataset_name: Optional[str] = None, *,
-             holdout: Optional[float] = None, jpeg_scan_index: bool = False) -> "EpisodeStore":
+             holdout: Optional[float] = None, jpeg_scan_index: bool = False, jpeg_quality: Optional[int] = None) -> "EpisodeStore":
         """``path``: a .pt episode file or a directory of them (concatenated in sorted order).  Validates the tables (ValueError that
         names the key), moves everything to the device and builds valid_off; ``dataset_name``: used when the file names none;
         ``holdout``: the fraction of episodes - the last ones - set aside for validation (see the class); ``jpeg_scan_index``: JPEG
-        frames get a scan index (EpisodeTables)."""
-        return cls(load_tables(path, device), device, chunk, dataset_name, _where=str(path), holdout=holdout, jpeg_scan_index=jpeg_scan_index)
+        frames get a scan index (EpisodeTables); ``jpeg_quality``: raw frames are coded on the device, shard by shard, into the JPEG
+        form at that quality (jpeg_store.encode_tables: LOSSY, and the store tools/pack_episodes_jpeg.py would have written); nothing
+        to do for a file already in the JPEG form."""
+        return cls(load_tables(path, device, jpeg_quality=jpeg_quality), device, chunk, dataset_name, _where=str(path), holdout=holdout, jpeg_scan_index=jpeg_scan_index)
 
     # ---- the batch -----------------------------------------------------------------------------------------------------------
     def sample_indices(self, B: int, seed: int, rank: int, world: int, step: int):
@@ -448,8 +450,9 @@ class EpisodeStore(EpisodeTables):
         return out
 
 
-def load_tables(path, device="cpu") -> dict:
-    """The tables of a .pt episode file or of a directory of them (validated shard by shard, concatenated in sorted order)."""
+def load_tables(path, device="cpu", jpeg_quality: Optional[int] = None) -> dict:
+    """The tables of a .pt episode file or of a directory of them (validated shard by shard, concatenated in sorted order).
+    ``jpeg_quality``: see concat_shards."""
     path = str(path)
     files = sorted(str(p) for p in Path(path).glob("*.pt")) if os.path.isdir(path) else [path]
     if not files:
@@ -459,13 +462,18 @@ def load_tables(path, device="cpu") -> dict:
         d = torch.load(f, weights_only=True, mmap=True)
         _check_shard(d, f)
         shards.append(d)
-    return concat_shards(shards, files, device)
+    return concat_shards(shards, files, device, jpeg_quality=jpeg_quality)
 
 
-def concat_shards(shards: List[dict], names: Optional[List[str]] = None, device="cpu") -> dict:
+def concat_shards(shards: List[dict], names: Optional[List[str]] = None, device="cpu", jpeg_quality: Optional[int] = None) -> dict:
     """The shards' tables back to back: rows concatenated, both offset tables shifted; dataset_name / action_mask must agree.  The
-    frames are assembled on ``device`` shard by shard (the host never holds a second copy of them)."""
+    frames are assembled on ``device`` shard by shard (the host never holds a second copy of them).  ``jpeg_quality``: every shard
+    of raw frames is first coded on ``device`` into the JPEG form (jpeg_store.encode_tables; ValueError naming the shard for sides that
+    are no multiples of 16); shards already in that form stay as they are."""
     names = names or [f"shard {i}" for i in range(len(shards))]
+    if jpeg_quality is not None:
+        from .jpeg_store import encode_tables
+        shards = [encode_tables(d, device, jpeg_quality, where=n) for d, n in zip(shards, names)]
     first = shards[0]
     jpeg = check_one_form(shards, names)
     for d, n in zip(shards[1:], names[1:]):

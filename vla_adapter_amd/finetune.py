@@ -145,6 +145,9 @@ class FinetuneConfig:
     frame_resize: str = "bicubic"         # how frames that are not at the model's size get there (every GPUInputStage of the run): "bicubic", the
                                           # processor's Pillow resize, or "lanczos3", the RLDS stage's tf.image.resize(method="lanczos3",
                                           # antialias=True) (obs_transforms.py:75).  Frames at the model's size: no effect
+    episode_jpeg_quality: int = 0         # --episode_file / --episode_mix whose frames are raw: code them on the device at load into the JPEG
+                                          # form at this quality (1 .. 100; jpeg_store.encode_tables) - a tenth of the bytes
+                                          # in HBM, and the run tools/pack_episodes_jpeg.py's file of the same quality gives.  LOSSY; 0 = off
     # fmt: on
 
 
@@ -208,6 +211,10 @@ def check_supported(cfg: FinetuneConfig, explicit=(), frame_batches: bool = Fals
         raise ValueError("--objective is l1 or token_ce")
     if cfg.frame_resize not in ("bicubic", "lanczos3"):
         raise ValueError(f"--frame_resize is bicubic or lanczos3, got {cfg.frame_resize!r}")
+    if isinstance(cfg.episode_jpeg_quality, bool) or not isinstance(cfg.episode_jpeg_quality, int) or not 0 <= cfg.episode_jpeg_quality <= 100:
+        raise ValueError(f"--episode_jpeg_quality is an int inside 0 .. 100 (0: off), got {cfg.episode_jpeg_quality!r}")
+    if cfg.episode_jpeg_quality and not (cfg.episode_file or cfg.episode_mix):
+        raise ValueError("--episode_jpeg_quality codes the frames of --episode_file / --episode_mix: no other batch source keeps frames on the device")
     if cfg.objective == "token_ce" and train_mode(cfg) == "adapter":
         raise NotImplementedError("--objective token_ce trains the VLM (LoRA or full fine-tune); --use_fz True freezes it")
     if cfg.backbone is not None:

@@ -448,3 +448,48 @@ def concat_jpeg(shards: List[dict], names: List[str], device) -> dict:
         b0 += nb
     out["frame_off"] = torch.cat(offs)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- raw frames -> files
+ENCODE_SLICE = 1024             # steps per encode: at 256 x 256 and one camera 201 MB of raw frames and as many bytes of workspace at a time
+
+
+def check_encode_quality(quality, restart_rows=1) -> int:
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_quality must be an int inside 1 .. 100, got {quality!r}")
+    if isinstance(restart_rows, bool) or not isinstance(restart_rows, int) or restart_rows < 1:
+        raise ValueError(f"restart_rows must be >= 1 on the device (0, one segment per file, is coded serially: tools/pack_episodes_jpeg.py "
+                         f"writes those with Pillow), got {restart_rows!r}")
+    return quality
+
+
+def encode_tables(tables: dict, device, quality: int = 95, restart_rows: int = 1, slice_frames: int = ENCODE_SLICE, where: str = "episode store") -> dict:
+    """The episode dict ``tables`` with its frames_u8 [T, n_img, H, W, 3] replaced by frames_jpeg / frame_off / frame_shape - what
+    tools/pack_episodes_jpeg.pack returns for the same quality and restart_rows, byte for byte - coded on ``device``
+    (ops.jpeg_encode).  The frames go up ``slice_frames`` steps at a time and only their files stay, so neither the host nor the device
+    ever holds the raw frames twice; frames_jpeg is on the device, the small tables stay where they were.  LOSSY.  ValueError naming
+    ``where`` for frames whose sides are no multiples of 16; a dict already in the JPEG form comes back as it is."""
+    from . import ops
+    check_encode_quality(quality, restart_rows)
+    if storage_form(tables, where) == "jpeg":
+        return tables
+    fr = tables["frames_u8"]
+    T, n_img, H, W, _ = fr.shape
+    if H % 16 or W % 16:
+        name = tables.get("dataset_name")
+        raise ValueError(f"{where}{f' (dataset {name!r})' if isinstance(name, str) and name else ''}: frames of {H} x {W}: the JPEG form needs "
+                         "sides that are multiples of 16 (resize or pad the frames first)")
+    step = max(1, int(slice_frames))
+    pieces, offs, b0 = [], [torch.zeros(1, dtype=torch.int64)], 0
+    for t0 in range(0, T, step):
+        part = fr[t0:t0 + step].to(device, non_blocking=False)
+        data, off = ops.jpeg_encode(part, quality, restart_rows)
+        pieces.append(data)
+        offs.append(off[1:].cpu() + b0)
+        b0 += int(data.numel())
+        del part
+    out = {k: v for k, v in tables.items() if k != "frames_u8"}
+    out["frames_jpeg"] = pieces[0] if len(pieces) == 1 else torch.cat(pieces)
+    out["frame_off"] = torch.cat(offs)
+    out["frame_shape"] = torch.tensor([n_img, H, W], dtype=torch.int64)
+    return out

@@ -148,18 +148,22 @@ class EpisodeMix(EpisodeTables):
 
     @classmethod
     def load(cls, entries, device, chunk: int = NUM_ACTIONS_CHUNK, period: int = DEFAULT_PERIOD, balance_weights: bool = True, *,
-             holdout: Optional[float] = None, jpeg_scan_index: bool = False) -> "EpisodeMix":
+             holdout: Optional[float] = None, jpeg_scan_index: bool = False, jpeg_quality: Optional[int] = None) -> "EpisodeMix":
         """``entries``: [(path or tables dict, weight)]; a path is anything ``EpisodeStore.load`` takes.  A dataset is called by its
         file's dataset_name, else by the path's stem.  ``holdout``: the fraction of every dataset's episodes - its last ones - set aside
         for validation (episodes.EpisodeStore); None: every table and batch is what it is without the argument.  ``jpeg_scan_index``:
-        JPEG frames get a scan index at load (episodes.EpisodeTables)."""
+        JPEG frames get a scan index at load (episodes.EpisodeTables).  ``jpeg_quality``: raw frames are coded on the device into the
+        JPEG form, dataset by dataset (EpisodeStore.load); a dataset already in that form stays as it is."""
         tables, weights, names = [], [], []
         for i, entry in enumerate(entries):
             src, w = entry if isinstance(entry, (tuple, list)) else (entry, 1.0)
             if isinstance(src, dict):
                 d, fallback = src, f"dataset_{i}"
+                if jpeg_quality is not None:
+                    from .jpeg_store import encode_tables
+                    d = encode_tables(d, device, jpeg_quality, where=str(d.get("dataset_name") or fallback))
             else:
-                d, fallback = load_tables(src, device), Path(str(src)).stem
+                d, fallback = load_tables(src, device, jpeg_quality=jpeg_quality), Path(str(src)).stem
             if not isinstance(d, dict):
                 raise ValueError(f"entry {i} of the mix: an episode file is a dict")
             name = d.get("dataset_name")

@@ -210,9 +210,23 @@ FAMILIES = (
 PROTOS = {name: sig for fam in FAMILIES for name, sig in fam.protos.items()}
 assert len(PROTOS) == sum(len(fam.protos) for fam in FAMILIES), "an entry point belongs to one header"
 
+# The families added behind the nine above: the same type, the same library, bound by the same loop of load().  They stand in a tuple of
+# their own because FAMILIES and PROTOS are pinned as they are (tests/test_abi_families.py); tests/test_abi_later_families.py checks these
+# the same way.
+LATER_FAMILIES = (
+    # the JPEG encoder (csrc/jpeg_encode.hip)
+    Family("jpeg_encode", "vla_jpeg_encode.h", {
+        "vla_jpeg_encode_workspace_bytes": ([_L, _I, _I, _I], _L),
+        "vla_jpeg_encode_plan": ([_P, _P, _L, _L, _I, _I, _P, _I, _P, _L, _P], _I),
+        "vla_jpeg_encode_write": ([_P, _L, _I, _I, _P, _I, _P, _L, _P, _P, _L], _I),
+    }),
+)
+LATER_PROTOS = {name: sig for fam in LATER_FAMILIES for name, sig in fam.protos.items()}
+assert len(LATER_PROTOS) == sum(len(fam.protos) for fam in LATER_FAMILIES) and not set(LATER_PROTOS) & set(PROTOS), "an entry point belongs to one header"
+
 
 def family(key: str) -> Family:
-    return next(fam for fam in FAMILIES if fam.key == key)
+    return next(fam for fam in FAMILIES + LATER_FAMILIES if fam.key == key)
 
 
 _lib = None
@@ -228,7 +242,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in PROTOS.items():
+    for name, (args, res) in [sig for fam in FAMILIES + LATER_FAMILIES for sig in fam.protos.items()]:
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

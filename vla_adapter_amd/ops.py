@@ -1282,3 +1282,45 @@ def policy_lanczos3_resize(frames: torch.Tensor, out_h: int, out_w: int, spans_v
     N.check(_lib().vla_policy_lanczos3_resize(_st(), _p(frames), stride, n, H, W, int(out_h), int(out_w), _p(sv), _p(wv), kv, _p(sh), _p(wh), kh,
                                               _p(workspace), workspace.numel() if workspace is not None else 0, _p(out)), "policy_lanczos3_resize")
     return out
+
+
+# ---- the JPEG encoder (include/vla_jpeg_encode.h, csrc/jpeg_encode.hip) -------------------------------------------------------------
+_ENC_QTABS = {}
+
+
+def _encode_qtab(quality: int, device) -> torch.Tensor:
+    """input_stage.jpeg_quant_tables(quality) on the device, int16 [2, 64] (the same bits as its uint16), uploaded once per quality."""
+    key = (int(quality), str(device))
+    if key not in _ENC_QTABS:
+        import numpy as np
+        from .input_stage import jpeg_quant_tables
+        _ENC_QTABS[key] = torch.from_numpy(jpeg_quant_tables(int(quality)).view(np.int16).copy()).to(device)
+    return _ENC_QTABS[key]
+
+
+def jpeg_encode(frames_u8: torch.Tensor, quality: int = 95, restart_rows: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """uint8 [N, H, W, 3] on the device (images a stride apart), or [T, n_img, H, W, 3] taken in (t, cam) order -> (frames_jpeg uint8
+    [n_bytes], frame_off int64 [N + 1]) on the device: the baseline 4:2:0 files of the frames back to back, every one byte for byte
+    what Pillow saves with quality, subsampling=2 and restart_marker_rows=restart_rows.  H and W must be multiples of 16 and
+    restart_rows >= 1: ValueError otherwise.  The byte count is read back once, between the two calls of the encode."""
+    if frames_u8.dim() == 5:
+        T, n_img = frames_u8.shape[:2]
+        if T > 1 and n_img > 1 and frames_u8.stride(0) != n_img * frames_u8.stride(1):
+            raise ValueError(f"jpeg_encode: [T, n_img, H, W, 3] frames must be one image stride apart in (t, cam) order; strides {frames_u8.stride()}")
+        st = frames_u8.stride(1) if n_img > 1 else frames_u8.stride(0)
+        frames_u8 = frames_u8.as_strided((T * n_img,) + tuple(frames_u8.shape[2:]), (st,) + tuple(frames_u8.stride()[2:]))
+    n, H, W, stride = _frames_nhwc(frames_u8, "jpeg_encode")
+    need = _lib().vla_jpeg_encode_workspace_bytes(n, H, W, int(restart_rows))
+    if need < 0:
+        raise ValueError(f"jpeg_encode: {n} frames of {H} x {W} with restart_rows {restart_rows} are refused: H and W must be multiples of 16 "
+                         "inside [16, 4096] and restart_rows >= 1 (a file without restart markers is coded serially: Pillow writes those)")
+    qtab = _encode_qtab(quality, frames_u8.device)
+    workspace = torch.empty(need, device=frames_u8.device, dtype=torch.uint8)
+    frame_off = torch.empty(n + 1, device=frames_u8.device, dtype=torch.int64)
+    N.check(_lib().vla_jpeg_encode_plan(_st(), _p(frames_u8), stride, n, H, W, _p(qtab), int(restart_rows), _p(workspace), need, _p(frame_off)),
+            "jpeg_encode_plan")
+    total = int(frame_off[-1].item())               # the one read-back of the encode: load time, not the step
+    out = torch.empty(total, device=frames_u8.device, dtype=torch.uint8)
+    N.check(_lib().vla_jpeg_encode_write(_st(), n, H, W, _p(qtab), int(restart_rows), _p(workspace), need, _p(frame_off), _p(out), total),
+            "jpeg_encode_write")
+    return out, frame_off

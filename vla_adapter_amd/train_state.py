@@ -118,6 +118,8 @@ def fingerprint(cfg, mode: str, world: int, n_img: int, batches_given: bool = Fa
         ddp_algo=str(cfg.ddp_algo))
     if getattr(cfg, "frame_resize", "bicubic") != "bicubic":      # (only when it is not the default: a state written before the flag existed resumes)
         fp["frame_resize"] = str(cfg.frame_resize)
+    if int(getattr(cfg, "episode_jpeg_quality", 0) or 0) != 0:    # (lossy, so it defines the trajectory; likewise only when it is set)
+        fp["episode_jpeg_quality"] = int(cfg.episode_jpeg_quality)
     return fp
 
 
