@@ -496,9 +496,10 @@ typedef struct vla_head_attn_desc {
   /* backward, optional: tables f32 [>= max(T,Ka,Kt), dh] of vla_rope_interleaved; dq and the three dk are then
    * returned through the transpose of that RoPE map (positions restart per segment, action_heads.py:383-388) */
   const float* rope_cos; const float* rope_sin;
-  /* backward, optional (ABI 3): f32 workspace of >= B*H*ceil((T+Ka+Kt)/32)*(T*dh + 1) floats.  With it the MFMA backward runs
-   * in its tile-uniform form (one wave per (sample, head, 32-key tile); dq and dgate summed from per-tile partials in tile
-   * order); without it (NULL / too small) the combined kernel of ABI 2 runs.  Contents are scratch. */
+  /* backward (ABI 3): f32 workspace of >= B*H*ceil((T+Ka+Kt)/32)*(T*dh + 1) floats, 16-B aligned.  REQUIRED at the MFMA head
+   * widths (dh 16, 32, 64, 112, 128, 192 with T <= 32): the backward runs one wave per (sample, head, 32-key tile) and sums dq and
+   * dgate from per-tile partials in tile order, so its result does not depend on timing.  NULL or fewer floats: VLA_ERR_ARG before
+   * anything is launched or written, the message naming the count.  Not read at other widths (VALU kernels).  Contents are scratch. */
   float* ws; long long ws_floats;
   /* forward, optional (ABI 5): 1 = the softmax weights are rounded to bf16 AFTER normalisation, P = bf16(exp(s - max) / sum), as ATen's
    * bf16 softmax emits them (action_heads.py:397: attn_weights = softmax(attn_scores) on a bf16 module) - two passes over the keys

@@ -653,21 +653,30 @@ def _head_inputs(B, T, Ka, Kt, H, dh, value, tg, seed):
     return [t.to(BF) for t in (q, ks, vs, ka, va, kt, vt)]
 
 
-HEAD_CASES = [  # B, Ka, Kt, D, value
-    (2, 31, 33, 64, "normal"), (3, 32, 31, 256, "peaked"), (2, 33, 32, 896, "normal"), (1, 65, 33, 896, "peaked"),
-    (2, 65, 256, 1536, "normal"), (1, 31, 40, 1536, "peaked"), (2, 65, 512, 512, "normal")]
+HEAD_CASES = [  # B, T, Ka, Kt, D, value
+    (2, 8, 31, 33, 64, "normal"), (3, 8, 32, 31, 256, "peaked"), (2, 8, 33, 32, 896, "normal"), (1, 8, 65, 33, 896, "peaked"),
+    (2, 8, 65, 256, 1536, "normal"), (1, 8, 31, 40, 1536, "peaked"), (2, 8, 65, 512, 512, "normal"),
+    # the MFMA kernels beyond the step's T = 8 (the VALU kernels refuse other T): the query contraction's second k-step (T > 16), a
+    # ragged last key tile (Kt = 7), nineteen key tiles (Kt = 512: five workgroups per (sample, head), the last partly idle), head dim 16
+    (2, 20, 65, 100, 1024, "normal"), (1, 32, 33, 7, 256, "normal"), (2, 8, 65, 512, 896, "normal"), (5, 8, 65, 16, 128, "normal")]
 
 
-@pytest.mark.parametrize("mode,B,Ka,Kt,D,value", [(m,) + c for m in ("mfma", "bwd_combined", "valu", "ref_softmax") for c in HEAD_CASES
-                                                  if m != "valu" or c[3] <= 896])       # (the VALU kernel: head dims up to 112)
-def test_head_attention_rows(ops, monkeypatch, mode, B, Ka, Kt, D, value):
+def _head_params():
+    for m in ("mfma", "valu", "ref_softmax"):
+        for i, c in enumerate(HEAD_CASES):
+            if m == "valu" and (i >= 7 or c[4] > 896):     # (the VALU kernel: the first seven cases, head dims up to 112)
+                continue
+            B, T, Ka, Kt, D, value = c
+            yield pytest.param(m, *c, id=f"{m}-{B}-{Ka}-{Kt}-{D}-{value}" if i < 7 else f"{m}-{B}-T{T}-{Ka}-{Kt}-{D}-{value}")
+
+
+@pytest.mark.parametrize("mode,B,T,Ka,Kt,D,value", list(_head_params()))
+def test_head_attention_rows(ops, monkeypatch, mode, B, T, Ka, Kt, D, value):
     """The action head's three-segment attention, forward and backward, per row against float64 (assert_row_budget, the attention
     family's constants) and the gate gradient against float64 under the same budget."""
-    if mode == "bwd_combined":
-        monkeypatch.setenv("VLA_HEAD_BWD_COMBINED", "1")
     if mode == "valu":
         monkeypatch.setenv("VLA_HEAD_ATTN_VALU", "1")
-    H, T = 8, 8
+    H = 8
     dh = D // H
     gate = _gate_near_midpoint().reshape(1)
     tgv = A.r64(torch.tanh(gate.to(F64)))
@@ -690,7 +699,7 @@ def test_head_attention_rows(ops, monkeypatch, mode, B, Ka, Kt, D, value):
 
     to, tgr, tdg = run(F64, False)
     eo, egr, edg = run(torch.float32, True)
-    name = f"head {mode} B{B} Ka{Ka} Kt{Kt} D{D} {value}"
+    name = f"head {mode} B{B} T{T} Ka{Ka} Kt{Kt} D{D} {value}"
     A.assert_row_budget(cpu(out).reshape(B, T, H, dh).transpose(1, 2), eo.to(BF), to, 1, A.ATTN_FACTOR, A.ATTN_FLOOR, name=name + " out")
     # the flash backward's delta from the bf16 output (accuracy.ATTN_DELTA_C): per query / key row, as for the main attention
     qq = ins[0].to(F64).transpose(1, 2)

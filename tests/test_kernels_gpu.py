@@ -541,47 +541,12 @@ def test_attention_bwd_fused_inverse_rope(ops, B, S, Hq, Hkv, dh):
     assert torch.equal(f(sl(g1)[2]), f(sl(g0)[2]))
 
 
-@pytest.mark.parametrize("B,T,Ka,Kt,D,rope", [(3, 8, 65, 256, 896, True), (2, 8, 65, 512, 896, False), (2, 8, 65, 40, 512, True), (2, 20, 65, 100, 1024, True),
-                                              (5, 8, 65, 16, 128, False), (1, 32, 33, 7, 256, True)])
-def test_head_attention_bwd_tile_uniform_equals_combined(ops, B, T, Ka, Kt, D, rope, monkeypatch):
-    """The tile-uniform MFMA backward (one wave per (sample, head, 32-key tile), dq / dgate from per-tile partials: ABI 3 workspace)
-    against the combined kernel it replaces (VLA_HEAD_BWD_COMBINED=1): dk / dv are the same MFMAs in the same order - equal up to isolated
-    one-ulp flips (7 of 1.7 M elements measured: the compiler contracts the score chain's multiplies and adds differently in the two
-    kernels); dq and dgate differ by fp32 summation order only.  T > 16 exercises the second k-step of the query contraction, Kt = 7 a ragged
-    last tile, Kt = 512 nineteen tiles (five workgroups per (sample, head), the last one partly idle)."""
-    H = 8
-    dh = D // H
-    x3, a2, t2 = gen(B, T, 3 * D, seed=60, scale=0.3), gen(B, Ka, 2 * D, seed=61, scale=0.3), gen(B, Kt, 2 * D, seed=62, scale=0.3)
-    gate, dout = torch.tensor([0.7]).to(BF).to(DEV), gen(B, T, D, seed=63).to(DEV)
-    dx3, da2, dt2 = x3.to(DEV), a2.to(DEV), t2.to(DEV)
-    args = (dx3[:, :, :D], dx3[:, :, D:2 * D], dx3[:, :, 2 * D:], da2[:, :, :D], da2[:, :, D:], dt2[:, :, :D], dt2[:, :, D:])
-    out, probs = ops.head_attn_fwd(*args, gate, H)
-    tabs = ops.rope_inter_tables(max(T, Ka, Kt), dh, DEV) if rope else None
-    res = []
-    for combined in (True, False):
-        if combined:
-            monkeypatch.setenv("VLA_HEAD_BWD_COMBINED", "1")
-        else:
-            monkeypatch.delenv("VLA_HEAD_BWD_COMBINED", raising=False)
-        g3, ga, gt = torch.zeros_like(dx3), torch.zeros_like(da2), torch.zeros_like(dt2)
-        dg = torch.zeros(1, device=DEV)
-        ops.head_attn_bwd(dout, out, *args, gate, probs, dg, g3[:, :, :D], g3[:, :, D:2 * D], g3[:, :, 2 * D:], ga[:, :, :D], ga[:, :, D:],
-                          gt[:, :, :D], gt[:, :, D:], H, rope=tabs)
-        res.append((g3, ga, gt, dg))
-    (c3, ca, ct, cg), (n3, na, nt, ng) = res
-    for name, a, b in (("dk|dv self", n3[:, :, D:], c3[:, :, D:]), ("dk|dv adapter", na, ca), ("dk|dv task", nt, ct)):
-        diff = (a.float() - b.float()).abs()
-        nz = diff > 0                                      # same MFMAs in the same order; the score chain's VALU code is compiled in another context
-        assert nz.float().mean().item() <= 1e-4, f"{name}: {int(nz.sum())} of {nz.numel()} elements differ"      # (fma contraction): isolated one-ulp flips
-        assert bool((diff <= 8e-3 * a.float().abs() + 1e-5 * a.float().abs().max()).all()), f"{name}: more than one bf16 ulp apart"
-    check(n3[:, :, :D], f(c3[:, :, :D]), rel=4e-3, mx=2e-2, name="dq: tile-uniform vs combined")
-    assert abs(ng.item() - cg.item()) <= 2e-3 * abs(cg.item()) + 1e-4, f"dgate {ng.item()} vs {cg.item()}"
-
-
-@pytest.mark.parametrize("D", [896, 64])
-def test_head_attention_bwd_fused_rope_transpose(ops, D):
-    """MFMA path (dh 112) and VALU fallback (dh 8): dq / dk returned through the transpose of the head's RoPE map."""
-    B, Ka, Kt, H, T = 2, 65, 40, 8, 8
+@pytest.mark.parametrize("D,T,Kt", [pytest.param(896, 8, 40, id="896"), pytest.param(64, 8, 40, id="64"),
+                                    pytest.param(1024, 20, 40, id="1024-T20"), pytest.param(256, 32, 7, id="256-T32-Kt7")])
+def test_head_attention_bwd_fused_rope_transpose(ops, D, T, Kt):
+    """MFMA path (dh 112) and VALU fallback (dh 8): dq / dk returned through the transpose of the head's RoPE map; on the MFMA path
+    also where the query contraction takes its second k-step (T > 16) and with a ragged last key tile (Kt = 7)."""
+    B, Ka, H = 2, 65, 8
     dh = D // H
     x3, a2, t2 = gen(B, T, 3 * D, seed=50, scale=0.3), gen(B, Ka, 2 * D, seed=51, scale=0.3), gen(B, Kt, 2 * D, seed=52, scale=0.3)
     gate, dout = torch.tensor([0.7]).to(BF).to(DEV), gen(B, T, D, seed=53).to(DEV)
@@ -602,6 +567,40 @@ def test_head_attention_bwd_fused_rope_transpose(ops, D):
         ops.rope_inter_(ref, tabs[0], tabs[1], L, H, dh, 1)          # stand-alone transpose kernel on the un-fused gradient
         check(fus.reshape(B * L, D), f(ref), rel=8e-3, mx=3e-2, name=f"fused rope transpose L={L}")
     assert torch.equal(f(r3[:, :, 2 * D:]), f(g3[:, :, 2 * D:])) and torch.equal(f(ra[:, :, D:]), f(ga[:, :, D:]))
+
+
+def test_head_attention_bwd_requires_workspace(ops):
+    """vla_head_attn_bwd at an MFMA width without its workspace (NULL, or one float short) is refused on the host, before any launch:
+    the error names the float count and no gradient byte is written; with exactly that many floats the call is ops.head_attn_bwd's."""
+    import ctypes
+    B, T, Ka, Kt, H, D = 1, 8, 31, 33, 8, 128
+    need = B * H * ((T + Ka + Kt + 31) // 32) * (T * (D // H) + 1)
+    x3, a2, t2 = gen(B, T, 3 * D, seed=70, scale=0.3).to(DEV), gen(B, Ka, 2 * D, seed=71, scale=0.3).to(DEV), gen(B, Kt, 2 * D, seed=72, scale=0.3).to(DEV)
+    gate, dout = torch.tensor([0.7]).to(BF).to(DEV), gen(B, T, D, seed=73).to(DEV)
+    args = (x3[:, :, :D], x3[:, :, D:2 * D], x3[:, :, 2 * D:], a2[:, :, :D], a2[:, :, D:], t2[:, :, :D], t2[:, :, D:])
+    out, probs = ops.head_attn_fwd(*args, gate, H)
+    views = lambda g3, ga, gt: (g3[:, :, :D], g3[:, :, D:2 * D], g3[:, :, 2 * D:], ga[:, :, :D], ga[:, :, D:], gt[:, :, :D], gt[:, :, D:])
+    want = [torch.zeros_like(t) for t in (x3, a2, t2)] + [torch.zeros(1, device=DEV)]
+    ops.head_attn_bwd(dout, out, *args, gate, probs, want[3], *views(*want[:3]), H)
+
+    got = [torch.full_like(t, 3.0) for t in (x3, a2, t2)] + [torch.full((1,), 3.0, device=DEV)]      # the sentinel
+    ws = torch.empty(need, device=DEV)
+    d = ops.head_attn_desc(*args, gate, probs, out, H)
+    d.dout, d.dgate = dout.data_ptr(), got[3].data_ptr()
+    d.dq, d.dk_self, d.dv_self, d.dk_adp, d.dv_adp, d.dk_task, d.dv_task = (t.data_ptr() for t in views(*got[:3]))
+
+    def call(ptr, floats):
+        d.ws, d.ws_floats = ptr, floats
+        ops.N.check(ops._lib().vla_head_attn_bwd(ops._st(), ctypes.byref(d)), "head_attn_bwd")
+    for ptr, floats in ((0, need), (ws.data_ptr(), need - 1)):
+        with pytest.raises(ops.N.NativeError, match=rf"\b{need} floats"):
+            call(ptr, floats)
+        torch.cuda.synchronize()
+        assert all(bool((t == 3.0).all()) for t in got), "a refused call wrote to a gradient buffer"
+    for t in got:
+        t.zero_()
+    call(ws.data_ptr(), need)
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
 
 
 def test_gemm_fused_swiglu_backward(ops):

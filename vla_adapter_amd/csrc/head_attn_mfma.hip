@@ -6,15 +6,15 @@
 // on wave-private LDS tiles and meet once at the end (flash-style merge of (m, l, O) through LDS): the key loop of one
 // (sample, head) is a serial chain of dependent global loads, and with one wave per (sample, head) a launch was 256 such
 // chains of 11 tiles on a quarter of the CUs (37 us); split four ways it is 3 tiles (18 us).
-// Backward: one WAVE per (sample, head) for dQ and per (sample, head, key tile) for dK/dV - 4 independent waves per
-// workgroup, wave-private LDS tiles, no workgroup barrier (the same four-way split of the dQ loop measured 81 vs 85 us
-// isolated but +60 us per layer inside the step: four times the workgroups queue for LDS behind the ViT's GEMMs).
+// Backward: one WAVE per (sample, head, 32-key tile) does everything its tile contributes (head_bwd_tiles): dK and dV of
+// its keys, complete after one pass, and its share of dQ and of the gate gradient as fp32 partials in the caller's
+// workspace; head_dq_reduce then sums the partials in tile order.  The sums have one order whatever the timing, so two
+// runs of a step agree bit for bit.  The workspace is required (HP::ws): a call without it is refused before any launch.
 // Same operand tricks as attention.hip: forward and dQ use the S^T[key x q] orientation (query on the lane, softmax
 // statistics lane-local, P^T feeds O^T = V^T.P^T directly, V^T from ds_read_b64_tr_b16); dK/dV use S[q x key] (key on
-// the lane) with the single 32-row query tile parked in LDS and K/V fragments loaded straight from global memory,
-// so every key tile's dK/dV is complete after one pass (no accumulation across tiles, no atomics).
+// the lane) with the workgroup's query rows parked in LDS and K/V fragments loaded straight from global memory.
 // Rounding points of the reference's bf16 module are kept: bf16(q.k) -> bf16(* tanh g) -> bf16(/ sqrt dh).
-// The VALU kernels of head_attn.hip remain the fallback for head dims that are not a multiple of 16.
+// The VALU kernels of head_attn.hip remain the fallback for the head dims outside HEAD_MFMA_WIDTHS.
 #include "attn_common.h"
 #include "head_attn_params.h"
 
@@ -47,9 +47,8 @@ __device__ __forceinline__ const bf16_t* hrow(const bf16_t* s0, const bf16_t* s1
 
 // 32 consecutive keys n0.. (clamped to N-1) of the segmented K AND V tensors -> registers -> wave-private LDS tiles.
 // K and V of a segment share row count and row stride (checked by the host wrapper), so one element offset serves both.
-// SELECT: branch-free segment select (backward: the three-way if/else became ~40 exec-mask regions per key tile, 117 ->
-// 79 us for the launch) or plain branches (forward: 18 vs 23 us - its waves visit three tiles only).
-template <int D, bool SELECT>
+// Plain branches, not hrow's branch-free select: the forward's waves visit three tiles only (18 vs 23 us).
+template <int D>
 __device__ __forceinline__ void seg_prefetch_kv(u32x4* __restrict__ vk, u32x4* __restrict__ vv, const HP& p, int b, int hoff, int n0,
                                                 int N, int lane) {
   using G = HG<D>;
@@ -58,15 +57,7 @@ __device__ __forceinline__ void seg_prefetch_kv(u32x4* __restrict__ vk, u32x4* _
     const int c = min(lane + i * 64, 32 * G::CPR - 1);
     const int r = c / G::CPR, ch = c - r * G::CPR;
     const int n = min(n0 + r, N - 1);
-    if constexpr (SELECT) {
-      const bool in0 = n < p.T, in1 = n < p.T + p.Ka;
-      const int len = in0 ? p.T : (in1 ? p.Ka : p.Kt);
-      const int ld = in0 ? p.ld_self : (in1 ? p.ld_adp : p.ld_task);
-      const int loc = in0 ? n : (in1 ? n - p.T : n - p.T - p.Ka);
-      const long long off = ((long long)b * len + loc) * ld + hoff + ch * 8;
-      vk[i] = *reinterpret_cast<const u32x4*>((in0 ? p.ks : (in1 ? p.ka : p.kt)) + off);
-      vv[i] = *reinterpret_cast<const u32x4*>((in0 ? p.vs : (in1 ? p.va : p.vt)) + off);
-    } else if (n < p.T) {
+    if (n < p.T) {
       const long long off = ((long long)b * p.T + n) * p.ld_self + hoff + ch * 8;
       vk[i] = *reinterpret_cast<const u32x4*>(p.ks + off);
       vv[i] = *reinterpret_cast<const u32x4*>(p.vs + off);
@@ -98,26 +89,6 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// transpose of the action head's RoPE map on a 32-row accumulator tile set (lane = row, registers = d): pairs (2i, 2i+1)
-template <int DT>
-__device__ __forceinline__ void rope_inter_bwd_acc(f32x16 (&X)[DT], const float* ct, const float* st, int pos, int dh, int D, int h) {
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d = 32 * t + 8 * g + 4 * h;
-      if (d < D) {
-        const float4 c = *reinterpret_cast<const float4*>(ct + (long long)pos * dh + d);
-        const float4 s = *reinterpret_cast<const float4*>(st + (long long)pos * dh + d);
-        const float a0 = X[t][4 * g], b0 = X[t][4 * g + 1], a1 = X[t][4 * g + 2], b1 = X[t][4 * g + 3];
-        X[t][4 * g] = a0 * c.x + b0 * s.y;
-        X[t][4 * g + 1] = b0 * c.y - a0 * s.x;
-        X[t][4 * g + 2] = a1 * c.z + b1 * s.w;
-        X[t][4 * g + 3] = b1 * c.w - a1 * s.z;
-      }
-    }
-}
-
 // score chain of the reference's bf16 module; returns the score in log2 domain (or -inf for padded keys)
 __device__ __forceinline__ float score_chain(float dot, bool gated, float tg, float rs, bool valid) {
   float s = rbf(dot);
@@ -127,6 +98,53 @@ __device__ __forceinline__ float score_chain(float dot, bool gated, float tg, fl
 }
 
 // ------------------------------------------------------------------------------------------------ forward
+// The pieces the two forward kernels share.  Lane = query (lane & 31, half h = lane >> 5), S^T[key x q] orientation.
+
+// Each is shaped so that both kernels compile to what they were with the text written out (registers, scratch: the same); the
+// add of the partial O and the row store stay written out in each kernel: as helpers, in any shape tried, they moved the
+// reference-rounding kernel's register allocation (188 -> 189 at head dim 112; 172 -> 244 B of scratch at 192).
+
+// k-step ks of query row qc of (sample b, head at hoff): the B operand of the score MFMAs, 8 consecutive d
+template <int D>
+__device__ __forceinline__ bf16x8 q_frag(const HP& p, int b, int qc, int hoff, int ks, int h) {
+  return *reinterpret_cast<const bf16x8*>(p.q + ((long long)b * p.T + qc) * p.ld_q + hoff + 16 * ks + 8 * h);
+}
+
+// S[r] = then(score) for the 32 keys n0.. staged in sK against the lane's query: each score through score_chain (log2 domain); the
+// task segment (key >= T + Ka) is the gated one, keys >= N are padding and score -inf
+template <int D, class F>
+__device__ __forceinline__ f32x16 score_tile(const bf16_t* sK, const bf16x8 (&qf)[HG<D>::KS], const HP& p, int n0, int N, float tg, float rs,
+                                             int lane, int h, F&& then) {
+  using G = HG<D>;
+  f32x16 S = zero16();
+#pragma unroll
+  for (int ks = 0; ks < G::KS; ++ks)
+    S = mfma32(*reinterpret_cast<const bf16x8*>(sK + (lane & 31) * G::LD + 16 * ks + 8 * h), qf[ks], S);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int key = n0 + acc_row(r, h);
+    S[r] = then(score_chain(S[r], key >= p.T + p.Ka, tg, rs, key < N));
+  }
+  return S;
+}
+
+// O^T += V^T . P^T over the 16 keys of half s of the tile (pack_acc rounds the weights P to bf16)
+template <int D>
+__device__ __forceinline__ void pv_half(f32x16 (&O)[HG<D>::DT], const f32x16& P, const bf16_t* sV, int s, int lane) {
+  const bf16x8 pf = pack_acc(P, s);
+#pragma unroll
+  for (int t = 0; t < HG<D>::DT; ++t) O[t] = mfma32(tr_frag(sV, HG<D>::LD, s, 32 * t, lane), pf, O[t]);
+}
+
+// a wave's partial O into its LDS region (free once its tiles are done), for wave 0 to add: element (t, r) of lane at (16 t + r) * 64 + lane
+template <int D>
+__device__ __forceinline__ void spill_partial_o(float* myO, const f32x16 (&O)[HG<D>::DT], int lane) {
+#pragma unroll
+  for (int t = 0; t < HG<D>::DT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) myO[(t * 16 + r) * 64 + lane] = O[t][r];
+}
+
 template <int D>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void head_fwd_mfma(HP p) {
   using G = HG<D>;
@@ -140,35 +158,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void h
   const int qi = lane & 31, qc = min(qi, p.T - 1);
   bf16x8 qf[G::KS];
 #pragma unroll
-  for (int ks = 0; ks < G::KS; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8*>(p.q + ((long long)b * p.T + qc) * p.ld_q + hoff + 16 * ks + 8 * h);
+  for (int ks = 0; ks < G::KS; ++ks) qf[ks] = q_frag<D>(p, b, qc, hoff, ks, h);
   const bf16_t graw = p.gate[0];
   f32x16 O[G::DT];
 #pragma unroll
   for (int t = 0; t < G::DT; ++t) O[t] = zero16();
   float m_run = -INFINITY, l_run = 0.f;
   u32x4 rk[G::NCH], rv[G::NCH];
-  seg_prefetch_kv<D, false>(rk, rv, p, b, hoff, 32 * w, N, lane);
+  seg_prefetch_kv<D>(rk, rv, p, b, hoff, 32 * w, N, lane);
   __builtin_amdgcn_sched_barrier(0);          // the first tile's loads go out BEFORE anything waits for the gate (tanhf sat on its
   const float tg = rbf(tanhf(bf2f(graw))), rs = sqrtf((float)D);      // load's round trip in front of the prefetch: hf_stamps.py)
   for (int n0 = 32 * w; n0 < N; n0 += 32 * HEAD_KV_WAVES) {
     tile_put<D>(rk, sK, lane);
     tile_put<D>(rv, sV, lane);
     if (n0 + 32 * HEAD_KV_WAVES < N) {
-      seg_prefetch_kv<D, false>(rk, rv, p, b, hoff, n0 + 32 * HEAD_KV_WAVES, N, lane);
+      seg_prefetch_kv<D>(rk, rv, p, b, hoff, n0 + 32 * HEAD_KV_WAVES, N, lane);
     }
     wave_lds_sync();
-    f32x16 S = zero16();
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks)
-      S = mfma32(*reinterpret_cast<const bf16x8*>(sK + (lane & 31) * G::LD + 16 * ks + 8 * h), qf[ks], S);
     float mt = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = n0 + acc_row(r, h);
-      S[r] = score_chain(S[r], key >= p.T + p.Ka, tg, rs, key < N);
-      mt = fmaxf(mt, S[r]);
-    }
+    f32x16 S = score_tile<D>(sK, qf, p, n0, N, tg, rs, lane, h, [&](float s) { mt = fmaxf(mt, s); return s; });
     mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
     const float m_new = fmaxf(m_run, mt);
     const float alpha = fexp2(m_run - m_new);       // every tile a wave visits holds a valid key: m_new is finite
@@ -186,11 +194,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void h
 #pragma unroll
       for (int r = 0; r < 16; ++r) O[t][r] *= alpha;
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const bf16x8 pf = pack_acc(S, s);
-#pragma unroll
-      for (int t = 0; t < G::DT; ++t) O[t] = mfma32(tr_frag(sV, G::LD, s, 32 * t, lane), pf, O[t]);
-    }
+    for (int s = 0; s < 2; ++s) pv_half<D>(O, S, sV, s, lane);
     wave_lds_sync();
   }
   // merge the waves' partial softmax states in wave 0 (a wave without tiles carries m = -inf, l = 0, O = 0)
@@ -198,10 +202,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void h
     float* myO = reinterpret_cast<float*>(smem + w * G::WAVE_BYTES);
     float* myml = reinterpret_cast<float*>(smem + w * G::WAVE_BYTES + 2 * G::TILE * 2);
     if (w > 0) {
-#pragma unroll
-      for (int t = 0; t < G::DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) myO[(t * 16 + r) * 64 + lane] = O[t][r];
+      spill_partial_o<D>(myO, O, lane);
       if (lane < 32) { myml[lane] = m_run; myml[32 + lane] = l_run; }
     }
     __syncthreads();
@@ -267,28 +268,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void h
   const int qi = lane & 31, qc = min(qi, p.T - 1);
   bf16x8 qf[G::KS];
 #pragma unroll
-  for (int ks = 0; ks < G::KS; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8*>(p.q + ((long long)b * p.T + qc) * p.ld_q + hoff + 16 * ks + 8 * h);
+  for (int ks = 0; ks < G::KS; ++ks) qf[ks] = q_frag<D>(p, b, qc, hoff, ks, h);
   const float tg = rbf(tanhf(bf2f(p.gate[0]))), rs = sqrtf((float)D);
   constexpr float LN2 = 0.6931471805599453f, LOG2E = 1.4426950408889634f;
   u32x4 rk[G::NCH], rv[G::NCH];
   // ---- pass 1: max and sum of exp over this wave's tiles (natural units)
   float m_run = -INFINITY, l_run = 0.f;
   for (int n0 = 32 * w; n0 < N; n0 += 32 * HEAD_KV_WAVES) {
-    seg_prefetch_kv<D, false>(rk, rv, p, b, hoff, n0, N, lane);
+    seg_prefetch_kv<D>(rk, rv, p, b, hoff, n0, N, lane);
     tile_put<D>(rk, sK, lane);
     wave_lds_sync();
-    f32x16 S = zero16();
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks)
-      S = mfma32(*reinterpret_cast<const bf16x8*>(sK + (lane & 31) * G::LD + 16 * ks + 8 * h), qf[ks], S);
-    float mt = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = n0 + acc_row(r, h);
-      S[r] = score_chain(S[r], key >= p.T + p.Ka, tg, rs, key < N) * LN2;      // (back to natural units; -inf stays -inf)
-      mt = fmaxf(mt, S[r]);
-    }
+    float mt = -INFINITY;                           // (scores back to natural units; -inf stays -inf)
+    f32x16 S = score_tile<D>(sK, qf, p, n0, N, tg, rs, lane, h, [&](float s) { s *= LN2; mt = fmaxf(mt, s); return s; });
     mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
     const float m_new = fmaxf(m_run, mt);
     float rsum = 0.f;
@@ -316,47 +307,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void h
 #pragma unroll
   for (int t = 0; t < G::DT; ++t) O[t] = zero16();
   for (int n0 = 32 * w; n0 < N; n0 += 32 * HEAD_KV_WAVES) {
-    seg_prefetch_kv<D, false>(rk, rv, p, b, hoff, n0, N, lane);
+    seg_prefetch_kv<D>(rk, rv, p, b, hoff, n0, N, lane);
     tile_put<D>(rk, sK, lane);
     tile_put<D>(rv, sV, lane);
     wave_lds_sync();
-    f32x16 S = zero16();
+    // (pack_acc rounds to bf16: the weight ATen's softmax emits; padded keys: 0)
+    f32x16 S = score_tile<D>(sK, qf, p, n0, N, tg, rs, lane, h, [&](float s) { return fexp2((s * LN2 - M) * LOG2E) / L; });
 #pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks)
-      S = mfma32(*reinterpret_cast<const bf16x8*>(sK + (lane & 31) * G::LD + 16 * ks + 8 * h), qf[ks], S);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = n0 + acc_row(r, h);
-      const float s = score_chain(S[r], key >= p.T + p.Ka, tg, rs, key < N) * LN2;
-      S[r] = fexp2((s - M) * LOG2E) / L;           // (pack_acc rounds to bf16: the weight ATen's softmax emits; padded keys: 0)
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const bf16x8 pf = pack_acc(S, s);
-#pragma unroll
-      for (int t = 0; t < G::DT; ++t) O[t] = mfma32(tr_frag(sV, G::LD, s, 32 * t, lane), pf, O[t]);
-    }
+    for (int s = 0; s < 2; ++s) pv_half<D>(O, S, sV, s, lane);
     wave_lds_sync();
   }
   __syncthreads();                                  // every wave is done with its tiles: the regions now carry the partial O
-  {
-    float* myO = reinterpret_cast<float*>(smem + w * G::WAVE_BYTES);
-    if (w > 0) {
-#pragma unroll
-      for (int t = 0; t < G::DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) myO[(t * 16 + r) * 64 + lane] = O[t][r];
-    }
-    __syncthreads();
-    if (w > 0) return;
+  if (w > 0) spill_partial_o<D>(reinterpret_cast<float*>(smem + w * G::WAVE_BYTES), O, lane);
+  __syncthreads();
+  if (w > 0) return;
 #pragma nounroll
-    for (int ww = 1; ww < HEAD_KV_WAVES; ++ww) {
-      const float* oO = reinterpret_cast<const float*>(smem + ww * G::WAVE_BYTES);
+  for (int ww = 1; ww < HEAD_KV_WAVES; ++ww) {      // the weights are normalised already: plain sums
+    const float* oO = reinterpret_cast<const float*>(smem + ww * G::WAVE_BYTES);
 #pragma unroll
-      for (int t = 0; t < G::DT; ++t)
+    for (int t = 0; t < G::DT; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) O[t][r] += oO[(t * 16 + r) * 64 + lane];
-    }
+      for (int r = 0; r < 16; ++r) O[t][r] += oO[(t * 16 + r) * 64 + lane];
   }
   if (qi < p.T) {
     bf16_t* op = p.out + ((long long)b * p.T + qi) * p.ld_out + hoff;
@@ -374,210 +345,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void h
   }
 }
 
-// ------------------------------------------------------------------------------------------------ dQ (+ gate gradient)
-template <int D>
-__device__ __forceinline__ void head_dq_body(const HP& p, const int blk, char* smem) {
-  using G = HG<D>;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5;
-  const int gid = blk * 4 + w;
-  if (gid >= p.B * p.H) return;
-  const int b = gid / p.H, hd = gid - b * p.H, hoff = hd * D, N = p.T + p.Ka + p.Kt;
-  bf16_t* sK = reinterpret_cast<bf16_t*>(smem + w * G::WAVE_BYTES);
-  bf16_t* sV = sK + G::TILE;
-  lds_zero16(sK, 2 * G::TILE * 2, lane, 64);
-  const int qi = lane & 31, qc = min(qi, p.T - 1);
-  bf16x8 qf[G::KS], dof[G::KS];
-  float delta = 0.f;
-  {
-    const long long ro = ((long long)b * p.T + qc);
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) {
-      const int d = hoff + 16 * ks + 8 * h;
-      qf[ks] = *reinterpret_cast<const bf16x8*>(p.q + ro * p.ld_q + d);
-      dof[ks] = *reinterpret_cast<const bf16x8*>(p.dout + ro * p.ld_out + d);
-      const bf16x8 ov = *reinterpret_cast<const bf16x8*>(p.out + ro * p.ld_out + d);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) delta += bf2f((bf16_t)ov[j]) * bf2f((bf16_t)dof[ks][j]);
-    }
-    delta += __shfl_xor(delta, 32, 64);
-  }
-  const float* slot = p.probs + (long long)gid * p.T * N;  // [0,T): LSE (forward)
-  const float lse2 = slot[qc] * 1.4426950408889634f;
-  const float g0 = bf2f(p.gate[0]);
-  const float tg = rbf(tanhf(g0)), rs = sqrtf((float)D), irs = 1.f / rs;
-  f32x16 dQ[G::DT];
-#pragma unroll
-  for (int t = 0; t < G::DT; ++t) dQ[t] = zero16();
-  float gpart = 0.f;
-  u32x4 rk[G::NCH], rv[G::NCH];
-  seg_prefetch_kv<D, true>(rk, rv, p, b, hoff, 0, N, lane);
-  for (int n0 = 0; n0 < N; n0 += 32) {
-    tile_put<D>(rk, sK, lane);
-    tile_put<D>(rv, sV, lane);
-    if (n0 + 32 < N) {
-      seg_prefetch_kv<D, true>(rk, rv, p, b, hoff, n0 + 32, N, lane);
-    }
-    wave_lds_sync();
-    f32x16 S = zero16(), dP = zero16();
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) {
-      S = mfma32(*reinterpret_cast<const bf16x8*>(sK + (lane & 31) * G::LD + 16 * ks + 8 * h), qf[ks], S);
-      dP = mfma32(*reinterpret_cast<const bf16x8*>(sV + (lane & 31) * G::LD + 16 * ks + 8 * h), dof[ks], dP);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = n0 + acc_row(r, h);
-      const bool gated = key >= p.T + p.Ka, valid = key < N && qi < p.T;
-      const float dot = rbf(S[r]);
-      const float pr = valid ? fexp2(score_chain(S[r], gated, tg, rs, true) - lse2) : 0.f;
-      const float ds = pr * (dP[r] - delta) * irs;         // d(score before the /sqrt(dh))
-      if (gated) gpart += ds * dot;                        // d tanh(g)
-      S[r] = gated ? ds * tg : ds;                         // d(q.k)
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const bf16x8 df = pack_acc(S, s);
-#pragma unroll
-      for (int t = 0; t < G::DT; ++t) dQ[t] = mfma32(tr_frag(sK, G::LD, s, 32 * t, lane), df, dQ[t]);
-    }
-    wave_lds_sync();
-  }
-  if (p.rope_cos) rope_inter_bwd_acc<G::DT>(dQ, p.rope_cos, p.rope_sin, qc, D, D, h);
-  if (qi < p.T) {
-    bf16_t* op = p.dq + ((long long)b * p.T + qi) * p.ld_q + hoff;
-#pragma unroll
-    for (int t = 0; t < G::DT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = 32 * t + 8 * g + 4 * h;
-        if (d < D) {
-          uint2 o = {pack2(dQ[t][4 * g], dQ[t][4 * g + 1]), pack2(dQ[t][4 * g + 2], dQ[t][4 * g + 3])};
-          *reinterpret_cast<uint2*>(op + d) = o;
-        }
-      }
-  }
-  gpart = wave_sum(gpart);
-  if (lane == 0 && p.dgate) {
-    const float th = tanhf(g0);
-    atomicAdd(p.dgate, gpart * (1.f - th * th));
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ dK, dV
-template <int D>
-__device__ __forceinline__ void head_dkv_body(const HP& p, const int blk, char* smem) {
-  using G = HG<D>;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5;
-  const int N = p.T + p.Ka + p.Kt, ntile = (N + 31) / 32;
-  const int wgid = blk * 4 + w;                        // one wave per (sample, head, 32-key tile): every tile's dK/dV is
-  if (wgid >= p.B * p.H * ntile) return;               // independent, so the pass is embarrassingly parallel
-  const int gid = wgid / ntile, n0 = (wgid - gid * ntile) * 32;
-  const int b = gid / p.H, hd = gid - b * p.H, hoff = hd * D;
-  bf16_t* sQ = reinterpret_cast<bf16_t*>(smem + w * G::WAVE_BYTES);
-  bf16_t* sdO = sQ + G::TILE;
-  float* sLse = reinterpret_cast<float*>(sdO + G::TILE);
-  float* sDelta = sLse + 32;
-  lds_zero16(sQ, 2 * G::TILE * 2, lane, 64);
-  wave_lds_sync();
-  // the single query tile (rows >= T stay zero) and its row constants
-  for (int c = lane; c < p.T * G::CPR; c += 64) {
-    const int r = c / G::CPR, ch = c - r * G::CPR;
-    const long long ro = ((long long)b * p.T + r);
-    *reinterpret_cast<u32x4*>(sQ + r * G::LD + ch * 8) = *reinterpret_cast<const u32x4*>(p.q + ro * p.ld_q + hoff + ch * 8);
-    *reinterpret_cast<u32x4*>(sdO + r * G::LD + ch * 8) = *reinterpret_cast<const u32x4*>(p.dout + ro * p.ld_out + hoff + ch * 8);
-  }
-  const float* slot = p.probs + (long long)gid * p.T * N;
-  if (lane < 32) {
-    sLse[lane] = lane < p.T ? slot[lane] * 1.4426950408889634f : 0.f;
-    sDelta[lane] = 0.f;
-  }
-  wave_lds_sync();
-  // delta[q] = rowsum(dO * O), recomputed here (8 lanes per query row) so that this pass does not depend on the dQ pass:
-  // both run as ONE launch (the dQ waves are few and long, the dK/dV waves many and short)
-  for (int r0 = 0; r0 < p.T; r0 += 8) {
-    const int r = r0 + (lane >> 3), part = lane & 7;
-    float acc = 0.f;
-    if (r < p.T) {
-      const long long ro = ((long long)b * p.T + r);
-      for (int ch = part; ch < G::CPR; ch += 8) {
-        const bf16x8 ov = *reinterpret_cast<const bf16x8*>(p.out + ro * p.ld_out + hoff + ch * 8);
-        const bf16x8 dv = *reinterpret_cast<const bf16x8*>(sdO + r * G::LD + ch * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc += bf2f((bf16_t)ov[j]) * bf2f((bf16_t)dv[j]);
-      }
-    }
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    acc += __shfl_xor(acc, 4, 64);
-    if (part == 0 && r < p.T) sDelta[r] = acc;
-  }
-  wave_lds_sync();
-  const float tg = rbf(tanhf(bf2f(p.gate[0]))), rs = sqrtf((float)D), irs = 1.f / rs;
-  {
-    const int key = n0 + (lane & 31), kc = min(key, N - 1);
-    const bool gated = key >= p.T + p.Ka;
-    const bf16_t* kp = hrow(p.ks, p.ka, p.kt, p, b, kc, hoff);
-    const bf16_t* vp = hrow(p.vs, p.va, p.vt, p, b, kc, hoff);
-    f32x16 S = zero16(), dP = zero16();
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) {
-      const bf16x8 kf = *reinterpret_cast<const bf16x8*>(kp + 16 * ks + 8 * h);
-      const bf16x8 vf = *reinterpret_cast<const bf16x8*>(vp + 16 * ks + 8 * h);
-      S = mfma32(*reinterpret_cast<const bf16x8*>(sQ + (lane & 31) * G::LD + 16 * ks + 8 * h), kf, S);     // S[q x key]
-      dP = mfma32(*reinterpret_cast<const bf16x8*>(sdO + (lane & 31) * G::LD + 16 * ks + 8 * h), vf, dP);  // dO . V^T
-    }
-    f32x16 dS;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int qr = acc_row(r, h);
-      const bool valid = key < N && qr < p.T;
-      const float pr = valid ? fexp2(score_chain(S[r], gated, tg, rs, true) - sLse[qr]) : 0.f;
-      const float ds = pr * (dP[r] - sDelta[qr]) * irs;
-      S[r] = pr;
-      dS[r] = gated ? ds * tg : ds;
-    }
-    // One 32-column block of dV and dK at a time, stored before the next is formed: 2 x 16 live accumulator registers instead of
-    // DT x 2 x 16 (128 at head dim 112) - the kernel needed 380 registers and spilled under its 256-register cap.
-    const bf16x8 pf0 = pack_acc(S, 0), pf1 = pack_acc(S, 1), dsf0 = pack_acc(dS, 0), dsf1 = pack_acc(dS, 1);
-    const int pos = kc < p.T ? kc : (kc < p.T + p.Ka ? kc - p.T : kc - p.T - p.Ka);   // positions restart per segment
-    bf16_t* okp = const_cast<bf16_t*>(hrow(p.dks, p.dka, p.dkt, p, b, kc, hoff));
-    bf16_t* ovp = const_cast<bf16_t*>(hrow(p.dvs, p.dva, p.dvt, p, b, kc, hoff));
-#pragma unroll
-    for (int t = 0; t < G::DT; ++t) {
-      f32x16 dVt = zero16(), dKt = zero16();
-      dVt = mfma32(tr_frag(sdO, G::LD, 0, 32 * t, lane), pf0, dVt);    // dV^T[d x key] = dO^T . P
-      dVt = mfma32(tr_frag(sdO, G::LD, 1, 32 * t, lane), pf1, dVt);
-      dKt = mfma32(tr_frag(sQ, G::LD, 0, 32 * t, lane), dsf0, dKt);    // dK^T[d x key] = Q^T . dDot
-      dKt = mfma32(tr_frag(sQ, G::LD, 1, 32 * t, lane), dsf1, dKt);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = 32 * t + 8 * g + 4 * h;
-        if (d < D) {
-          float a0 = dKt[4 * g], b0 = dKt[4 * g + 1], a1 = dKt[4 * g + 2], b1 = dKt[4 * g + 3];
-          if (p.rope_cos) {                                              // inverse interleaved RoPE (rope_inter_bwd_acc, one block)
-            const float4 c = *reinterpret_cast<const float4*>(p.rope_cos + (long long)pos * D + d);
-            const float4 sn = *reinterpret_cast<const float4*>(p.rope_sin + (long long)pos * D + d);
-            const float x0 = a0 * c.x + b0 * sn.y, y0 = b0 * c.y - a0 * sn.x, x1 = a1 * c.z + b1 * sn.w, y1 = b1 * c.w - a1 * sn.z;
-            a0 = x0; b0 = y0; a1 = x1; b1 = y1;
-          }
-          if (key < N) {
-            *reinterpret_cast<uint2*>(okp + d) = uint2{pack2(a0, b0), pack2(a1, b1)};
-            *reinterpret_cast<uint2*>(ovp + d) = uint2{pack2(dVt[4 * g], dVt[4 * g + 1]), pack2(dVt[4 * g + 2], dVt[4 * g + 3])};
-          }
-        }
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ backward, tile-uniform form
-// (round 3) One WAVE per (sample, head, 32-key tile) does everything that tile contributes: dK and dV of its keys (complete),
-// its share of dQ and of the gate gradient (fp32 partials in a workspace, summed in tile order by head_dq_reduce).  The long dQ
-// waves of the combined kernel above (one per (sample, head): a serial loop over all key tiles with 64 accumulator + 112
-// operand / prefetch registers) set that kernel's register allocation at 380 (256 with spills) and its LDS at 17.6 KB per
-// wave; here every wave is the same short chain at <= 128 registers, and a workgroup = four consecutive key tiles of ONE
-// (sample, head) shares the staged Q / dO rows (T + 1 rows each: row T is the zero row every padded query row reads), so
-// four workgroups fit a CU.  Both score orientations are formed from the SAME fragments (S = Q.K^T with the key on the lane
+// ------------------------------------------------------------------------------------------------ backward
+// One WAVE per (sample, head, 32-key tile) does everything that tile contributes: dK and dV of its keys (complete),
+// its share of dQ and of the gate gradient (fp32 partials in a workspace, summed in tile order by head_dq_reduce).  Every
+// wave is the same short chain at <= 128 registers (a wave that loops over all key tiles of a (sample, head) for dQ took 380,
+// and 17.6 KB of LDS), and a workgroup = four consecutive key tiles of ONE (sample, head) shares the staged Q / dO rows
+// (T + 1 rows each: row T is the zero row every padded query row reads), so four workgroups fit a CU.  Both score orientations are formed from the SAME fragments (S = Q.K^T with the key on the lane
 // for dK / dV, S^T = K.Q^T with the query on the lane for dQ: the operands of one are the swapped operands of the other).
 template <int D>
 __global__ __launch_bounds__(256, 3) void head_bwd_tiles(HP p, float* __restrict__ ws_dq, float* __restrict__ ws_gate) {
@@ -759,7 +532,7 @@ __global__ __launch_bounds__(256, 3) void head_bwd_tiles(HP p, float* __restrict
         for (int g = 0; g < 4; ++g) {
           const int d = 32 * t + 8 * g + 4 * h;
           float a0 = acc[4 * g], b0 = acc[4 * g + 1], a1 = acc[4 * g + 2], b1 = acc[4 * g + 3];
-          if (pass == 1 && p.rope_cos) {                     // inverse interleaved RoPE (rope_inter_bwd_acc, one block)
+          if (pass == 1 && p.rope_cos) {                     // transpose of the head's interleaved RoPE: pairs (2i, 2i+1)
             const float4 c = rcv[g], sn = rsv[g];
             const float x0 = a0 * c.x + b0 * sn.y, y0 = b0 * c.y - a0 * sn.x, x1 = a1 * c.z + b1 * sn.w, y1 = b1 * c.w - a1 * sn.z;
             a0 = x0; b0 = y0; a1 = x1; b1 = y1;
@@ -830,18 +603,6 @@ __global__ __launch_bounds__(256) void head_dq_reduce(HP p, const float* __restr
   }
 }
 
-// dQ (+ gate) and dK/dV in one launch: blocks [0, ndq) run the dQ body, the rest the dK/dV body
-// Two waves per SIMD (<= 256 registers; unconstrained the compiler takes 380 and spills nothing).  Alone the launch is
-// SLOWER this way (85 -> 117 us, 34 spilled dwords) but the training step is 0.27 ms FASTER (same box): the kernel sits on
-// the backward's critical chain while the vision stream's GEMM workgroups hold 352 of a SIMD's 512 registers, and a
-// 380-register wave can only start on a CU that has drained.  (<= 168 registers: 179 us alone, +1.1 ms on the step.)
-template <int D>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void head_bwd_mfma(HP p, int ndq) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  if ((int)blockIdx.x < ndq) head_dq_body<D>(p, blockIdx.x, smem);
-  else head_dkv_body<D>(p, blockIdx.x - ndq, smem);
-}
-
 template <int D>
 int launch_fwd(const HP& p, hipStream_t st) {
   constexpr int lds = 4 * HG<D>::WAVE_BYTES;
@@ -856,47 +617,45 @@ int launch_fwd(const HP& p, hipStream_t st) {
 }
 template <int D>
 int launch_bwd(const HP& p, hipStream_t st) {
-  const int ntile = (p.T + p.Ka + p.Kt + 31) / 32;
-  const long long need = (long long)p.B * p.H * ntile * ((long long)p.T * D + 1);
-  if (p.ws != nullptr && p.ws_floats >= need && !getenv("VLA_HEAD_BWD_COMBINED")) {     // tile-uniform form (needs the workspace)
-    if (int rc = vla_lds_limit<head_bwd_tiles<D>>(4 * 33 * HG<D>::LD + 256 + 4 * HG<D>::TILE * 2, "head_bwd_tiles")) return rc;
-    float* ws_gate = p.ws + (long long)p.B * p.H * ntile * p.T * D;
-    const size_t lds2 = (size_t)4 * (p.T + 1) * HG<D>::LD + 256 + (size_t)4 * HG<D>::TILE * 2;
-    hipLaunchKernelGGL(head_bwd_tiles<D>, dim3(p.B * p.H * ((ntile + 3) / 4)), dim3(256), lds2, st, p, p.ws, ws_gate);
-    hipLaunchKernelGGL(head_dq_reduce<D>, dim3(p.B * p.H), dim3(256), 0, st, p, (const float*)p.ws, (const float*)ws_gate);
-    return VLA_OK;
-  }
-  constexpr int lds = 4 * HG<D>::WAVE_BYTES;
-  if (int rc = vla_lds_limit<head_bwd_mfma<D>>(lds, "head_bwd_mfma")) return rc;
-  const int ndq = (p.B * p.H + 3) / 4, ndkv = (p.B * p.H * ntile + 3) / 4;
-  hipLaunchKernelGGL(head_bwd_mfma<D>, dim3(ndq + ndkv), dim3(256), lds, st, p, ndq);
+  const int ntile = (p.T + p.Ka + p.Kt + 31) / 32;       // (head_attn_mfma_bwd has checked the workspace)
+  if (int rc = vla_lds_limit<head_bwd_tiles<D>>(4 * 33 * HG<D>::LD + 256 + 4 * HG<D>::TILE * 2, "head_bwd_tiles")) return rc;
+  float* ws_gate = p.ws + (long long)p.B * p.H * ntile * p.T * D;
+  const size_t lds = (size_t)4 * (p.T + 1) * HG<D>::LD + 256 + (size_t)4 * HG<D>::TILE * 2;
+  hipLaunchKernelGGL(head_bwd_tiles<D>, dim3(p.B * p.H * ((ntile + 3) / 4)), dim3(256), lds, st, p, p.ws, ws_gate);
+  hipLaunchKernelGGL(head_dq_reduce<D>, dim3(p.B * p.H), dim3(256), 0, st, p, (const float*)p.ws, (const float*)ws_gate);
   return VLA_OK;
+}
+
+// The head widths the kernels are instantiated for (192: Qwen2.5-1.5B, d 1536 / 8 heads, BASELINE configs[4]).
+#define HEAD_MFMA_WIDTHS(X) X(16) X(32) X(64) X(112) X(128) X(192)
+
+int dispatch(const HP& p, hipStream_t st, bool bwd) {
+  switch (p.dh) {
+#define X(D) case D: return bwd ? launch_bwd<D>(p, st) : launch_fwd<D>(p, st);
+    HEAD_MFMA_WIDTHS(X)
+#undef X
+  }
+  vla_set_error("head_attn (MFMA): head width without a kernel");
+  return VLA_ERR_UNSUPPORTED;
 }
 
 }  // namespace
 
 bool head_attn_mfma_supported(const HP& p) {
-  return (p.dh == 16 || p.dh == 32 || p.dh == 64 || p.dh == 112 || p.dh == 128 || p.dh == 192) && p.T <= 32 && p.T >= 1 &&
+#define X(D) || p.dh == D
+  return (false HEAD_MFMA_WIDTHS(X)) && p.T <= 32 && p.T >= 1 &&
          (long long)p.T * (p.T + p.Ka + p.Kt) >= 2 * p.T;   // probs slab must hold LSE + delta
+#undef X
 }
 
-int head_attn_mfma_fwd(const HP& p, hipStream_t st) {
-  switch (p.dh) {
-    case 16: return launch_fwd<16>(p, st);
-    case 32: return launch_fwd<32>(p, st);
-    case 64: return launch_fwd<64>(p, st);
-    case 112: return launch_fwd<112>(p, st);
-    case 192: return launch_fwd<192>(p, st);      // Qwen2.5-1.5B: d 1536 / 8 heads (BASELINE configs[4])
-    default: return launch_fwd<128>(p, st);
-  }
-}
+int head_attn_mfma_fwd(const HP& p, hipStream_t st) { return dispatch(p, st, false); }
+
 int head_attn_mfma_bwd(const HP& p, hipStream_t st) {
-  switch (p.dh) {
-    case 16: return launch_bwd<16>(p, st);
-    case 32: return launch_bwd<32>(p, st);
-    case 64: return launch_bwd<64>(p, st);
-    case 112: return launch_bwd<112>(p, st);
-    case 192: return launch_bwd<192>(p, st);
-    default: return launch_bwd<128>(p, st);
+  const long long need = (long long)p.B * p.H * ((p.T + p.Ka + p.Kt + 31) / 32) * ((long long)p.T * p.dh + 1);
+  if (p.ws == nullptr || p.ws_floats < need) {                // before any launch or attribute call: a refused call writes nothing
+    char msg[160];
+    snprintf(msg, sizeof(msg), "head_attn_bwd: the MFMA path needs a workspace (desc.ws) of %lld floats, got %lld", need, p.ws_floats);
+    VLA_REQUIRE(false, msg);
   }
+  return dispatch(p, st, true);
 }

@@ -657,7 +657,9 @@ def head_attn_fwd(q, ks, vs, ka, va, kt, vt, gate, H: int = 8, ref_softmax: bool
 def head_attn_bwd(dout, out, q, ks, vs, ka, va, kt, vt, gate, probs, dgate_f32, dq, dks, dvs, dka, dva, dkt, dvt, H: int = 8,
                   rope=None):
     """``out`` = the forward output, ``probs`` = the forward's workspace.  Gradient tensors are caller-provided views
-    with the SAME row strides as their forward counterparts."""
+    with the SAME row strides as their forward counterparts.  The MFMA backward's workspace (B*H*ceil((T+Ka+Kt)/32)*(T*dh + 1)
+    floats of dQ / gate partials, one set per 32-key tile) is REQUIRED by the library at the MFMA head widths - a descriptor without
+    it is refused before anything is launched - and is passed here at exactly that size."""
     _chk_bf16(dout, out, dq, dks, dvs, dka, dva, dkt, dvt)
     d = head_attn_desc(q, ks, vs, ka, va, kt, vt, gate, probs, out, H)
     d.dout = dout.data_ptr()
@@ -669,7 +671,6 @@ def head_attn_bwd(dout, out, q, ks, vs, ka, va, kt, vt, gate, probs, dgate_f32, 
     if rope is not None:          # (cos, sin) f32 [>= max(T,Ka,Kt), dh]: dq / dk come back through the RoPE transpose
         assert rope[0].shape[0] >= max(q.shape[1], ka.shape[1], kt.shape[1]) and rope[0].shape[1] == d.dh
         d.rope_cos, d.rope_sin = rope[0].data_ptr(), rope[1].data_ptr()
-    # workspace of the tile-uniform MFMA backward (dQ / gate partials per 32-key tile): B*H*ceil(N/32)*(T*dh + 1) floats
     ntile = (d.T + d.Ka + d.Kt + 31) // 32
     ws = _splitk_ws(d.B * d.H * ntile * (d.T * d.dh + 1), q.device)
     d.ws, d.ws_floats = ws.data_ptr(), ws.numel()
