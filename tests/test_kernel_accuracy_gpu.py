@@ -491,6 +491,7 @@ ATTN_CASES = [  # B, S, Hq, Hkv, dh, causal, mask, value
     (1, 64, 14, 2, 64, True, "isolated", "peaked"), (2, 65, 4, 4, 72, True, "row_dead", "normal"), (1, 127, 7, 7, 72, False, "trailing", "peaked"),
     (1, 129, 14, 2, 64, True, "leading", "sink@0"), (1, 352, 14, 2, 64, True, "trailing", "normal"), (2, 369, 2, 1, 128, False, "none", "sink@368"),
     (1, 625, 14, 2, 64, True, "trailing", "sink@40"), (1, 129, 7, 1, 64, True, "isolated", "peaked"), (2, 100, 2, 2, 72, False, "leading", "sink@70"),
+    (1, 70, 6, 2, 64, True, "trailing", "normal"), (1, 40, 8, 1, 64, False, "isolated", "normal"),      # GQA groups of 3 and 8 (the host's limit)
 ]
 
 

@@ -305,7 +305,9 @@ def test_attention_fwd_keys_split_over_the_waves(ops, B, S, Hq, Hkv, dh, causal,
 
 @pytest.mark.parametrize("B,S,Hq,Hkv,dh,causal,masked", [(2, 96, 2, 2, 64, False, False), (2, 77, 4, 2, 64, True, True),
                                                        (1, 352, 14, 2, 64, True, True), (1, 100, 2, 2, 72, False, False),
-                                                       (1, 352, 12, 2, 128, True, True)])     # Qwen2.5-1.5B head geometry
+                                                       (1, 352, 12, 2, 128, True, True),      # Qwen2.5-1.5B head geometry
+                                                       (2, 65, 4, 2, 72, True, True),         # dh 72 with a GQA group: pad columns in the group sum
+                                                       (1, 33, 2, 2, 128, True, False)])      # dh 128, group 1: four key tiles' K / V LDS images
 def test_attention_bwd(ops, B, S, Hq, Hkv, dh, causal, masked):
     qkv, q, k, v = _attn_inputs(B, S, Hq, Hkv, dh, 41)
     dout = gen(B, S, Hq * dh, seed=42)
@@ -517,7 +519,8 @@ def test_gemm_fused_rope_interleaved(ops, tile, monkeypatch):
     check(out, torch.cat([k, y[:, D:]], 1), name="gemm + interleaved rope")
 
 
-@pytest.mark.parametrize("B,S,Hq,Hkv,dh", [(2, 77, 4, 2, 64), (2, 77, 4, 2, 128), (1, 600, 12, 2, 128)])   # dh 128: Qwen2.5-1.5B geometry (round 4)
+@pytest.mark.parametrize("B,S,Hq,Hkv,dh", [(2, 77, 4, 2, 64), (2, 77, 4, 2, 128), (1, 600, 12, 2, 128),   # dh 128: Qwen2.5-1.5B geometry (round 4)
+                                           (1, 40, 2, 2, 64), (1, 33, 2, 2, 128)])                       # one query head per kv head: dK rotated in registers
 def test_attention_bwd_fused_inverse_rope(ops, B, S, Hq, Hkv, dh):
     qkv, q, k, v = _attn_inputs(B, S, Hq, Hkv, dh, 96)
     dout = gen(B, S, Hq * dh, seed=97)

@@ -36,4 +36,8 @@ __device__ __forceinline__ bf16x8 pack_acc(const f32x16& x, int s) {
   for (int j = 0; j < 8; ++j) r[j] = (short)f2bf(x[8 * s + j]);
   return r;
 }
-
+// a wave's own LDS writes are visible to its own later LDS reads (and the reverse): release fence + wave barrier, no s_barrier
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}

@@ -84,10 +84,6 @@ __device__ __forceinline__ void tile_put(const u32x4* __restrict__ v, bf16_t* ds
     }
   }
 }
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // score chain of the reference's bf16 module; returns the score in log2 domain (or -inf for padded keys)
 __device__ __forceinline__ float score_chain(float dot, bool gated, float tg, float rs, bool valid) {
