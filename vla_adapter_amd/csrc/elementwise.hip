@@ -1,6 +1,7 @@
 // HBM-bound glue kernels of the fine-tune hot path (gfx950): im2col, action masks, embedding splice, gathers,
 // RoPE (both conventions), SwiGLU backward, transposes, casts, L1 loss, AdamW.  All bf16 traffic is 16 B per lane.
 #include "gemm_epilogue.h"
+#include "argmax_order.h"
 #include <type_traits>
 
 namespace {
@@ -1046,17 +1047,8 @@ extern "C" int vla_embed_grad(void* stream, const void* dx, const long long* ids
 //
 // The row arithmetic is stated once (token_ce_row) for this kernel and for token_ce_metrics_kernel below.  ARGMAX = true makes
 // the max pass also carry each thread's (value, lowest index) pair and leaves the row's argmax in `best`: torch.argmax's rule
-// on the CPU - the lowest index among equal values, a NaN greater than everything, the first NaN wins.
-
-// Does the pair (bv, bi) come before (av, ai) in that order?
-__device__ __forceinline__ bool argmax_before(float bv, int bi, float av, int ai) {
-  const bool an = av != av, bn = bv != bv;
-  return an ? (bn && bi < ai) : (bn || bv > av || (bv == av && bi < ai));
-}
-// A thread meets its columns in ascending order: a strictly greater value (or the first NaN) replaces the pair.
-__device__ __forceinline__ void argmax_take(float v, int i, float& bv, int& bi) {
-  if (v > bv || (v != v && bv == bv)) { bv = v; bi = i; }
-}
+// on the CPU - the lowest index among equal values, a NaN greater than everything, the first NaN wins (argmax_before / argmax_take of
+// argmax_order.h, shared with the decoder's lm_head argmax).
 
 // Row maximum (as every thread's return value; fmaxf: NaNs are skipped, as before) through red[0..3]; ARGMAX: the row's argmax in
 // `best` (every thread) through red[4..7] / redi[0..3].  One read of the row.

@@ -499,28 +499,93 @@ class LLM(_BufferSets):
         a, b = c.heads * c.dh, (c.heads + c.kv_heads) * c.dh
         return t3[:, :, :a], t3[:, :, a:b], t3[:, :, b:]
 
+    def _layer(self, i: int, lin: Linear, x, x1, y, n1, n2, h, gu, r1, r2, attend, c_live=None):
+        """The ONE statement of decoder layer i, rows x -> y: which weights, norms and GEMM epilogues it runs.  ``attend(n1)`` is the
+        part that differs between the full-sequence forward (fwd_layer) and the cached single-token step (decode_step): the q|k|v
+        projection with its RoPE and the attention, returning the rows that enter o_proj."""
+        c, L, k = self.cfg, self.layers[i], f"llm.{i}."
+        # (RMSNorm folded into the neighbouring GEMMs - 47 launches fewer, built and measured SLOWER in round 3 - left the tree in
+        #  round 4: DESIGN section 4, tools/diag/gemm256_pruned_paths.patch)
+        n1 = lin._rms(x, L["n1"], n1, r1, c.eps)
+        ao = attend(n1)
+        lin._lin(k + "o", ao, L["wo"], None, out=x1, residual=x)
+        n2 = lin._rms(x1, L["n2"], n2, r2, c.eps)
+        # the pre-activations are kept for the backward only: rows below the live window are never read again
+        lin._lin(k + "gu", n2, L["wgu"], None, act=ACT_SWIGLU, out=gu, out2=h, c_live=c_live)
+        lin._lin(k + "down", h, L["wd"], None, out=y, residual=x1)
+
     def fwd_layer(self, i: int):
         """Layer i over the whole batch."""
         c, B, S, lin = self.cfg, self.B, self.S, self._flin
         D, H, KV, dh = c.d, c.heads, c.kv_heads, c.dh
         L, k = self.layers[i], f"llm.{i}."
-        x, qkv, x1 = self.HS[i].view(-1, D), self.QKV[i], self.X1[i]
+        qkv = self.QKV[i]
         n1, n2, h = self._keeps(i)
-        # (RMSNorm folded into the neighbouring GEMMs - 47 launches fewer, built and measured SLOWER in round 3 - left the tree in
-        #  round 4: DESIGN section 4, tools/diag/gemm256_pruned_paths.patch)
-        n1 = lin._rms(x, L["n1"], n1, self.R1[i], c.eps)
-        if dh in (64, 128):   # RoPE fused into the projection's epilogue (head dim 128: the 128-row kernel's column map, round 4)
-            lin._lin(k + "qkv", n1, L["wqkv"], L["bqkv"], out=qkv, rope=(1, self.cos, self.sin, S, dh, (H + KV) * dh))
-        else:
-            lin._lin(k + "qkv", n1, L["wqkv"], L["bqkv"], out=qkv)
-            ops.rope_half_(qkv[:, :H * dh], self.cos, self.sin, S, H, dh)
-            ops.rope_half_(qkv[:, H * dh:(H + KV) * dh], self.cos, self.sin, S, KV, dh)
-        ops.attn_fwd(*self._attn_views(qkv.view(B, S, -1)), H, KV, dh, True, self.kmask, out=self.AO[i].view(B, S, -1), lse=self.LSE[i])
-        lin._lin(k + "o", self.AO[i], L["wo"], None, out=x1, residual=x)
-        n2 = lin._rms(x1, L["n2"], n2, self.R2[i], c.eps)
-        # the pre-activations are kept for the backward only: rows below the live window are never read again
-        lin._lin(k + "gu", n2, L["wgu"], None, act=ACT_SWIGLU, out=self.GU[i], out2=h, c_live=(S, self.gu_row0) if self.gu_row0 else None)
-        lin._lin(k + "down", h, L["wd"], None, out=self.HS[self.out_slot(i)].view(-1, D), residual=x1)
+
+        def attend(n1):
+            if dh in (64, 128):   # RoPE fused into the projection's epilogue (head dim 128: the 128-row kernel's column map, round 4)
+                lin._lin(k + "qkv", n1, L["wqkv"], L["bqkv"], out=qkv, rope=(1, self.cos, self.sin, S, dh, (H + KV) * dh))
+            else:
+                lin._lin(k + "qkv", n1, L["wqkv"], L["bqkv"], out=qkv)
+                ops.rope_half_(qkv[:, :H * dh], self.cos, self.sin, S, H, dh)
+                ops.rope_half_(qkv[:, H * dh:(H + KV) * dh], self.cos, self.sin, S, KV, dh)
+            ops.attn_fwd(*self._attn_views(qkv.view(B, S, -1)), H, KV, dh, True, self.kmask, out=self.AO[i].view(B, S, -1), lse=self.LSE[i])
+            return self.AO[i]
+
+        self._layer(i, lin, self.HS[i].view(-1, D), self.X1[i], self.HS[self.out_slot(i)].view(-1, D), n1, n2, h, self.GU[i], self.R1[i],
+                    self.R2[i], attend, c_live=(S, self.gu_row0) if self.gu_row0 else None)
+
+    # ---- greedy decoding with a key/value cache (VLAEngine.generate; include/vla_decode.h) ------------------------------------------
+    def decode_alloc(self, B: int, S: int, T: int) -> dict:
+        """Everything T cached single-token steps behind a prefill of S rows own: the cache K / V [n, B, S_cap, KV dh] with
+        S_cap = S + T, the RoPE tables at that capacity (the values of a position do not depend on the table's length), the M = B
+        activations of a step, the per-row positions, the device step counter and the tokens."""
+        c, dev = self.cfg, self.device
+        n, D, kvw = c.n_layers, c.d, c.kv_heads * c.dh
+        W = getattr(self, "lm_head", None)
+        W = self.embed if W is None else W
+        e = lambda *s, dt=BF16: torch.empty(*s, device=dev, dtype=dt)
+        cos, sin = ops.rope_half_tables(S + T, c.dh, c.theta, dev)
+        return dict(B=B, S=S, T=T, S_cap=S + T, W=W, cos=cos, sin=sin, K=e(n, B, S + T, kvw), V=e(n, B, S + T, kvw),
+                    X=e(n + 1, B, D), X1=e(B, D), NB=e(B, D), NF=e(B, D), QKV=e(B, (c.heads + 2 * c.kv_heads) * c.dh), AO=e(B, c.heads * c.dh),
+                    GU=e(B, 2 * c.inter), H=e(B, c.inter), R=e(3, rup(B, 4), dt=torch.float32)[:, :B], XG=e(B, D),
+                    pos=torch.zeros(B, device=dev, dtype=torch.int32), step=torch.zeros(1, device=dev, dtype=torch.int32),
+                    ids=e(B, dt=torch.int64), out_ids=torch.zeros(B, T, device=dev, dtype=torch.int64), ws=ops.decode_argmax_workspace(B, W.shape[0], dev))
+
+    def cache_fill(self, st: dict):
+        """The rotated k and the v of every prefill row, from QKV[i] into rows 0 .. S - 1 of the cache (a strided copy per layer and
+        operand; the rows behind a sample's prompt hold its padding and are overwritten one per step before they are read)."""
+        c, B, S = self.cfg, st["B"], st["S"]
+        W, kvw, q = (c.heads + 2 * c.kv_heads) * c.dh, c.kv_heads * c.dh, c.heads * c.dh
+        for i in range(c.n_layers):
+            for dst, col in ((st["K"], q), (st["V"], q + kvw)):
+                ops.copy_rows3d(self.QKV[i][:, col:], dst[i], B, S, kvw, S * W, W, st["S_cap"] * kvw, kvw)
+
+    def decode_first(self, st: dict, last_row: torch.Tensor, pos0: torch.Tensor, logits_out=None):
+        """Behind the prefill: the final-norm rows of every sample's last prompt id -> the first token, the embedding of it as the
+        first step's input, pos = pos0 + 1, step = 1."""
+        n, D = self.cfg.n_layers, self.cfg.d
+        ops.gather_rows(self.HS[n].view(-1, D), last_row, st["XG"])
+        ops.decode_lm_head_argmax(st["XG"], st["W"], st["ws"], st["ids"], logits_out,
+                                  advance=(st["out_ids"], st["step"], st["pos"], self.embed, st["X"][0]), pos_from=pos0)
+
+    def decode_step(self, st: dict, logits_out=None):
+        """One cached single-token step for all B rows: the layers of _layer at M = B with the cache attention, the final norm, the
+        lm_head argmax and the advance.  Nothing here depends on the host knowing a position or the step index."""
+        c, lin = self.cfg, self.lin
+        H, KV, dh = c.heads, c.kv_heads, c.dh
+        for i in range(c.n_layers):
+            L, k = self.layers[i], f"llm.{i}."
+
+            def attend(n1):
+                lin._lin(k + "qkv", n1, L["wqkv"], L["bqkv"], out=st["QKV"])
+                ops.decode_rope_append_(st["QKV"], st["cos"], st["sin"], st["pos"], st["K"][i], st["V"][i], H, KV, dh)
+                return ops.decode_attn(st["QKV"][:, :H * dh], st["K"][i], st["V"][i], st["pos"], H, KV, dh, out=st["AO"])
+
+            self._layer(i, lin, st["X"][i], st["X1"], st["X"][i + 1], st["NB"], st["NB"], st["H"], st["GU"], st["R"][0], st["R"][1], attend)
+        ops.rmsnorm_fwd(st["X"][c.n_layers], self.norm, c.eps, out=st["NF"], rstd=st["R"][2])
+        ops.decode_lm_head_argmax(st["NF"], st["W"], st["ws"], st["ids"], logits_out,
+                                  advance=(st["out_ids"], st["step"], st["pos"], self.embed, st["X"][0]))
 
     def fwd_final(self):
         """hidden_states[n] = final RMSNorm of the last layer's output (HF convention)."""
@@ -1079,6 +1144,7 @@ class VLAEngine(schedule.StepControls):
         self._vis_bufs = {}        # (feats, patches) per (batch, patches): captured graphs keep their addresses
         self._val_pred = None
         self._predict_graphs, self._val_graphs = {}, None      # predict(): (graphs, static batch, segments) per input shape; val_step_graphed()
+        self._generate_sets = {}   # generate(): buffers, static batch and the two graphs per (B, L, T, pixel shape)
         self._timeline = None      # a list collects (kind, index, start, end) events of every segment run (tools/*_timeline.py)
         # captured step (capture()): its graphs, the vision graph, events of the vision stage in flight / of its pixel copy, pending update, exchange events
         self._graphs = self._g_vis = self._vis_ev = self._px_copied = self._pending_lr = self._reduced = None
@@ -1196,6 +1262,109 @@ class VLAEngine(schedule.StepControls):
 
         return segs + schedule.pipeline_forward(head, ch, llm_fwd, lambda: (llm.HS, self.pos1, batch["proprio"], self.Np, noise), at_end,
                                                 wait=[sg.signal for sg in segs], signal=("end", 0))
+
+    # ---- greedy decoding of action tokens (prismatic/models/vlas/openvla.py:81-94: `generate`, do_sample off) ---------------------------
+    _GEN_SCOPE = ("B", "S", "Np", "feats", "patches", "qidx0", "_vis_bufs")
+    _GEN_LLM_SCOPE = ("kmask", "B", "S", "gu_row0", "_flin")
+
+    def generate(self, batch: Dict[str, torch.Tensor], max_new_tokens: int, return_logits: bool = False):
+        """Greedy decoding of T = max_new_tokens tokens behind B right-padded prompts of different lengths -> int64 [B, T] on the
+        device, no host synchronisation.  batch: input_ids int64 [B, L], attention_mask [B, L], pixel_values, and from
+        ops.decode_prompt ``pos`` int32 [B] (sequence row of each sample's last prompt id) and ``last_row`` int32 [B] (the same row in
+        the flattened hidden states).  One prefill - the plain VLM forward of forward_vlm(action_queries=False), every layer and the
+        final norm, no [B, S, V] logits: the last valid row of every sample is gathered and goes through the fused lm_head argmax -
+        then T - 1 cached single-token steps (LLM.decode_step).  There is no early stop at an end-of-sequence id: T tokens are
+        always produced.
+
+        Captured by default: one prefill graph and ONE step graph per (B, L, T, pixel shape), the step graph replayed T - 1 times
+        (positions and the step index live in device memory).  VLA_PREDICT_EAGER=1 runs both parts eagerly; return_logits (eager
+        only) also returns the bf16 logits the argmax compared, [B, T, V].
+        Generation owns its buffers - LLM activations, vision features, cache - and rebinds what was bound before it returns: the
+        buffers a captured predict() or training graph holds are not written."""
+        T = int(max_new_tokens)
+        if T < 1:
+            raise ValueError(f"generate: max_new_tokens must be at least 1, got {max_new_tokens}")
+        if self.fp8_frozen or self.llm.lin.fp8:
+            raise NotImplementedError("generate: the fp8 weight path (enable_fp8_frozen) is not covered by the cached decoder")
+        eager = bool(os.environ.get("VLA_PREDICT_EAGER"))
+        if return_logits and not eager:
+            raise ValueError("generate: return_logits needs the eager path (VLA_PREDICT_EAGER=1): the captured graphs store no logits")
+        ids, px = batch["input_ids"], batch["pixel_values"]
+        B, L = ids.shape
+        for k in ("pos", "last_row"):
+            if k not in batch or batch[k].dtype != torch.int32 or batch[k].numel() != B:
+                raise ValueError(f"generate: batch[{k!r}] must be the int32 [{B}] vector of ops.decode_prompt")
+        key = (B, L, T, tuple(px.shape), px.dtype, eager)
+        llm = self.llm
+        saved = {k: self.__dict__[k] for k in self._GEN_SCOPE if k in self.__dict__}
+        saved_llm = {k: llm.__dict__[k] for k in self._GEN_LLM_SCOPE if k in llm.__dict__}
+        saved_set = llm.buffer_set() if hasattr(llm, "_buf_names") else None
+        try:
+            ent = self._generate_sets.get(key)
+            if ent is None:
+                ent = self._generate_sets[key] = self._generate_build(batch, T, eager)
+            llm.bind_buffer_set(ent["llm"])
+            self._vis_bufs = ent["vis"]
+            static, st = ent["static"], ent["state"]
+            for k, v in static.items():
+                v.copy_(batch[k])
+            logits = torch.empty(B, T, st["W"].shape[0], device=self.device, dtype=BF16) if return_logits else None
+            if eager:
+                self._generate_prefill(static, st, None if logits is None else logits[:, 0])
+                for t in range(1, T):
+                    self._generate_step(st, None if logits is None else logits[:, t])
+            else:
+                ent["prefill"].replay()
+                for _ in range(T - 1):
+                    ent["step"].replay()
+            out = st["out_ids"].clone()
+        finally:
+            self.__dict__.update(saved)
+            llm.__dict__.update(saved_llm)
+            if saved_set is not None:
+                llm.bind_buffer_set(saved_set)
+            else:
+                llm._buf_key = None                  # nothing was bound before: the next forward allocates its own set
+        return (out, logits) if return_logits else out
+
+    # Kernel selection is part of the arithmetic (ops.latency_hint: the short-M tiles and the uneven split-K associate the fp32 sums
+    # differently), so the eager and the captured path run under ONE rule and give the same tokens: the prefill as predict() has it (the
+    # hint at batch 1, where it was measured), the steps - M = B rows, every launch a fraction of the chip - always.
+    def _generate_prefill(self, static, st, logits0=None):
+        with (ops.latency_hint() if st["B"] == 1 else contextlib.nullcontext()):
+            self.forward_vlm(static, action_queries=False)
+            self.llm.cache_fill(st)
+            self.llm.decode_first(st, static["last_row"], static["pos"], logits0)
+
+    def _generate_step(self, st, logits_t=None):
+        with ops.latency_hint():
+            self.llm.decode_step(st, logits_t)
+
+    def _generate_build(self, batch, T: int, eager: bool) -> dict:
+        """The cache entry of one generate() shape: a set of LLM activation buffers and vision buffers of its own (a fresh
+        allocation, whatever is bound), the decode state, static inputs, and - unless eager - the prefill graph and the step graph,
+        captured on one stream behind two eager warm-up runs (every kernel launched and its LDS attribute set before the capture)."""
+        llm = self.llm
+        B, L = batch["input_ids"].shape
+        static = {k: batch[k].clone() for k in ("input_ids", "attention_mask", "pixel_values", "pos", "last_row")}
+        self._vis_bufs = {}
+        llm._buf_key = None
+        self._vision_begin(static)                   # allocates the set this entry keeps
+        st = llm.decode_alloc(B, self.S, T)
+        ent = dict(static=static, state=st, llm=llm.buffer_set(), vis=self._vis_bufs)
+        if eager:
+            return ent
+        self._ensure_streams()
+        for _ in range(2):
+            self._generate_prefill(static, st)
+            if T > 1:
+                self._generate_step(st)
+        torch.cuda.synchronize()
+        pool = torch.cuda.graph_pool_handle()
+        ent["prefill"] = capture_graph(lambda: self._generate_prefill(static, st), pool, self._cap_main)
+        ent["step"] = capture_graph(lambda: self._generate_step(st), pool, self._cap_main) if T > 1 else None
+        torch.cuda.synchronize()
+        return ent
 
     # modeling_prismatic.py:596-655 (multimodal forward): fills llm.HS with the n+1 hidden states
     def forward_vlm(self, batch: Dict[str, torch.Tensor], for_training: bool = False, action_queries: bool = True):

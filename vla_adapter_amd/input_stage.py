@@ -525,6 +525,26 @@ class GPUInputStage:
                                                             stop_id=STOP_INDEX, action_label=ACTION_TOKEN_BEGIN_IDX + 1, ignore_index=IGNORE_INDEX)
         return dict(input_ids=ids, labels=labels, attention_mask=am.view(torch.bool), hid_row=hid_row, row_ok=row_ok)
 
+    def decode_prompt(self, prompt_ids, n_patches: int, len_multiple: int = 32) -> Dict[str, torch.Tensor]:
+        """The prompt-only batch of a generation (VLAEngine.generate), right-padded to the longest prompt rounded up to
+        ``len_multiple``, in one launch (vla_decode_prompt): dict(input_ids int64 [B, L], attention_mask bool [B, L], pos int32 [B],
+        last_row int32 [B], row_ok u8 [B]).  Unlike serve_tokens no placeholders and no stop id stand behind the prompt: the decoder
+        writes its own tokens there.  prompt_ids: list of id lists, or (prompt_flat, prompt_off) tensors with the offsets on the host."""
+        lens = serve_prompt_lens(prompt_ids)
+        if lens is None or len(lens) < 1 or min(lens) < 1:
+            raise ValueError("decode_prompt: host-side prompt lengths, every one at least 1")
+        if len_multiple < 1:
+            raise ValueError("decode_prompt: len_multiple must be at least 1")
+        L = -(-max(lens) // len_multiple) * len_multiple
+        if isinstance(prompt_ids, (tuple, list)) and len(prompt_ids) == 2 and all(isinstance(t, torch.Tensor) for t in prompt_ids):
+            flat, off = prompt_ids
+        else:
+            flat = torch.tensor([t for r in prompt_ids for t in r], dtype=torch.int64)
+            off = torch.tensor(serve_layout(lens, len_multiple)[0], dtype=torch.int32)
+        flat, off = flat.to(self.device, torch.int64).contiguous(), off.to(self.device, torch.int32).contiguous()
+        ids, am, pos, last_row, row_ok = ops.decode_prompt(flat, off, L, int(n_patches), pad_id=self.pad)
+        return dict(input_ids=ids, attention_mask=am.view(torch.bool), pos=pos, last_row=last_row, row_ok=row_ok)
+
     def _serve_stats(self, stats: dict, kind: str):
         """(low f64 [D], high f64 [D], mask u8 [D] or None) on the device, uploaded once per (stats object, kind)."""
         if kind not in SERVE_STATS_KINDS:

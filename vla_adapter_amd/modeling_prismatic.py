@@ -241,6 +241,70 @@ class OpenVLAForActionPrediction:
         hid = ops.serve_gather_hidden(eng.llm.HS[self.cfg.llm.n_layers], tok["hid_row"], self.cfg.n_patches, K.NUM_TOKENS)
         return (actions, hid) if return_tensors else (actions.cpu().numpy(), hid)
 
+    # ---- serving a token-CE model: greedy action tokens with a key/value cache (prismatic/models/vlas/openvla.py:36-106) -------------
+    def generate_actions(self, prompt_ids, *, pixel_values=None, frames_u8=None, center_crop: bool = False, policy_resize: bool = False,
+                         unnorm_key=None, max_new_tokens: Optional[int] = None, return_tokens: bool = False, return_tensors: bool = False,
+                         use_film: bool = False):
+        """OpenVLA.predict_action for a batch of B observations, for a model trained with the token cross-entropy objective
+        (``--objective token_ce``): greedy decoding of T = max_new_tokens action tokens behind every prompt (VLAEngine.generate: one
+        prefill, T - 1 cached steps, one device pass), ActionTokenizer.decode_token_ids_to_actions on them (the rule the trainers'
+        metrics use: GPUInputStage.decode_token_ids_to_actions, the tokenizer length and bin count of set_objective's defaults), then
+        the un-normalisation of openvla.py:99-105 - ``where(mask, 0.5 (a + 1) (q99 - q01) + q01, a)``, which unlike the HF class's
+        _unnormalize_actions has no 1e-8 - in float64 on the device.  Returns float64 [B, T / action_dim, action_dim] (an ndarray, or a
+        device tensor and no host synchronisation with return_tensors); with return_tokens the pair (actions, tokens int64 [B, T]).
+
+        prompt_ids: a list of id lists - per sample the ids the training collator put in front of the action tokens (a prompt_flat
+        row) - or (prompt_flat int64 [n], prompt_off int32 [B + 1]) tensors with the offsets on the host.  Rows are right-padded to a
+        multiple of 32.  T defaults to chunk * action_dim, the action ids the collator puts behind the prompt (56 for LIBERO); with
+        return_tokens it need not be a multiple of action_dim, and the actions are then None.  There is NO early stop at an
+        end-of-sequence id: T tokens are always produced (the reference's `generate` would stop at one; a model trained on action ids
+        behind the prompt does not emit it before them).  pixel_values / frames_u8, center_crop, policy_resize: as in predict_actions.
+        A LoRA run is served from its merged checkpoint.  Sampling is not built: the choice is the argmax, lowest id among equals."""
+        if use_film:
+            raise NotImplementedError("generate_actions: FiLM (use_film) is outside the accelerated path")
+        if self.engine.fp8_frozen:
+            raise NotImplementedError("generate_actions: the fp8 weight path (enable_fp8_frozen) is not covered by the cached decoder")
+        Da = self.cfg.action_dim
+        T = self.cfg.chunk * Da if max_new_tokens is None else int(max_new_tokens)
+        if T < 1:
+            raise ValueError(f"generate_actions: max_new_tokens must be at least 1, got {max_new_tokens}")
+        if T % Da and not return_tokens:
+            raise ValueError(f"generate_actions: max_new_tokens = {T} is not a multiple of action_dim = {Da}; pass return_tokens=True for the bare tokens")
+        if (pixel_values is None) == (frames_u8 is None):
+            raise ValueError("generate_actions: pass exactly one of pixel_values / frames_u8")
+        if policy_resize and frames_u8 is None:
+            raise ValueError("generate_actions: policy_resize works on raw frames (frames_u8); pixel_values are already processed")
+        stats = None
+        if T % Da == 0:
+            if not self.norm_stats or (unnorm_key is None and len(self.norm_stats) != 1) or (unnorm_key is not None and unnorm_key not in self.norm_stats):
+                raise ValueError(f"generate_actions: no statistics entry for unnorm_key = {unnorm_key!r}: the model holds {sorted(self.norm_stats)}")
+            stats = self.get_action_stats(unnorm_key)
+            if "q01" not in stats or "q99" not in stats or len(stats["q01"]) != Da:
+                raise ValueError(f"generate_actions: the statistics entry needs q01 and q99 of {Da} dimensions (openvla.py:99-105)")
+        from . import input_stage as IS
+        lens = IS.serve_prompt_lens(prompt_ids)
+        if lens is None:
+            raise ValueError("generate_actions: prompt offsets on the device are not accepted (the padded length comes from the lengths)")
+        if len(lens) < 1 or min(lens) < 1:
+            raise ValueError("generate_actions: every sample needs a prompt of at least one id")
+        stage, dev = self.input_stage(), self.device
+        tok = stage.decode_prompt(prompt_ids, self.cfg.n_patches)
+        if policy_resize:
+            frames_u8 = stage.policy_frames(frames_u8)
+        px = stage.pixels(frames_u8, center_crop=center_crop) if frames_u8 is not None else pixel_values.to(dev).contiguous()
+        batch = dict(input_ids=tok["input_ids"], attention_mask=tok["attention_mask"], pixel_values=px, pos=tok["pos"], last_row=tok["last_row"])
+        tokens = self.engine.generate(batch, T)                                        # int64 [B, T] on the device
+        actions = None
+        if stats is not None:
+            low, high, mask = stage._serve_stats(stats, "bounds_q99")                  # f64 [Da] on the device, mask u8 or None
+            a = stage.decode_token_ids_to_actions(tokens).view(tokens.shape[0], T // Da, Da)
+            actions = (0.5 * (a + 1.0)) * (high - low) + low                           # numpy's association; every operation rounds on its own
+            if mask is not None:
+                actions = torch.where(mask.bool(), actions, a)
+            if not return_tensors:
+                actions = actions.cpu().numpy()
+        return (actions, tokens) if return_tokens else actions
+
 
 @dataclass
 class CausalLMOutputWithPast:                     # transformers.modeling_outputs.CausalLMOutputWithPast (what the reference returns)

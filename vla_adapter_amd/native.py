@@ -225,8 +225,26 @@ LATER_PROTOS = {name: sig for fam in LATER_FAMILIES for name, sig in fam.protos.
 assert len(LATER_PROTOS) == sum(len(fam.protos) for fam in LATER_FAMILIES) and not set(LATER_PROTOS) & set(PROTOS), "an entry point belongs to one header"
 
 
+# The open end of the registry: LATER_FAMILIES is pinned as a literal list too (tests/test_abi_later_families.py), so families from here on
+# are rows of this tuple - tests/test_abi_decode_family.py runs the same agreement checks over every row, whatever its key.
+ADDED_FAMILIES = (
+    # greedy action-token decoding with a key/value cache (csrc/decode.hip)
+    Family("decode", "vla_decode.h", {
+        "vla_decode_prompt": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _L], _I),
+        "vla_decode_rope_append": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _I], _I),
+        "vla_decode_attn": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _I, _F], _I),
+        "vla_decode_argmax_slabs": ([_I], _I),
+        "vla_decode_lm_head_argmax": ([_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P, _I, _P, _P, _P, _P, _I, _I, _P, _I], _I),
+    }),
+)
+ADDED_PROTOS = {name: sig for fam in ADDED_FAMILIES for name, sig in fam.protos.items()}
+assert len(ADDED_PROTOS) == sum(len(fam.protos) for fam in ADDED_FAMILIES) and not set(ADDED_PROTOS) & (set(PROTOS) | set(LATER_PROTOS)), \
+    "an entry point belongs to one header"
+ALL_FAMILIES = FAMILIES + LATER_FAMILIES + ADDED_FAMILIES
+
+
 def family(key: str) -> Family:
-    return next(fam for fam in FAMILIES + LATER_FAMILIES if fam.key == key)
+    return next(fam for fam in ALL_FAMILIES if fam.key == key)
 
 
 _lib = None
@@ -242,7 +260,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in [sig for fam in FAMILIES + LATER_FAMILIES for sig in fam.protos.items()]:
+    for name, (args, res) in [sig for fam in ALL_FAMILIES for sig in fam.protos.items()]:
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

@@ -1325,3 +1325,131 @@ def jpeg_encode(frames_u8: torch.Tensor, quality: int = 95, restart_rows: int = 
     N.check(_lib().vla_jpeg_encode_write(_st(), n, H, W, _p(qtab), int(restart_rows), _p(workspace), need, _p(frame_off), _p(out), total),
             "jpeg_encode_write")
     return out, frame_off
+
+
+# ---- greedy decoding with a key/value cache (include/vla_decode.h, csrc/decode.hip) -------------------------------------------------
+def _cache_view(name: str, k_cache: torch.Tensor, v_cache: torch.Tensor, B: int, Hkv: int, dh: int):
+    """(S_cap, sample stride, row stride) of one layer's cache pair [B, S_cap, Hkv * dh] (same strides, unit inner stride)."""
+    _chk_bf16(k_cache, v_cache)
+    if k_cache.dim() != 3 or k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride():
+        raise ValueError(f"{name}: k_cache and v_cache must be [B, S_cap, Hkv * dh] views of one layout, got {tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+    if k_cache.shape[0] != B or k_cache.shape[2] != Hkv * dh or k_cache.stride(2) != 1:
+        raise ValueError(f"{name}: the cache is [B = {B}, S_cap, Hkv * dh = {Hkv * dh}] with unit inner stride, got {tuple(k_cache.shape)}")
+    return k_cache.shape[1], k_cache.stride(0), k_cache.stride(1)
+
+
+def _chk_pos(name: str, pos: torch.Tensor, B: int, dev):
+    if pos.dtype != torch.int32 or not pos.is_contiguous() or pos.numel() != B or pos.device != dev:
+        raise ValueError(f"{name}: pos must be a contiguous int32 [{B}] on {dev}, got {pos.dtype} {tuple(pos.shape)} on {pos.device}")
+
+
+def decode_prompt(prompt_flat: torch.Tensor, prompt_off: torch.Tensor, L: int, Np: int, *, pad_id: int):
+    """vla_decode_prompt: prompt_flat int64 [n] + prompt_off int32 [B + 1] -> (input_ids int64 [B, L], attention_mask u8 [B, L], pos int32
+    [B] = Np + P - 1, last_row int32 [B] = b (Np + L) + pos, row_ok u8 [B]): the prompt-only batch of a generation, right-padded."""
+    B, dev = prompt_off.numel() - 1, prompt_off.device
+    if prompt_flat.dtype != torch.int64 or prompt_flat.dim() != 1 or not prompt_flat.is_contiguous():
+        raise ValueError("decode_prompt: prompt_flat must be a contiguous int64 vector")
+    if prompt_off.dtype != torch.int32 or prompt_off.dim() != 1 or not prompt_off.is_contiguous() or B < 1 or not prompt_off.is_cuda or prompt_flat.device != dev:
+        raise ValueError("decode_prompt: prompt_off must be a contiguous int32 [B + 1] on the device of prompt_flat, B >= 1")
+    if L < 1 or Np < 0:
+        raise ValueError(f"decode_prompt: L >= 1 and Np >= 0, got L = {L}, Np = {Np}")
+    ids, am = torch.empty(B, L, device=dev, dtype=torch.int64), torch.empty(B, L, device=dev, dtype=torch.uint8)
+    pos, last_row = torch.empty(B, device=dev, dtype=torch.int32), torch.empty(B, device=dev, dtype=torch.int32)
+    row_ok = torch.empty(B, device=dev, dtype=torch.uint8)
+    N.check(_lib().vla_decode_prompt(_st(), _p(prompt_flat) if prompt_flat.numel() else None, _p(prompt_off), prompt_flat.numel(), _p(ids), _p(am),
+                                     _p(pos), _p(last_row), _p(row_ok), B, int(L), int(Np), int(pad_id)), "decode_prompt")
+    return ids, am, pos, last_row, row_ok
+
+
+def decode_rope_append_(qkv: torch.Tensor, cos_t: torch.Tensor, sin_t: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
+                        v_cache: torch.Tensor, Hq: int, Hkv: int, dh: int):
+    """vla_decode_rope_append: qkv bf16 [B, (Hq + 2 Hkv) dh] (rows may be strided) - q rotated in place at pos[b], the rotated k and
+    the v written to row pos[b] of sample b of k_cache / v_cache [B, S_cap, Hkv dh]; tables f32 [S_cap, dh / 2]."""
+    _chk_bf16(qkv)
+    B = qkv.shape[0]
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] != (Hq + 2 * Hkv) * dh:
+        raise ValueError(f"decode_rope_append: qkv must be [B, (Hq + 2 Hkv) dh = {(Hq + 2 * Hkv) * dh}] with unit inner stride, got {tuple(qkv.shape)}")
+    S_cap, sb, ss = _cache_view("decode_rope_append", k_cache, v_cache, B, Hkv, dh)
+    _chk_pos("decode_rope_append", pos, B, qkv.device)
+    for t in (cos_t, sin_t):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (S_cap, dh // 2) or t.device != qkv.device:
+            raise ValueError(f"decode_rope_append: the tables are contiguous f32 [S_cap = {S_cap}, dh / 2 = {dh // 2}], got {t.dtype} {tuple(t.shape)}")
+    N.check(_lib().vla_decode_rope_append(_st(), _p(qkv), _p(cos_t), _p(sin_t), _p(pos), _p(k_cache), _p(v_cache), B, Hq, Hkv, dh, qkv.stride(0),
+                                          S_cap, sb, ss), "decode_rope_append")
+    return qkv
+
+
+def decode_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, Hq: int, Hkv: int, dh: int,
+                out: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+    """vla_decode_attn: q bf16 [B, Hq dh] (one rotated query row per sample; rows may be strided) against keys / values 0 .. pos[b] of
+    the cache -> out bf16 [B, Hq dh]."""
+    _chk_bf16(q, out)
+    B = q.shape[0]
+    if q.dim() != 2 or q.stride(1) != 1 or q.shape[1] != Hq * dh:
+        raise ValueError(f"decode_attn: q must be [B, Hq dh = {Hq * dh}] with unit inner stride, got {tuple(q.shape)}")
+    if dh not in (64, 128) or Hq % Hkv or Hq // Hkv > 8:
+        raise ValueError(f"decode_attn: head dim 64 or 128 and at most 8 query heads per kv head, got Hq = {Hq}, Hkv = {Hkv}, dh = {dh}")
+    S_cap, sb, ss = _cache_view("decode_attn", k_cache, v_cache, B, Hkv, dh)
+    _chk_pos("decode_attn", pos, B, q.device)
+    if out is None:
+        out = torch.empty(B, Hq * dh, device=q.device, dtype=BF16)
+    if tuple(out.shape) != (B, Hq * dh) or out.stride(1) != 1:
+        raise ValueError(f"decode_attn: out must be [B, Hq dh] with unit inner stride, got {tuple(out.shape)}")
+    N.check(_lib().vla_decode_attn(_st(), _p(q), _p(k_cache), _p(v_cache), _p(pos), _p(out), B, Hq, Hkv, dh, q.stride(0), out.stride(0), S_cap, sb,
+                                   ss, float(dh ** -0.5 if scale is None else scale)), "decode_attn")
+    return out
+
+
+def decode_argmax_workspace(B: int, V: int, device):
+    """(part_val f32 [B, slabs], part_idx int32 [B, slabs]) of decode_lm_head_argmax for a vocabulary of V rows."""
+    n = _lib().vla_decode_argmax_slabs(int(V))
+    if n < 1 or B < 1:
+        raise ValueError(f"decode_argmax_workspace: B >= 1 and V >= 1, got B = {B}, V = {V}")
+    return torch.empty(B, n, device=device, dtype=torch.float32), torch.empty(B, n, device=device, dtype=torch.int32)
+
+
+def decode_lm_head_argmax(x: torch.Tensor, W: torch.Tensor, ws, ids: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
+                          advance=None, pos_from: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vla_decode_lm_head_argmax: x bf16 [B, D], W bf16 [V, D] -> ids int64 [B], the argmax of bf16(x W^T) in torch.argmax's order, no
+    [B, V] tensor formed unless logits_out (bf16 [B, V], rows may be strided) asks for the compared values.  ws: decode_argmax_workspace.
+    advance = (out_ids int64 [B, T], step int32 [1], pos int32 [B], embed bf16 [vocab, D], x_next bf16 [B, D]): out_ids[:, step] = ids,
+    x_next = embed[ids], pos += 1, step += 1 in the finishing pass.  pos_from int32 [B] (with advance): the first advance of a generation -
+    step counts from 0 and pos = pos_from + 1."""
+    _chk_bf16(x, W, logits_out)
+    if x.dim() != 2 or W.dim() != 2 or x.stride(1) != 1 or W.stride(1) != 1 or x.shape[1] != W.shape[1]:
+        raise ValueError(f"decode_lm_head_argmax: x [B, D] and W [V, D] with unit inner strides, got {tuple(x.shape)} / {tuple(W.shape)}")
+    (B, D), V, dev = x.shape, W.shape[0], x.device
+    if not 1 <= B <= 64 or D % 8 or D > 4096:
+        raise ValueError(f"decode_lm_head_argmax: B in [1, 64] and D a multiple of 8 up to 4096, got B = {B}, D = {D}")
+    pv, pi = ws
+    n = _lib().vla_decode_argmax_slabs(V)
+    if pv.dtype != torch.float32 or pi.dtype != torch.int32 or not pv.is_contiguous() or not pi.is_contiguous() or pv.numel() < B * n or pi.numel() < B * n:
+        raise ValueError(f"decode_lm_head_argmax: the workspace holds f32 and int32 [B = {B}, slabs = {n}] (decode_argmax_workspace)")
+    if ids is None:
+        ids = torch.empty(B, device=dev, dtype=torch.int64)
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or ids.numel() != B:
+        raise ValueError(f"decode_lm_head_argmax: ids must be a contiguous int64 [{B}]")
+    ldl = 0
+    if logits_out is not None:
+        if tuple(logits_out.shape) != (B, V) or logits_out.stride(1) != 1:
+            raise ValueError(f"decode_lm_head_argmax: logits_out must be [B, V] = [{B}, {V}] with unit inner stride, got {tuple(logits_out.shape)}")
+        ldl = logits_out.stride(0)
+    a = [None, 0, None, None, None, None, 0, 0, None, 0]
+    if pos_from is not None and advance is None:
+        raise ValueError("decode_lm_head_argmax: pos_from belongs to an advance")
+    if advance is not None:
+        out_ids, step, pos, embed, x_next = advance
+        _chk_bf16(embed, x_next)
+        _chk_pos("decode_lm_head_argmax", pos, B, dev)
+        if out_ids.dtype != torch.int64 or not out_ids.is_contiguous() or out_ids.dim() != 2 or out_ids.shape[0] != B:
+            raise ValueError(f"decode_lm_head_argmax: out_ids must be a contiguous int64 [B = {B}, T], got {out_ids.dtype} {tuple(out_ids.shape)}")
+        if step.dtype != torch.int32 or step.numel() != 1:
+            raise ValueError("decode_lm_head_argmax: step must be one int32 on the device")
+        if embed.dim() != 2 or embed.shape[1] != D or embed.stride(1) != 1 or tuple(x_next.shape) != (B, D) or x_next.stride(1) != 1:
+            raise ValueError(f"decode_lm_head_argmax: embed [vocab, D = {D}] and x_next [B, D] with unit inner strides, got {tuple(embed.shape)} / {tuple(x_next.shape)}")
+        if pos_from is not None:
+            _chk_pos("decode_lm_head_argmax", pos_from, B, dev)
+        a = [_p(out_ids), out_ids.shape[1], _p(step), _p(pos), _p(pos_from), _p(embed), embed.shape[0], embed.stride(0), _p(x_next), x_next.stride(0)]
+    N.check(_lib().vla_decode_lm_head_argmax(_st(), _p(x), x.stride(0), _p(W), W.stride(0), B, D, V, _p(pv), _p(pi), _p(ids), _p(logits_out), ldl, *a),
+            "decode_lm_head_argmax")
+    return ids
