@@ -299,7 +299,7 @@ def test_llm_only_backward_identical_inputs(setup):
     for i in range(1, n + 1):
         budget(llm.HS[i].float().cpu()[valid], res[True][0][i][valid], res[False][0][i][valid], f"LLM-only hidden_states[{i}]")
     budget(dx.float().cpu()[valid], res[True][1][valid], res[False][1][valid], "LLM-only dX")
-    llm._buf_key = None      # other tests use a different (B, S)
+    llm.unbind()             # other tests use a different (B, S)
 
 
 def test_pipelined_eager_matches_sequential(setup):

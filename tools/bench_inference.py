@@ -44,7 +44,7 @@ for name, cfg in configs.items():
     t = (time.perf_counter() - t0) / n
     # device-side time of one replay of the captured segments (events on the caller's stream around the call)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    batch_static = next(iter(vla.engine._predict_graphs.values()))[1]
+    batch_static = next(iter(vla.engine._predict_graphs.values()))["static"]
     e0.record()
     for _ in range(n):
         vla.engine.predict(batch_static)

@@ -30,9 +30,9 @@ _alloc0 = E.LLM._alloc
 
 
 def _alloc_random(self, B, S):
-    fresh = self._buf_key != (B, S)
+    before = self._bound
     _alloc0(self, B, S)
-    if fresh:                                                            # buffers whose producer is skipped hold random data
+    if self._bound is not before:                                                           # buffers whose producer is skipped hold random data
         self.nbuf.copy_((torch.randn(self.nbuf.shape, device=self.nbuf.device) * 0.5).to(self.nbuf.dtype))
         self.AO.copy_((torch.randn(self.AO.shape, device=self.AO.device) * 0.5).to(self.AO.dtype))
         self.R1.fill_(1.0); self.R2.fill_(1.0)

@@ -27,6 +27,6 @@ end = torch.cuda.Event(enable_timing=True)
 end.record()
 torch.cuda.synchronize()
 print(f"predict: {ref.elapsed_time(end):.3f} ms")
-segs = next(iter(eng._predict_graphs.values()))[2]
+segs = next(iter(eng._predict_graphs.values()))["segs"]
 for st, k, t0, t1 in eng._timeline:
     print(f"{st:3s} seg {k:2d} start {ref.elapsed_time(t0):7.3f} end {ref.elapsed_time(t1):7.3f} dur {t0.elapsed_time(t1):6.3f} wait={segs[k][2]} signal={segs[k][3]}")

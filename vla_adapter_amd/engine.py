@@ -383,21 +383,29 @@ class ViT:
 
 # ------------------------------------------------------------------------------------------------ frozen LLM
 class _BufferSets:
-    """Mixin of the classes whose ``_alloc`` rebinds one set of activation buffers per shape (LLM, Head).  A captured graph holds the
-    addresses of the set it was captured on, so whoever keeps graphs of several shapes alive (VLAEngine.predict: one per (B, L))
-    takes ``buffer_set()`` after the capture and ``bind_buffer_set()`` before each replay: the tensors stay allocated and the
-    attributes the host reads afterwards (llm.HS, ...) are those of the replayed shape.  ``_track_alloc`` runs inside ``_alloc``: the
-    attributes an allocation rebinds are found by identity, their names accumulated over all allocations."""
+    """Base of the classes that work on one set of activation buffers per shape (LLM, Head).  THE rule: a captured
+    graph holds the addresses of the set it was captured on, so whoever keeps a graph keeps that set (buffer_set() after the capture) and
+    binds it (bind_buffer_set()) before every replay: the tensors stay allocated, and the attributes the host reads afterwards (llm.HS,
+    ...) are the replayed shape's.  A set is the dict ``build_buffer_set`` declares: its keys are the attribute names.  What a forward
+    records about a set's contents (``_FWD_FIELDS``, declared beside the fwd_begin that sets them) is taken and bound with it."""
+    _bound = _buf_key = None             # the set whose members are this object's attributes, and its key
 
-    def _track_alloc(self, before: dict):
-        names = getattr(self, "_buf_names", set())
-        self._buf_names = names | {k for k, v in self.__dict__.items() if k != "_buf_names" and (k not in before or before[k] is not v)}
+    def _alloc(self, *key):
+        if self._buf_key != key:
+            self.bind_buffer_set(self.build_buffer_set(*key))
 
-    def buffer_set(self) -> dict:
-        return {k: self.__dict__[k] for k in self._buf_names}
+    def buffer_set(self) -> Optional[dict]:  # the bound set (None: nothing is bound) with the per-forward fields as they stand now
+        if self._bound is not None:
+            self._bound = dict(self._bound, **{k: getattr(self, k) for k in self._FWD_FIELDS if hasattr(self, k)})
+        return self._bound
 
     def bind_buffer_set(self, bufs: dict):
-        self.__dict__.update(bufs)
+        if bufs is not self._bound:          # (an identity check when it is the bound one)
+            self.__dict__.update(bufs)
+            self._bound = bufs
+
+    def unbind(self):                        # nothing is bound: the next _alloc builds a fresh set (holders of the old one keep it alive)
+        self._bound = self._buf_key = None
 
 
 class LLM(_BufferSets):
@@ -425,7 +433,6 @@ class LLM(_BufferSets):
                                     wdT=wd.t().contiguous()))
         self.norm = g("norm.weight")
         self.embed = g("embed_tokens.weight")
-        self._buf_key = None
         self.gu_row0 = 0
         self.per_layer, self.norm_grads = False, False
         self._flin = self._blin = self.lin
@@ -435,34 +442,25 @@ class LLM(_BufferSets):
         G_gu, G_qkv; norm_grads: of the two RMSNorms too, G_n1 / G_n2) in slots of their own - the gradient stream reads them any
         time after the dX chain has moved on (3.4 GB at batch 16)."""
         self.per_layer, self.norm_grads = True, norm_grads
-        self._buf_key = None
+        self.unbind()
 
-    def _alloc(self, B: int, S: int):
-        if self._buf_key == (B, S):
-            return
-        before = dict(self.__dict__)
+    def build_buffer_set(self, B: int, S: int) -> dict:
         c, dev = self.cfg, self.device
         n, M, D = c.n_layers, B * S, c.d
         W = (c.heads + 2 * c.kv_heads) * c.dh
         e = lambda *s, dt=BF16: torch.empty(*s, device=dev, dtype=dt)
         # slots 0..n-1: residual stream entering layer i (slot 0 = inputs_embeds); slot n = FINAL-NORM output
         # (= hidden_states[n] of the HF convention); slot n+1 = raw output of the last layer.
-        self.HS = e(n + 2, B, S, D)
-        self.X1, self.QKV, self.AO = e(n, M, D), e(n, M, W), e(n, M, c.heads * c.dh)
-        self.GU = e(n, M, 2 * c.inter)
-        self.LSE = e(n, B, c.heads, S, dt=torch.float32)
-        self.R1, self.R2, self.RF = e(n, M, dt=torch.float32), e(n, M, dt=torch.float32), e(M, dt=torch.float32)
-        self.nbuf, self.hbuf = e(M, D), e(M, c.inter)
-        self.d_a, self.d_b, self.d_gu, self.d_qkv, self.d_n = e(M, D), e(M, D), e(M, 2 * c.inter), e(M, W), e(M, D)
+        b = dict(HS=e(n + 2, B, S, D), X1=e(n, M, D), QKV=e(n, M, W), AO=e(n, M, c.heads * c.dh), GU=e(n, M, 2 * c.inter),
+                 LSE=e(n, B, c.heads, S, dt=torch.float32), R1=e(n, M, dt=torch.float32), R2=e(n, M, dt=torch.float32), RF=e(M, dt=torch.float32),
+                 nbuf=e(M, D), hbuf=e(M, c.inter), d_a=e(M, D), d_b=e(M, D), d_gu=e(M, 2 * c.inter), d_qkv=e(M, W), d_n=e(M, D))
         if self.per_layer:
-            self.N1, self.N2, self.Hs = e(n, M, D), e(n, M, D), e(n, M, c.inter)
-            self.G_res, self.G_d1, self.G_gu, self.G_qkv = e(n, M, D), e(n, M, D), e(n, M, 2 * c.inter), e(n, M, W)
-            self.d_last = e(M, D)
+            b.update(N1=e(n, M, D), N2=e(n, M, D), Hs=e(n, M, c.inter),
+                     G_res=e(n, M, D), G_d1=e(n, M, D), G_gu=e(n, M, 2 * c.inter), G_qkv=e(n, M, W), d_last=e(M, D))
             if self.norm_grads:
-                self.G_n1, self.G_n2 = e(n, M, D), e(n, M, D)
-        self.cos, self.sin = ops.rope_half_tables(S, c.dh, c.theta, dev)
-        self._buf_key = (B, S)
-        self._track_alloc(before)
+                b.update(G_n1=e(n, M, D), G_n2=e(n, M, D))
+        b["cos"], b["sin"] = ops.rope_half_tables(S, c.dh, c.theta, dev)
+        return dict(b, _buf_key=(B, S))
 
     def out_slot(self, i: int) -> int:
         """HS slot holding the output of layer i (0-based)."""
@@ -481,6 +479,8 @@ class LLM(_BufferSets):
             self.fwd_layer(i)
         if hi == self.cfg.n_layers:
             self.fwd_final()
+
+    _FWD_FIELDS = ("kmask", "B", "S", "gu_row0", "_flin")      # what fwd_begin records about the bound set's contents
 
     def fwd_begin(self, B: int, S: int, kmask_u8: torch.Tensor, keep_from_row: int = 0, lin: Optional[Linear] = None):
         """keep_from_row: the backward of this forward will only visit the rows >= keep_from_row of every sequence
@@ -747,8 +747,6 @@ class Head(_BufferSets):
         self.fc2T = z(D, 64)                       # fc2^T zero-padded to K=64
         self.pfc1_pad = z(D, 64)                   # proprio fc1 weight zero-padded to K=64
         self.dirty = True
-        self._key = None
-        self._prep_key = None    # (B, S, Np, row0) of the last prep_backward()
         self.rope_tab = None     # f32 [max(T, Ka, Kt), dh] cos/sin tables (positions restart per segment: one table serves all)
         # attention weights rounded to bf16 AFTER normalisation, as the reference's bf16 softmax emits them (action_heads.py:397): a second
         # pass over the keys (vla_head_attn_desc.ref_softmax).  Off by default: +N us per block on a chain the step's turn-around waits
@@ -840,56 +838,39 @@ class Head(_BufferSets):
         ops.transpose(P.view("fc2_w"), out=self.fc2T)             # [7, D] -> columns 0..6 of the zero-padded [D, 64]
         self._stale_bwd = False
 
-    def _alloc(self, B: int, Kt: int):
-        if self._key == (B, Kt):
-            return
-        before = dict(self.__dict__)
+    def build_buffer_set(self, B: int, Kt: int) -> dict:
         D, nb, T, dev = self.D, self.nb, self.cfg.chunk, self.device
         Ka = NUM_TOKENS + 1
         e = lambda *s, dt=BF16: torch.empty(*s, device=dev, dtype=dt)
         z = lambda *s, dt=BF16: torch.zeros(*s, device=dev, dtype=dt)
         R = B * T
-        self.Ka, self.Kt, self.R = Ka, Kt, R
-        self.h_adp = e(nb, B, Ka, D)
-        self.KV_adp, self.KV_task = e(nb, B * Ka, 2 * D), e(nb, B * Kt, 2 * D)
-        self.dKV_adp, self.dKV_task = e(nb, B * Ka, 2 * D), e(nb, B * Kt, 2 * D)
-        self.X = e(nb + 1, R, D)                       # block inputs; X[nb] = output of the last block
-        self.QKVx, self.dQKVx = e(nb, R, 3 * D), e(nb, R, 3 * D)
-        self.AOx, self.O2, self.LNo = e(nb, R, D), e(nb, R, D), e(nb, R, D)
-        self.dO2, self.dFF = e(nb, R, D), e(nb, R, D)
-        self.probs = e(nb, B, self.H, T, T + Ka + Kt, dt=torch.float32)
-        self.stats = e(nb, R, 2, dt=torch.float32)
+        b = dict(Ka=Ka, Kt=Kt, R=R, h_adp=e(nb, B, Ka, D),
+                 KV_adp=e(nb, B * Ka, 2 * D), KV_task=e(nb, B * Kt, 2 * D), dKV_adp=e(nb, B * Ka, 2 * D), dKV_task=e(nb, B * Kt, 2 * D),
+                 X=e(nb + 1, R, D),                    # block inputs; X[nb] = output of the last block
+                 QKVx=e(nb, R, 3 * D), dQKVx=e(nb, R, 3 * D), AOx=e(nb, R, D), O2=e(nb, R, D), LNo=e(nb, R, D), dO2=e(nb, R, D), dFF=e(nb, R, D),
+                 probs=e(nb, B, self.H, T, T + Ka + Kt, dt=torch.float32), stats=e(nb, R, 2, dt=torch.float32))
         # fp32 gradient accumulators (bias column sums, LayerNorm dw/db, gate): views of ONE buffer, zeroed by one fill
         bkeys = tuple(k for k in ("b_x", "b_adp", "b_task", "b_o", "b_ffn", "fc1_b", "fc2_b", "p_fc1_b", "p_fc2_b") if k in self.P.offsets)
         shapes = [("dgate", (nb,)), ("ln_dw", (nb, D)), ("ln_db", (nb, D)), ("ln1_dw", (self.Din,)), ("ln1_db", (self.Din,)),
                   ("ln2_dw", (D,)), ("ln2_db", (D,)), ("d_pf", (B, D))] + [("b:" + k, tuple(self.P.offsets[k][1])) for k in bkeys]
-        self.acc32 = z(sum(rup(math.prod(sh), 4) for _, sh in shapes), dt=torch.float32)
+        acc32 = b["acc32"] = z(sum(rup(math.prod(sh), 4) for _, sh in shapes), dt=torch.float32)
         off, views = 0, {}
         for name, sh in shapes:
-            views[name] = self.acc32[off:off + math.prod(sh)].view(sh)
+            views[name] = acc32[off:off + math.prod(sh)].view(sh)
             off += rup(math.prod(sh), 4)
-        self.dgate, self.ln_dw, self.ln_db = views["dgate"], views["ln_dw"], views["ln_db"]
-        self.ln1_dw, self.ln1_db, self.ln2_dw, self.ln2_db = views["ln1_dw"], views["ln1_db"], views["ln2_dw"], views["ln2_db"]
-        self.b_f32 = {k: views["b:" + k] for k in bkeys}
-        self.d_pf32 = views["d_pf"]
-        # gather / scatter row indices of the action-query hidden states (+ proprio slot) and the live-row guard: static buffers
-        # filled by vla_head_index_prep (a captured step replays the kernel on the new batch's mask positions)
-        self.row_idx_ka = torch.empty(B, Ka, device=dev, dtype=torch.int32)
-        self.row_idx_live_ka = torch.empty(B, Ka, device=dev, dtype=torch.int32)
-        self._idx_scratch = torch.empty(B, Ka, device=dev, dtype=torch.int32)
-        self.guard = torch.zeros(1, device=dev, dtype=torch.float32)
-        self.x_in = z(R, self.Din)
-        self.pr_in = z(B, 64)
-        # (the dW products read dY and X as they lie: vla_gemm_bf16_tn contracts over their rows - no transposed operand copies)
-        self.h_task_c = e(nb, B * Kt, D) if Kt % 64 else None      # plumbing sizes only: task rows compacted (row groups need Kt % 64 == 0)
-        self.dfc2 = e(64, D)
-        self.dpfc1 = e(D, 64)                          # proprio fc1 weight gradient against the 64-column padded input (any proprio_dim)
-        self.dh_adp = e(nb, B * Ka, D)
-        self.dpad = z(R, 64)
-        self.rope_tab = ops.rope_inter_tables(max(T, Ka, Kt), D // self.H, dev)
-        self._key = (B, Kt)
-        self._prep_key = None    # (the scatter indices of a backward were those of the buffers just replaced)
-        self._track_alloc(before)
+        b.update({k: views[k] for k in ("dgate", "ln_dw", "ln_db", "ln1_dw", "ln1_db", "ln2_dw", "ln2_db")}, b_f32={k: views["b:" + k] for k in bkeys}, d_pf32=views["d_pf"])
+        i32 = lambda: torch.empty(B, Ka, device=dev, dtype=torch.int32)
+        b.update(
+            # gather / scatter row indices of the action-query hidden states (+ proprio slot) and the live-row guard: static buffers
+            # filled by vla_head_index_prep (a captured step replays the kernel on the new batch's mask positions)
+            row_idx_ka=i32(), row_idx_live_ka=i32(), _idx_scratch=i32(), guard=torch.zeros(1, device=dev, dtype=torch.float32),
+            x_in=z(R, self.Din), pr_in=z(B, 64),
+            # (the dW products read dY and X as they lie: vla_gemm_bf16_tn contracts over their rows - no transposed operand copies)
+            h_task_c=e(nb, B * Kt, D) if Kt % 64 else None,      # plumbing sizes only: task rows compacted (row groups need Kt % 64 == 0)
+            dfc2=e(64, D), dpfc1=e(D, 64),             # (dpfc1: proprio fc1 weight gradient against the 64-column padded input, any proprio_dim)
+            dh_adp=e(nb, B * Ka, D), dpad=z(R, 64), rope_tab=ops.rope_inter_tables(max(T, Ka, Kt), D // self.H, dev),
+            _buf_key=(B, Kt), _prep_key=None)          # (the scatter indices of a backward were those of the buffers just replaced)
+        return b
 
     # ---- forward (action_heads.py:43-81, 111-121, 337-410) -------------------------------------------------
     def forward(self, HS: torch.Tensor, pos1: torch.Tensor, proprio: torch.Tensor, Np: int,
@@ -903,6 +884,8 @@ class Head(_BufferSets):
         for i in range(self.nb):
             self.fwd_layer(i)
         return self.fwd_end()
+
+    _FWD_FIELDS = ("HSref", "Np", "S", "B", "pos1", "_prep_key")      # what fwd_begin / prep_backward record about the bound set
 
     def fwd_begin(self, HS, pos1, proprio, Np, noise=None):
         """Everything that does not depend on the LLM's output: buffers, proprio projector, input stage
@@ -1113,6 +1096,15 @@ class Head(_BufferSets):
 
 
 # ------------------------------------------------------------------------------------------------ whole model
+class Workspace:
+    """What one input shape owns (_BufferSets' rule at engine level): the LLM's buffer set (None: nothing bound), the head's (None: left
+    as it is - generation runs no head), the engine's fields (_vis_bufs: the pairs per (B, Np) that all but generation share)."""
+    FIELDS = ("feats", "patches", "_vis_bufs", "B", "S", "Np", "qidx0", "pos0", "cnt0", "pos1", "cnt1", "_pred_out", "_dHS")
+
+    def __init__(self, llm: Optional[dict] = None, head: Optional[dict] = None, fields: Optional[dict] = None):
+        self.llm, self.head, self.fields = llm, head, fields or dict.fromkeys(self.FIELDS)
+
+
 class VLAEngine(schedule.StepControls):
     """Adapter-only fine-tune step of VLA-Adapter (finetune.py:288-447 + 1039-1082) on one GPU."""
 
@@ -1127,7 +1119,8 @@ class VLAEngine(schedule.StepControls):
         g = lambda k: weights["proj"][k].to(device=device, dtype=BF16).contiguous()
         self.proj = {k: g(k) for k in weights["proj"]}
         self.step_count = 0
-        self._dHS = None
+        self._ws = None
+        self.bind_workspace(Workspace())             # nothing is bound
         # adapter-only fine-tune: the LLM backward only has to cover the rows that can reach `action_queries`
         # (LLM.backward).  VLA_FULL_LLM_BWD=1 / full_llm_backward=True runs the reference-shaped full-sequence backward.
         self.full_llm_backward = bool(int(os.environ.get("VLA_FULL_LLM_BWD", "0")))
@@ -1143,7 +1136,7 @@ class VLAEngine(schedule.StepControls):
         self.side = None           # head stream: the streams are created on first use (_ensure_streams)
         self._vis_bufs = {}        # (feats, patches) per (batch, patches): captured graphs keep their addresses
         self._val_pred = None
-        self._predict_graphs, self._val_graphs = {}, None      # predict(): (graphs, static batch, segments) per input shape; val_step_graphed()
+        self._predict_graphs, self._val_graphs = {}, None      # predict(): dict(graphs, static, segs, ws) per input shape; val_step_graphed()
         self._generate_sets = {}   # generate(): buffers, static batch and the two graphs per (B, L, T, pixel shape)
         self._timeline = None      # a list collects (kind, index, start, end) events of every segment run (tools/*_timeline.py)
         # captured step (capture()): its graphs, the vision graph, events of the vision stage in flight / of its pixel copy, pending update, exchange events
@@ -1184,6 +1177,31 @@ class VLAEngine(schedule.StepControls):
         g, aq_off = self.head.P.grad, self.head.P.offsets["action_queries"][0]
         return [(g, 0, aq_off), (g, aq_off, self.head.P.numel)]
 
+    def workspace(self, head: bool = True) -> Workspace:
+        """The workspace that is bound now: every holder of captured graphs keeps theirs and binds it before a replay."""
+        self._ws = Workspace(self.llm.buffer_set(), self.head.buffer_set() if head else None, {k: getattr(self, k) for k in Workspace.FIELDS})
+        return self._ws
+
+    def bind_workspace(self, ws: Workspace):
+        """The LLM's set, the head's and the engine's fields together; identity checks alone when ``ws`` is still bound (a steady replay)."""
+        if ws is self._ws and ws.llm is self.llm._bound and (ws.head is None or ws.head is self.head._bound):
+            return
+        self.llm.unbind() if ws.llm is None else self.llm.bind_buffer_set(ws.llm)
+        if ws.head is not None:
+            self.head.bind_buffer_set(ws.head)
+        for k, v in ws.fields.items():
+            setattr(self, k, v)
+        self._ws = ws
+
+    @contextlib.contextmanager
+    def bound_workspace(self, ws: Workspace):
+        """``ws`` for the duration of a call; what was bound before is bound after."""
+        prev = self.workspace()
+        try:
+            yield self.bind_workspace(ws)
+        finally:
+            self.bind_workspace(prev)
+
     def forward(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None, for_training: bool = False):
         """VLM forward + action head (finetune.py:336-411) -> predicted actions [B, chunk, 7]."""
         self.forward_vlm(batch, for_training)
@@ -1198,11 +1216,10 @@ class VLAEngine(schedule.StepControls):
         hipGraph captured on first use of an input shape and replayed on static input buffers afterwards.
 
         B > 1 (a serving batch: right-padded rows, every sample's 64 action rows found from its labels by the mask / splice /
-        head-index kernels, attention masking the padding): one cache entry - graphs, static inputs and the LLM's and the head's
-        activation buffers - per (B, L, pixel shape).  The activation buffers are one set per shape and a graph holds the addresses
-        of the set it was captured on, so every entry keeps its set and rebinds it before a replay: calls of different shapes may
-        alternate, and llm.HS read after a call is that call's.  The cache therefore grows by one such set per shape served
-        (DESIGN, "Serving a batch"); callers bound the number of shapes by rounding L (input_stage.serve_layout).
+        head-index kernels, attention masking the padding): one cache entry - dict(graphs, static inputs, segs, ws: the workspace they
+        were captured on, _BufferSets' rule) - per (B, L, pixel shape).  The workspace is bound before the replay and stays bound: calls
+        of different shapes may alternate, and llm.HS read after a call is that call's.  The cache therefore grows by one workspace per
+        shape served (DESIGN, "Serving a batch"); callers bound the number of shapes by rounding L (input_stage.serve_layout).
 
         latency_hint: capture under ops.latency_hint() - kernel variants for sub-chip launches on an idle chip (deep-ring GEMMs,
         short-M skinny tiles, uneven split-K, key-split attention), baked into the graphs.  Default (None): at B == 1 only, where it
@@ -1224,14 +1241,9 @@ class VLAEngine(schedule.StepControls):
                 segs = self._predict_segments(static)
                 graphs = schedule.capture(segs, {}, self._cap_stream)
             torch.cuda.synchronize()
-            bound = dict(llm=self.llm.buffer_set(), head=self.head.buffer_set(),
-                         eng={k: getattr(self, k) for k in ("B", "S", "Np", "feats", "patches", "qidx0", "pos0", "cnt0", "pos1", "cnt1", "_pred_out")},
-                         hint=hint)
-            cache[key] = (graphs, static, segs, bound)
-        graphs, static, segs, bound = cache[key]
-        self.llm.bind_buffer_set(bound["llm"])
-        self.head.bind_buffer_set(bound["head"])
-        self.__dict__.update(bound["eng"])
+            cache[key] = dict(graphs=graphs, static=static, segs=segs, ws=self.workspace())
+        graphs, static, segs, ws = cache[key].values()
+        self.bind_workspace(ws)                  # stays bound: callers read llm.HS and the returned tensor
         for k, v in batch.items():
             static[k].copy_(v)
         self.head.refresh_forward_operands()     # parameters may have changed since the capture (no-op when fresh)
@@ -1264,9 +1276,6 @@ class VLAEngine(schedule.StepControls):
                                                 wait=[sg.signal for sg in segs], signal=("end", 0))
 
     # ---- greedy decoding of action tokens (prismatic/models/vlas/openvla.py:81-94: `generate`, do_sample off) ---------------------------
-    _GEN_SCOPE = ("B", "S", "Np", "feats", "patches", "qidx0", "_vis_bufs")
-    _GEN_LLM_SCOPE = ("kmask", "B", "S", "gu_row0", "_flin")
-
     def generate(self, batch: Dict[str, torch.Tensor], max_new_tokens: int, return_logits: bool = False):
         """Greedy decoding of T = max_new_tokens tokens behind B right-padded prompts of different lengths -> int64 [B, T] on the
         device, no host synchronisation.  batch: input_ids int64 [B, L], attention_mask [B, L], pixel_values, and from
@@ -1279,8 +1288,8 @@ class VLAEngine(schedule.StepControls):
         Captured by default: one prefill graph and ONE step graph per (B, L, T, pixel shape), the step graph replayed T - 1 times
         (positions and the step index live in device memory).  VLA_PREDICT_EAGER=1 runs both parts eagerly; return_logits (eager
         only) also returns the bf16 logits the argmax compared, [B, T, V].
-        Generation owns its buffers - LLM activations, vision features, cache - and rebinds what was bound before it returns: the
-        buffers a captured predict() or training graph holds are not written."""
+        Generation owns its workspace - LLM activations, vision features; no head - and runs inside bound_workspace(): what was bound
+        before is bound after, and the buffers a captured predict() or training graph holds are not written."""
         T = int(max_new_tokens)
         if T < 1:
             raise ValueError(f"generate: max_new_tokens must be at least 1, got {max_new_tokens}")
@@ -1295,16 +1304,10 @@ class VLAEngine(schedule.StepControls):
             if k not in batch or batch[k].dtype != torch.int32 or batch[k].numel() != B:
                 raise ValueError(f"generate: batch[{k!r}] must be the int32 [{B}] vector of ops.decode_prompt")
         key = (B, L, T, tuple(px.shape), px.dtype, eager)
-        llm = self.llm
-        saved = {k: self.__dict__[k] for k in self._GEN_SCOPE if k in self.__dict__}
-        saved_llm = {k: llm.__dict__[k] for k in self._GEN_LLM_SCOPE if k in llm.__dict__}
-        saved_set = llm.buffer_set() if hasattr(llm, "_buf_names") else None
-        try:
-            ent = self._generate_sets.get(key)
+        ent = self._generate_sets.get(key)
+        with self.bound_workspace(Workspace() if ent is None else ent["ws"]):
             if ent is None:
                 ent = self._generate_sets[key] = self._generate_build(batch, T, eager)
-            llm.bind_buffer_set(ent["llm"])
-            self._vis_bufs = ent["vis"]
             static, st = ent["static"], ent["state"]
             for k, v in static.items():
                 v.copy_(batch[k])
@@ -1318,13 +1321,6 @@ class VLAEngine(schedule.StepControls):
                 for _ in range(T - 1):
                     ent["step"].replay()
             out = st["out_ids"].clone()
-        finally:
-            self.__dict__.update(saved)
-            llm.__dict__.update(saved_llm)
-            if saved_set is not None:
-                llm.bind_buffer_set(saved_set)
-            else:
-                llm._buf_key = None                  # nothing was bound before: the next forward allocates its own set
         return (out, logits) if return_logits else out
 
     # Kernel selection is part of the arithmetic (ops.latency_hint: the short-M tiles and the uneven split-K associate the fp32 sums
@@ -1341,17 +1337,17 @@ class VLAEngine(schedule.StepControls):
             self.llm.decode_step(st, logits_t)
 
     def _generate_build(self, batch, T: int, eager: bool) -> dict:
-        """The cache entry of one generate() shape: a set of LLM activation buffers and vision buffers of its own (a fresh
-        allocation, whatever is bound), the decode state, static inputs, and - unless eager - the prefill graph and the step graph,
+        """The cache entry of one generate() shape: a workspace of its own (a fresh allocation, whatever is bound; the caller puts
+        the previous one back), the decode state, static inputs, and - unless eager - the prefill graph and the step graph,
         captured on one stream behind two eager warm-up runs (every kernel launched and its LDS attribute set before the capture)."""
         llm = self.llm
         B, L = batch["input_ids"].shape
         static = {k: batch[k].clone() for k in ("input_ids", "attention_mask", "pixel_values", "pos", "last_row")}
         self._vis_bufs = {}
-        llm._buf_key = None
-        self._vision_begin(static)                   # allocates the set this entry keeps
+        llm.unbind()
+        self._vision_begin(static)                   # allocates the workspace this entry keeps
         st = llm.decode_alloc(B, self.S, T)
-        ent = dict(static=static, state=st, llm=llm.buffer_set(), vis=self._vis_bufs)
+        ent = dict(static=static, state=st, ws=self.workspace(head=False))
         if eager:
             return ent
         self._ensure_streams()
@@ -1412,6 +1408,7 @@ class VLAEngine(schedule.StepControls):
         cfg = self.cfg
         B, L = batch["input_ids"].shape
         Np = cfg.n_patches
+        self._ws = None                              # (the fields below change: no workspace is known to be bound)
         self.llm._alloc(B, L + Np)
         bufs = self._vis_bufs
         if (B, Np) not in bufs:
@@ -1665,6 +1662,7 @@ class VLAEngine(schedule.StepControls):
         self._segs = self._segments(batch, noise)
         self._graphs = schedule.capture(self._segs, {}, self._cap_stream)
         torch.cuda.synchronize()
+        self._step_ws = self.workspace()             # kept for the graphs' lifetime, bound before every replay
         self._pending_lr = None
         # the vision stage of step k+1 starts behind this forward segment of step k: it runs under the backward, whose two
         # dependent kernel chains leave most CUs idle.  Default: the third-last forward segment (the last two hold one LLM
@@ -1718,8 +1716,9 @@ class VLAEngine(schedule.StepControls):
         AdamW) is left pending and applied inside the next call, after that step's vision graph - or by flush()."""
         cur = torch.cuda.current_stream()
         self.executed_steps += 1
+        self.bind_workspace(self._step_ws)
         self.flush(join=False)
-        cur.wait_event(self._vis_ev)           # patches of THIS step (computed during the previous call)
+        cur.wait_event(self._vis_ev)          # patches of THIS step (computed during the previous call)
         def after(k, seg, ev):
             if k == self._vis_after:
                 self._launch_vision(ev)
@@ -1846,9 +1845,10 @@ class VLAEngine(schedule.StepControls):
 
         def make():
             segs = self._predict_segments(batch, noise, loss_of=batch["actions"])
-            return schedule.capture(segs, {}, self._cap_stream), segs
+            return schedule.capture(segs, {}, self._cap_stream), segs, self.workspace()
 
-        def replay(graphs, segs):
+        def replay(graphs, segs, ws):
+            self.bind_workspace(ws)
             self.head.refresh_forward_operands()
             torch.cuda.current_stream().wait_event(schedule.run(segs, self._stream_of, graphs)[("end", 0)])
         return schedule.captured_validation(self, batch, noise, make, replay)

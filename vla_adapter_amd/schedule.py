@@ -318,8 +318,8 @@ class StepControls:
 
 def captured_validation(model, batch, noise, make, replay):
     """val_step_graphed of an engine / trainer: on the first call two eager model.val_forward() (every buffer allocated and
-    kernel attribute set outside the capture), then make() -> (graphs, segs), timed into model.val_capture_seconds and kept;
-    every call replay(graphs, segs) -> model._val_loss3.  The graphs write the loss and the prediction (model._val_pred) of the
+    kernel attribute set outside the capture), then make() -> (graphs, segs, the workspace they were captured on), timed into
+    model.val_capture_seconds and kept; every call replay(graphs, segs, workspace) -> model._val_loss3.  The graphs write the loss and the prediction (model._val_pred) of the
     capture; an eager val_forward in between rebinds both names, so every replay binds them back to the captured tensors."""
     if model._val_graphs is None:
         for _ in range(2):

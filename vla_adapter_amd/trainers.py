@@ -872,6 +872,7 @@ class BackboneTrainer(E.Linear, schedule.StepControls):
         self.head.dirty = True                       # the head's own W^T / padded-operand refresh becomes part of its graphs
         self._segs = self._segments(batch, noise, 1.0 / self.ga)
         self._graphs, caps, pools = self._capture(self._segs)
+        self._step_ws = self.eng.workspace()         # kept for the graphs' lifetime, bound before every replay
         self._seg_ranges = [r for sg in self._segs for r in (sg.ranges or [])]
         if self.ga == 1 and self._clip is not None:  # the norm's slots of the captured schedule: reserved and checked here, once
             self._clip_begin(self._seg_ranges)
@@ -902,6 +903,7 @@ class BackboneTrainer(E.Linear, schedule.StepControls):
         torch.cuda.synchronize()
 
     def train_step_graphed(self, lr: float):
+        self.eng.bind_workspace(self._step_ws)
         return self._step(self._segs, self._graphs, lr)
 
     # ---- validation pass (vla-scripts/finetune.py:605-685: vla.eval(), torch.no_grad()) --------------------------------------
@@ -949,8 +951,12 @@ class BackboneTrainer(E.Linear, schedule.StepControls):
         def make():
             with self._eval_mode():
                 segs = self._val_segments(batch, noise)
-                return self._capture(segs)[0], segs
-        return schedule.captured_validation(self, batch, noise, make, lambda graphs, segs: self._run(segs, graphs, exchange=False))
+                return self._capture(segs)[0], segs, self.eng.workspace()
+
+        def replay(graphs, segs, ws):
+            self.eng.bind_workspace(ws)
+            self._run(segs, graphs, exchange=False)
+        return schedule.captured_validation(self, batch, noise, make, replay)
 
     def _after_update(self, refresh: bool):
         if self.eng.reducer is not None:
