@@ -721,7 +721,8 @@ def test_gemm_split_k_matches_single_pass(ops, M, N, K, act, res, monkeypatch):
     kw = dict(bias=bias.to(DEV), act=act, residual=r.to(DEV) if res else None)
     out = torch.empty(M, N, dtype=BF, device=DEV)
     ops.gemm_nt(a.to(DEV), w.to(DEV), out=out, **kw)
-    assert (torch.cuda.current_stream().cuda_stream, str(out.device)) in ops._SPLITK_WS, "the split-K path must have run"
+    from vla_adapter_amd.scratch import ARENA
+    assert (torch.cuda.current_stream().cuda_stream, str(out.device)) in ARENA.buffers, "the split-K path must have run"
     monkeypatch.setenv("VLA_NO_SPLITK", "1")
     ref = torch.empty(M, N, dtype=BF, device=DEV)
     ops.gemm_nt(a.to(DEV), w.to(DEV), out=ref, **kw)

@@ -29,6 +29,7 @@ from tests import accuracy as A
 from tests.arena import Arena, assert_bits_equal, default_poison
 from vla_adapter_amd import native as N
 from vla_adapter_amd import ops
+from vla_adapter_amd.scratch import ARENA
 
 DEV = "cuda"
 BF, F32, U8, I32, I64, F64 = torch.bfloat16, torch.float32, torch.uint8, torch.int32, torch.int64, torch.float64
@@ -301,7 +302,7 @@ def test_gemm_nt(kernel, feature, monkeypatch):
             kw["split_k"], kw["act"] = 2, ops.ACT_GELU
             out = mk.out((M, Nn4), BF, (ld_of(Nn4) + 8, 1))
             ws = mk.out((2, M, Nn4), F32, name="workspace [split, M, N]")     # changes only inside [split, M, N]
-            monkeypatch.setattr(ops, "_splitk_ws", lambda numel, device: ws.view(-1))
+            monkeypatch.setattr(ARENA, "get", lambda nbytes, device: ws.view(-1).view(U8))
         elif feature == "swiglu_bwd":
             I = 128                                          # the product is dH [M, I]; R = GU [M, 2I], C = dGU [M, 2I]
             A_, B_ = mk.inp(a, st2(M, K)), mk.inp(gen(I, K, seed=2, scale=0.05), st2(I, K))
@@ -406,8 +407,7 @@ def test_gemm_tn(tile, form, monkeypatch):
             a, b = mk.inp(gen(Ms, N1, seed=21), st2(Ms, N1)), mk.inp(gen(Ms, N2, seed=22), st2(Ms, N2))
             out = mk.out((N1, N2), BF, (N2 + 4, 1), align=8)
             ws = mk.out((1, 2, N1, N2), F32, name="workspace [batch, split, N1, N2]")
-            key = (torch.cuda.current_stream().cuda_stream, str(a.device))
-            monkeypatch.setitem(ops._TN_WS, key, ws.view(-1))
+            monkeypatch.setattr(ARENA, "get", lambda nbytes, device: ws.view(-1).view(U8))
             ops.gemm_tn(a, b, out=out, split=2)
         return {"C": out}
 
@@ -773,7 +773,7 @@ def test_head_attention(path, rope, monkeypatch):
             cos, sin = ops.rope_inter_tables(max(T, Ka, Kt), dh, "cpu")
             rp = (mk.inp(cos, name="cos"), mk.inp(sin, name="sin"))
         ws = mk.out((wsn,), F32, name="workspace")
-        monkeypatch.setattr(ops, "_splitk_ws", lambda numel, device: ws)
+        monkeypatch.setattr(ARENA, "get", lambda nbytes, device: ws.view(U8))
         ops.head_attn_bwd(dout, out, q, ks, vs, ka, va, kt, vt, gate, probs, dgate, dq, dks, dvs, dka, dva, dkt, dvt, H=H, rope=rp)
         return {"out": out, "dq": dq, "dks": dks, "dvs": dvs, "dka": dka, "dva": dva, "dkt": dkt, "dvt": dvt, "dgate": dgate}
 

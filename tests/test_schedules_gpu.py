@@ -176,10 +176,12 @@ def test_trainer_schedule_equals_the_serial_step(geom, mode, sched, B, monkeypat
 def test_trainer_scratch_has_one_owner_stream(mode, monkeypatch):
     """Timing-independent race check on the twin geometry with every stream on: during an eager step, and while the step is
     captured, every buffer of LoRAFinetune's per-shape scratch (_qscratch: fp8 row codes / scales, _uscratch: lora_dropout's u / h),
-    the norm -> quantise hand-over (_xq) and the per-stream split-K / head-backward workspace (ops._splitk_ws) is used from ONE stream
-    only.  The only cross-stream edges inside a step are the segment events, and none of them orders two uses of one of these
-    buffers - so a second stream is a race, whether or not the streams happened to overlap."""
-    from vla_adapter_amd import ops
+    the norm -> quantise hand-over (_xq) and the per-stream kernel scratch (scratch.ARENA.get: split-K and TN planes, head-backward
+    partials, digest sums) is used from ONE stream only.  The only cross-stream edges inside a step are the segment events, and none
+    of them orders two uses of one of these buffers - so a second stream is a race, whether or not the streams happened to overlap.
+    The capture allocates no scratch: every capture stream's buffer was reserved before its capture began (the arena's
+    under-capture counter does not move)."""
+    from vla_adapter_amd.scratch import ARENA
     _env(monkeypatch, {})
     cfg = _cfg("twin")
     batch = _batch(cfg, 2)
@@ -199,7 +201,7 @@ def test_trainer_scratch_has_one_owner_stream(mode, monkeypatch):
         for t in tensors:
             uses.setdefault(ph, {}).setdefault((what, t.data_ptr()), set()).add(where)
 
-    q0, u0, quant0, ws0, run0 = tr._qscratch, tr._uscratch, tr._quant, ops._splitk_ws, tr._run
+    q0, u0, quant0, ws0, run0 = tr._qscratch, tr._uscratch, tr._quant, ARENA.get, tr._run
 
     def qscratch(rows, cols, slot):
         b = q0(rows, cols, slot)
@@ -218,9 +220,9 @@ def test_trainer_scratch_has_one_owner_stream(mode, monkeypatch):
             record("_xq", out)
         return out
 
-    def splitk_ws(numel, device):
-        ws = ws0(numel, device)
-        record("_splitk_ws", (ws,))
+    def scratch(nbytes, device):
+        ws = ws0(nbytes, device)
+        record("scratch", (ws,))
         return ws
 
     def run(*a, **k):
@@ -229,14 +231,16 @@ def test_trainer_scratch_has_one_owner_stream(mode, monkeypatch):
     monkeypatch.setattr(tr, "_qscratch", qscratch)
     monkeypatch.setattr(tr, "_uscratch", uscratch)
     monkeypatch.setattr(tr, "_quant", quant)
-    monkeypatch.setattr(ops, "_splitk_ws", splitk_ws)
+    monkeypatch.setattr(ARENA, "get", scratch)
     monkeypatch.setattr(tr, "_run", run)
     tr.train_step(batch, LR)
+    under_capture = ARENA.under_capture
     tr.capture(batch, None)
+    assert ARENA.under_capture == under_capture, "scratch was allocated while the step was captured"
     tr.train_step_graphed(LR)
     torch.cuda.synchronize()
     kinds = {w for ph in uses.values() for (w, _) in ph}
-    want = {"_qscratch", "_xq", "_splitk_ws"} if mode == "lora_fp8" else {"_uscratch", "_splitk_ws"}
+    want = {"_qscratch", "_xq", "scratch"} if mode == "lora_fp8" else {"_uscratch", "scratch"}
     assert want <= kinds, (want, kinds)
     assert "capture" in uses and len(uses) >= 2, sorted(uses)
     shared = [(ph, w, len(s)) for ph, d in uses.items() for (w, _), s in d.items() if len(s) > 1]

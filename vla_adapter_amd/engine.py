@@ -1224,8 +1224,8 @@ class VLAEngine(schedule.StepControls):
         latency_hint: capture under ops.latency_hint() - kernel variants for sub-chip launches on an idle chip (deep-ring GEMMs,
         short-M skinny tiles, uneven split-K, key-split attention), baked into the graphs.  Default (None): at B == 1 only, where it
         was measured; the setting is part of the cache key.  The warm-up always runs under the same
-        setting as the capture, so that every kernel the graphs use has been launched, its LDS attribute set and its split-K
-        workspace allocated before the capture."""
+        setting as the capture, so that every kernel the graphs use has been launched and its LDS attribute set before the capture,
+        and the capture streams' scratch is reserved at the size the warm-up asked for (schedule.graph_capture, scratch.ARENA)."""
         hint = batch["input_ids"].shape[0] == 1 if latency_hint is None else bool(latency_hint)
         key = (tuple(batch["input_ids"].shape), tuple(batch["pixel_values"].shape), batch["pixel_values"].dtype, hint)
         cache = self._predict_graphs
@@ -1648,7 +1648,7 @@ class VLAEngine(schedule.StepControls):
         if row0 is not None:
             assert 0 <= int(row0) < self.S and int(row0) % 32 == 0, f"row0 {row0}: a multiple of 32 inside the sequence"
             self._row0 = int(row0)
-        for _ in range(warmup):                      # allocate every buffer / set kernel attributes outside capture
+        for _ in range(warmup):                      # allocate every buffer / set kernel attributes outside capture (kernel scratch: graph_capture reserves it)
             self.head.dirty = True
             self._fwd_bwd(batch, noise)
         torch.cuda.synchronize()

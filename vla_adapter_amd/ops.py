@@ -13,6 +13,7 @@ import torch
 
 from . import native as N
 from .native import ACT_GELU, ACT_GELU_TANH, ACT_NONE, ACT_RELU, ACT_SWIGLU, ACT_SWIGLU_BWD  # noqa: F401
+from .scratch import ARENA
 
 BF16 = torch.bfloat16
 
@@ -121,7 +122,7 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, *, bias=None, residual=None, res_m
     if split_k is None and not batched and K >= 2048:    # (shorter contractions and batched products never split)
         split_k = _nt_plan(d)[1]
     if split_k and split_k > 1:
-        d.split_k, d.ws = split_k, _splitk_ws(split_k * M * Nn, a.device).data_ptr()
+        d.split_k, d.ws = split_k, _scratch_f32(split_k * M * Nn, a.device).data_ptr()
     if query_plan or query_256:
         plan = _nt_plan(d)
         return plan if query_plan else plan[0] == N.KERNEL_NT_256
@@ -159,16 +160,9 @@ class latency_hint:
         return False
 
 
-_SPLITK_WS = {}
-
-
-def _splitk_ws(numel: int, device) -> torch.Tensor:
-    """fp32 workspace of the CURRENT stream (streams overlap, so each has its own)."""
-    key = (torch.cuda.current_stream().cuda_stream, str(device))
-    ws = _SPLITK_WS.get(key)
-    if ws is None or ws.numel() < numel:
-        ws = _SPLITK_WS[key] = torch.empty(max(numel, 8 << 20), device=device, dtype=torch.float32)
-    return ws
+def _scratch_f32(numel: int, device) -> torch.Tensor:
+    """The current stream's scratch (scratch.ARENA) as floats: at least ``numel`` of them."""
+    return ARENA.get(4 * numel, device).view(torch.float32)
 
 
 def gemm_swiglu_bwd(d: torch.Tensor, w_downT: torch.Tensor, gu: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -209,9 +203,6 @@ def gemm_swiglu_bwd(d: torch.Tensor, w_downT: torch.Tensor, gu: torch.Tensor, ou
         return _nt_plan(desc)
     N.check(_lib().vla_gemm_bf16_nt(_st(), C.byref(desc)), "gemm_bf16_nt(swiglu_bwd)")
     return out
-
-
-_TN_WS = {}
 
 
 def gemm_tn(a: torch.Tensor, b: torch.Tensor, *, out: Optional[torch.Tensor] = None, alpha: float = 1.0, accumulate: bool = False,
@@ -256,12 +247,7 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, *, out: Optional[torch.Tensor] = N
         N.check(min(_lib().vla_gemm_tn_plan(C.byref(d), 0, C.byref(split_c)), 0), "gemm_tn_plan")
         split = split_c.value
     if split and split > 1:
-        key = (torch.cuda.current_stream().cuda_stream, str(a.device))
-        need = nb * split * N1 * N2
-        ws = _TN_WS.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _TN_WS[key] = torch.empty(max(need, 4 << 20), device=a.device, dtype=torch.float32)
-        d.split, d.ws = split, ws.data_ptr()
+        d.split, d.ws = split, _scratch_f32(nb * split * N1 * N2, a.device).data_ptr()
     N.check(_lib().vla_gemm_bf16_tn(_st(), C.byref(d)), "gemm_bf16_tn")
     return out
 
@@ -672,7 +658,7 @@ def head_attn_bwd(dout, out, q, ks, vs, ka, va, kt, vt, gate, probs, dgate_f32, 
         assert rope[0].shape[0] >= max(q.shape[1], ka.shape[1], kt.shape[1]) and rope[0].shape[1] == d.dh
         d.rope_cos, d.rope_sin = rope[0].data_ptr(), rope[1].data_ptr()
     ntile = (d.T + d.Ka + d.Kt + 31) // 32
-    ws = _splitk_ws(d.B * d.H * ntile * (d.T * d.dh + 1), q.device)
+    ws = _scratch_f32(d.B * d.H * ntile * (d.T * d.dh + 1), q.device)
     d.ws, d.ws_floats = ws.data_ptr(), ws.numel()
     N.check(_lib().vla_head_attn_bwd(_st(), C.byref(d)), "head_attn_bwd")
 
@@ -1192,14 +1178,11 @@ def heldout_l1_accumulate(pred: torch.Tensor, target: torch.Tensor, ds: Optional
 
 
 # ---- state digest (include/vla_digest.h, csrc/digest.hip) ---------------------------------------------------------------------------
-_DIGEST_SCRATCH = {}
-
-
 def state_digest(t: torch.Tensor, salt: int = 0, out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """vla_state_digest: the position-weighted 64-bit digest of the contiguous tensor ``t`` of 16-bit elements (bf16,
     fp16, int16) -> int64 [1] on t's device holding the u64's bits (``out``: given, 8-byte aligned).  Launched on the current stream;
-    nothing synchronises - digest_value() reads it.  ``scratch``: int64 [>= 1] for the workgroups' partial sums; by default one buffer
-    per device, so that calls sharing it must be ordered on one stream."""
+    nothing synchronises - digest_value() reads it.  ``scratch``: int64 [>= 1] for the workgroups' partial sums; by default the current
+    stream's scratch (scratch.ARENA)."""
     assert t.is_cuda and t.element_size() == 2 and t.is_contiguous(), f"state_digest: a contiguous CUDA tensor of 16-bit elements, got {t.dtype} {t.device}"
     n = t.numel()
     if n == 0:
@@ -1208,9 +1191,8 @@ def state_digest(t: torch.Tensor, salt: int = 0, out: Optional[torch.Tensor] = N
         out = torch.empty(1, device=t.device, dtype=torch.int64)
     assert out.dtype == torch.int64 and out.numel() == 1 and out.device == t.device, "state_digest: out is int64 [1] on t's device"
     if scratch is None:
-        scratch = _DIGEST_SCRATCH.get(t.device)
-        if scratch is None:
-            scratch = _DIGEST_SCRATCH[t.device] = torch.empty(_lib().vla_state_digest_slots(), device=t.device, dtype=torch.int64)
+        slots = _lib().vla_state_digest_slots()
+        scratch = ARENA.get(8 * slots, t.device).view(torch.int64)[:slots]
     assert scratch.dtype == torch.int64 and scratch.is_contiguous() and scratch.device == t.device and scratch.numel() >= 1
     N.check(_lib().vla_state_digest(_st(), _p(t), n, int(salt) & (2 ** 64 - 1), _p(scratch), scratch.numel(), _p(out)), "state_digest")
     return out

@@ -21,6 +21,8 @@ from typing import Any, Callable, List, NamedTuple, Optional, Tuple
 
 import torch
 
+from .scratch import ARENA
+
 
 class Segment(NamedTuple):
     """stream: kind of the segment's stream ("M": the caller's); fn: its call, or None; wait: None, one event key or a list of
@@ -336,15 +338,18 @@ def captured_validation(model, batch, noise, make, replay):
 
 
 @contextlib.contextmanager
-def graph_capture(g, **kw):
-    """``torch.cuda.graph(g, **kw)`` with Python's cyclic garbage collector paused for the capture.  A dead reference cycle (an
+def graph_capture(g, *, stream, **kw):
+    """``torch.cuda.graph(g, stream=stream, **kw)``: the one place this package enters a capture.  The kernels' scratch of ``stream``
+    is reserved first (scratch.ARENA.reserve: allocated outside the capture, at the size the warm-up needed, and kept from then on),
+    and Python's cyclic garbage collector is paused for the capture.  A dead reference cycle (an
     earlier engine / trainer with its graphs, events and memory pools) collected in the middle of a capture runs destructors
     (hipEventDestroy, hipGraphExecDestroy, frees of a graph pool) that this thread may not call while it captures: the runtime
     refuses, the destructor cannot raise, and the process aborts.  Paused, such cycles are collected after the capture."""
+    ARENA.reserve(stream)
     was = gc.isenabled()
     gc.disable()
     try:
-        with torch.cuda.graph(g, **kw):
+        with torch.cuda.graph(g, stream=stream, **kw):
             yield
     finally:
         if was:

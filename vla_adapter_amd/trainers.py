@@ -865,7 +865,7 @@ class BackboneTrainer(E.Linear, schedule.StepControls):
         multi-rank step run underneath the remaining backward exactly as in the eager step (collectives themselves are not
         captured).  AdamW stays outside (host-side bias corrections); the derived-operand rebuild is a last small graph.  A step is
         3000-5000 launches: issued from Python they cost more host time than GPU time."""
-        for _ in range(warmup):                      # allocate every buffer / set kernel attributes outside the capture
+        for _ in range(warmup):                      # allocate every buffer / set kernel attributes outside the capture (kernel scratch: graph_capture reserves it)
             self.head.dirty = True
             self._run(self._segments(batch, noise, 1.0 / self.ga), exchange=False)
         torch.cuda.synchronize()
