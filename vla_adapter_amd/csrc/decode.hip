@@ -8,6 +8,7 @@
 // output element is written by one thread and every reduction has a fixed order.
 #include "gemm_epilogue.h"
 #include "argmax_order.h"
+#include "decode_advance.h"
 #include "../../include/vla_decode.h"
 #include <limits.h>
 
@@ -292,7 +293,7 @@ lm_head_finish_kernel(const float* __restrict__ part_val, const int* __restrict_
   __shared__ float red_v[DEC_THREADS / 64];
   __shared__ int red_i[DEC_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int t = (out_ids && !pos_from) ? *step : 0;    // (read by every thread before thread 0 advances it behind the last barrier)
+  const int t = decode_step_index(out_ids, pos_from, step);   // (read by every thread before thread 0 advances it behind the last barrier)
   for (int b = 0; b < B; ++b) {
     float bv = -__builtin_inff();
     int bi = INT_MAX;
@@ -317,21 +318,11 @@ lm_head_finish_kernel(const float* __restrict__ part_val, const int* __restrict_
     for (int k = 1; k < DEC_THREADS / 64; ++k)
       if (argmax_before(red_v[k], red_i[k], bv, bi)) { bv = red_v[k]; bi = red_i[k]; }
     bi = min(max(bi, 0), V - 1);                       // (every slab holds a row: bi is one already)
-    if (tid == 0) {
-      id[b] = bi;
-      if (out_ids && t >= 0 && t < T) out_ids[(long long)b * T + t] = bi;
-    }
-    if (out_ids) {
-      const uint4* src = reinterpret_cast<const uint4*>(embed + (long long)min(bi, vocab_e - 1) * ld_embed);
-      uint4* dst = reinterpret_cast<uint4*>(x_next + (long long)b * ld_next);
-      for (int c = tid; c < D / 8; c += DEC_THREADS) dst[c] = src[c];
-    }
+    if (tid == 0) id[b] = bi;
+    if (out_ids) decode_advance_row(b, bi, t, tid, DEC_THREADS, out_ids, T, embed, vocab_e, ld_embed, x_next, ld_next, D);
     __syncthreads();                                   // red_v / red_i are reused by the next sample
   }
-  if (out_ids) {
-    for (int b = tid; b < B; b += DEC_THREADS) pos[b] = (pos_from ? pos_from[b] : pos[b]) + 1;
-    if (tid == 0) *step = t + 1;
-  }
+  if (out_ids) decode_advance_counters(B, t, tid, DEC_THREADS, step, pos, pos_from);
 }
 
 inline unsigned grid_for(long long n) {

@@ -536,21 +536,39 @@ class LLM(_BufferSets):
                     self.R2[i], attend, c_live=(S, self.gu_row0) if self.gu_row0 else None)
 
     # ---- greedy decoding with a key/value cache (VLAEngine.generate; include/vla_decode.h) ------------------------------------------
-    def decode_alloc(self, B: int, S: int, T: int) -> dict:
+    def decode_alloc(self, B: int, S: int, T: int, sample: bool = False) -> dict:
         """Everything T cached single-token steps behind a prefill of S rows own: the cache K / V [n, B, S_cap, KV dh] with
         S_cap = S + T, the RoPE tables at that capacity (the values of a position do not depend on the table's length), the M = B
-        activations of a step, the per-row positions, the device step counter and the tokens."""
+        activations of a step, the per-row positions, the device step counter and the tokens.  sample: also what the sampler of
+        include/vla_sample.h works on - the step's logits bf16 [B, V], the log-probabilities f32 [B, T], the parameter block and the
+        stream id of every row (row b draws from stream b until the caller says otherwise)."""
         c, dev = self.cfg, self.device
         n, D, kvw = c.n_layers, c.d, c.kv_heads * c.dh
         W = getattr(self, "lm_head", None)
         W = self.embed if W is None else W
         e = lambda *s, dt=BF16: torch.empty(*s, device=dev, dtype=dt)
         cos, sin = ops.rope_half_tables(S + T, c.dh, c.theta, dev)
-        return dict(B=B, S=S, T=T, S_cap=S + T, W=W, cos=cos, sin=sin, K=e(n, B, S + T, kvw), V=e(n, B, S + T, kvw),
-                    X=e(n + 1, B, D), X1=e(B, D), NB=e(B, D), NF=e(B, D), QKV=e(B, (c.heads + 2 * c.kv_heads) * c.dh), AO=e(B, c.heads * c.dh),
-                    GU=e(B, 2 * c.inter), H=e(B, c.inter), R=e(3, rup(B, 4), dt=torch.float32)[:, :B], XG=e(B, D),
-                    pos=torch.zeros(B, device=dev, dtype=torch.int32), step=torch.zeros(1, device=dev, dtype=torch.int32),
-                    ids=e(B, dt=torch.int64), out_ids=torch.zeros(B, T, device=dev, dtype=torch.int64), ws=ops.decode_argmax_workspace(B, W.shape[0], dev))
+        st = dict(B=B, S=S, T=T, S_cap=S + T, W=W, cos=cos, sin=sin, K=e(n, B, S + T, kvw), V=e(n, B, S + T, kvw),
+                  X=e(n + 1, B, D), X1=e(B, D), NB=e(B, D), NF=e(B, D), QKV=e(B, (c.heads + 2 * c.kv_heads) * c.dh), AO=e(B, c.heads * c.dh),
+                  GU=e(B, 2 * c.inter), H=e(B, c.inter), R=e(3, rup(B, 4), dt=torch.float32)[:, :B], XG=e(B, D),
+                  pos=torch.zeros(B, device=dev, dtype=torch.int32), step=torch.zeros(1, device=dev, dtype=torch.int32),
+                  ids=e(B, dt=torch.int64), out_ids=torch.zeros(B, T, device=dev, dtype=torch.int64), ws=ops.decode_argmax_workspace(B, W.shape[0], dev))
+        if sample:
+            st.update(logits=e(B, W.shape[0]), logprobs=torch.zeros(B, T, device=dev, dtype=torch.float32),
+                      sparams=ops.sample_params(greedy=True).to(dev), streams=torch.arange(B, device=dev, dtype=torch.int64))
+        return st
+
+    def _decode_choose(self, st: dict, x: torch.Tensor, logits_out, pos_from=None):
+        """The last launches of a decoding step: the greedy lm_head argmax with its advance - or, on a state with a sampler
+        (decode_alloc(sample=True)), the lm_head pass storing the logits, then vla_sample_tokens with the advance."""
+        advance = (st["out_ids"], st["step"], st["pos"], self.embed, st["X"][0])
+        if "sparams" not in st:
+            ops.decode_lm_head_argmax(x, st["W"], st["ws"], st["ids"], logits_out, advance=advance, pos_from=pos_from)
+            return
+        ops.decode_lm_head_argmax(x, st["W"], st["ws"], st["ids"], st["logits"])
+        ops.sample_tokens(st["logits"], st["sparams"], st["step"], st["ids"], st["streams"], st["logprobs"], advance=advance, pos_from=pos_from)
+        if logits_out is not None:
+            logits_out.copy_(st["logits"])                       # (eager return_logits: the logits the sampler saw)
 
     def cache_fill(self, st: dict):
         """The rotated k and the v of every prefill row, from QKV[i] into rows 0 .. S - 1 of the cache (a strided copy per layer and
@@ -566,8 +584,7 @@ class LLM(_BufferSets):
         first step's input, pos = pos0 + 1, step = 1."""
         n, D = self.cfg.n_layers, self.cfg.d
         ops.gather_rows(self.HS[n].view(-1, D), last_row, st["XG"])
-        ops.decode_lm_head_argmax(st["XG"], st["W"], st["ws"], st["ids"], logits_out,
-                                  advance=(st["out_ids"], st["step"], st["pos"], self.embed, st["X"][0]), pos_from=pos0)
+        self._decode_choose(st, st["XG"], logits_out, pos_from=pos0)
 
     def decode_step(self, st: dict, logits_out=None):
         """One cached single-token step for all B rows: the layers of _layer at M = B with the cache attention, the final norm, the
@@ -584,8 +601,7 @@ class LLM(_BufferSets):
 
             self._layer(i, lin, st["X"][i], st["X1"], st["X"][i + 1], st["NB"], st["NB"], st["H"], st["GU"], st["R"][0], st["R"][1], attend)
         ops.rmsnorm_fwd(st["X"][c.n_layers], self.norm, c.eps, out=st["NF"], rstd=st["R"][2])
-        ops.decode_lm_head_argmax(st["NF"], st["W"], st["ws"], st["ids"], logits_out,
-                                  advance=(st["out_ids"], st["step"], st["pos"], self.embed, st["X"][0]))
+        self._decode_choose(st, st["NF"], logits_out)
 
     def fwd_final(self):
         """hidden_states[n] = final RMSNorm of the last layer's output (HF convention)."""
@@ -1276,7 +1292,8 @@ class VLAEngine(schedule.StepControls):
                                                 wait=[sg.signal for sg in segs], signal=("end", 0))
 
     # ---- greedy decoding of action tokens (prismatic/models/vlas/openvla.py:81-94: `generate`, do_sample off) ---------------------------
-    def generate(self, batch: Dict[str, torch.Tensor], max_new_tokens: int, return_logits: bool = False):
+    def generate(self, batch: Dict[str, torch.Tensor], max_new_tokens: int, return_logits: bool = False, sample: Optional[dict] = None,
+                 return_logprobs: bool = False):
         """Greedy decoding of T = max_new_tokens tokens behind B right-padded prompts of different lengths -> int64 [B, T] on the
         device, no host synchronisation.  batch: input_ids int64 [B, L], attention_mask [B, L], pixel_values, and from
         ops.decode_prompt ``pos`` int32 [B] (sequence row of each sample's last prompt id) and ``last_row`` int32 [B] (the same row in
@@ -1289,7 +1306,16 @@ class VLAEngine(schedule.StepControls):
         (positions and the step index live in device memory).  VLA_PREDICT_EAGER=1 runs both parts eagerly; return_logits (eager
         only) also returns the bf16 logits the argmax compared, [B, T, V].
         Generation owns its workspace - LLM activations, vision features; no head - and runs inside bound_workspace(): what was bound
-        before is bound after, and the buffers a captured predict() or training graph holds are not written."""
+        before is bound after, and the buffers a captured predict() or training graph holds are not written.
+
+        sample = dict(temperature=, top_k=, top_p=, seed=, streams=None): every token is drawn by the rule of include/vla_sample.h
+         instead - streams: B ints, the stream id of every row (default 0 .. B - 1); K samples of one observation
+        are that row repeated under K stream ids.  return_logprobs: the log-probability of every emitted token, f32 [B, T], comes last in
+        the returned tuple; without `sample` the tokens are the greedy ones, bit for bit, and the log-probability is log_softmax of the
+        logits.  Either of the two takes a second cache entry (the key gains a flag) whose prefill and step graphs end in the lm_head
+        pass storing the logits and vla_sample_tokens; the settings, the seed and the greedy flag live in a device block filled by a
+        small copy in front of the prefill, so changing them never captures again.  With neither, the path, the key and the graphs
+        are the greedy ones."""
         T = int(max_new_tokens)
         if T < 1:
             raise ValueError(f"generate: max_new_tokens must be at least 1, got {max_new_tokens}")
@@ -1303,14 +1329,25 @@ class VLAEngine(schedule.StepControls):
         for k in ("pos", "last_row"):
             if k not in batch or batch[k].dtype != torch.int32 or batch[k].numel() != B:
                 raise ValueError(f"generate: batch[{k!r}] must be the int32 [{B}] vector of ops.decode_prompt")
-        key = (B, L, T, tuple(px.shape), px.dtype, eager)
+        sampled = sample is not None or return_logprobs
+        key = (B, L, T, tuple(px.shape), px.dtype, eager) + (("sample",) if sampled else ())
+        if sampled:                                  # refusals and the host copy of the block before any device work
+            opts = dict(sample or {})
+            streams = opts.pop("streams", None)
+            block = ops.sample_params(greedy=sample is None, **opts)
+            streams = list(range(B)) if streams is None else [int(v) for v in streams]
+            if len(streams) != B:
+                raise ValueError(f"generate: sample['streams'] must hold B = {B} ints, got {len(streams)}")
         ent = self._generate_sets.get(key)
         with self.bound_workspace(Workspace() if ent is None else ent["ws"]):
             if ent is None:
-                ent = self._generate_sets[key] = self._generate_build(batch, T, eager)
+                ent = self._generate_sets[key] = self._generate_build(batch, T, eager, sampled)
             static, st = ent["static"], ent["state"]
             for k, v in static.items():
                 v.copy_(batch[k])
+            if sampled:
+                st["sparams"].copy_(block)
+                st["streams"].copy_(torch.tensor(streams, dtype=torch.int64))
             logits = torch.empty(B, T, st["W"].shape[0], device=self.device, dtype=BF16) if return_logits else None
             if eager:
                 self._generate_prefill(static, st, None if logits is None else logits[:, 0])
@@ -1321,7 +1358,9 @@ class VLAEngine(schedule.StepControls):
                 for _ in range(T - 1):
                     ent["step"].replay()
             out = st["out_ids"].clone()
-        return (out, logits) if return_logits else out
+            logprobs = st["logprobs"].clone() if return_logprobs else None
+        res = (out,) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
+        return res if len(res) > 1 else out
 
     # Kernel selection is part of the arithmetic (ops.latency_hint: the short-M tiles and the uneven split-K associate the fp32 sums
     # differently), so the eager and the captured path run under ONE rule and give the same tokens: the prefill as predict() has it (the
@@ -1336,7 +1375,7 @@ class VLAEngine(schedule.StepControls):
         with ops.latency_hint():
             self.llm.decode_step(st, logits_t)
 
-    def _generate_build(self, batch, T: int, eager: bool) -> dict:
+    def _generate_build(self, batch, T: int, eager: bool, sampled: bool = False) -> dict:
         """The cache entry of one generate() shape: a workspace of its own (a fresh allocation, whatever is bound; the caller puts
         the previous one back), the decode state, static inputs, and - unless eager - the prefill graph and the step graph,
         captured on one stream behind two eager warm-up runs (every kernel launched and its LDS attribute set before the capture)."""
@@ -1346,7 +1385,7 @@ class VLAEngine(schedule.StepControls):
         self._vis_bufs = {}
         llm.unbind()
         self._vision_begin(static)                   # allocates the workspace this entry keeps
-        st = llm.decode_alloc(B, self.S, T)
+        st = llm.decode_alloc(B, self.S, T, sample=sampled)
         ent = dict(static=static, state=st, ws=self.workspace(head=False))
         if eager:
             return ent

@@ -244,7 +244,8 @@ class OpenVLAForActionPrediction:
     # ---- serving a token-CE model: greedy action tokens with a key/value cache (prismatic/models/vlas/openvla.py:36-106) -------------
     def generate_actions(self, prompt_ids, *, pixel_values=None, frames_u8=None, center_crop: bool = False, policy_resize: bool = False,
                          unnorm_key=None, max_new_tokens: Optional[int] = None, return_tokens: bool = False, return_tensors: bool = False,
-                         use_film: bool = False):
+                         use_film: bool = False, do_sample: bool = False, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
+                         seed: Optional[int] = None, sample_streams=None, return_logprobs: bool = False):
         """OpenVLA.predict_action for a batch of B observations, for a model trained with the token cross-entropy objective
         (``--objective token_ce``): greedy decoding of T = max_new_tokens action tokens behind every prompt (VLAEngine.generate: one
         prefill, T - 1 cached steps, one device pass), ActionTokenizer.decode_token_ids_to_actions on them (the rule the trainers'
@@ -259,11 +260,33 @@ class OpenVLAForActionPrediction:
         return_tokens it need not be a multiple of action_dim, and the actions are then None.  There is NO early stop at an
         end-of-sequence id: T tokens are always produced (the reference's `generate` would stop at one; a model trained on action ids
         behind the prompt does not emit it before them).  pixel_values / frames_u8, center_crop, policy_resize: as in predict_actions.
-        A LoRA run is served from its merged checkpoint.  Sampling is not built: the choice is the argmax, lowest id among equals."""
+        A LoRA run is served from its merged checkpoint.  By default the choice is the argmax, lowest id among equals.
+
+        do_sample, temperature, top_k, top_p: HF's names with HF's GenerationConfig defaults (the reference passes them through
+        **kwargs into `generate`): every token is drawn on the device by the rule of include/vla_sample.h -
+        temperature, then top-k (0 switches it off), then top-p, then a Gumbel-max draw whose noise is a function of (seed, stream id
+        of the row, step, token id) alone.  seed (an int) is required with do_sample: the same call gives the same tokens.
+        sample_streams: B ints, the stream id of every row (default 0 .. B - 1); K samples of one observation are that row repeated
+        under K different stream ids (num_return_sequences is not built).  Without do_sample the four settings and the seed must stay
+        at their defaults: nothing is silently dropped.  return_logprobs: the log-probability of every emitted token under the
+        distribution it was chosen from (greedy: log_softmax of the logits), float32 [B, T] - an ndarray, or a device tensor with
+        return_tensors - comes last in the returned tuple."""
         if use_film:
             raise NotImplementedError("generate_actions: FiLM (use_film) is outside the accelerated path")
         if self.engine.fp8_frozen:
             raise NotImplementedError("generate_actions: the fp8 weight path (enable_fp8_frozen) is not covered by the cached decoder")
+        sample = None
+        if not do_sample:
+            if temperature != 1.0 or top_k != 50 or top_p != 1.0 or seed is not None or sample_streams is not None:
+                raise ValueError("generate_actions: temperature, top_k, top_p, seed and sample_streams belong to do_sample=True; greedy decoding reads none of them")
+        else:
+            if isinstance(seed, bool) or not isinstance(seed, int):
+                raise ValueError(f"generate_actions: do_sample needs an int seed (draws are reproducible by construction), got {seed!r}")
+            try:
+                ops.sample_params(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+            except ValueError as e:
+                raise ValueError("generate_actions: " + str(e).split(": ", 1)[1]) from None
+            sample = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
         Da = self.cfg.action_dim
         T = self.cfg.chunk * Da if max_new_tokens is None else int(max_new_tokens)
         if T < 1:
@@ -287,13 +310,25 @@ class OpenVLAForActionPrediction:
             raise ValueError("generate_actions: prompt offsets on the device are not accepted (the padded length comes from the lengths)")
         if len(lens) < 1 or min(lens) < 1:
             raise ValueError("generate_actions: every sample needs a prompt of at least one id")
+        if sample_streams is not None:
+            streams = list(sample_streams)
+            if len(streams) != len(lens) or any(isinstance(v, bool) or not isinstance(v, int) for v in streams):
+                raise ValueError(f"generate_actions: sample_streams must be B = {len(lens)} ints, got {sample_streams!r}")
+            sample["streams"] = streams
         stage, dev = self.input_stage(), self.device
         tok = stage.decode_prompt(prompt_ids, self.cfg.n_patches)
         if policy_resize:
             frames_u8 = stage.policy_frames(frames_u8)
         px = stage.pixels(frames_u8, center_crop=center_crop) if frames_u8 is not None else pixel_values.to(dev).contiguous()
         batch = dict(input_ids=tok["input_ids"], attention_mask=tok["attention_mask"], pixel_values=px, pos=tok["pos"], last_row=tok["last_row"])
-        tokens = self.engine.generate(batch, T)                                        # int64 [B, T] on the device
+        logprobs = None
+        if sample is None and not return_logprobs:
+            tokens = self.engine.generate(batch, T)                                    # int64 [B, T] on the device
+        elif return_logprobs:
+            tokens, logprobs = self.engine.generate(batch, T, sample=sample, return_logprobs=True)
+            logprobs = logprobs if return_tensors else logprobs.cpu().numpy()
+        else:
+            tokens = self.engine.generate(batch, T, sample=sample)
         actions = None
         if stats is not None:
             low, high, mask = stage._serve_stats(stats, "bounds_q99")                  # f64 [Da] on the device, mask u8 or None
@@ -303,7 +338,8 @@ class OpenVLAForActionPrediction:
                 actions = torch.where(mask.bool(), actions, a)
             if not return_tensors:
                 actions = actions.cpu().numpy()
-        return (actions, tokens) if return_tokens else actions
+        res = (actions,) + ((tokens,) if return_tokens else ()) + ((logprobs,) if return_logprobs else ())
+        return res if len(res) > 1 else actions
 
 
 @dataclass

@@ -225,8 +225,9 @@ LATER_PROTOS = {name: sig for fam in LATER_FAMILIES for name, sig in fam.protos.
 assert len(LATER_PROTOS) == sum(len(fam.protos) for fam in LATER_FAMILIES) and not set(LATER_PROTOS) & set(PROTOS), "an entry point belongs to one header"
 
 
-# The open end of the registry: LATER_FAMILIES is pinned as a literal list too (tests/test_abi_later_families.py), so families from here on
-# are rows of this tuple - tests/test_abi_decode_family.py runs the same agreement checks over every row, whatever its key.
+# The third tuple: LATER_FAMILIES is pinned as a literal list too (tests/test_abi_later_families.py).  tests/test_abi_decode_family.py runs
+# the same agreement checks over every row of this one, whatever its key - and pins its keys as a literal list in turn, so this tuple is
+# closed as well: the open end of the registry is OPEN_FAMILIES below.
 ADDED_FAMILIES = (
     # greedy action-token decoding with a key/value cache (csrc/decode.hip)
     Family("decode", "vla_decode.h", {
@@ -242,9 +243,22 @@ assert len(ADDED_PROTOS) == sum(len(fam.protos) for fam in ADDED_FAMILIES) and n
     "an entry point belongs to one header"
 ALL_FAMILIES = FAMILIES + LATER_FAMILIES + ADDED_FAMILIES
 
+# The open end of the registry.  ALL_FAMILIES is pinned as the sum of the three tuples above (tests/test_abi_decode_family.py), so the
+# families behind them are rows of this tuple, bound by the same loop of load() and found by the same family();
+# tests/test_sample_cpu.py runs the agreement checks over every row, whatever its key, and pins no key list.
+OPEN_FAMILIES = (
+    # sampling of action tokens: temperature, top-k, top-p, the draw and its log-probability (csrc/sample.hip)
+    Family("sample", "vla_sample.h", {
+        "vla_sample_tokens": ([_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I], _I),
+    }),
+)
+OPEN_PROTOS = {name: sig for fam in OPEN_FAMILIES for name, sig in fam.protos.items()}
+assert len(OPEN_PROTOS) == sum(len(fam.protos) for fam in OPEN_FAMILIES) and \
+    not set(OPEN_PROTOS) & {n for fam in ALL_FAMILIES for n in fam.protos}, "an entry point belongs to one header"
+
 
 def family(key: str) -> Family:
-    return next(fam for fam in ALL_FAMILIES if fam.key == key)
+    return next(fam for fam in ALL_FAMILIES + OPEN_FAMILIES if fam.key == key)
 
 
 _lib = None
@@ -260,7 +274,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {os.path.join(_HERE, 'csrc')}`).  There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in [sig for fam in ALL_FAMILIES for sig in fam.protos.items()]:
+    for name, (args, res) in [sig for fam in ALL_FAMILIES + OPEN_FAMILIES for sig in fam.protos.items()]:
         fn = getattr(lib, name, None)
         if fn is None:       # (entry points added without an ABI version change, e.g. vla_token_ce_metrics: an older build lacks them)
             raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it was built from an older source tree, rebuild (make -C csrc)")

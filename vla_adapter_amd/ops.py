@@ -1435,3 +1435,80 @@ def decode_lm_head_argmax(x: torch.Tensor, W: torch.Tensor, ws, ids: Optional[to
     N.check(_lib().vla_decode_lm_head_argmax(_st(), _p(x), x.stride(0), _p(W), W.stride(0), B, D, V, _p(pv), _p(pi), _p(ids), _p(logits_out), ldl, *a),
             "decode_lm_head_argmax")
     return ids
+
+
+# ---- sampling of action tokens (include/vla_sample.h, csrc/sample.hip) ---------------------------------------------------------------
+SAMPLE_PARAM_BYTES = 24
+
+
+def sample_params(*, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, greedy: bool = False) -> torch.Tensor:
+    """The parameter block of vla_sample_tokens as a uint8 [24] tensor on the host (f32 temperature, f32 top_p, i32 top_k, i32 greedy,
+    u64 seed): copied into the device block a captured graph reads.  Refuses what the rule does not define."""
+    import struct
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not temperature > 0:
+        raise ValueError(f"sample_params: temperature must be a number above 0, got {temperature!r}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
+        raise ValueError(f"sample_params: top_k must be an int >= 0 (0 switches the filter off), got {top_k!r}")
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0 < top_p <= 1:
+        raise ValueError(f"sample_params: top_p must lie in (0, 1], got {top_p!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"sample_params: seed must be an int, got {seed!r}")
+    raw = struct.pack("<ffiiQ", float(temperature), float(top_p), int(top_k), 1 if greedy else 0, seed & (2 ** 64 - 1))
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+
+
+def sample_tokens(logits: torch.Tensor, params: torch.Tensor, step: torch.Tensor, ids: Optional[torch.Tensor] = None,
+                  streams: Optional[torch.Tensor] = None, logprob_out: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
+                  advance=None, pos_from: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vla_sample_tokens: logits bf16 [B, V] (rows may be strided; what decode_lm_head_argmax stores in logits_out) -> ids int64 [B], one
+    decoding step of the rule of include/vla_sample.h.  params: the device copy of sample_params() (uint8 [24], 8-B aligned).  step: the
+    int32 [1] device step counter t (read; advanced only by an advance).  streams int64 [B] or None (row b draws from stream b).
+    logprob_out f32 [B, T] (column t is written), probs_out f32 [B, V] (the filtered, renormalised probabilities; rows may be strided).
+    advance = (out_ids, step, pos, embed, x_next) and pos_from: as decode_lm_head_argmax takes them."""
+    if logits.dtype != BF16 or logits.dim() != 2 or logits.stride(1) != 1 or not logits.is_cuda:
+        raise ValueError(f"sample_tokens: logits must be a bf16 [B, V] device tensor with unit inner stride, got {tuple(logits.shape)}")
+    (B, V), dev = logits.shape, logits.device
+    if not 1 <= B <= 64 or V < 1 or (B > 1 and logits.stride(0) < V):
+        raise ValueError(f"sample_tokens: B in [1, 64], V >= 1 and a row stride of at least V, got B = {B}, V = {V}")
+    if params.dtype != torch.uint8 or params.numel() != SAMPLE_PARAM_BYTES or not params.is_contiguous() or params.device != dev or params.data_ptr() % 8:
+        raise ValueError("sample_tokens: params must be the 8-B aligned uint8 [24] device copy of ops.sample_params()")
+    if step.dtype != torch.int32 or step.numel() != 1 or step.device != dev:
+        raise ValueError("sample_tokens: step must be one int32 on the device")
+    if ids is None:
+        ids = torch.empty(B, device=dev, dtype=torch.int64)
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or ids.numel() != B or ids.device != dev:
+        raise ValueError(f"sample_tokens: ids must be a contiguous int64 [{B}]")
+    if streams is not None and (streams.dtype != torch.int64 or not streams.is_contiguous() or streams.numel() != B or streams.device != dev):
+        raise ValueError(f"sample_tokens: streams must be a contiguous int64 [{B}] on {dev}")
+    T = 0
+    if logprob_out is not None:
+        if logprob_out.dtype != torch.float32 or logprob_out.dim() != 2 or logprob_out.shape[0] != B or not logprob_out.is_contiguous() or logprob_out.device != dev:
+            raise ValueError(f"sample_tokens: logprob_out must be a contiguous f32 [B = {B}, T]")
+        T = logprob_out.shape[1]
+    ldp = 0
+    if probs_out is not None:
+        if probs_out.dtype != torch.float32 or tuple(probs_out.shape) != (B, V) or probs_out.stride(1) != 1 or probs_out.device != dev:
+            raise ValueError(f"sample_tokens: probs_out must be f32 [B, V] = [{B}, {V}] with unit inner stride")
+        ldp = probs_out.stride(0)
+    if pos_from is not None and advance is None:
+        raise ValueError("sample_tokens: pos_from belongs to an advance")
+    a = [None, T, _p(step), None, None, None, 0, 0, None, 0, 0]
+    if advance is not None:
+        out_ids, step_a, pos, embed, x_next = advance
+        _chk_bf16(embed, x_next)
+        _chk_pos("sample_tokens", pos, B, dev)
+        if step_a is not step:
+            raise ValueError("sample_tokens: the advance moves the step counter the draw reads")
+        if out_ids.dtype != torch.int64 or not out_ids.is_contiguous() or out_ids.dim() != 2 or out_ids.shape[0] != B:
+            raise ValueError(f"sample_tokens: out_ids must be a contiguous int64 [B = {B}, T], got {out_ids.dtype} {tuple(out_ids.shape)}")
+        if logprob_out is not None and out_ids.shape[1] != T:
+            raise ValueError("sample_tokens: out_ids and logprob_out hold the same T columns")
+        D = embed.shape[1] if embed.dim() == 2 else 0
+        if embed.dim() != 2 or D % 8 or embed.stride(1) != 1 or tuple(x_next.shape) != (B, D) or x_next.stride(1) != 1:
+            raise ValueError(f"sample_tokens: embed [vocab, D] and x_next [B, D] with unit inner strides and D a multiple of 8, got {tuple(embed.shape)} / {tuple(x_next.shape)}")
+        if pos_from is not None:
+            _chk_pos("sample_tokens", pos_from, B, dev)
+        a = [_p(out_ids), out_ids.shape[1], _p(step), _p(pos), _p(pos_from), _p(embed), embed.shape[0], embed.stride(0), _p(x_next), x_next.stride(0), D]
+    N.check(_lib().vla_sample_tokens(_st(), _p(logits), logits.stride(0), B, V, _p(params), _p(streams), _p(ids), _p(logprob_out), _p(probs_out),
+                                     ldp, *a), "sample_tokens")
+    return ids
